@@ -1276,7 +1276,7 @@ def test_one_process_per_gpu_job_rehearsed_on_one_gpu(ranks, transport, group):
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY=os.environ.get("HSA_ENABLE_IPC_MODE_LEGACY", "0"))
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", str(ranks), "--rehearse", "--transport", transport, "--scene", "S3", "--steps", "9", "--warmup", "3",
-                        "--no-cpu"] + (["--group", str(group)] if group else []),  # (no --group: bench.py's own rule -- one launch of nine frames when the frames can be mapped)
+                        "--full", "--no-cpu"] + (["--group", str(group)] if group else []),  # (no --group: bench.py's own rule -- one launch of nine frames when the frames can be mapped)
                        capture_output=True, text=True, timeout=500, env=env, cwd=root)
     assert r.returncode == 0, (r.stdout[-800:], r.stderr[-2500:])
     line = json.loads([ln for ln in r.stdout.strip().splitlines() if ln.startswith("{")][-1])

@@ -14,11 +14,11 @@ round=${tag%%_*}
 done
 [ "$PART" = pmc ] && { ls $out; exit 0; }
 # 2. the bench line (default invocation) and the driver's invocation
-timeout -k 10 300 python bench.py > $out/bench_S3.json 2> $out/bench_S3.err || echo "bench failed"
+timeout -k 10 300 python bench.py --full > $out/bench_S3.json 2> $out/bench_S3.err || echo "bench failed"
 timeout -k 10 300 python bench.py --gpus 1 --steps 20 --warmup 5 > $out/bench_S3_driver.json 2>> $out/bench_S3.err
 # 3. rocprofv3 kernel stats of the same command
 cd /tmp && export TMPDIR=/tmp
-timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $root/$out/prof --output-format csv -- python3 $root/bench.py --steps 200 --warmup 20 --no-cpu > $root/$out/prof.log 2>&1
+timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $root/$out/prof --output-format csv -- python3 $root/bench.py --full --steps 200 --warmup 20 --no-cpu > $root/$out/prof.log 2>&1
 cd $root
 cp $(find $out/prof -name "*kernel_stats.csv" | head -1) $out/bench_S3_kernel_stats.csv 2>/dev/null
 rm -rf $out/prof
