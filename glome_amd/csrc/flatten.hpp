@@ -556,7 +556,6 @@ class Flattener {
     // (w: the tree's depth -- the generic tier walks a tree as a packet when its per-wave stack holds it -- and, in bit 31, whether
     // every item is answered in place: kBihItemsInPlace)
     in_place = in_place && !T.nodes.empty() && !T.nodes[0].leaf;
-    if (getenv("GLOME_DEBUG_NO_ITEM_PACKETS")) in_place = false;  // (A/B switch: such trees walked lane by lane over frames, as until round 4)
     F.bihhdr[3 * hdr + 2] = F4{as_float_bits(delta), as_float_bits(pkroot), as_float_bits(pk ? 1u : 0u), as_float_bits((uint32_t)T.depth | (in_place ? kBihItemsInPlace : 0u))};
     if (cls == BC_SPHERE || cls == BC_TRI || in_place) F.max_sphere_bih_depth = std::max(F.max_sphere_bih_depth, T.depth);
     return U4{R_BIH, hdr, 0, (uint32_t)n.uid};

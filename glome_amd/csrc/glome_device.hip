@@ -217,24 +217,15 @@ __device__ __forceinline__ bool work_to_pixel(const DRenderArgs& A, uint32_t w, 
 // atomics queued on its line: measured 4x slower), so a wave rarely pays for more than one failed take.  The last wave to
 // leave puts everything back to zero: the next launch on the slot needs no reset packet on the stream.
 constexpr uint32_t kNoTicket = 0xffffffffu;
-// A wave may take several tickets per atomic while the head is far from empty and single ones towards the end (guided
-// self-scheduling).  Measured in round 3 and left OFF (largest batch 1): in-kernel stamps put a wave's wait for a ticket at
-// 2,500-3,100 cycles, 3-4 % of its lifetime on the flagship frame (21 % on a frame of empty sky, where the 46 us that 32,400
-// serialised atomics take on 8 heads are most of the frame); batches of 4 or 8 won 0-7 % pipelined and lost 15-30 % on a launch
-// alone, whose last items then run on too few waves (tools/probe/empty_frame.py; fixed and guided batches alike).
-#ifndef GLOME_TICKET_BATCH
-#define GLOME_TICKET_BATCH 1  // the largest batch
-#endif
+// One ticket per atomic.  (Several per atomic while a head is far from empty -- guided self-scheduling -- was measured in round 3:
+// batches of 4 or 8 won 0-7 % pipelined and lost 15-30 % on a launch alone, whose last items then run on too few waves.)
+// A ticket the atomic returns is handed out at the top of the loop, from inext / cur: returning it on the spot frees two scalar
+// registers for the kernel's lifetime and moves the register allocation of every render kernel (tools/kernel_mix.py; the
+// flagship's SGPR spills 49 -> 45, a Mesh instance 5 -> 4 waves per SIMD), so that change waits for a measurement of its own.
 struct TicketQueue {
   uint32_t shard, dry;
-  uint32_t inext = 0, left = 0, cur = 0;  // a batch in hand: its next queue index, tickets left in it, the head it came from (lane 0's)
-  uint32_t batch;
-  __device__ __forceinline__ uint32_t batch_for(const DRenderArgs& A, uint32_t remaining) const {  // ~half a fair share of what is left, 1..GLOME_TICKET_BATCH
-    const uint32_t waves_per_head = (gridDim.x + kQueueShards - 1) / kQueueShards;
-    const uint32_t b = remaining / (2u * waves_per_head);
-    return b < 1u ? 1u : (b > (uint32_t)GLOME_TICKET_BATCH ? (uint32_t)GLOME_TICKET_BATCH : b);
-  }
-  __device__ __forceinline__ TicketQueue(const DRenderArgs& A) : shard(blockIdx.x % kQueueShards), dry(0) { batch = batch_for(A, A.shard_cap); }
+  uint32_t inext = 0, left = 0, cur = 0;  // a ticket in hand: its queue index, 1 while it is unused, the head it came from (lane 0's)
+  __device__ __forceinline__ TicketQueue() : shard(blockIdx.x % kQueueShards), dry(0) {}
   // Every lane of the wave makes the call; the state is wave-uniform (scalar registers) and only the atomics themselves are lane 0's.
   // (Until round 3 the whole take ran on lane 0 under a branch: its six state words then lived in vector registers for the kernel's lifetime.)
   __device__ __forceinline__ uint32_t take(const DRenderArgs& A) {
@@ -244,18 +235,17 @@ struct TicketQueue {
         left--;
         const uint32_t i = inext++;
         if (i < A.shard_cap) return ((i / kQueueChunk) * kQueueShards + cur) * kQueueChunk + (i % kQueueChunk);
-        left = 0;  // the batch reached past the head's last ticket
+        left = 0;
       }
       if (dry == kAll) return kNoTicket;
       if (!((dry >> shard) & 1u)) {
         uint32_t i = 0;
-        if (LaneStack::lane() == 0) i = atomicAdd(&A.counters->heads[shard * kQueueHeadStride], batch);
+        if (LaneStack::lane() == 0) i = atomicAdd(&A.counters->heads[shard * kQueueHeadStride], 1u);
         i = uni(i);
-        if (i < A.shard_cap) { inext = i; left = batch; cur = shard; batch = batch_for(A, A.shard_cap - i); continue; }
+        if (i < A.shard_cap) { inext = i; left = 1; cur = shard; continue; }
         uint32_t d = 0;
         if (LaneStack::lane() == 0) { atomicOr(&A.counters->dry, 1u << shard); d = __hip_atomic_load(&A.counters->dry, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
         dry |= (1u << shard) | uni(d);
-        batch = 1;  // what other heads have left is shared by everybody who comes by
       }
       shard = (shard + 1) % kQueueShards;
     }
@@ -270,14 +260,6 @@ struct TicketQueue {
   }
 };
 
-// GLOME_PROBE (a measurement build, tools/probe/empty_frame.py; never the product): GLOME_DEBUG_FLAGS leaves parts of a work item
-// out (1 no pixel store, 2 no trace, 4 no item -> pixel lookup, 8 static items instead of tickets) or (16) stamps its sections
-// with s_memtime into DCounters::dbg.  Compiled out of the product: the stamps alone cost the flagship kernel 5 %.
-#ifdef GLOME_PROBE
-#define GLOME_PROBE_FLAG(A, bit) ((A).debug_flags & (bit))
-#else
-#define GLOME_PROBE_FLAG(A, bit) false
-#endif
 // LEAN (the flagship instance: every step the hand-written walk's, six waves per SIMD, 80 vector registers): the three measures of
 // DESIGN.md 4.1c that take registers out of the walks' way -- arguments re-read per item through an opaque pointer, the ticket taken as
 // a scalar, the pixel made a second time after the trace.  They are worth 8-10 % there and COST the other instances, whose C++ walks
@@ -285,43 +267,20 @@ struct TicketQueue {
 // (profiles/r04_probes/mesh_regress_ab.txt); so the other flat-tier instances keep round 3's loop.
 template <bool LEAN, class TIER>
 __device__ __forceinline__ void render_loop(const DRenderArgs& A_, TIER& Tk) {
-#ifdef GLOME_PROBE
-  int lane = threadIdx.x & 63;
-#endif
-  TicketQueue Q(A_);
+  TicketQueue Q;
   // The launch's arguments are read where the dispatch put them (the kernarg segment: scalar loads), through a pointer the compiler
   // cannot see through from one work item to the next: what an item derives from them -- (float)width, the reciprocals of the
   // item -> pixel divisions, the table pointers -- is then made afresh per item (tens of instructions in eleven thousand) instead of
   // being hoisted out of the loop and carried, spilled, through both walks.
   const DRenderArgs __attribute__((address_space(4)))* ap_ = (const DRenderArgs __attribute__((address_space(4)))*)__builtin_amdgcn_kernarg_segment_ptr();
-#ifdef GLOME_PROBE
-  uint32_t stat = blockIdx.x;
-  unsigned long long ts0 = 0, ts1 = 0, ts2 = 0, ts3 = 0, t_s[3] = {0, 0, 0};  // item -> pixel lookup, ray generation, trace
-  unsigned long long t_take = 0, n_take = 0, t_begin = (A.debug_flags & 16) ? __builtin_amdgcn_s_memtime() : 0ull;
-  const unsigned long long rt_begin = __builtin_amdgcn_s_memrealtime();  // the 100 MHz clock every CU shares
-  unsigned long long rt_last_item = rt_begin, worst = 0;
-  uint32_t worst_steps = 0, steps_before = 0;
-#endif
   for (;;) {
     if constexpr (LEAN) asm volatile("" : "+s"(ap_));
     const DRenderArgs& A = LEAN ? *(const DRenderArgs*)ap_ : A_;
     TIER T = Tk.rebound(A);
     uint32_t w = kNoTicket;
-#ifdef GLOME_PROBE
-    if (A.debug_flags & 8) { w = stat < A.total_waves * (uint32_t)A.nframes ? stat : kNoTicket; stat += gridDim.x; }
-    else {
-      const unsigned long long t0 = (A.debug_flags & 16) ? __builtin_amdgcn_s_memtime() : 0ull;
-      w = Q.take(A);
-      if (A.debug_flags & 16) { ts0 = __builtin_amdgcn_s_memtime(); t_take += ts0 - t0; n_take++; }
-    }
-#else
     if constexpr (LEAN) w = Q.take(A);  // a SCALAR: the frame, the tile and the camera the ticket names are then scalar loads, not a lane's
     else { if (LaneStack::lane() == 0) w = Q.take(A); w = __shfl(w, 0, 64); }
-#endif
     if (w == kNoTicket) break;
-#ifdef GLOME_PROBE
-    rt_last_item = __builtin_amdgcn_s_memrealtime();
-#endif
     uint32_t frame;  // wave-uniform
     if (A.chunks_per_frame) {
       // chunk by chunk through all frames: the same 64x64 work tile of every view one after the other (neighbouring views walk the
@@ -338,67 +297,28 @@ __device__ __forceinline__ void render_loop(const DRenderArgs& A_, TIER& Tk) {
     }
     int px = 0, py = 0;
     size_t dense_off = 0;
-    bool valid;
-    if (GLOME_PROBE_FLAG(A, 4)) { const uint32_t l_ = LaneStack::lane(); px = (int)((w * 64u + l_) % (uint32_t)A.width); py = (int)((w * 64u + l_) / (uint32_t)A.width); valid = py < A.height; }
-    else valid = work_to_pixel(A, w, (int)LaneStack::lane(), px, py, dense_off);  // lanes past the end of a leftover strip idle along
-#ifdef GLOME_PROBE
-    if (A.debug_flags & 16) { asm volatile("" :: "v"(px), "v"(py)); ts1 = __builtin_amdgcn_s_memtime(); }
-#endif
+    bool valid = work_to_pixel(A, w, (int)LaneStack::lane(), px, py, dense_off);  // lanes past the end of a leftover strip idle along
     float xc, yc;
     get_coordsf(A.width, A.height, (float)px, (float)py, xc, yc);
     Ray ray = primary_ray(frame == 0 ? A.cam : A.more_cams[frame - 1], xc, yc);
     count_wave(T.cnt.primary, T.cnt.w_primary, valid);
-#ifdef GLOME_PROBE
-    if (A.debug_flags & 16) { asm volatile("" :: "v"(ray.d.x), "v"(ray.d.y), "v"(ray.d.z)); ts2 = __builtin_amdgcn_s_memtime(); }
-#endif
     HitG h;
-    CA c;
-    if (GLOME_PROBE_FLAG(A, 2)) { c = ca(ray.d.x, ray.d.y, ray.d.z, 1.0f); h = hit_miss(); }
-    else c = trace_primary(T, ray, kInf, A.maxdepth, valid, &h);  // Trace.trace lights shader sld ray infinity maxdepth (Glome.hs:33)
+    CA c = trace_primary(T, ray, kInf, A.maxdepth, valid, &h);  // Trace.trace lights shader sld ray infinity maxdepth (Glome.hs:33)
     Tk.absorb(T);  // (counters and the error flag back into the kernel's tier)
-#ifdef GLOME_PROBE
-    if (A.debug_flags & 16) { asm volatile("" :: "v"(c.r), "v"(c.g), "v"(c.b)); ts3 = __builtin_amdgcn_s_memtime(); t_s[0] += ts1 - ts0; t_s[1] += ts2 - ts1; t_s[2] += ts3 - ts2; }
-    if (A.debug_flags & 32) {  // the longest item, and the C++ steps its walks needed
-      const unsigned long long dt = __builtin_amdgcn_s_memrealtime() - rt_last_item;
-      if (lane == 0) { if (dt > worst) { worst = dt; worst_steps = w; } }  // (which item)
-      steps_before = T.cnt.bih;
-    }
-#endif
     if (!valid) continue;
     // the pixel once more (rather than three registers carried, spilled, through both walks): the item is a scalar, the lane a v_mbcnt
-    if constexpr (LEAN) { if (!GLOME_PROBE_FLAG(A, 4)) { px = 0; py = 0; dense_off = 0; (void)work_to_pixel(A, w, (int)LaneStack::lane(), px, py, dense_off); } }
+    if constexpr (LEAN) { px = 0; py = 0; dense_off = 0; (void)work_to_pixel(A, w, (int)LaneStack::lane(), px, py, dense_off); }
     float depth = h.hit ? h.t : kInf;      // ridepth
     float r = c.r;
     if (A.fog) r = r + (depth / 400);      // renderTile's debug fog (Glome.hs:174, Q20)
     size_t o = (A.dense ? dense_off : (size_t)py * A.width + px) + (size_t)frame * A.frame_stride;
-    if (GLOME_PROBE_FLAG(A, 1)) { if (r == 12345.678f) A.packed[o] = 1u; continue; }
     if (A.out5) {
       float* out = A.out5 + o * 5;
       out[0] = r; out[1] = c.g; out[2] = c.b; out[3] = c.a; out[4] = depth;
     }
-#ifdef GLOME_PROBE
-    if (A.debug_flags & 64) { A.packed[o] = (uint32_t)(__builtin_amdgcn_s_memrealtime() - rt_last_item); continue; }  // a cost image: the item's duration (10 ns units) in its pixels
-#endif
     if (A.packed) A.packed[o] = rgbf(r * c.a, c.g * c.a, c.b * c.a);  // blitTile (Glome.hs:353-358)
   }
-#ifdef GLOME_PROBE
-  if ((A_.debug_flags & 16) && lane == 0) {  // cycles waiting for tickets, tickets asked for, the wave's lifetime, waves, cycles per section
-    atomicAdd(&A_.counters->dbg[0], t_take); atomicAdd(&A_.counters->dbg[1], n_take);
-    atomicAdd(&A_.counters->dbg[2], __builtin_amdgcn_s_memtime() - t_begin); atomicAdd(&A_.counters->dbg[3], 1ull);
-    atomicAdd(&A_.counters->dbg[4], t_s[0]); atomicAdd(&A_.counters->dbg[5], t_s[1]); atomicAdd(&A_.counters->dbg[6], t_s[2]);
-  }
-  if ((A_.debug_flags & 32) && lane == 0) {  // the launch's timeline on the shared clock: first / last wave start, first / last wave's last ticket, first / last wave end
-    const unsigned long long rt_end = __builtin_amdgcn_s_memrealtime();
-    atomicMin(&A_.counters->dbg[8], rt_begin); atomicMax(&A_.counters->dbg[9], rt_begin);
-    atomicMin(&A_.counters->dbg[10], rt_last_item); atomicMax(&A_.counters->dbg[11], rt_last_item);
-    atomicMin(&A_.counters->dbg[12], rt_end); atomicMax(&A_.counters->dbg[13], rt_end);
-    atomicAdd(&A_.counters->dbg[14], (unsigned long long)Tk.cnt.bih);                        // C++ steps of all walks
-    atomicMax(&A_.counters->dbg[15], (worst << 20) | (unsigned long long)worst_steps);     // the longest item (10 ns units) and its C++ steps
-  }
-  if (!(A_.debug_flags & 8)) Q.leave(A_);
-#else
   Q.leave(A_);
-#endif
 }
 
 // TWO_ROWS: the wave's LDS holds two stack rows per entry instead of three (lane_stack); legal when no lane ever pushes on
@@ -409,7 +329,6 @@ template <bool FAITHFUL, bool COUNT, bool FULL, int CLS, int LB = 1, bool TWO_RO
 __global__ void __launch_bounds__(64, LB) k_render_flat(DRenderArgs A, int stack_cap, uint32_t* ovf, int ovf_cap) {
   extern __shared__ uint32_t lds[];
   FlatTier<FAITHFUL, COUNT, FULL, CLS> T{A.S, A.lights, A.nlights, lane_stack<TWO_ROWS>(lds, stack_cap, ovf, ovf_cap), Cnt()};
-  T.stk.dbg = A.counters->dbg;
   render_loop<TWO_ROWS>(A, T);
   if (A.want_counters) flush_counters(A.counters, T.cnt, T.err);
   else if ((CLS & (CLS_CSG | CLS_MESH)) && __builtin_amdgcn_ballot_w64(T.err != 0) && (threadIdx.x & 63) == 0) atomicOr(&A.counters->error, 1u);
@@ -909,14 +828,6 @@ static int get_tiles(glome_ctx* ctx, const glome_render_params* P, int first, in
   if (it == ctx->tile_cache.end()) {
     glome_ctx::TileTable tt;
     owned_tiles(P->width, P->height, blocksize, first, stride, P->rank0_share_pct, tt.host, tt.total_waves, tt.pixels);
-    if (const char* e = getenv("GLOME_DEBUG_TILE_ORDER")) {  // (experiment: the order in which a launch works through its tiles; pixels do not move)
-      const std::string how = e;
-      if (how == "bottomup") std::stable_sort(tt.host.begin(), tt.host.end(), [](const DTile& a, const DTile& b) { return a.y > b.y; });
-      else if (how == "rowmajor") std::stable_sort(tt.host.begin(), tt.host.end(), [](const DTile& a, const DTile& b) { return a.y < b.y; });
-      else if (how == "reverse") std::reverse(tt.host.begin(), tt.host.end());
-      uint32_t wb = 0;
-      for (auto& t : tt.host) { t.wave_base = wb; wb += tile_waves(t.w, t.h); }
-    }
     size_t bytes = std::max<size_t>(1, tt.host.size()) * sizeof(DTile);
     HIPCHK(ctx, hipMalloc((void**)&tt.dev, bytes));
     if (!tt.host.empty()) HIPCHK(ctx, hipMemcpy(tt.dev, tt.host.data(), tt.host.size() * sizeof(DTile), hipMemcpyHostToDevice));
@@ -971,10 +882,6 @@ glome_ctx* glome_ctx_create(int device_ordinal) {
   if ((e = hipEventCreate(&c->ev1)) != hipSuccess) return fail("hipEventCreate", e);
   for (int k = 0; k < glome_ctx::kSlots; k++)
     if ((e = hipMalloc((void**)&c->slots[k].d_counters, sizeof(DCounters))) != hipSuccess || (e = hipMemset(c->slots[k].d_counters, 0, sizeof(DCounters))) != hipSuccess) return fail("hipMalloc", e);
-#ifdef GLOME_PROBE
-  for (int k = 0; k < glome_ctx::kSlots; k++)
-    for (int q : {8, 10, 12}) (void)hipMemset(&c->slots[k].d_counters->dbg[q], 0xff, sizeof(unsigned long long));  // (the timeline's minima, render_loop)
-#endif
   {  // kernel_args<>()'s assumption about the kernarg segment, checked once per process on the first context
     static std::once_flag once;
     static bool good = true;
@@ -1082,13 +989,6 @@ int glome_ctx_synchronize(glome_ctx* c) {
   }
   return rc;
 }
-int glome_ctx_debug_words(glome_ctx* c, uint64_t* out16) {  // DCounters::dbg of the current slot (measurement builds write them)
-  if (!c || !out16) return GLOME_E_INVALID;
-  HIPCHK(c, hipSetDevice(c->device));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  HIPCHK(c, hipMemcpy(out16, c->slot().d_counters->dbg, 16 * sizeof(uint64_t), hipMemcpyDeviceToHost));
-  return 0;
-}
 // ---- a framebuffer several PROCESSES render into (one process per GPU: glome_amd/dist.py) ----
 // rank 0 allocates the frames and exports a handle; the other ranks open it and hand the pointer to their render calls, whose kernels
 // then store their tiles' pixels straight into rank 0's memory over xGMI (hipIpc*: dmabuf handles on this driver).
@@ -1119,14 +1019,6 @@ int glome_ipc_close(glome_ctx* c, void* dev_ptr, int owner) {  // owner: the pro
   if (!c || !dev_ptr) return GLOME_E_INVALID;
   HIPCHK(c, hipSetDevice(c->device));
   if (owner) HIPCHK(c, hipFree(dev_ptr)); else HIPCHK(c, hipIpcCloseMemHandle(dev_ptr));
-  return 0;
-}
-int glome_ctx_debug_reset(glome_ctx* c) {  // (measurement builds: the timeline words of the current slot back to "nothing seen")
-  if (!c) return GLOME_E_INVALID;
-  HIPCHK(c, hipSetDevice(c->device));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  HIPCHK(c, hipMemset(c->slot().d_counters->dbg, 0, 16 * sizeof(uint64_t)));
-  for (int q : {8, 10, 12}) HIPCHK(c, hipMemset(&c->slot().d_counters->dbg[q], 0xff, sizeof(unsigned long long)));
   return 0;
 }
 int glome_ctx_device_info(glome_ctx* c, char* name, int cap, int* cu_count, int* warp_size) {
@@ -1243,10 +1135,9 @@ glome_scene* glome_scene_commit(glome_ctx* ctx, glome_sb* sb, int32_t root) {
   // LDS holds up to kLdsStack entries per lane (LDS per wave bounds occupancy); a deeper tree keeps its correctness
   // through the global overflow columns.
   constexpr int kLdsStack = kAsmLdsCap;
-  int lds_cap = getenv("GLOME_DEBUG_STACK_CAP") ? atoi(getenv("GLOME_DEBUG_STACK_CAP")) : kLdsStack;
   int total = std::min(kFlatStack, std::max(4, need));
   if (F.tier == 0 && F.max_mesh_depth > 0) total = std::max(total, std::min(kFlatStackMesh, 2 * F.max_mesh_depth));  // (the Mesh packet walk: up to two entries per level)
-  s->stack_cap = std::max(4, std::min(lds_cap, total));
+  s->stack_cap = std::max(4, std::min(kLdsStack, total));
   s->ovf_cap = std::max(0, total - s->stack_cap);
   return s;
 }
@@ -1411,8 +1302,7 @@ static int render_impl(glome_scene* s, const glome_camera* cam, const glome_ligh
   memcpy(A.thresholds, P->thresholds, 16);
   A.tiles = tt->dev; A.tile_lut = tt->lut; A.ntiles = (int)tt->host.size(); A.total_waves = tt->total_waves;
   {  // tickets per queue head: the launch's chunks dealt round-robin over the heads, the last round padded
-    static const bool no_interleave = getenv("GLOME_DEBUG_NO_INTERLEAVE") != nullptr;  // (A/B: frame after frame, as until round 3)
-    A.chunks_per_frame = (nframes > 1 && P->mode == GLOME_MODE_TILE && !no_interleave) ? (A.total_waves + kQueueChunk - 1) / kQueueChunk : 0u;
+    A.chunks_per_frame = (nframes > 1 && P->mode == GLOME_MODE_TILE) ? (A.total_waves + kQueueChunk - 1) / kQueueChunk : 0u;
     const uint32_t tickets = A.chunks_per_frame ? A.chunks_per_frame * kQueueChunk * (uint32_t)nframes : A.total_waves * (uint32_t)nframes, round = kQueueChunk * kQueueShards;
     A.shard_cap = ((tickets + round - 1) / round) * kQueueChunk;
   }
@@ -1423,9 +1313,6 @@ static int render_impl(glome_scene* s, const glome_camera* cam, const glome_ligh
   const bool bare = !stats && P->mode == GLOME_MODE_TILE && !P->faithful && !P->count_work;
   if (!bare && (rc = reset_counters(ctx))) return rc;
   A.want_counters = (bare || (P->mode == GLOME_MODE_SUBSAMPLE && !stats)) ? 0 : 1;  // nobody reads them without `stats`
-#ifdef GLOME_PROBE
-  if (const char* e = getenv("GLOME_DEBUG_FLAGS")) A.debug_flags = atoi(e);  // (render_loop)
-#endif
   hipEvent_t ev_start = ctx->ev0, ev_stop = ctx->ev1;
   if (A.ntiles > 0 && P->mode == GLOME_MODE_SUBSAMPLE) {
     // scratch: v (5 float planes over the owned pixels) | queue heads, one per 128-byte line, then the dry mask | one
@@ -1439,24 +1326,19 @@ static int render_impl(glome_scene* s, const glome_camera* cam, const glome_ligh
     A.ss_plane = (uint32_t)npx;
     A.blocksize = P->blocksize;
     // Region size by the frames of the launch: what hides a tile's chain of five dependent passes is other frames' tiles
-    // (tools/probe/ss_tune.py, profiles/r02_f_ss_regions.log: one frame alone wants the small regions whatever its tile count)
+    // (profiles/r02_f_ss_regions.log: one frame alone wants the small regions whatever its tile count)
     for (int pass = 1; pass <= 5; pass++) {
       int rw, rh;
       ss_region_shape(pass, nframes >= 8 ? 2 : (nframes >= 3 ? 1 : 0), rw, rh);
       // The generic tier's rays cost fifty times a flat-tier ray and its kernel runs eight waves per CU: parallelism is worth
       // more than shared compaction.  One block per region for a frame alone (GlomeView's default scene: 68.5 -> 37.0 ms), two
-      // blocks in passes 3-5 of a batch (12.1 -> 9.1 ms per frame; tools/probe/ts_variants.sh with GLOME_DEBUG_SS_REGIONS)
+      // blocks in passes 3-5 of a batch (12.1 -> 9.1 ms per frame)
       if (s->dev.tier != 0) { rw = (nframes >= 3 && pass >= 3) ? 2 : 1; rh = 1; }
       // ... and once the interpreter's rays had become three times cheaper (round 3) a launch of twelve or more frames wants larger
       // regions in the later passes: 5.8 -> 5.1 ms per frame with 1x1, 2x1, 2x2, 2x2, 3x3 blocks (a launch of eight alone: 7.1 -> 10.2,
       // so those keep the rule above; profiles/r03_probes/generic_tier_sampler_regions.txt)
       if (s->dev.tier != 0 && nframes >= 12) { static const int8_t W[6] = {0, 1, 2, 2, 2, 3}, H[6] = {0, 1, 1, 2, 2, 3}; rw = W[pass]; rh = H[pass]; }
       A.ss_rw[pass] = (int8_t)rw; A.ss_rh[pass] = (int8_t)rh;
-    }
-    if (const char* e = getenv("GLOME_DEBUG_SS_REGIONS")) {  // "1x5,3x5,5x5,5x5,5x5"
-      int q[10];
-      if (sscanf(e, "%dx%d,%dx%d,%dx%d,%dx%d,%dx%d", q, q + 1, q + 2, q + 3, q + 4, q + 5, q + 6, q + 7, q + 8, q + 9) == 10)
-        for (int pass = 1; pass <= 5; pass++) { A.ss_rw[pass] = (int8_t)q[2 * pass - 2]; A.ss_rh[pass] = (int8_t)q[2 * pass - 1]; }
     }
     HIPCHK(ctx, hipMemsetAsync(A.ss_cnt, 0, ctl_words * sizeof(unsigned int), ctx->stream));
     bool pooled = ctx->timing && (ctx->timing_seen++ % ctx->timing_stride) == 0 && ctx->pool_used + 2 <= (int)ctx->pool.size();

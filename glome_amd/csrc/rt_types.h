@@ -136,8 +136,6 @@ struct DCounters {  // device-side atomics, one block per launch slot
   unsigned int done_pad[31];
   unsigned int done;       // waves of the running launch that have left the queue (the last one resets the heads)
   unsigned int error;      // sticky: set when a device-side limit was hit (stack overflow guard, CSG cap); reset_counters stops short of it
-  unsigned int dbg_pad;
-  unsigned long long dbg[16];  // measurement builds only (GLOME_PKW_STAMPS: the packet walk's wait cycles by kind); glome_ctx_debug_words reads them
 };
 
 struct DRenderArgs {
@@ -172,7 +170,6 @@ struct DRenderArgs {
                               // c + 1 of every frame ...; a chunk = kQueueChunk items of ONE frame), chunks_per_frame = ceil(total_waves / kQueueChunk);
                               // 0: frame after frame
   int32_t want_counters;  // 0: nobody will read the ray / work counters of this launch -- the waves skip the flush
-  int32_t debug_flags;    // GLOME_PROBE builds only (glome_device.hip render_loop)
   DCamera more_cams[kMaxBatchFrames - 1];
 };
 

@@ -27,4 +27,4 @@ for nf in [int(x) for x in os.environ.get('NF', '1,2,4,8').split(',')]:
             assert ctx.lib.glome_render_packed_batch_dev(sc.h, cams, nf, la, len(lights), C.byref(P), C.c_void_p(buf.data_ptr()), H * W, None) == 0
             ctx.synchronize()
         ms = np.zeros(reps, np.float32); n = ctx.lib.glome_ctx_timing_end(ctx.h, ms.ctypes.data_as(L.c_fp), reps)
-        print(json.dumps({"scene": name, "frames_per_launch": nf, "grid_per_cu": per_cu, "interleave": os.environ.get("GLOME_DEBUG_INTERLEAVE", "default"), "launch_ms_median": round(float(np.median(ms[:n])), 4), "ms_per_frame": round(float(np.median(ms[:n])) / nf, 4)}), flush=True)
+        print(json.dumps({"scene": name, "frames_per_launch": nf, "grid_per_cu": per_cu, "launch_ms_median": round(float(np.median(ms[:n])), 4), "ms_per_frame": round(float(np.median(ms[:n])) / nf, 4)}), flush=True)
