@@ -359,4 +359,23 @@ int glome_tiles_layout(const glome_render_params* P, int tile_first, int tile_st
   return (int)t.size();
 }
 
+int64_t glome_items_layout(const glome_render_params* P, int tile_first, int tile_stride, int blocksize_override, int which, int32_t* out, int64_t cap_items) {
+  if (!P || P->width <= 0 || P->height <= 0 || P->blocksize <= 0 || tile_stride <= 0 || tile_first < 0 || blocksize_override < 0) return GLOME_E_INVALID;
+  std::vector<DTile> t; uint32_t total; int64_t px;
+  owned_tiles(P->width, P->height, blocksize_override ? blocksize_override : P->blocksize, tile_first, tile_stride, P->rank0_share_pct, t, total, px);
+  std::vector<DItem> items;
+  if (which) build_item_table(t, total, items);
+  size_t tile = 0;
+  for (uint32_t w = 0; w < total && (int64_t)w < cap_items; w++) {
+    while (tile + 1 < t.size() && t[tile + 1].wave_base <= w) tile++;
+    for (int lane = 0; lane < 64; lane++) {
+      int x = 0, y = 0; size_t off = 0;
+      const bool valid = which ? item_pixel(items[w], t.data(), lane, x, y, off) : tile_item_pixel(t[tile], w - t[tile].wave_base, lane, x, y, off);
+      int32_t* o = out + ((size_t)w * 64 + lane) * 4;
+      o[0] = valid ? 1 : 0; o[1] = valid ? x : 0; o[2] = valid ? y : 0; o[3] = valid ? (int32_t)off : 0;
+    }
+  }
+  return (int64_t)total;
+}
+
 }  // extern "C"

@@ -105,6 +105,24 @@ __global__ void k_kernarg_selftest(DRenderArgs, const DRenderArgs* expect, unsig
   for (size_t i = threadIdx.x; i < sizeof(DRenderArgs); i += blockDim.x) same &= a[i] == b[i] ? 1u : 0u;
   if (!same) atomicAnd(ok, 0u);
 }
+// The lean render loop's pixel coordinates: xc of every column and yc of every row of a width x height frame, made by get_coordsf itself
+// (bit-identical by construction; the host would have to reproduce the device's contraction of q * 2 - 1).  xc depends on the column
+// only and yc on the row only, so the other coordinate is passed as 0.
+__global__ void k_coord_tables(int width, int height, float* xc_tab, float* yc_tab) {
+  const int i = (int)(blockIdx.x * blockDim.x + threadIdx.x);
+  float xc, yc;
+  if (i < width) { get_coordsf(width, height, (float)i, 0.0f, xc, yc); xc_tab[i] = xc; }
+  if (i < height) { get_coordsf(width, height, 0.0f, (float)i, xc, yc); yc_tab[i] = yc; }
+}
+// what the tables are checked against (glome_ctx_coord_tables): get_coordsf of whole pixels (i mod width, i mod height), as a render loop calls it
+__global__ void k_coords_direct(int width, int height, float* xc_out, float* yc_out) {
+  const int i = (int)(blockIdx.x * blockDim.x + threadIdx.x);
+  if (i >= width && i >= height) return;
+  float xc, yc;
+  get_coordsf(width, height, (float)(i % width), (float)(i % height), xc, yc);
+  if (i < width) xc_out[i] = xc;
+  if (i < height) yc_out[i] = yc;
+}
 #endif
 // PKMIN: lanes that must wait before the packet service walks (rt_generic.hpp vm_run).  COUNT: bih_nodes / prim_tests are counted -- asked for by
 // glome_render_params.count_work; the instances that do not count are 4 % (renderTile) and 2 % (sampler) faster on GlomeView's default scene
@@ -178,31 +196,13 @@ __device__ __forceinline__ void flush_counters(DCounters* c, const Cnt& cnt, uns
   }
 }
 
-// work item w -> tile + 64 pixels.  A tile is cut into 8x8 blocks (coherent rays per wave); the pixels left over on
-// the right and bottom edges (65 = 8*8 + 1) are packed 64 at a time, so lanes are not wasted on partial blocks.
+// work item w -> tile + 64 pixels (tiles.hpp tile_item_pixel).  The adaptive kernels and the round-3 loop; the lean loop reads the
+// plan's item table instead (DItem).
 __device__ __forceinline__ bool work_to_pixel(const DRenderArgs& A, uint32_t w, int lane, int& px, int& py, size_t& dense_off) {
   int lo = (int)A.tile_lut[w >> 6];  // the tile of item (w & ~63); w's own is that one or one of the next few
   while (lo + 1 < A.ntiles && A.tiles[lo + 1].wave_base <= w) lo++;
   DTile t = A.tiles[lo];
-  uint32_t j = w - t.wave_base;
-  uint32_t nbx = t.w / kBlockW, nby = t.h / kBlockH, nblk = nbx * nby;
-  int lx, ly;
-  if (j < nblk) {
-    lx = (j % nbx) * kBlockW + (lane % kBlockW);
-    ly = (j / nbx) * kBlockH + (lane / kBlockW);
-  } else {
-    uint32_t i = (j - nblk) * 64 + lane;
-    uint32_t rw = t.w - kBlockW * nbx, rcount = rw * t.h;
-    if (i < rcount) { lx = kBlockW * nbx + i % rw; ly = i / rw; }
-    else {
-      uint32_t i2 = i - rcount, bw = kBlockW * nbx, bh = t.h - kBlockH * nby;
-      if (i2 >= bw * bh) return false;
-      lx = i2 % bw; ly = kBlockH * nby + i2 / bw;
-    }
-  }
-  px = t.x + lx; py = t.y + ly;
-  dense_off = (size_t)t.pix_base + (size_t)ly * t.w + lx;
-  return true;
+  return tile_item_pixel(t, w - t.wave_base, lane, px, py, dense_off);
 }
 
 // The work queue of a render launch.  One ticket counter cannot feed the GPU: a returning atomic on one word completes
@@ -220,12 +220,19 @@ constexpr uint32_t kNoTicket = 0xffffffffu;
 // One ticket per atomic.  (Several per atomic while a head is far from empty -- guided self-scheduling -- was measured in round 3:
 // batches of 4 or 8 won 0-7 % pipelined and lost 15-30 % on a launch alone, whose last items then run on too few waves.)
 // A ticket the atomic returns is handed out at the top of the loop, from inext / cur: returning it on the spot frees two scalar
-// registers for the kernel's lifetime and moves the register allocation of every render kernel (tools/kernel_mix.py; the
-// flagship's SGPR spills 49 -> 45, a Mesh instance 5 -> 4 waves per SIMD), so that change waits for a measurement of its own.
+// registers for the kernel's lifetime and moves the register allocation of every render kernel (tools/kernel_mix.py; a Mesh
+// instance 5 -> 4 waves per SIMD), so only the lean loop does that (take_direct).
 struct TicketQueue {
   uint32_t shard, dry;
   uint32_t inext = 0, left = 0, cur = 0;  // a ticket in hand: its queue index, 1 while it is unused, the head it came from (lane 0's)
   __device__ __forceinline__ TicketQueue() : shard(blockIdx.x % kQueueShards), dry(0) {}
+  // what both takes share: ticket i of head h -> its place in the launch's item order, and the marking of a head found dry
+  static __device__ __forceinline__ uint32_t ticket_item(uint32_t i, uint32_t h) { return ((i / kQueueChunk) * kQueueShards + h) * kQueueChunk + (i % kQueueChunk); }
+  __device__ __forceinline__ void mark_dry(const DRenderArgs& A) {
+    uint32_t d = 0;
+    if (LaneStack::lane() == 0) { atomicOr(&A.counters->dry, 1u << shard); d = __hip_atomic_load(&A.counters->dry, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+    dry |= (1u << shard) | uni(d);
+  }
   // Every lane of the wave makes the call; the state is wave-uniform (scalar registers) and only the atomics themselves are lane 0's.
   // (Until round 3 the whole take ran on lane 0 under a branch: its six state words then lived in vector registers for the kernel's lifetime.)
   __device__ __forceinline__ uint32_t take(const DRenderArgs& A) {
@@ -234,7 +241,7 @@ struct TicketQueue {
       if (left) {
         left--;
         const uint32_t i = inext++;
-        if (i < A.shard_cap) return ((i / kQueueChunk) * kQueueShards + cur) * kQueueChunk + (i % kQueueChunk);
+        if (i < A.shard_cap) return ticket_item(i, cur);
         left = 0;
       }
       if (dry == kAll) return kNoTicket;
@@ -243,9 +250,23 @@ struct TicketQueue {
         if (LaneStack::lane() == 0) i = atomicAdd(&A.counters->heads[shard * kQueueHeadStride], 1u);
         i = uni(i);
         if (i < A.shard_cap) { inext = i; left = 1; cur = shard; continue; }
-        uint32_t d = 0;
-        if (LaneStack::lane() == 0) { atomicOr(&A.counters->dry, 1u << shard); d = __hip_atomic_load(&A.counters->dry, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-        dry |= (1u << shard) | uni(d);
+        mark_dry(A);
+      }
+      shard = (shard + 1) % kQueueShards;
+    }
+  }
+  // The lean loop's take: the ticket the atomic returns is handed out on the spot (inext / left / cur are then dead: two scalar registers
+  // fewer through both walks of the flagship instance).
+  __device__ __forceinline__ uint32_t take_direct(const DRenderArgs& A) {
+    constexpr uint32_t kAll = (1u << kQueueShards) - 1u;
+    for (;;) {
+      if (dry == kAll) return kNoTicket;
+      if (!((dry >> shard) & 1u)) {
+        uint32_t i = 0;
+        if (LaneStack::lane() == 0) i = atomicAdd(&A.counters->heads[shard * kQueueHeadStride], 1u);
+        i = uni(i);
+        if (i < A.shard_cap) return ticket_item(i, shard);
+        mark_dry(A);
       }
       shard = (shard + 1) % kQueueShards;
     }
@@ -265,7 +286,10 @@ struct TicketQueue {
 // a scalar, the pixel made a second time after the trace.  They are worth 8-10 % there and COST the other instances, whose C++ walks
 // then re-read table pointers inside their loops: the 1M-triangle Mesh 0.797 -> 0.872 ms with all three, 0.84 with any one of them off
 // (profiles/r04_probes/mesh_regress_ab.txt); so the other flat-tier instances keep round 3's loop.
-template <bool LEAN, class TIER>
+// ITEMS (the flagship instance only): round 5's item path -- the plan's item table, the coordinate tables, the multiplier split, the scalar
+// camera and the ticket returned by the atomic.  The interpreter's kernel keeps round 4's lean loop: TS measured 0.2 % slower with the
+// item path (2.3633 / 2.3649 against the parent's 2.3585-2.3594 ms, profiles/r05_probes/item_path_ab.txt).
+template <bool LEAN, bool ITEMS, class TIER>
 __device__ __forceinline__ void render_loop(const DRenderArgs& A_, TIER& Tk) {
   TicketQueue Q;
   // The launch's arguments are read where the dispatch put them (the kernarg segment: scalar loads), through a pointer the compiler
@@ -278,7 +302,8 @@ __device__ __forceinline__ void render_loop(const DRenderArgs& A_, TIER& Tk) {
     const DRenderArgs& A = LEAN ? *(const DRenderArgs*)ap_ : A_;
     TIER T = Tk.rebound(A);
     uint32_t w = kNoTicket;
-    if constexpr (LEAN) w = Q.take(A);  // a SCALAR: the frame, the tile and the camera the ticket names are then scalar loads, not a lane's
+    if constexpr (ITEMS) w = Q.take_direct(A);  // a SCALAR: the frame, the item and the camera the ticket names are then scalar loads, not a lane's
+    else if constexpr (LEAN) w = Q.take(A);
     else { if (LaneStack::lane() == 0) w = Q.take(A); w = __shfl(w, 0, 64); }
     if (w == kNoTicket) break;
     uint32_t frame;  // wave-uniform
@@ -287,27 +312,51 @@ __device__ __forceinline__ void render_loop(const DRenderArgs& A_, TIER& Tk) {
       // same part of the tree), and what a launch ends with is the last chunks of ALL its frames, not the whole of its last frame
       const uint32_t g = w / kQueueChunk, nf = (uint32_t)A.nframes;
       if (g >= A.chunks_per_frame * nf) continue;  // padding of the last round of chunks
-      frame = g % nf;
-      w = (g / nf) * kQueueChunk + (w % kQueueChunk);
+      // (lean: the quotient by the launch's multiplier -- s_mul_hi_u32 -- instead of two emulated 32-bit divisions of ~25 instructions each)
+      const uint32_t q = ITEMS ? __umulhi(g, A.nframes_rcp) : g / nf;
+      frame = g - q * nf;
+      w = q * kQueueChunk + (w % kQueueChunk);
       if (w >= A.total_waves) continue;            // padding of a frame's last chunk
     } else {
       if (w >= A.total_waves * (uint32_t)A.nframes) continue;  // padding of the last round of chunks
-      frame = w / A.total_waves;
-      w -= frame * A.total_waves;
+      frame = 0;
+      if (!ITEMS || w >= A.total_waves) {  // (a launch of one frame never divides)
+        frame = w / A.total_waves;
+        w -= frame * A.total_waves;
+      }
     }
     int px = 0, py = 0;
     size_t dense_off = 0;
-    bool valid = work_to_pixel(A, w, (int)LaneStack::lane(), px, py, dense_off);  // lanes past the end of a leftover strip idle along
+    bool valid;
     float xc, yc;
-    get_coordsf(A.width, A.height, (float)px, (float)py, xc, yc);
-    Ray ray = primary_ray(frame == 0 ? A.cam : A.more_cams[frame - 1], xc, yc);
+    DItem it{};  // the item's entry of the plan's table, four scalars
+    if constexpr (ITEMS) {
+      it = ld_item_u(A.items, w);
+      valid = item_pixel(it, A.tiles, (int)LaneStack::lane(), px, py, dense_off);  // lanes past the end of a leftover strip idle along
+      // get_coordsf's values from the two tables k_coord_tables filled with it (three IEEE divisions per lane per item otherwise)
+      xc = ldf(A.xc_tab, valid ? (uint32_t)px : 0u); yc = ldf(A.yc_tab, valid ? (uint32_t)py : 0u);
+    } else {
+      valid = work_to_pixel(A, w, (int)LaneStack::lane(), px, py, dense_off);
+      get_coordsf(A.width, A.height, (float)px, (float)py, xc, yc);
+    }
+    Ray ray;
+    if constexpr (ITEMS) {  // the frame's camera: twelve scalars out of the argument segment
+      const uint32_t cam_off = frame == 0 ? (uint32_t)offsetof(DRenderArgs, cam) : (uint32_t)offsetof(DRenderArgs, more_cams) + (frame - 1) * (uint32_t)sizeof(DCamera);
+      ray = primary_ray(ld_camera_u(ap_, cam_off), xc, yc);
+    }
+    else ray = primary_ray(frame == 0 ? A.cam : A.more_cams[frame - 1], xc, yc);
     count_wave(T.cnt.primary, T.cnt.w_primary, valid);
     HitG h;
     CA c = trace_primary(T, ray, kInf, A.maxdepth, valid, &h);  // Trace.trace lights shader sld ray infinity maxdepth (Glome.hs:33)
     Tk.absorb(T);  // (counters and the error flag back into the kernel's tier)
     if (!valid) continue;
-    // the pixel once more (rather than three registers carried, spilled, through both walks): the item is a scalar, the lane a v_mbcnt
-    if constexpr (LEAN) { px = 0; py = 0; dense_off = 0; (void)work_to_pixel(A, w, (int)LaneStack::lane(), px, py, dense_off); }
+    // the pixel once more (rather than three registers carried, spilled, through both walks): from the entry's four scalars, which the
+    // compiler must take for new values here, or it would keep the first decode's lanes alive instead
+    if constexpr (ITEMS) {
+      asm volatile("" : "+s"(it.x), "+s"(it.y), "+s"(it.off), "+s"(it.pitch));
+      px = 0; py = 0; dense_off = 0;
+      (void)item_pixel(it, A.tiles, (int)LaneStack::lane(), px, py, dense_off);
+    } else if constexpr (LEAN) { px = 0; py = 0; dense_off = 0; (void)work_to_pixel(A, w, (int)LaneStack::lane(), px, py, dense_off); }
     float depth = h.hit ? h.t : kInf;      // ridepth
     float r = c.r;
     if (A.fog) r = r + (depth / 400);      // renderTile's debug fog (Glome.hs:174, Q20)
@@ -329,7 +378,7 @@ template <bool FAITHFUL, bool COUNT, bool FULL, int CLS, int LB = 1, bool TWO_RO
 __global__ void __launch_bounds__(64, LB) k_render_flat(DRenderArgs A, int stack_cap, uint32_t* ovf, int ovf_cap) {
   extern __shared__ uint32_t lds[];
   FlatTier<FAITHFUL, COUNT, FULL, CLS> T{A.S, A.lights, A.nlights, lane_stack<TWO_ROWS>(lds, stack_cap, ovf, ovf_cap), Cnt()};
-  render_loop<TWO_ROWS>(A, T);
+  render_loop<TWO_ROWS, TWO_ROWS>(A, T);
   if (A.want_counters) flush_counters(A.counters, T.cnt, T.err);
   else if ((CLS & (CLS_CSG | CLS_MESH)) && __builtin_amdgcn_ballot_w64(T.err != 0) && (threadIdx.x & 63) == 0) atomicOr(&A.counters->error, 1u);
 }
@@ -345,7 +394,7 @@ __global__ void __launch_bounds__(64, GLOME_GENERIC_LB) k_render_generic(DRender
   // registers), and with refilling the lanes fall out of step, every closest-hit call then runs for a part of the wave, and the frame took 5.8 ms
   // against 4.3: what keeps the lanes idle -- 28 % of the vector lane slots are used -- is the interpreter's own divergence
   // inside a call, not pixels of unequal cost.)
-  render_loop<true>(A, T);  // (the interpreter, short of registers like the flagship, measures better with the lean loop: TS 2.70 against 2.74 ms)
+  render_loop<true, false>(A, T);  // (the interpreter, short of registers like the flagship, measures better with the lean loop: TS 2.70 against 2.74 ms)
   if (A.want_counters) flush_counters(A.counters, T.cnt, T.err);
   else if (__builtin_amdgcn_ballot_w64(T.err != 0) && (threadIdx.x & 63) == 0) atomicOr(&A.counters->error, 1u);
 }
@@ -789,8 +838,10 @@ struct glome_ctx {
   int grid_per_cu = 0;  // 0: persistent grids sized by work (tuned for several launches in flight); > 0: this many waves per CU, resources permitting
   // tile tables cached per (w, h, blocksize, first, stride)
   // lut[w >> 6] = the tile that holds work item (w & ~63): the kernel's item -> tile lookup is one table read and a step or two
-  struct TileTable { std::vector<DTile> host; DTile* dev = nullptr; uint32_t* lut = nullptr; uint32_t total_waves = 0; int64_t pixels = 0; };
+  // items: the plan's item table (DItem: one entry per work item, read by the lean render loop)
+  struct TileTable { std::vector<DTile> host; DTile* dev = nullptr; uint32_t* lut = nullptr; DItem* items = nullptr; uint32_t total_waves = 0; int64_t pixels = 0; };
   std::map<std::vector<int>, TileTable> tile_cache;
+  std::map<std::pair<int, int>, float*> coord_cache;  // (width, height) -> xc[width] then yc[height] (k_coord_tables)
 };
 struct glome_scene {
   glome_ctx* ctx = nullptr;
@@ -838,9 +889,47 @@ static int get_tiles(glome_ctx* ctx, const glome_render_params* P, int first, in
     }
     HIPCHK(ctx, hipMalloc((void**)&tt.lut, lut.size() * sizeof(uint32_t)));
     HIPCHK(ctx, hipMemcpy(tt.lut, lut.data(), lut.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+    std::vector<DItem> items;
+    build_item_table(tt.host, tt.total_waves, items);
+    HIPCHK(ctx, hipMalloc((void**)&tt.items, std::max<size_t>(1, items.size()) * sizeof(DItem)));
+    if (!items.empty()) HIPCHK(ctx, hipMemcpy(tt.items, items.data(), items.size() * sizeof(DItem), hipMemcpyHostToDevice));
     it = ctx->tile_cache.emplace(key, std::move(tt)).first;
   }
   *out = &it->second;
+  return 0;
+}
+// xc[width] | yc[height] of a frame size, filled once per context (and complete before this returns: the slots launch on streams of their own)
+static int get_coord_tables(glome_ctx* ctx, int width, int height, float** out) {
+  auto it = ctx->coord_cache.find({width, height});
+  if (it == ctx->coord_cache.end()) {
+    float* d = nullptr;
+    HIPCHK(ctx, hipMalloc((void**)&d, ((size_t)width + (size_t)height) * sizeof(float)));
+    const int n = std::max(width, height);
+    hipLaunchKernelGGL(k_coord_tables, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, width, height, d, d + width);
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+    if (e != hipSuccess) { (void)hipFree(d); ctx->err = std::string("k_coord_tables: ") + hipGetErrorString(e); return GLOME_E_HIP; }
+    it = ctx->coord_cache.emplace(std::make_pair(width, height), d).first;
+  }
+  *out = it->second;
+  return 0;
+}
+int glome_ctx_coord_tables(glome_ctx* ctx, int width, int height, float* xc, float* yc, int direct) {
+  if (!ctx || width <= 0 || height <= 0 || !xc || !yc || (int64_t)width * height > (1ll << 30)) return GLOME_E_INVALID;
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  float* d = nullptr;
+  if (direct) {
+    HIPCHK(ctx, hipMalloc((void**)&d, ((size_t)width + (size_t)height) * sizeof(float)));
+    const int n = std::max(width, height);
+    hipLaunchKernelGGL(k_coords_direct, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, width, height, d, d + width);
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+    if (e != hipSuccess) { (void)hipFree(d); ctx->err = std::string("k_coords_direct: ") + hipGetErrorString(e); return GLOME_E_HIP; }
+  } else if (int rc = get_coord_tables(ctx, width, height, &d)) return rc;
+  hipError_t e = hipMemcpy(xc, d, (size_t)width * sizeof(float), hipMemcpyDeviceToHost);
+  if (e == hipSuccess) e = hipMemcpy(yc, d + width, (size_t)height * sizeof(float), hipMemcpyDeviceToHost);
+  if (direct) (void)hipFree(d);
+  if (e != hipSuccess) { ctx->err = std::string("hipMemcpy: ") + hipGetErrorString(e); return GLOME_E_HIP; }
   return 0;
 }
 
@@ -907,7 +996,8 @@ glome_ctx* glome_ctx_create(int device_ordinal) {
 void glome_ctx_destroy(glome_ctx* c) {
   if (!c) return;
   (void)hipSetDevice(c->device);
-  for (auto& kv : c->tile_cache) { if (kv.second.dev) (void)hipFree(kv.second.dev); if (kv.second.lut) (void)hipFree(kv.second.lut); }
+  for (auto& kv : c->tile_cache) { if (kv.second.dev) (void)hipFree(kv.second.dev); if (kv.second.lut) (void)hipFree(kv.second.lut); if (kv.second.items) (void)hipFree(kv.second.items); }
+  for (auto& kv : c->coord_cache) (void)hipFree(kv.second);
   for (auto& sl : c->slots) {
     if (sl.d_counters) (void)hipFree(sl.d_counters);
     if (sl.d_ovf) (void)hipFree(sl.d_ovf);
@@ -1300,7 +1390,13 @@ static int render_impl(glome_scene* s, const glome_camera* cam, const glome_ligh
   }
   A.nlights = nlights; A.width = P->width; A.height = P->height; A.fog = P->fog; A.maxdepth = P->maxdepth;
   memcpy(A.thresholds, P->thresholds, 16);
-  A.tiles = tt->dev; A.tile_lut = tt->lut; A.ntiles = (int)tt->host.size(); A.total_waves = tt->total_waves;
+  A.tiles = tt->dev; A.tile_lut = tt->lut; A.items = tt->items; A.ntiles = (int)tt->host.size(); A.total_waves = tt->total_waves;
+  {
+    float* ct = nullptr;
+    if ((rc = get_coord_tables(ctx, P->width, P->height, &ct))) return rc;
+    A.xc_tab = ct; A.yc_tab = ct + P->width;
+  }
+  A.nframes_rcp = nframes > 1 ? (uint32_t)((1ull << 32) / (uint64_t)nframes) + 1u : 0u;
   {  // tickets per queue head: the launch's chunks dealt round-robin over the heads, the last round padded
     A.chunks_per_frame = (nframes > 1 && P->mode == GLOME_MODE_TILE) ? (A.total_waves + kQueueChunk - 1) / kQueueChunk : 0u;
     const uint32_t tickets = A.chunks_per_frame ? A.chunks_per_frame * kQueueChunk * (uint32_t)nframes : A.total_waves * (uint32_t)nframes, round = kQueueChunk * kQueueShards;

@@ -69,9 +69,11 @@ struct Ray { V3 o, d; };
 template <class T> GD const T __attribute__((address_space(1)))* as_global(const T* p) { return (const T __attribute__((address_space(1)))*)(uintptr_t)p; }
 GD F4 ld4(const F4* p, uint32_t i) { return as_global(p)[i]; }
 GD U4 ldu4(const U4* p, uint32_t i) { return as_global(p)[i]; }
+GD float ldf(const float* p, uint32_t i) { return as_global(p)[i]; }
 #else
 GD F4 ld4(const F4* p, uint32_t i) { return p[i]; }
 GD U4 ldu4(const U4* p, uint32_t i) { return p[i]; }
+GD float ldf(const float* p, uint32_t i) { return p[i]; }
 #endif
 
 // ------------------------------------------------------------------ wave-level helpers
@@ -105,6 +107,23 @@ GD void ld_tri_u(const F4* p, uint32_t tri, F4& q0, F4& q1, F4& q2) {
   cf32x4* q = (cf32x4*)(b + (uint32_t)(uni(tri) * 48u));
   f32x4 a = q[0], c = q[1], e = q[2];
   q0.x = a.x; q0.y = a.y; q0.z = a.z; q0.w = a.w; q1.x = c.x; q1.y = c.y; q1.z = c.z; q1.w = c.w; q2.x = e.x; q2.y = e.y; q2.z = e.z; q2.w = e.w;
+}
+// Wave-uniform reads of what a launch never writes (the plan's item table, the cameras in the argument segment): the same idiom,
+// one s_load_dwordx4 per 16 bytes -- no vector load + s_waitcnt vmcnt(0) + v_readfirstlane round trip.
+typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
+GD DItem ld_item_u(const DItem* p, uint32_t i) {  // (a frame is at most 2^30 pixels = 2^24 items: the byte offset fits 32 bits)
+  const char __attribute__((address_space(4)))* b = (const char __attribute__((address_space(4)))*)(uintptr_t)p;
+  u32x4 v = *(const u32x4 __attribute__((address_space(4)))*)(b + (uint32_t)(uni(i) << 4));
+  DItem r; r.x = v.x; r.y = v.y; r.off = v.z; r.pitch = v.w; return r;
+}
+typedef float f32x4_a4 __attribute__((ext_vector_type(4), aligned(4)));  // (the cameras sit at 4-byte aligned offsets of the argument segment; s_load_dwordx4 needs no more)
+GD DCamera ld_camera_u(const void __attribute__((address_space(4)))* base, uint32_t byte_off) {  // both wave-uniform
+  const f32x4_a4 __attribute__((address_space(4)))* q = (const f32x4_a4 __attribute__((address_space(4)))*)((const char __attribute__((address_space(4)))*)base + byte_off);
+  f32x4 a = q[0], b = q[1], c = q[2];
+  DCamera r;
+  r.pos[0] = a.x; r.pos[1] = a.y; r.pos[2] = a.z; r.fwd[0] = a.w; r.fwd[1] = b.x; r.fwd[2] = b.y;
+  r.up[0] = b.z; r.up[1] = b.w; r.up[2] = c.x; r.right[0] = c.y; r.right[1] = c.z; r.right[2] = c.w;
+  return r;
 }
 #endif
 

@@ -125,6 +125,12 @@ struct DTile { int32_t x, y, w, h; uint32_t wave_base; uint32_t pix_base; };  //
 #define GLOME_BLOCK_W 8
 #endif
 constexpr int kBlockW = GLOME_BLOCK_W, kBlockH = 64 / GLOME_BLOCK_W;
+// One entry per 64-pixel work item of a plan (tiles.hpp build_item_table): the lean render loop reads it with one scalar 16-byte load
+// where the item -> pixel mapping used to go tile_lut -> tiles scan -> DTile -> two divisions.
+//   a full block:  lane l is pixel (x + l % kBlockW, y + l / kBlockW), dense offset off + (l / kBlockW) * pitch + l % kBlockW
+//   a leftover-strip item (pitch == kItemStrip): x = its tile, y = the item's index inside that tile; the lanes take the strip mapping from the DTile
+struct DItem { uint32_t x, y, off, pitch; };
+constexpr uint32_t kItemStrip = 0xffffffffu;
 constexpr uint32_t kQueueShards = 8;       // heads of a render launch's work queue (one per XCD)
 constexpr uint32_t kQueueHeadStride = 32;  // words between heads: every head on its own 128-byte line
 constexpr uint32_t kQueueChunk = 64;       // consecutive tickets that belong to one head (one 64x64 work tile of 8x8 blocks)
@@ -149,6 +155,9 @@ struct DRenderArgs {
   float thresholds[4];
   const DTile* tiles;  // owned tiles
   const uint32_t* tile_lut;  // tile of every 64th work item
+  const DItem* items;        // [total_waves] the plan's item table
+  const float* xc_tab;       // [width] get_coordsf's xc of every pixel column, [height] its yc of every row (filled once per frame size
+  const float* yc_tab;       // and context by k_coord_tables, which calls get_coordsf itself)
   int32_t ntiles;
   uint32_t total_waves;
   uint32_t shard_cap;   // tickets per queue head of this launch (whole chunks; the last round of chunks may be padding)
@@ -169,8 +178,11 @@ struct DRenderArgs {
   uint32_t chunks_per_frame;  // > 0: the frames of the launch are interleaved in the queue chunk by chunk (chunk c of every frame, then chunk
                               // c + 1 of every frame ...; a chunk = kQueueChunk items of ONE frame), chunks_per_frame = ceil(total_waves / kQueueChunk);
                               // 0: frame after frame
+  uint32_t nframes_rcp;   // m = floor(2^32 / nframes) + 1 (nframes >= 2): chunk / nframes = mulhi(chunk, m).  m * nframes = 2^32 + e with 0 < e <= nframes,
+                          // so the quotient is exact while chunk * e < 2^32, that is for chunk < 2^32 / nframes; a chunk index is < 2^32 / kQueueChunk (static_assert below)
   int32_t want_counters;  // 0: nobody will read the ray / work counters of this launch -- the waves skip the flush
   DCamera more_cams[kMaxBatchFrames - 1];
 };
+static_assert(kMaxBatchFrames <= (int)kQueueChunk, "DRenderArgs::nframes_rcp: chunk indices (< 2^32 / kQueueChunk) must stay below 2^32 / nframes");
 
 }  // namespace glome

@@ -6,6 +6,12 @@
 
 #include "rt_types.h"
 
+#if defined(__HIPCC__)
+#define GLOME_HD __host__ __device__ inline
+#else
+#define GLOME_HD inline
+#endif
+
 namespace glome {
 
 inline std::vector<std::pair<int, int>> chunk(int size, int blocksize) {  // Glome.hs:371-377: the last chunk is the remainder
@@ -67,6 +73,52 @@ inline void owned_tiles(int width, int height, int blocksize, int first, int str
       }
       k++;
     }
+}
+
+// item j of tile t -> its 64 pixels.  A tile is cut into 8x8 blocks (coherent rays per wave); the pixels left over on
+// the right and bottom edges (65 = 8*8 + 1) are packed 64 at a time, so lanes are not wasted on partial blocks.
+GLOME_HD bool tile_item_pixel(const DTile& t, uint32_t j, int lane, int& px, int& py, size_t& dense_off) {
+  uint32_t nbx = t.w / kBlockW, nby = t.h / kBlockH, nblk = nbx * nby;
+  int lx, ly;
+  if (j < nblk) {
+    lx = (j % nbx) * kBlockW + (lane % kBlockW);
+    ly = (j / nbx) * kBlockH + (lane / kBlockW);
+  } else {
+    uint32_t i = (j - nblk) * 64 + lane;
+    uint32_t rw = t.w - kBlockW * nbx, rcount = rw * t.h;
+    if (i < rcount) { lx = kBlockW * nbx + i % rw; ly = i / rw; }
+    else {
+      uint32_t i2 = i - rcount, bw = kBlockW * nbx, bh = t.h - kBlockH * nby;
+      if (i2 >= bw * bh) return false;
+      lx = i2 % bw; ly = kBlockH * nby + i2 / bw;
+    }
+  }
+  px = t.x + lx; py = t.y + ly;
+  dense_off = (size_t)t.pix_base + (size_t)ly * t.w + lx;
+  return true;
+}
+// The item table of a plan: entry w is work item w's block, decoded once on the host (DItem, rt_types.h).
+inline void build_item_table(const std::vector<DTile>& tiles, uint32_t total_waves, std::vector<DItem>& out) {
+  out.clear();
+  out.reserve(total_waves);
+  for (size_t k = 0; k < tiles.size(); k++) {
+    const DTile& t = tiles[k];
+    const uint32_t nbx = t.w / kBlockW, nby = t.h / kBlockH, nblk = nbx * nby, n = tile_waves(t.w, t.h);
+    for (uint32_t j = 0; j < n; j++) {
+      if (j < nblk) {
+        const uint32_t lx = (j % nbx) * kBlockW, ly = (j / nbx) * kBlockH;
+        out.push_back(DItem{(uint32_t)t.x + lx, (uint32_t)t.y + ly, t.pix_base + ly * (uint32_t)t.w + lx, (uint32_t)t.w});
+      } else out.push_back(DItem{(uint32_t)k, j, 0u, kItemStrip});
+    }
+  }
+}
+// an entry of the item table -> the lane's pixel: what tile_item_pixel gives for the item the entry was made from
+GLOME_HD bool item_pixel(const DItem& it, const DTile* tiles, int lane, int& px, int& py, size_t& dense_off) {
+  if (it.pitch == kItemStrip) return tile_item_pixel(tiles[it.x], it.y, lane, px, py, dense_off);
+  const uint32_t lx = (uint32_t)lane % kBlockW, ly = (uint32_t)lane / kBlockW;
+  px = (int)(it.x + lx); py = (int)(it.y + ly);
+  dense_off = (size_t)it.off + (size_t)(ly * it.pitch) + (size_t)lx;
+  return true;
 }
 
 }  // namespace glome

@@ -319,6 +319,13 @@ int64_t glome_tiles_payload_floats(const glome_render_params*, int tile_first, i
 /* Host-only: the tiles owned by (tile_first, tile_stride) in renderTiles' order (Glome.hs:382-384).  Writes 5 ints per
  * tile (x, y, w, h, pixel offset of the tile inside the dense payload) and returns the tile count. */
 int glome_tiles_layout(const glome_render_params*, int tile_first, int tile_stride, int32_t* xywh_base, int cap);
+/* Host-only: the pixels of the 64-lane work items of that plan (blocksize_override > 0: tiles of that edge instead of the params'), 4 ints
+ * per lane: valid, x, y, offset inside the dense payload.  which 0: by the tile arithmetic (work_to_pixel); 1: by the plan's item table, as
+ * the lean render loop decodes it.  Writes up to cap_items items and returns the item count. */
+int64_t glome_items_layout(const glome_render_params*, int tile_first, int tile_stride, int blocksize_override, int which, int32_t* out, int64_t cap_items);
+/* The lean render loop's pixel-coordinate tables of a frame size (xc[width], yc[height]; made on the device, once per context), or with
+ * direct != 0 the same values evaluated per pixel by the coordinate function itself. */
+int glome_ctx_coord_tables(glome_ctx*, int width, int height, float* xc, float* yc, int direct);
 int glome_tiles_pack_dev(glome_ctx*, const glome_render_params*, const float* rgbad_dev, float* payload_dev);
 int glome_tiles_blit_dev(glome_ctx*, const glome_render_params*, int tile_first, int tile_stride,
                          const float* payload_dev, float* rgbad_dev, uint32_t* packed_dev);
