@@ -1,5 +1,5 @@
 // bih_build_device.hpp -- `bih` (Bih.hs:211-324) built on the GPU: the same tree as Graph::bih / the reference's
-// build_rec, node for node and bit for bit, level by level instead of by recursion.  Included by glome_device.hip.
+// build_rec, node for node and bit for bit, level by level instead of by recursion.  Included by runtime.hip.
 //
 // build_rec looks at a node's objects three times: to sort them into four candidate partitions (bbox centre below the
 // node's midpoint on x / y / z, and big-vs-small by surface area), to take each candidate's split planes (max of the

@@ -1,5 +1,6 @@
 // capi_host.cpp -- host half of the C ABI (include/glome_hip.h): the scene builder (one call per glome
-// constructor), the transform helpers and the host-side inspection calls.  No HIP here.
+// constructor), the transform helpers and the host-side inspection calls (among them the choice of a kernel instance, instances.hpp).
+// No HIP here.
 #include <algorithm>
 #include <array>
 #include <cstdlib>
@@ -376,6 +377,38 @@ int64_t glome_items_layout(const glome_render_params* P, int tile_first, int til
     }
   }
   return (int64_t)total;
+}
+
+// ---- the choice of a kernel instance, seen from the host (instances.hpp) ----
+static_assert(all_choices_listed(std::make_integer_sequence<int, 128>{}), "a choice rule names a kernel instance that no X-list holds");
+
+int64_t glome_kernel_choice(int64_t n, const int64_t* in, int32_t* out) {
+  if (n < 0 || (n > 0 && (!in || !out))) return GLOME_E_INVALID;
+  for (int64_t i = 0; i < n; i++) {
+    const int64_t* v = in + 14 * i;
+    SceneTraits s;
+    s.tier = (int)v[0]; s.cls_mask = (int)v[1]; s.has_secondary_mats = v[2] != 0; s.has_nested_mats = v[3] != 0; s.has_refract = v[4] != 0; s.pk_all = v[5] != 0;
+    s.stack_cap = (int)v[6]; s.n_bih_nodes = v[7];
+    if (v[8] != GLOME_MODE_TILE && v[8] != GLOME_MODE_SUBSAMPLE) return GLOME_E_INVALID;
+    const bool sampler = v[8] == GLOME_MODE_SUBSAMPLE;
+    const Choice c = sampler ? choose_sampler(s, v[9] != 0, v[10] != 0, (int)v[11], (int)v[12]) : choose_render(s, v[9] != 0, v[10] != 0, (int)v[11], (int)v[12], (uint32_t)v[13]);
+    int32_t* o = out + 4 * i;
+    o[0] = sampler ? KIND_SAMPLER : KIND_RENDER; o[1] = c.generic ? (c.generic_counts ? -1 : -2) : c.key; o[2] = c.two_rows ? 1 : 0; o[3] = waves_per_cu(c);
+  }
+  return n;
+}
+int glome_sb_scene_traits(glome_sb* sb, int32_t root, int64_t* out) {
+  if (!sb || !out) return GLOME_E_INVALID;
+  try {
+    FlatScene F;
+    Flattener fl(sb_graph(sb), F);
+    fl.run(root);
+    const CommitRules R = commit_rules(sb_graph(sb), F);
+    const SceneTraits& t = R.traits;
+    const int64_t v[11] = {t.tier, t.cls_mask, t.has_secondary_mats, t.has_nested_mats, t.has_refract, t.pk_all, t.stack_cap, t.n_bih_nodes, R.caps.ovf_cap, R.caps.pk_generic_cap, t.n_mesh_nodes};
+    memcpy(out, v, sizeof(v));
+    return 0;
+  } catch (const std::exception& e) { sb->err = e.what(); return GLOME_E_INVALID; }
 }
 
 }  // extern "C"

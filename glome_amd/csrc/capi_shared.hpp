@@ -1,11 +1,31 @@
-// capi_shared.hpp -- what the host half (capi_host.cpp) and the device half (glome_device.hip) of the C ABI share.
+// capi_shared.hpp -- what the host half (capi_host.cpp) and the device half (runtime.hip) of the C ABI share: the scene builder's
+// handle and what a commit derives from a flattened scene for the choice of kernel instances.
 #pragma once
 #include <string>
 
+#include "flatten.hpp"
 #include "host_graph.hpp"
+#include "instances.hpp"
 
 struct glome_sb {
   glome::Graph graph;
   std::string err;
 };
 inline const glome::Graph& sb_graph(const glome_sb* sb) { return sb->graph; }
+
+// The commit-time rules in one place: the product's commit (runtime.hip glome_scene_commit), the host's view of them
+// (capi_host.cpp glome_sb_scene_traits) and tests/hostsim all take them from here.
+struct CommitRules { glome::SceneTraits traits; glome::SceneCaps caps; };
+inline CommitRules commit_rules(const glome::Graph& G, const glome::FlatScene& F) {
+  CommitRules R;
+  R.caps = glome::scene_caps(F);
+  glome::SceneTraits& t = R.traits;
+  t.tier = (int)F.tier; t.cls_mask = R.caps.cls_mask; t.stack_cap = R.caps.stack_cap; t.pk_all = F.pk_all;
+  t.n_bih_nodes = (int64_t)F.bihnodes.size(); t.n_mesh_nodes = (int64_t)F.meshnodes.size() / 4;
+  for (const glome::Mat& m : G.mats) {
+    if (m.kind == glome::MAT_REFLECT || m.kind == glome::MAT_REFRACT || m.kind == glome::MAT_WARP) t.has_secondary_mats = true;
+    if (m.kind == glome::MAT_REFRACT) t.has_refract = true;
+    if (m.kind == glome::MAT_LAYERS || m.kind == glome::MAT_BLEND) t.has_nested_mats = true;
+  }
+  return R;
+}

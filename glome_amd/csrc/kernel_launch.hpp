@@ -1,0 +1,66 @@
+// kernel_launch.hpp -- the seam between the host runtime (runtime.hip) and the kernel parts (kernel_parts.hip): the launchers the parts
+// define and what a launch is described by.  No kernel lives here.  Two device-side conventions are here as well because both
+// sides must agree on them and runtime.hip does not include the kernels: kernel_args (the runtime's self-test checks what the
+// kernels assume) and the adaptive sampler's plan of a launch (the runtime sizes the grid and the control words by the same
+// ss_plan the kernel walks).
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <type_traits>
+
+#include "instances.hpp"
+#include "tiles.hpp"
+#include "rt_device.hpp"
+
+using namespace glome;
+
+// the kernel's own arguments where the dispatch put them (constant memory; the first explicit argument is at offset 0)
+// (relies on the code-object ABI placing the first explicit by-value argument at offset 0 of the kernarg segment in host layout:
+// checked once per process by k_kernarg_selftest, glome_ctx_create)
+template <class ARGS> __device__ __forceinline__ const ARGS& kernel_args() {
+  static_assert(std::is_trivially_copyable<ARGS>::value && alignof(ARGS) <= 16, "kernel_args: a by-value kernel argument in host layout");
+  return *(const ARGS*)(const ARGS __attribute__((address_space(4)))*)__builtin_amdgcn_kernarg_segment_ptr();
+}
+
+// ---- a launch
+// LDS carve per wave: three stack rows of cap * 64 words, or two (render_kernels.hpp lane_stack)
+inline size_t flat_lds_bytes(int cap, bool two_rows = false) { return (size_t)cap * 64 * (two_rows ? 8 : 12); }
+struct FlatLaunch { int grid; size_t lds; hipStream_t st; int stack_cap; uint32_t* ovf; int ovf_cap; };
+struct RayStream { const float *ox, *oy, *oz, *dx, *dy, *dz, *tmax; };
+struct HitStream { float* t; int32_t* prim; float *nx, *ny, *nz; int32_t* tex8; };
+
+// ---- the adaptive sampler's plan of a launch: queue heads and, per pass, the items of a head's sequence (render_kernels.hpp ss_frame_loop)
+constexpr uint32_t kSSHeads = 8, kSSHeadStride = 32;
+struct SSPlan {  // per pass: regions per tile, regions per tile row, first item of the pass in a head's sequence
+  uint32_t per_tile[6], nrx[6], first[7];
+  uint32_t tiles_per_head;
+};
+__host__ __device__ inline SSPlan ss_plan(const DRenderArgs& A) {
+  SSPlan P;
+  P.tiles_per_head = ((uint32_t)A.ntiles * (uint32_t)A.nframes + kSSHeads - 1) / kSSHeads;  // (a tile of every frame of the launch)
+  P.first[1] = 0; P.per_tile[0] = 0; P.nrx[0] = 1; P.first[0] = 0;
+  for (int p = 1; p <= 5; p++) {
+    int nrx;
+    P.per_tile[p] = (uint32_t)ss_regions_per_tile(p, A.blocksize, A.ss_rw[p], A.ss_rh[p], nrx);  // laid out for full tiles; edge tiles leave regions empty
+    P.nrx[p] = (uint32_t)nrx;
+    P.first[p + 1] = P.first[p] + P.per_tile[p] * P.tiles_per_head;
+  }
+  return P;
+}
+
+// ---- the launchers (kernel_parts.hip; a flat launcher answers false when its part does not hold instance `key`)
+bool launch_flat_p1(int key, const FlatLaunch& L, const DRenderArgs& A);
+bool launch_flat_p2(int key, const FlatLaunch& L, const DRenderArgs& A);
+bool launch_flat_p3(int key, const FlatLaunch& L, const DRenderArgs& A);
+bool launch_flat_p4(int key, const FlatLaunch& L, const DRenderArgs& A);
+bool launch_ss_flat_p5(int key, const FlatLaunch& L, const DRenderArgs& A);
+bool launch_ss_flat_p9(int key, const FlatLaunch& L, const DRenderArgs& A);
+void launch_render_generic(int grid, hipStream_t st, const DRenderArgs& A);        // counts bih_nodes / prim_tests (part 6)
+void launch_ss_generic(int grid, hipStream_t st, const DRenderArgs& A);            // (part 7)
+void launch_render_generic_lean(int grid, hipStream_t st, const DRenderArgs& A);   // does not (part 10)
+void launch_ss_generic_lean(int grid, hipStream_t st, const DRenderArgs& A);       // (part 11)
+void launch_rayint_batch_flat(const FlatLaunch& L, DScene S, size_t n, RayStream R, HitStream H, DCounters* c);
+void launch_shadow_batch_flat(const FlatLaunch& L, DScene S, size_t n, RayStream R, uint8_t* occ, DCounters* c);
+void launch_rayint_batch_generic(int grid, hipStream_t st, DScene S, size_t n, RayStream R, HitStream H, DCounters* c);
+void launch_shadow_batch_generic(int grid, hipStream_t st, DScene S, size_t n, RayStream R, uint8_t* occ, DCounters* c);
+void launch_inside_batch(int grid, hipStream_t st, DScene S, size_t n, const float* px, const float* py, const float* pz, uint8_t* in, DCounters* c);

@@ -740,10 +740,7 @@ GD bool bih_tri(const DScene& S, uint32_t hdr, const Ray& r, float d, STK& stk, 
 // `valid`: the lane holds a ray.  All lanes of the wave must make this call together.
 // The packet loop proper.  Every branch in it is wave-uniform (the per-lane decisions are selects), and it takes and
 // returns everything by value, so it can be compiled as a function of its own with plain scalar control flow.
-#ifndef GLOME_LDS_STACK
-#define GLOME_LDS_STACK 12
-#endif
-constexpr int kAsmLdsCap = GLOME_LDS_STACK;  // entries of the LDS part of the flat tier's stack: the hand-written walk is instantiated for it
+// (kAsmLdsCap, the LDS part of the flat tier's stack the hand-written walk is instantiated for: rt_types.h)
 struct PacketResult { float best_t; uint32_t best_rec; uint32_t occ_lo, occ_hi, n_bih, n_prim; };
 template <int MODE, bool COUNT, int LEAFK, class STK>
 GD PacketResult bih_tri_packet(const F4* nodes, const F4* tris, uint32_t ref, uint32_t delta, uint32_t fwdbits, uint32_t am_lo, uint32_t am_hi,
@@ -1367,7 +1364,7 @@ constexpr uint32_t CAND_MESH = 0x80000000u;
 // CLS is the set of entry classes the kernel instance is compiled for (the device analogue of the reference's
 // SPECIALIZE pragmas for Bih Triangle / Bih Sphere, Bih.hs:370-374): an all-triangle scene runs a kernel that contains
 // only the triangle loops, which keeps it small enough to stay in registers and in the instruction cache.
-constexpr int CLS_BIH_TRI = 1, CLS_BIH_SPHERE = 2, CLS_BIH_SIMPLE = 4, CLS_MESH = 8, CLS_PRIMS = 16, CLS_ALL = 31, CLS_CSG = 32, CLS_EVERY = 63;
+// (the CLS_* constants: rt_types.h)
 constexpr uint32_t CAND_CSG = 0x40000000u;  // aux flag: the candidate is a CSG item's hit, complete in the side record
 // WAVE: the call is made by all lanes of a wave together (`valid` = this lane holds a ray); triangle BIHs are then
 // walked as one packet (bih_tri_wave), everything else per lane as before.

@@ -76,6 +76,13 @@ constexpr int kMaxTraceDepth = 8;  // maxdepth values the shading state machine 
 constexpr int kMaxMatNest = 4;     // Blend / AdditiveLayers nesting it has material frames for (reference: any)
 constexpr int kMaxBatchFrames = 32;  // frames one render launch can carry (a launch costs ~0.3 ms besides its frames -- it ends with its slowest work items -- so the more the better: DESIGN.md 4.1b)
 
+#ifndef GLOME_LDS_STACK
+#define GLOME_LDS_STACK 12
+#endif
+constexpr int kAsmLdsCap = GLOME_LDS_STACK;  // entries of the LDS part of the flat tier's stack: the hand-written walk is instantiated for it
+// the entry classes of a flat root program, as a set: what a scene holds (its cls_mask) and what a kernel instance is compiled for (rt_device.hpp closest_flat)
+constexpr int CLS_BIH_TRI = 1, CLS_BIH_SPHERE = 2, CLS_BIH_SIMPLE = 4, CLS_MESH = 8, CLS_PRIMS = 16, CLS_ALL = 31, CLS_CSG = 32, CLS_EVERY = 63;
+
 constexpr int kPairWords = 20;  // a pair record: 18 floats, the leaf's remaining count, the first triangle's record index (80 bytes)
 
 struct F4 { float x, y, z, w; };
@@ -136,7 +143,7 @@ constexpr uint32_t kQueueHeadStride = 32;  // words between heads: every head on
 constexpr uint32_t kQueueChunk = 64;       // consecutive tickets that belong to one head (one 64x64 work tile of 8x8 blocks)
 struct DCounters {  // device-side atomics, one block per launch slot
   unsigned long long rays_primary, rays_shadow, rays_secondary, bih_nodes, mesh_nodes, prim_tests;
-  unsigned int heads[kQueueShards * kQueueHeadStride];  // persistent-kernel work queue heads (glome_device.hip TicketQueue)
+  unsigned int heads[kQueueShards * kQueueHeadStride];  // persistent-kernel work queue heads (render_kernels.hpp TicketQueue)
   unsigned int dry_pad[31];
   unsigned int dry;        // mask of heads found empty (own line: written a few times per launch, read whenever a wave changes heads)
   unsigned int done_pad[31];

@@ -323,6 +323,17 @@ int glome_tiles_layout(const glome_render_params*, int tile_first, int tile_stri
  * per lane: valid, x, y, offset inside the dense payload.  which 0: by the tile arithmetic (work_to_pixel); 1: by the plan's item table, as
  * the lean render loop decodes it.  Writes up to cap_items items and returns the item count. */
 int64_t glome_items_layout(const glome_render_params*, int tile_first, int tile_stride, int blocksize_override, int which, int32_t* out, int64_t cap_items);
+/* Host-only: which kernel instance a launch gets (the rules of glome_amd/csrc/instances.hpp; no device is touched).  n rows of 14 inputs
+ *   tier, cls_mask, has_secondary_mats, has_nested_mats, has_refract, pk_all, stack_cap, n_bih_nodes,   (the scene: glome_sb_scene_traits)
+ *   mode, faithful, count_work, maxdepth, tile_stride, items                                            (the params; items: work items of the launch)
+ * give n rows of 4 outputs: the kind (0 render kernel, 1 adaptive sampler); the instance -- a flat-tier key, which holds the kernel's
+ * template arguments as bits 0 FAITHFUL, 1 COUNT, 2 FULL, 3 TWO_ROWS, 4-7 LB (waves per SIMD), 8-13 CLS (entry classes), or -1 / -2 for
+ * the generic tier's kernel that counts work / does not --; two_rows; the wave slots per CU a persistent grid is capped by.
+ * Returns n, or GLOME_E_INVALID for a null array or an unknown mode. */
+int64_t glome_kernel_choice(int64_t n, const int64_t* in14, int32_t* out4);
+/* Host-only: what a commit of `root` would derive for that choice.  out11: the first eight inputs above, then ovf_cap, pk_generic_cap
+ * (without the debug switch of the environment) and n_mesh_nodes. */
+int glome_sb_scene_traits(glome_sb*, int32_t root, int64_t* out11);
 /* The lean render loop's pixel-coordinate tables of a frame size (xc[width], yc[height]; made on the device, once per context), or with
  * direct != 0 the same values evaluated per pixel by the coordinate function itself. */
 int glome_ctx_coord_tables(glome_ctx*, int width, int height, float* xc, float* yc, int direct);

@@ -67,8 +67,7 @@ struct HostGenericTier {
 };
 
 
-// the product's launch rule (glome_device.hip launch_render): a flat-tier frame of a scene with a Refract material, traced
-// deeper than the primary ray, is traversed as the reference traverses (its transmitted rays are not unit length)
+// has the scene a Refract material?  (What the product's rule of the faithful instance asks: instances.hpp exact_traversal, used below.)
 static bool refract_scene(const SimScene* s) {
   for (uint32_t k = 0; k < s->D.n_mats; k++) { uint32_t kind; memcpy(&kind, &s->D.mats[3 * k].x, 4); if (kind == DM_REFRACT) return true; }
   return false;
@@ -88,8 +87,8 @@ void* hostsim_commit(glome_sb* sb, int root, char* errbuf, int cap) {
   D.bihnodes = F.bihnodes.data(); D.pknodes = F.pknodes.data(); D.pknodes_bytes = (uint32_t)(F.pknodes.size() * sizeof(F4)); D.meshhdr = F.meshhdr.data(); D.meshnodes = F.meshnodes.data(); D.mtris = F.mtris.data();
   D.mtrimeta = F.mtrimeta.data(); D.mats = F.mats.data(); D.wlights = F.wlights.data(); D.matkids = F.matkids.data(); D.entries = F.entries.data();
   D.n_entries = F.tier == 0 ? (uint32_t)F.entries.size() : 0; D.root_rec = F.root_rec; D.tier = F.tier; D.n_mats = (uint32_t)sb_graph(sb).mats.size(); D.tex_bits = F.tex_bits;
-  D.pk_generic_cap = (F.tier != 0 && F.max_sphere_bih_depth > 0) ? (uint32_t)std::min(kGenericPacketStack, std::max(4, F.max_sphere_bih_depth)) : 0u;
-  if (getenv("GLOME_DEBUG_NO_GENERIC_PACKETS")) D.pk_generic_cap = 0;  // (the product's switch, glome_device.hip glome_scene_commit)
+  D.pk_generic_cap = scene_caps(F).pk_generic_cap;  // (the product's commit-time rule, instances.hpp)
+  if (getenv("GLOME_DEBUG_NO_GENERIC_PACKETS")) D.pk_generic_cap = 0;  // (the product's switch, runtime.hip glome_scene_commit)
   return s;
 }
 void hostsim_free(void* s) { delete (SimScene*)s; }
@@ -160,7 +159,7 @@ int hostsim_render(void* sv, int tier, const float* cam, const float* lights, in
   HostStack hs;
   Cnt total;
   unsigned int err = 0;
-  const bool exact = refract_scene(s) && maxdepth > 1;
+  const bool exact = exact_traversal(refract_scene(s), maxdepth);
   for (int py = 0; py < height; py++)
     for (int px = 0; px < width; px++) {
       float xc, yc;
@@ -208,7 +207,7 @@ int hostsim_block_work(void* sv, const float* cam, const float* light_pos, int w
 }
 
 // renderTileSubsample through the device headers' pass helpers (ss_candidate / ss_neighbours / ccmp / cavg / blend),
-// executed sequentially tile by tile.  Mirrors subsample_tile() in glome_device.hip.
+// executed sequentially tile by tile.  Mirrors ss_frame_loop in render_kernels.hpp.
 int hostsim_render_subsample(void* sv, int tier, const float* cam, const float* lights, int nl, int width, int height, int maxdepth, int blocksize,
                              const float* thresholds, float* out5, unsigned long long* counters) {
   SimScene* s = (SimScene*)sv;
@@ -220,7 +219,7 @@ int hostsim_render_subsample(void* sv, int tier, const float* cam, const float* 
   HostStack hs;
   unsigned long long nprim = 0, nshadow = 0, nsec = 0;
   unsigned int err = 0;
-  const bool exact = refract_scene(s) && maxdepth > 1;
+  const bool exact = exact_traversal(refract_scene(s), maxdepth);
   auto sample = [&](float xp, float yp) {
     float xc, yc; get_coordsf(width, height, xp, yp, xc, yc);
     Ray ray = primary_ray(C, xc, yc);

@@ -1,5 +1,5 @@
 // rccl_stub.cpp -- TEST INFRASTRUCTURE: a stand-in for librccl.so with the six entry points glome_multi_* resolves
-// (glome_device.hip, struct Rccl), so that the RCCL branch of glome_multi_render -- ncclCommInitAll, one group of ncclSend /
+// (runtime.hip, struct Rccl), so that the RCCL branch of glome_multi_render -- ncclCommInitAll, one group of ncclSend /
 // ncclRecv per call on the ranks' own streams, the slab offsets, the stream ordering -- can execute on a box with ONE GPU
 // (GLOME_DEBUG_RCCL_LIB=<this library>, GLOME_DEBUG_RCCL_SAME_DEVICE=1).  A send / recv pair of a group becomes, at
 // ncclGroupEnd: an event on the sender's stream, a wait for it on the receiver's stream, a hipMemcpyAsync there, and an event

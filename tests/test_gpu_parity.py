@@ -1211,7 +1211,7 @@ def test_closure_fallback_host_shading_over_the_batch_seams(gpu_ctx):
 @pytest.mark.parametrize("nframes,w,h", [(32, 200, 120), (5, 333, 97), (32, 1920, 1080)])
 def test_renderTile_frame_batches_equal_the_frames_rendered_alone(gpu_ctx, s3_full, nframes, w, h):
     """Up to 32 frames per launch, interleaved in the work queue chunk by chunk (chunk c of every frame, then chunk c + 1 ...;
-    glome_device.hip render_loop): every frame of a batch -- different views, frame sizes whose item counts are no multiple of a
+    render_kernels.hpp render_loop): every frame of a batch -- different views, frame sizes whose item counts are no multiple of a
     chunk -- is, pixel for pixel, the frame rendered alone; through the whole-frame entry and through a rank's dense tile payload."""
     import torch
     sd, sc = s3_full

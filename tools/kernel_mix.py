@@ -1,4 +1,5 @@
-"""Static look at what the compiler made of each kernel of one part of glome_device.hip: registers, spills, scratch bytes
+"""Static look at what the compiler made of each kernel of one unit of the device half (PART 0: runtime.hip; 1..11: that part of
+kernel_parts.hip): registers, spills, scratch bytes
 and the count of every kind of memory instruction (flat_load where global_load / s_load was meant is a pool base the
 compiler could not place: DESIGN.md 4.4a).
 
@@ -20,7 +21,8 @@ def main():
     part = int(sys.argv[1])
     out = f"/tmp/kernel_mix/p{part}"
     os.makedirs(out, exist_ok=True)
-    cmd = [build.HIPCC] + build.HIPFLAGS + [f"-DGLOME_PART={part}", "-I" + os.path.join(ROOT, "include"), "-c", os.path.join(ROOT, "glome_amd/csrc/glome_device.hip"), "-o", "p.o",
+    src = "kernel_parts" if part else "runtime"
+    cmd = [build.HIPCC] + build.HIPFLAGS + ([f"-DGLOME_PART={part}"] if part else []) + ["-I" + os.path.join(ROOT, "include"), "-c", os.path.join(ROOT, f"glome_amd/csrc/{src}.hip"), "-o", "p.o",
                                             "-Rpass-analysis=kernel-resource-usage", "-save-temps"] + sys.argv[2:]
     r = subprocess.run(cmd, cwd=out, capture_output=True, text=True)
     if r.returncode:
@@ -34,7 +36,7 @@ def main():
             cur = m.group(2); usage[cur] = {}
         elif cur:
             usage[cur][m.group(1).split(" [")[0]] = m.group(2)
-    asm = open(os.path.join(out, "glome_device-hip-amdgcn-amd-amdhsa-gfx950.s")).read().splitlines()
+    asm = open(os.path.join(out, f"{src}-hip-amdgcn-amd-amdhsa-gfx950.s")).read().splitlines()
     body, name = {}, None
     for line in asm:
         m = re.match(r"^(_Z\w+):", line)
