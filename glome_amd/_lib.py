@@ -39,6 +39,10 @@ class Stats(C.Structure):  # glome_stats
                 ("kernel_ms", C.c_float), ("n_tiles", C.c_int32), ("n_pixels", C.c_int32)]
 
 
+class TraceParams(C.Structure):  # glome_trace_params
+    _fields_ = [("maxdepth", C.c_int32), ("faithful", C.c_int32), ("count_work", C.c_int32)]
+
+
 class SceneInfo(C.Structure):  # glome_scene_info
     _fields_ = [("tier", C.c_int32), ("nesting_depth", C.c_int32), ("n_records", C.c_int64), ("n_bih_nodes", C.c_int64),
                 ("n_mesh_nodes", C.c_int64), ("n_triangles", C.c_int64), ("n_spheres", C.c_int64),
@@ -130,6 +134,11 @@ SYMBOLS = [
     ("glome_inside_batch", C.c_int, [vp, C.c_size_t, c_fp, c_fp, c_fp, c_bp]),
     ("glome_rayint_batch_dev", C.c_int, [vp, C.c_size_t] + [vp] * 13),
     ("glome_shadow_batch_dev", C.c_int, [vp, C.c_size_t] + [vp] * 8),
+    ("glome_trace_params_default", None, [C.POINTER(TraceParams)]),
+    ("glome_trace_batch", C.c_int, [vp, C.c_size_t] + [c_fp] * 7 + [C.POINTER(Light), C.c_int, C.POINTER(TraceParams), c_fp, c_fp, c_ip, c_fp, c_fp, c_fp, c_ip,
+                                    C.POINTER(Stats)]),
+    ("glome_trace_batch_dev", C.c_int, [vp, C.c_size_t] + [vp] * 7 + [C.POINTER(Light), C.c_int, C.POINTER(TraceParams)] + [vp] * 7 + [C.POINTER(Stats)]),
+    ("glome_trace_kernel_choice", C.c_int64, [C.c_int64, C.POINTER(C.c_int64), c_ip]),
     ("glome_camera_lookat", C.c_int, [c_dp, c_dp, c_dp, C.c_double, C.POINTER(Camera)]),
     ("glome_render_params_default", None, [C.POINTER(RenderParams)]),
     ("glome_render", C.c_int, [vp, C.POINTER(Camera), C.POINTER(Light), C.c_int, C.POINTER(RenderParams), c_fp, c_up, C.POINTER(Stats)]),

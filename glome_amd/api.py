@@ -111,6 +111,15 @@ def render_params(width=720, height=480, mode=0, blocksize=65, maxdepth=3, fog=0
     return p
 
 
+def trace_params(maxdepth=3, faithful=0, count_work=0):
+    """glome_trace_params: faithful=1 is required when ray directions are not unit length (include/glome_hip.h, the trace seam)."""
+    lib = L.load()
+    p = L.TraceParams()
+    lib.glome_trace_params_default(C.byref(p))
+    p.maxdepth, p.faithful, p.count_work = maxdepth, faithful, count_work
+    return p
+
+
 # ---------------------------------------------------------------- scene builder
 class Builder:
     """One method per reference constructor; returns integer node / material ids."""
@@ -397,6 +406,42 @@ class Scene:
         cols = [_f32(p[:, 0]), _f32(p[:, 1]), _f32(p[:, 2])]
         self._chk(self.lib.glome_inside_batch(self.h, n, *[c.ctypes.data_as(L.c_fp) for c in cols], ins.ctypes.data_as(L.c_bp)), "glome_inside_batch")
         return ins.astype(bool)
+
+    def trace(self, o, d, lights, tmax=None, params=None, want_hit=False):
+        """Trace.trace over a batch of rays (Trace.hs:59-82): returns dict rgba (nx4), depth (n; 1e6 = miss), stats, and with want_hit
+        the trace's own Rayint t, prim, n, tex as `rayint` returns them.  Directions are used as given: unit length, or params.faithful."""
+        o = np.asarray(o, dtype=np.float32).reshape(-1, 3)
+        d = np.asarray(d, dtype=np.float32).reshape(-1, 3)
+        n = o.shape[0]
+        cols = [_f32(o[:, 0]), _f32(o[:, 1]), _f32(o[:, 2]), _f32(d[:, 0]), _f32(d[:, 1]), _f32(d[:, 2])]
+        tm = None if tmax is None else _f32(np.broadcast_to(np.asarray(tmax, dtype=np.float32), (n,)))
+        params = trace_params() if params is None else params
+        out = np.zeros((n, 5), np.float32)
+        hit, hp = {}, [None] * 6
+        if want_hit:
+            t = np.zeros(n, np.float32); prim = np.zeros(n, np.int32)
+            nx = np.zeros(n, np.float32); ny = np.zeros(n, np.float32); nz = np.zeros(n, np.float32)
+            tex = np.zeros((n, self.lib.glome_tex_words()), np.int32)
+            hp = [t.ctypes.data_as(L.c_fp), prim.ctypes.data_as(L.c_ip), nx.ctypes.data_as(L.c_fp), ny.ctypes.data_as(L.c_fp), nz.ctypes.data_as(L.c_fp),
+                  tex.ctypes.data_as(L.c_ip)]
+        la = (L.Light * max(1, len(lights)))(*lights)
+        st = L.Stats()
+        self._chk(self.lib.glome_trace_batch(self.h, n, *[c.ctypes.data_as(L.c_fp) for c in cols], tm.ctypes.data_as(L.c_fp) if tm is not None else None,
+                                             la, len(lights), C.byref(params), out.ctypes.data_as(L.c_fp), *hp, C.byref(st)), "glome_trace_batch")
+        if want_hit:
+            hit = {"t": t, "prim": prim, "n": np.stack([nx, ny, nz], 1), "tex": tex}
+        return {"rgba": out[:, :4], "depth": out[:, 4], "stats": _stats_dict(st), **hit}
+
+    def trace_dev(self, n, ray_ptrs7, lights, params, rgbad_ptr, hit_ptrs=None, want_stats=True):
+        """Device-pointer trace: ray_ptrs7 = ox, oy, oz, dx, dy, dz, tmax (tmax may be None / 0); hit_ptrs = t, prim, nx, ny, nz, tex8 (any may be
+        None / 0); asynchronous on the context's stream unless want_stats."""
+        vp = lambda p: C.c_void_p(p) if p else None
+        hit = list(hit_ptrs) if hit_ptrs is not None else [None] * 6
+        la = (L.Light * max(1, len(lights)))(*lights)
+        st = L.Stats()
+        self._chk(self.lib.glome_trace_batch_dev(self.h, int(n), *[vp(p) for p in ray_ptrs7], la, len(lights), C.byref(params), vp(rgbad_ptr),
+                                                 *[vp(p) for p in hit], C.byref(st) if want_stats else None), "glome_trace_batch_dev")
+        return _stats_dict(st) if want_stats else None
 
     def render(self, cam, lights, params, want_packed=True, init=None):
         """renderTiles (Glome.hs:379-386): returns (rgbad[h,w,5] float32, packed[h,w] uint32 or None, stats dict)."""

@@ -49,6 +49,12 @@ void glome_render_params_default(glome_render_params* p) {
   p->tile_first = 0; p->tile_stride = 1; p->rank0_share_pct = 0;
 }
 
+void glome_trace_params_default(glome_trace_params* p) {
+  if (!p) return;
+  memset(p, 0, sizeof(*p));
+  p->maxdepth = 3;  // Glome.hs:25
+}
+
 int glome_xfm_translate(const double v[3], double out[24]) { return xguard([&] { xf_to(xf_translate(d3(v)), out); }); }
 int glome_xfm_scale(const double v[3], double out[24]) { return xguard([&] { xf_to(xf_scale(d3(v)), out); }); }
 int glome_xfm_rotate(const double axis[3], double angle, double out[24]) { return xguard([&] { xf_to(xf_rotate(d3(axis), angle), out); }); }
@@ -394,6 +400,19 @@ int64_t glome_kernel_choice(int64_t n, const int64_t* in, int32_t* out) {
     const Choice c = sampler ? choose_sampler(s, v[9] != 0, v[10] != 0, (int)v[11], (int)v[12]) : choose_render(s, v[9] != 0, v[10] != 0, (int)v[11], (int)v[12], (uint32_t)v[13]);
     int32_t* o = out + 4 * i;
     o[0] = sampler ? KIND_SAMPLER : KIND_RENDER; o[1] = c.generic ? (c.generic_counts ? -1 : -2) : c.key; o[2] = c.two_rows ? 1 : 0; o[3] = waves_per_cu(c);
+  }
+  return n;
+}
+int64_t glome_trace_kernel_choice(int64_t n, const int64_t* in, int32_t* out) {
+  if (n < 0 || (n > 0 && (!in || !out))) return GLOME_E_INVALID;
+  for (int64_t i = 0; i < n; i++) {
+    const int64_t* v = in + 11 * i;
+    SceneTraits s;
+    s.tier = (int)v[0]; s.cls_mask = (int)v[1]; s.has_secondary_mats = v[2] != 0; s.has_nested_mats = v[3] != 0; s.has_refract = v[4] != 0; s.pk_all = v[5] != 0;
+    s.stack_cap = (int)v[6]; s.n_bih_nodes = v[7];
+    const Choice c = choose_trace(s, v[8] != 0, v[9] != 0, (int)v[10]);
+    int32_t* o = out + 3 * i;
+    o[0] = c.generic ? (c.generic_counts ? -1 : -2) : c.key; o[1] = c.lb; o[2] = waves_per_cu(c);
   }
   return n;
 }

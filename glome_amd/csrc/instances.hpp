@@ -4,7 +4,7 @@
 //   X-lists     every flat-tier instance, listed once by the part that compiles it; kernel_parts.hip makes the launchers from them,
 //               instance_listed() the compile-time check that the rules below only ever name a listed instance
 //   scene_caps  the commit-time rules (entry classes, LDS / overflow stack entries, the generic tier's packet stack)
-//   choose_render / choose_sampler   scene traits + render params -> Choice (instance key, launch bound, stack rows)
+//   choose_render / choose_sampler / choose_trace   scene traits + params -> Choice (instance key, launch bound, stack rows)
 #pragma once
 #include <algorithm>
 #include <cstring>
@@ -43,15 +43,26 @@ constexpr int ss_flat_key(bool U, int CLS, int LB, bool TWO, bool F) { return (F
 #define GLOME_SS_FLAT_P5(X) X(false, CLS_BIH_TRI, 5, true, false) X(false, CLS_BIH_TRI, 4, true, false) X(false, CLS_BIH_TRI, 1, false, false) X(true, CLS_BIH_TRI, 1, false, false)
 #define GLOME_SS_FLAT_P9(X) X(true, CLS_EVERY, 1, false, true) X(false, CLS_EVERY, 2, false, false) X(true, CLS_EVERY, 2, false, false) \
   X(false, (CLS_CSG | CLS_PRIMS), 2, false, false) X(true, (CLS_CSG | CLS_PRIMS), 2, false, false)
+// k_trace_batch_flat<FAITHFUL, COUNT, FULL, CLS, LB> (trace_kernels.hpp): what choose_trace can name -- choose_render's instances without the two-row one
+#define GLOME_TRACE_FLAT_P12(X) /* production, lean */                                                                      \
+  X(false, false, false, CLS_BIH_TRI, 1) X(false, false, false, (CLS_BIH_SPHERE | CLS_PRIMS), 1) X(false, false, false, CLS_MESH, 1) \
+  X(false, false, false, CLS_ALL, 1) X(false, false, false, CLS_EVERY, 2) X(false, false, false, (CLS_CSG | CLS_PRIMS), GLOME_CSG_LB)
+#define GLOME_TRACE_FLAT_P13(X) /* production, full */                                                                      \
+  X(false, false, true, CLS_BIH_TRI, 1) X(false, false, true, (CLS_BIH_SPHERE | CLS_PRIMS), 1) X(false, false, true, CLS_MESH, 1) \
+  X(false, false, true, CLS_ALL, 1) X(false, false, true, CLS_EVERY, 2) X(false, false, true, (CLS_CSG | CLS_PRIMS), GLOME_CSG_LB)
+#define GLOME_TRACE_FLAT_P14(X) /* faithful / counting */                                                                   \
+  X(true, true, true, CLS_EVERY, 1) X(true, true, false, CLS_EVERY, 1) X(false, true, true, CLS_EVERY, 1) X(false, true, false, CLS_EVERY, 1)
 // the units of the device half: 0 is runtime.hip, 1..kParts-1 are kernel_parts.hip with -DGLOME_PART=k (glome_amd/build.py reads the count from here)
-#define GLOME_NPARTS 12
+#define GLOME_NPARTS 15
 constexpr int kParts = GLOME_NPARTS;
 
 // is `key` one of the listed instances (the lists the launchers of kernel_parts.hip are made from)
 #define GLOME_KEY_OF_RENDER_FLAT(F, C, U, K, B, T) || key == render_flat_key(F, C, U, K, B, T)
 #define GLOME_KEY_OF_SS_FLAT(U, K, B, T, F) || key == ss_flat_key(U, K, B, T, F)
-enum InstanceKind : int { KIND_RENDER = 0, KIND_SAMPLER = 1 };
+#define GLOME_KEY_OF_TRACE_FLAT(F, C, U, K, B) || key == render_flat_key(F, C, U, K, B, false)
+enum InstanceKind : int { KIND_RENDER = 0, KIND_SAMPLER = 1, KIND_TRACE = 2 };
 constexpr bool instance_listed(InstanceKind kind, int key) {
+  if (kind == KIND_TRACE) return false GLOME_TRACE_FLAT_P12(GLOME_KEY_OF_TRACE_FLAT) GLOME_TRACE_FLAT_P13(GLOME_KEY_OF_TRACE_FLAT) GLOME_TRACE_FLAT_P14(GLOME_KEY_OF_TRACE_FLAT);
   return kind == KIND_RENDER
              ? (false GLOME_RENDER_FLAT_P1(GLOME_KEY_OF_RENDER_FLAT) GLOME_RENDER_FLAT_P2(GLOME_KEY_OF_RENDER_FLAT) GLOME_RENDER_FLAT_P3(GLOME_KEY_OF_RENDER_FLAT) GLOME_RENDER_FLAT_P4(GLOME_KEY_OF_RENDER_FLAT))
              : (false GLOME_SS_FLAT_P5(GLOME_KEY_OF_SS_FLAT) GLOME_SS_FLAT_P9(GLOME_KEY_OF_SS_FLAT));
@@ -161,6 +172,17 @@ constexpr Choice choose_sampler(const SceneTraits& s, bool faithful_asked, bool 
   if (full && refr) return Choice{false, false, ss_flat_key(true, CLS_EVERY, 1, false, true), false, 1, true};
   return Choice{false, false, ss_flat_key(full, scene_class(s.cls_mask) == (CLS_CSG | CLS_PRIMS) ? (CLS_CSG | CLS_PRIMS) : CLS_EVERY, 2, false, false), false, 2, false};
 }
+// Trace.trace over a caller's ray streams (trace_kernels.hpp): choose_render's rule without the two-row instance, which is tied to the
+// frame's item loop (item table, coordinate tables) and to rays that are all packets -- a caller's rays need not be.
+constexpr Choice choose_trace(const SceneTraits& s, bool faithful_asked, bool count_work, int maxdepth) {
+  if (s.tier != 0) return Choice{true, count_work, 0, false, GLOME_GENERIC_LB, false};
+  const bool faithful = faithful_asked || exact_traversal(s.has_refract, maxdepth), count = count_work || faithful;
+  const bool full = full_shading(s, maxdepth);
+  if (faithful) return Choice{false, false, render_flat_key(true, true, full, CLS_EVERY, 1, false), false, 1, true};
+  if (count) return Choice{false, false, render_flat_key(false, true, full, CLS_EVERY, 1, false), false, 1, false};
+  const int cls = scene_class(s.cls_mask), lb = cls == CLS_EVERY ? 2 : (cls == (CLS_CSG | CLS_PRIMS) ? GLOME_CSG_LB : 1);
+  return Choice{false, false, render_flat_key(false, false, full, cls, lb, false), false, lb, false};
+}
 
 // ------------------------------------------------------------------------------------------------ soundness, at compile time
 // Every combination of the inputs the rules look at (the value grid of tests/test_kernel_choice.py), one (tier, cls_mask) slice per
@@ -182,6 +204,10 @@ constexpr bool choices_listed(int tier, int cls_mask) {
         const Choice a = choose_sampler(s, faithful, count_work, maxdepth, tile_stride);
         if (!r.generic && !instance_listed(KIND_RENDER, r.key)) return false;
         if (!a.generic && !instance_listed(KIND_SAMPLER, a.key)) return false;
+        if (p < 8) {  // (the trace rule looks at faithful, count_work and maxdepth only)
+          const Choice t = choose_trace(s, faithful, count_work, maxdepth);
+          if (!t.generic && !instance_listed(KIND_TRACE, t.key)) return false;
+        }
       }
   return true;
 }

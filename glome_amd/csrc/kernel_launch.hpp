@@ -64,3 +64,9 @@ void launch_shadow_batch_flat(const FlatLaunch& L, DScene S, size_t n, RayStream
 void launch_rayint_batch_generic(int grid, hipStream_t st, DScene S, size_t n, RayStream R, HitStream H, DCounters* c);
 void launch_shadow_batch_generic(int grid, hipStream_t st, DScene S, size_t n, RayStream R, uint8_t* occ, DCounters* c);
 void launch_inside_batch(int grid, hipStream_t st, DScene S, size_t n, const float* px, const float* py, const float* pz, uint8_t* in, DCounters* c);
+// the trace seam (trace_kernels.hpp): the flat instances of parts 12-14, the generic tier's two kernels beside them
+bool launch_trace_flat_p12(int key, const FlatLaunch& L, const DTraceArgs& A);
+bool launch_trace_flat_p13(int key, const FlatLaunch& L, const DTraceArgs& A);
+bool launch_trace_flat_p14(int key, const FlatLaunch& L, const DTraceArgs& A);
+void launch_trace_generic(int grid, hipStream_t st, const DTraceArgs& A);       // counts bih_nodes / prim_tests (part 14)
+void launch_trace_generic_lean(int grid, hipStream_t st, const DTraceArgs& A);  // does not (part 13)

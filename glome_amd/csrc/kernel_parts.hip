@@ -1,7 +1,8 @@
 // kernel_parts.hip -- the kernel instances of the library, cut into parts that compile in parallel: -DGLOME_PART=k (k = 1..kParts-1,
 // glome_amd/build.py) keeps the instances instances.hpp lists for part k and defines the launcher that knows them (kernel_launch.hpp).
-// The device code itself is render_kernels.hpp; the host runtime (runtime.hip) is a unit of its own and holds none of it.
+// The device code itself is render_kernels.hpp and trace_kernels.hpp; the host runtime (runtime.hip) is a unit of its own and holds none of it.
 #include "render_kernels.hpp"
+#include "trace_kernels.hpp"
 
 #if !defined(GLOME_PART) || GLOME_PART < 1 || GLOME_PART >= GLOME_NPARTS
 #error "kernel_parts.hip is compiled once per part: -DGLOME_PART=k with k = 1..GLOME_NPARTS-1 (instances.hpp)"
@@ -92,4 +93,21 @@ void launch_shadow_batch_generic(int grid, hipStream_t st, DScene S, size_t n, R
 void launch_inside_batch(int grid, hipStream_t st, DScene S, size_t n, const float* px, const float* py, const float* pz, uint8_t* in, DCounters* c) {
   hipLaunchKernelGGL(k_inside_batch, dim3(grid), dim3(64), 0, st, S, n, px, py, pz, in, c);
 }
+#endif
+// the trace seam
+#define GLOME_TRY_TRACE_FLAT(F, C, U, K, B)                                                                                                       \
+  if (key == render_flat_key(F, C, U, K, B, false)) {                                                                                             \
+    hipLaunchKernelGGL((k_trace_batch_flat<F, C, U, K, B>), dim3(L.grid), dim3(64), L.lds, L.st, A, L.stack_cap, L.ovf, L.ovf_cap);               \
+    return true;                                                                                                                                  \
+  }
+#if GLOME_IN_PART(12)
+bool launch_trace_flat_p12(int key, const FlatLaunch& L, const DTraceArgs& A) { GLOME_TRACE_FLAT_P12(GLOME_TRY_TRACE_FLAT) return false; }
+#endif
+#if GLOME_IN_PART(13)
+bool launch_trace_flat_p13(int key, const FlatLaunch& L, const DTraceArgs& A) { GLOME_TRACE_FLAT_P13(GLOME_TRY_TRACE_FLAT) return false; }
+void launch_trace_generic_lean(int grid, hipStream_t st, const DTraceArgs& A) { hipLaunchKernelGGL(k_trace_batch_generic<false>, dim3(grid), dim3(64), flat_lds_bytes((int)A.S.pk_generic_cap), st, A); }
+#endif
+#if GLOME_IN_PART(14)
+bool launch_trace_flat_p14(int key, const FlatLaunch& L, const DTraceArgs& A) { GLOME_TRACE_FLAT_P14(GLOME_TRY_TRACE_FLAT) return false; }
+void launch_trace_generic(int grid, hipStream_t st, const DTraceArgs& A) { hipLaunchKernelGGL(k_trace_batch_generic<true>, dim3(grid), dim3(64), flat_lds_bytes((int)A.S.pk_generic_cap), st, A); }
 #endif

@@ -148,8 +148,10 @@ struct DCounters {  // device-side atomics, one block per launch slot
   unsigned int dry;        // mask of heads found empty (own line: written a few times per launch, read whenever a wave changes heads)
   unsigned int done_pad[31];
   unsigned int done;       // waves of the running launch that have left the queue (the last one resets the heads)
-  unsigned int error;      // sticky: set when a device-side limit was hit (stack overflow guard, CSG cap); reset_counters stops short of it
+  unsigned int error;      // sticky: kErr* bits, set when a device-side limit was hit (stack overflow guard, CSG cap) or a trace launch refused a ray; reset_counters stops short of it
 };
+constexpr unsigned int kErrLimit = 1u;    // a device-side limit (what every kernel reports)
+constexpr unsigned int kErrNonUnit = 2u;  // a trace launch without `faithful` met a direction that is not unit length (trace_kernels.hpp; no other kernel sets it)
 
 struct DRenderArgs {
   DScene S;
@@ -189,6 +191,23 @@ struct DRenderArgs {
                           // so the quotient is exact while chunk * e < 2^32, that is for chunk < 2^32 / nframes; a chunk index is < 2^32 / kQueueChunk (static_assert below)
   int32_t want_counters;  // 0: nobody will read the ray / work counters of this launch -- the waves skip the flush
   DCamera more_cams[kMaxBatchFrames - 1];
+};
+
+// The arguments of a trace launch (trace_kernels.hpp: Trace.trace over a caller's SoA ray streams).  No frame, no tile, item or
+// coordinate table: work item w is rays 64 w .. 64 w + 63.
+struct DTraceArgs {
+  DScene S;
+  DLight lights[kMaxLights];
+  int32_t nlights;
+  int32_t maxdepth;
+  uint32_t n;             // rays (<= 2^31: the item count and a ray's index fit 32 bits)
+  int32_t check_unit;     // generic tier: 1 = refuse directions that are not unit length (the flat tier's instances know by FAITHFUL)
+  int32_t want_counters;  // 0: nobody will read the ray / work counters of this launch -- the waves skip the flush
+  const float *ox, *oy, *oz, *dx, *dy, *dz;
+  const float* tmax;      // null: every ray runs to infinity
+  float* rgbad;           // n * 5: (r, g, b, a, depth)
+  float* t; int32_t* prim; float *nx, *ny, *nz; int32_t* tex8;  // the trace's own Rayint, as the rayint seam writes it; any may be null
+  DCounters* counters;
 };
 static_assert(kMaxBatchFrames <= (int)kQueueChunk, "DRenderArgs::nframes_rcp: chunk indices (< 2^32 / kQueueChunk) must stay below 2^32 / nframes");
 

@@ -96,6 +96,7 @@ static bool launch_render_flat(int key, const FlatLaunch& L, const DRenderArgs& 
   return launch_flat_p1(key, L, A) || launch_flat_p2(key, L, A) || launch_flat_p3(key, L, A) || launch_flat_p4(key, L, A);
 }
 static bool launch_ss_flat(int key, const FlatLaunch& L, const DRenderArgs& A) { return launch_ss_flat_p5(key, L, A) || launch_ss_flat_p9(key, L, A); }
+static bool launch_trace_flat(int key, const FlatLaunch& L, const DTraceArgs& A) { return launch_trace_flat_p12(key, L, A) || launch_trace_flat_p13(key, L, A) || launch_trace_flat_p14(key, L, A); }
 struct glome_ctx {
   int device = 0;
   hipStream_t stream = nullptr;
@@ -563,14 +564,22 @@ static int ensure_scratch(glome_ctx* ctx, size_t need) {
 // and cleared -- where the host waits anyway (statistics, the host-buffer seams, glome_ctx_synchronize).  So a launch
 // that nobody asked statistics of (the pipelined frame path) still reports a CSG-advance or frame-pool limit, at the
 // next synchronize.  The caller has synchronised the slot's stream.
+// the status and message of a non-zero error word (kErr* bits, rt_types.h)
+static int device_error_status(glome_ctx* ctx, unsigned int e) {
+  if (e & kErrNonUnit) {  // (only a trace launch sets it)
+    ctx->err = "a ray direction is not unit length: set glome_trace_params.faithful to trace such rays (the reference's own traversal)";
+    return GLOME_E_INVALID;
+  }
+  ctx->err = "device-side limit hit (traversal stack or CSG advance cap)";
+  return GLOME_E_LIMIT;
+}
 static int poll_device_error(glome_ctx* ctx, glome_ctx::Slot& sl) {
   unsigned int e = 0;
   unsigned int* d = &sl.d_counters->error;
   HIPCHK(ctx, hipMemcpy(&e, d, sizeof(e), hipMemcpyDeviceToHost));
   if (!e) return 0;
   HIPCHK(ctx, hipMemset(d, 0, sizeof(e)));
-  ctx->err = "device-side limit hit (traversal stack or CSG advance cap)";
-  return GLOME_E_LIMIT;
+  return device_error_status(ctx, e);
 }
 static int check_device_error(glome_ctx* ctx) { return poll_device_error(ctx, ctx->slot()); }
 
@@ -716,7 +725,7 @@ static int render_impl(glome_scene* s, const glome_camera* cam, const glome_ligh
     ctx->slot().launched = false;
     if (c.error) {
       HIPCHK(ctx, hipMemset(&ctx->slot().d_counters->error, 0, sizeof(unsigned int)));
-      ctx->err = "device-side limit hit (traversal stack or CSG advance cap)"; return GLOME_E_LIMIT;
+      return device_error_status(ctx, c.error);
     }
   } else if (A.ntiles > 0) { ctx->slot().launched = true; ctx->slot().launched_on = ctx->stream; }
   return 0;
@@ -908,6 +917,104 @@ int glome_inside_batch(glome_scene* s, size_t n, const float* px, const float* p
   int rc = check_device_error(ctx);
   if (rc) return rc;
   HIPCHK(ctx, hipMemcpy(inside, din, n, hipMemcpyDeviceToHost));
+  return 0;
+}
+
+// ---- the trace seam: Trace.trace over a caller's ray streams (trace_kernels.hpp) ----
+int glome_trace_batch_dev(glome_scene* s, size_t n, const float* ox, const float* oy, const float* oz, const float* dx, const float* dy,
+                          const float* dz, const float* tmax, const glome_light* lights, int nlights, const glome_trace_params* P,
+                          float* rgbad, float* t, int32_t* prim, float* nx, float* ny, float* nz, int32_t* tex8, glome_stats* stats) {
+  if (!s) return GLOME_E_INVALID;
+  glome_ctx* ctx = s->ctx;
+  if (n == 0) return 0;
+  if (!ox || !oy || !oz || !dx || !dy || !dz) { ctx->err = "null ray stream"; return GLOME_E_INVALID; }
+  if (!rgbad || !P || nlights < 0 || (nlights > 0 && !lights)) { ctx->err = "bad argument"; return GLOME_E_INVALID; }
+  if (nlights > kMaxLights) { ctx->err = "too many lights"; return GLOME_E_LIMIT; }
+  if (P->maxdepth < 1 || P->maxdepth > kMaxTraceDepth) { ctx->err = "maxdepth must be in 1.." + std::to_string(kMaxTraceDepth); return GLOME_E_LIMIT; }
+  if (n > ((size_t)1 << 31)) { ctx->err = "a trace launch carries at most 2^31 rays"; return GLOME_E_LIMIT; }
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  DTraceArgs A;
+  memset(&A, 0, sizeof(A));
+  A.S = s->dev;
+  for (int i = 0; i < nlights; i++) {
+    memcpy(A.lights[i].pos, lights[i].pos, 12); memcpy(A.lights[i].color, lights[i].color, 12);
+    A.lights[i].rad = lights[i].rad; A.lights[i].shadow = lights[i].shadow;
+  }
+  A.nlights = nlights; A.maxdepth = P->maxdepth; A.n = (uint32_t)n;
+  A.check_unit = P->faithful ? 0 : 1;
+  A.want_counters = stats ? 1 : 0;
+  A.ox = ox; A.oy = oy; A.oz = oz; A.dx = dx; A.dy = dy; A.dz = dz; A.tmax = tmax;
+  A.rgbad = rgbad; A.t = t; A.prim = prim; A.nx = nx; A.ny = ny; A.nz = nz; A.tex8 = tex8;
+  A.counters = ctx->slot().d_counters;
+  int rc;
+  if (stats && (rc = reset_counters(ctx))) return rc;  // (nobody reads the counters of a launch without `stats`, and a trace launch has no queue heads)
+  const uint32_t items = (uint32_t)((n + 63) / 64);
+  const Choice ch = choose_trace(s->tr, P->faithful != 0, P->count_work != 0, P->maxdepth);
+  const size_t lds = ch.generic ? flat_lds_bytes((int)s->dev.pk_generic_cap) : flat_lds_bytes(s->tr.stack_cap);
+  // four blocks per wave slot the kernel can hold: the items are dealt statically, and the dispatcher evens out what they cost (trace_batch_loop)
+  const int grid = (int)std::min<uint64_t>(items, (uint64_t)persistent_grid(ctx, lds, 0x7fffffff, waves_per_cu(ch)) * 4);
+  if (!ch.generic && (rc = ensure_overflow(ctx, grid, 1, s->ovf_cap))) return rc;
+  hipEvent_t ev_start = ctx->ev0, ev_stop = ctx->ev1;
+  const bool pooled = launch_events(ctx, ev_start, ev_stop), timed = stats || pooled;
+  if (timed) HIPCHK(ctx, hipEventRecord(ev_start, ctx->stream));
+  if (ch.generic) { if (ch.generic_counts) launch_trace_generic(grid, ctx->stream, A); else launch_trace_generic_lean(grid, ctx->stream, A); }
+  else {
+    const FlatLaunch L{grid, lds, ctx->stream, s->tr.stack_cap, ctx->slot().d_ovf, s->ovf_cap};
+    // (choose_trace only names listed instances -- instances.hpp choices_listed)
+    if (!launch_trace_flat(ch.key, L, A)) { ctx->err = "no trace kernel instance for this scene class (build error)"; return GLOME_E_INVALID; }
+  }
+  HIPCHK(ctx, hipGetLastError());
+  if (timed) HIPCHK(ctx, hipEventRecord(ev_stop, ctx->stream));
+  if (!stats) { ctx->slot().launched = true; ctx->slot().launched_on = ctx->stream; return 0; }  // (a refusal or a limit is reported at the next synchronize)
+  memset(stats, 0, sizeof(*stats));
+  HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+  DCounters c;
+  HIPCHK(ctx, hipMemcpy(&c, ctx->slot().d_counters, sizeof(c), hipMemcpyDeviceToHost));
+  stats->rays_primary = c.rays_primary; stats->rays_shadow = c.rays_shadow; stats->rays_secondary = c.rays_secondary;
+  stats->bih_nodes = c.bih_nodes; stats->mesh_nodes = c.mesh_nodes; stats->prim_tests = c.prim_tests;
+  HIPCHK(ctx, hipEventElapsedTime(&stats->kernel_ms, ev_start, ev_stop));
+  stats->n_tiles = (int32_t)items; stats->n_pixels = (int32_t)std::min<size_t>(n, 0x7fffffff);
+  ctx->slot().launched = false;
+  if (c.error) {
+    HIPCHK(ctx, hipMemset(&ctx->slot().d_counters->error, 0, sizeof(unsigned int)));
+    return device_error_status(ctx, c.error);
+  }
+  return 0;
+}
+int glome_trace_batch(glome_scene* s, size_t n, const float* ox, const float* oy, const float* oz, const float* dx, const float* dy,
+                      const float* dz, const float* tmax, const glome_light* lights, int nlights, const glome_trace_params* P,
+                      float* rgbad, float* t, int32_t* prim, float* nx, float* ny, float* nz, int32_t* tex8, glome_stats* stats) {
+  if (!s) return GLOME_E_INVALID;
+  glome_ctx* ctx = s->ctx;
+  if (n == 0) return 0;
+  if (!ox || !oy || !oz || !dx || !dy || !dz) { ctx->err = "null ray stream"; return GLOME_E_INVALID; }
+  if (!rgbad || !P) { ctx->err = "bad argument"; return GLOME_E_INVALID; }
+  if (n > ((size_t)1 << 31)) { ctx->err = "a trace launch carries at most 2^31 rays"; return GLOME_E_LIMIT; }
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  Staging st{ctx, {}};
+  float* din[7] = {};
+  {
+    const float* const h[7] = {ox, oy, oz, dx, dy, dz, tmax};
+    for (int k = 0; k < (tmax ? 7 : 6); k++) if (!(din[k] = st.in(h[k], n))) { ctx->err = "staging allocation failed"; return GLOME_E_HIP; }
+  }
+  float* d5 = st.in<float>(nullptr, n * 5);
+  float* dt = t ? st.in<float>(nullptr, n) : nullptr;
+  int32_t* dprim = prim ? st.in<int32_t>(nullptr, n) : nullptr;
+  float* dnx = nx ? st.in<float>(nullptr, n) : nullptr;
+  float* dny = ny ? st.in<float>(nullptr, n) : nullptr;
+  float* dnz = nz ? st.in<float>(nullptr, n) : nullptr;
+  int32_t* dtex = tex8 ? st.in<int32_t>(nullptr, 8 * n) : nullptr;
+  if (!d5 || (t && !dt) || (prim && !dprim) || (nx && !dnx) || (ny && !dny) || (nz && !dnz) || (tex8 && !dtex)) { ctx->err = "staging allocation failed"; return GLOME_E_HIP; }
+  glome_stats local;
+  int rc = glome_trace_batch_dev(s, n, din[0], din[1], din[2], din[3], din[4], din[5], din[6], lights, nlights, P, d5, dt, dprim, dnx, dny, dnz, dtex, stats ? stats : &local);
+  if (rc) return rc;
+  HIPCHK(ctx, hipMemcpy(rgbad, d5, n * 20, hipMemcpyDeviceToHost));
+  if (t) HIPCHK(ctx, hipMemcpy(t, dt, n * 4, hipMemcpyDeviceToHost));
+  if (prim) HIPCHK(ctx, hipMemcpy(prim, dprim, n * 4, hipMemcpyDeviceToHost));
+  if (nx) HIPCHK(ctx, hipMemcpy(nx, dnx, n * 4, hipMemcpyDeviceToHost));
+  if (ny) HIPCHK(ctx, hipMemcpy(ny, dny, n * 4, hipMemcpyDeviceToHost));
+  if (nz) HIPCHK(ctx, hipMemcpy(nz, dnz, n * 4, hipMemcpyDeviceToHost));
+  if (tex8) HIPCHK(ctx, hipMemcpy(tex8, dtex, n * 32, hipMemcpyDeviceToHost));
   return 0;
 }
 

@@ -5,6 +5,7 @@
  * sits behind are (paths relative to the reference tree):
  *   - the `Solid` class methods  rayint / shadow / inside   GlomeTrace/Data/Glome/Solid.hs:146-166
  *   - the tile map               renderTiles                 GlomeView/Glome.hs:379-386
+ *   - the ray tracer's entry     trace                       GlomeTrace/Data/Glome/Trace.hs:53-82
  *   - the scene constructors     sphere, triangle, box, ...  (cited per function below)
  * Each entry point cites the reference interface it replaces.  INTEGRATION.md shows the Haskell
  * `foreign import ccall` stubs a maintainer would add.
@@ -277,6 +278,40 @@ int glome_render_tiles_packed_batch_dev(glome_scene*, const glome_camera* cams, 
                                         const glome_render_params*, uint32_t* payload_dev, int64_t frame_stride_pixels, glome_stats*);
 int glome_render_packed_batch_dev(glome_scene*, const glome_camera* cams, int nframes, const glome_light* lights, int nlights,
                                   const glome_render_params*, uint32_t* packed_dev, int64_t frame_stride_pixels, glome_stats*);
+/* ---- the trace seam (Trace.trace, Trace.hs:53-82: "for most applications ... the entry point into the ray tracer") ----
+ * For a host with a ray generator of its own (depth of field, a fisheye or stereo camera, a light probe, a sampler other than
+ * renderTileSubsample, a picking ray): the device's own trace -- closest hit, the texture stack's fold (Trace.hs:67-80), the materials'
+ * shaders with their shadow and secondary rays (Shader.hs:65-189) -- over caller-supplied SoA ray streams, in one launch.  A ray's result
+ * is what glome_render computes for a pixel with that primary ray, and does not depend on the rays beside it in the stream. */
+typedef struct glome_trace_params {
+  int32_t maxdepth;    /* `recurs` of Trace.trace; 1..8, default 3 (Glome.hs:25) */
+  int32_t faithful;    /* as glome_render_params.faithful; REQUIRED when directions are not unit length (below) */
+  int32_t count_work;  /* as glome_render_params.count_work */
+} glome_trace_params;
+void glome_trace_params_default(glome_trace_params*);
+/* trace lights materialShader root (Ray o d) tmax maxdepth, for n <= 2^31 rays (Trace.hs:59-82, Shader.hs:65-189).
+ * rgbad: n*5 floats, (r, g, b, a, depth) per ray -- the tuple glome_render stores per pixel with fog = 0 (depth = ridepth, 1e6 for a
+ * miss).  tmax may be NULL (every ray: infinity = 1e6, Vec.hs:14).  t / prim / nx / ny / nz / tex8: the trace's own Rayint
+ * (TraceResult's third component, Trace.hs:49-51), laid out exactly as glome_rayint_batch writes them; any of them may be NULL.
+ * Directions are used as given: `trace` does not normalise and neither does this.  The production traversal (ordered early-out) is
+ * exact for unit-length rays only, so with faithful == 0 every direction must be unit length (|d|^2 within 1e-5 of 1); a launch that
+ * meets another one fails with GLOME_E_INVALID -- at once when `stats` is given, else at the next glome_ctx_synchronize -- and its
+ * outputs are not to be used.  With faithful == 1 the traversal is the reference's own and any direction is legal.
+ * The _dev form takes device pointers and is asynchronous on the context's stream and slot unless stats != NULL; it takes part in
+ * glome_ctx_timing_begin / _end like a render launch.  stats: rays_primary = n, shadow and secondary rays as in a render, n_tiles = the
+ * 64-ray work items, n_pixels = n. */
+int glome_trace_batch(glome_scene*, size_t n, const float* ox, const float* oy, const float* oz, const float* dx, const float* dy,
+                      const float* dz, const float* tmax, const glome_light* lights, int nlights, const glome_trace_params*,
+                      float* rgbad, float* t, int32_t* prim, float* nx, float* ny, float* nz, int32_t* tex8, glome_stats*);
+int glome_trace_batch_dev(glome_scene*, size_t n, const float* ox, const float* oy, const float* oz, const float* dx, const float* dy,
+                          const float* dz, const float* tmax, const glome_light* lights, int nlights, const glome_trace_params*,
+                          float* rgbad, float* t, int32_t* prim, float* nx, float* ny, float* nz, int32_t* tex8, glome_stats*);
+/* Host-only, no device: the kernel instance a trace launch gets (choose_trace, glome_amd/csrc/instances.hpp).  n rows of 11 inputs -- the
+ * eight scene traits of glome_sb_scene_traits, then faithful, count_work, maxdepth -- give n rows of 3 outputs: the instance (a flat-tier
+ * key with the bits glome_kernel_choice describes, TWO_ROWS never set; -1 / -2: the generic tier's kernel that counts work / does not),
+ * LB, and the wave slots per CU.  Returns n, or GLOME_E_INVALID for a null array. */
+int64_t glome_trace_kernel_choice(int64_t n, const int64_t* in11, int32_t* out3);
+
 /* ---- the whole-frame seam on several GPUs driven by ONE process (renderTiles' parMap over tiles + blitTile, Glome.hs:379-386) ----
  * scenes[i] = the same scene committed on context i (a context per GPU; rank 0's GPU receives the frame).  Tile k of the
  * frame -- 64x64 work tiles in renderTile mode, the 65x65 reference tiles in adaptive mode (whose pixels depend on the tile

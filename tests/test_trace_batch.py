@@ -1,0 +1,296 @@
+"""GPU suite (-m gpu): the trace seam, glome_trace_batch -- Trace.trace (Trace.hs:59-82) over caller-supplied ray streams -- against the
+oracle and against the product's own frames and rayint seam.
+
+The oracle has no per-ray trace; a 1 x 1 frame whose camera is (pos = o, fwd = d, up = 0, right = 0) traces exactly `Ray o (vnorm d)` to
+infinity with the scene's lights, so the oracle checks one ray with one such frame (oracle_trace below)."""
+import ctypes as C
+
+import numpy as np
+import pytest
+
+import parity
+import zoo
+from helpers import oracle_for, product_camera_lights, random_rays
+from glome_amd import _lib as L
+from glome_amd import api, scenes
+
+pytestmark = pytest.mark.gpu
+
+SCENES = dict(zoo.ALL)
+SCENES.update({"S1": lambda: scenes.s1(nlights=2), "S3small": lambda: scenes.s3(24), "S3mesh_small": lambda: scenes.s3(24, as_mesh=True), "S4": scenes.s4})
+N_RAYS = 4096
+
+
+def rays(seed, n=N_RAYS):
+    return random_rays(n, seed, center=(0, 1.5, 0), radius=13, spread=7)
+
+
+class Committed:
+    """a scene on the GPU with what the tests share: its lights, and the 4,096-ray trace of a seed (made once, never written to)"""
+
+    def __init__(self, ctx, name):
+        self.sd = SCENES[name]()
+        self.b = api.Builder()
+        self.nm, _ = self.sd.replay(self.b)
+        self.sc = ctx.commit(self.b, self.nm[self.sd.root])
+        self.cam, self.lights = product_camera_lights(self.sd)
+        self._base = {}
+
+    def base(self, seed=11):
+        if seed not in self._base:
+            ro, rd = rays(seed)
+            r = self.sc.trace(ro, rd, self.lights, want_hit=True)
+            for v in r.values():
+                if isinstance(v, np.ndarray):
+                    v.setflags(write=False)
+            self._base[seed] = (ro, rd, r)
+        return self._base[seed]
+
+
+@pytest.fixture(scope="module")
+def committed(gpu_ctx):
+    cache = {}
+
+    def get(name):
+        if name not in cache:
+            cache[name] = Committed(gpu_ctx, name)
+        return cache[name]
+    yield get
+    for c in cache.values():
+        c.sc.release()
+
+
+def rgbad(r):
+    return np.concatenate([r["rgba"], r["depth"][:, None]], axis=1)
+
+
+def frame_rays(cam, w, h):
+    """the primary rays of a w x h frame of the product's fp32 camera: get_coordsf and get_rayint (Glome.hs:27-33, 119-140) evaluated in
+    float64, rounded to float32 and renormalised as helpers.random_rays does -- the device's own rays to an ulp"""
+    x, y = np.meshgrid(np.arange(w, dtype=np.float64), np.arange(h, dtype=np.float64))
+    xc = ((x / w) * 2 - 1) * (w / h)
+    yc = -((y / h) * 2 - 1)
+    pos, fwd, up, right = (np.array(list(v), np.float64) for v in (cam.pos, cam.fwd, cam.up, cam.right))
+    d = fwd + right * (-xc[..., None]) + up * yc[..., None]
+    d = (d / np.linalg.norm(d, axis=-1, keepdims=True)).reshape(-1, 3).astype(np.float32)
+    d = (d / np.linalg.norm(d.astype(np.float64), axis=1, keepdims=True)).astype(np.float32)
+    o = np.broadcast_to(pos.astype(np.float32), d.shape).copy()
+    return o, d
+
+
+def oracle_trace(o, ro, rd, maxdepth):
+    """n x 5 (r, g, b, a, depth) from the oracle, one 1 x 1 frame per ray"""
+    out = np.zeros((len(ro), 5))
+    for i in range(len(ro)):
+        o.set_camera_vectors(ro[i].astype(np.float64), rd[i].astype(np.float64), [0, 0, 0], [0, 0, 0])
+        out[i] = o.render(1, 1, maxdepth=maxdepth, want_packed=False)[0][0, 0]
+    return out
+
+
+# ---------------------------------------------------------------- 1. the frame's own rays, against the oracle frame
+@pytest.mark.parametrize("name", ["S1", "S3small", "S3mesh_small", "S4", "flat_mixed", "materials", "mirror_terrain", "csg", "nested", "portal"])
+def test_frame_rays_traced_as_a_batch_give_the_oracle_frame(committed, name):
+    """Every flat class, the faithful instance (materials' Refract) and the generic tier: the 320 x 180 frame of test_render_vs_oracle, its
+    primary rays made on the host, under the gates that test holds the render kernels to -- ray counts included."""
+    c = committed(name)
+    o, d = frame_rays(c.cam, 320, 180)
+    r = c.sc.trace(o, d, c.lights, params=api.trace_params(maxdepth=3))
+    st = r["stats"]
+    assert st["n_pixels"] == 320 * 180 and st["n_tiles"] == 320 * 180 // 64
+    parity.check_image(rgbad(r).reshape(180, 320, 5), (st["rays_primary"], st["rays_shadow"], st["rays_secondary"]), c.sd, 320, 180, 3)
+
+
+# ---------------------------------------------------------------- 2. arbitrary rays, against the oracle ray by ray
+# Caps: rays beyond 1e-4 <= 24 of 4,096 -- twice the worst count (12) the oracle itself shows when it computes in fp32 on these rays
+# (0-12 per scene and seed); hit / miss flips <= 2 (the fp32 oracle: 0; parity.MISMATCH_MAX allows 1e-4); depth beyond 1e-4 relative on
+# rays both sides hit <= 4 (the fp32 oracle: 0-1).  The GPU's own counts on an MI355X, per scene and seed: beyond
+# 1e-4 0-13 (S1 0 / 0, S4 2 / 11, materials 7 / 10, nested 0 / 0, portal 1 / 3, textures 13 / 10), flips 0, depth 0.
+AWAY_MAX, FLIP_MAX, DEPTH_MAX = 24, 2, 4
+
+
+@pytest.mark.parametrize("seed", [11, 29])
+@pytest.mark.parametrize("name", ["S1", "S4", "materials", "nested", "portal", "textures"])
+def test_arbitrary_rays_against_the_oracle_ray_by_ray(committed, name, seed):
+    c = committed(name)
+    ro, rd, r = c.base(seed)
+    got = rgbad(r).astype(np.float64)
+    o, _, _ = oracle_for(c.sd)
+    ref = oracle_trace(o, ro, rd, 3)
+    hit_g, hit_r = got[:, 4] < 1e6, ref[:, 4] < 1e6
+    assert 0.5 < hit_r.mean() < 0.95, hit_r.mean()  # (the inputs are not empty: the oracle hits something with 65-89 % of these rays)
+    e = (np.abs(got[:, :4] - ref[:, :4]) / np.maximum(1.0, np.abs(ref[:, :4]))).max(axis=1)
+    both = hit_g & hit_r
+    drel = np.abs(got[both, 4] - ref[both, 4]) / np.maximum(1.0, ref[both, 4])
+    levels = {"away": int((e > 1e-4).sum()), "flips": int((hit_g != hit_r).sum()), "depth": int((drel > 1e-4).sum()), "hit_frac": float(hit_r.mean())}
+    print("trace_vs_oracle", name, seed, levels)
+    assert levels["away"] <= AWAY_MAX, levels
+    assert levels["flips"] <= FLIP_MAX, levels
+    assert levels["depth"] <= DEPTH_MAX, levels
+
+
+# ---------------------------------------------------------------- 3. tail and order
+def _trace_into_sentinels(c, ro, rd, n, params=None):
+    """the first n rays through the C ABI into buffers one element longer than n, pre-filled with a sentinel"""
+    params = params or api.trace_params(maxdepth=3)
+    cols = [np.ascontiguousarray(a[:n]) for a in (ro[:, 0], ro[:, 1], ro[:, 2], rd[:, 0], rd[:, 1], rd[:, 2])]
+    out = np.full((n + 1, 5), -7.5, np.float32)
+    t = np.full(n + 1, -7.5, np.float32); prim = np.full(n + 1, -77, np.int32)
+    nx, ny, nz = (np.full(n + 1, -7.5, np.float32) for _ in range(3))
+    tex = np.full((n + 1, 8), -77, np.int32)
+    la = (L.Light * max(1, len(c.lights)))(*c.lights)
+    st = L.Stats()
+    rc = c.sc.lib.glome_trace_batch(c.sc.h, n, *[a.ctypes.data_as(L.c_fp) for a in cols], None, la, len(c.lights), C.byref(params), out.ctypes.data_as(L.c_fp),
+                                    t.ctypes.data_as(L.c_fp), prim.ctypes.data_as(L.c_ip), nx.ctypes.data_as(L.c_fp), ny.ctypes.data_as(L.c_fp), nz.ctypes.data_as(L.c_fp),
+                                    tex.ctypes.data_as(L.c_ip), C.byref(st))
+    return rc, out, t, prim, np.stack([nx, ny, nz], 1), tex, st
+
+
+@pytest.mark.parametrize("name", ["S4", "nested"])
+def test_tail_and_order(committed, name):
+    """A ray's result depends neither on how many rays follow it nor on its place in the stream: the first n rays (a lone ray, a wave less
+    one, a wave, a wave and one, five waves and 37) give the first n rows of the 4,096-ray result bit for bit, a permutation of the rays the
+    permuted rows, and nothing is written past row n."""
+    c = committed(name)
+    ro, rd, base = c.base()
+    want = rgbad(base)
+    for n in (1, 63, 64, 65, 357):
+        rc, out, t, prim, nrm, tex, st = _trace_into_sentinels(c, ro, rd, n)
+        assert rc == 0, c.sc.ctx.err()
+        assert np.array_equal(out[:n], want[:n]) and np.array_equal(prim[:n], base["prim"][:n]), n
+        assert np.array_equal(t[:n], base["t"][:n]) and np.array_equal(nrm[:n], base["n"][:n]) and np.array_equal(tex[:n], base["tex"][:n]), n
+        assert np.all(out[n] == -7.5) and t[n] == -7.5 and prim[n] == -77 and np.all(nrm[n] == -7.5) and np.all(tex[n] == -77), n
+        assert (st.rays_primary, st.n_pixels, st.n_tiles) == (n, n, (n + 63) // 64)
+    perm = np.random.default_rng(3).permutation(357)
+    r = c.sc.trace(ro[:357][perm], rd[:357][perm], c.lights, params=api.trace_params(maxdepth=3), want_hit=True)
+    assert np.array_equal(rgbad(r), want[:357][perm]) and np.array_equal(r["prim"], base["prim"][:357][perm])
+
+
+# ---------------------------------------------------------------- 4. the trace's Rayint is rayint's
+@pytest.mark.parametrize("name", ["S1", "S3small", "nested"])
+def test_the_traces_rayint_is_the_rayint_seams(committed, name):
+    """TraceResult's third component: the closest hit comes before any shading, so it is what glome_rayint_batch answers, bit for bit."""
+    c = committed(name)
+    ro, rd, r = c.base()
+    ri = c.sc.rayint(ro, rd)
+    assert np.array_equal(r["prim"], ri["prim"]) and np.array_equal(r["tex"], ri["tex"])
+    assert np.array_equal(r["t"], ri["t"]) and np.array_equal(r["n"], ri["n"])
+    assert np.array_equal(r["depth"], np.where(r["t"] >= 0, r["t"], np.float32(1e6)))
+    assert 0.3 < np.mean(r["t"] >= 0) < 0.98
+
+
+# ---------------------------------------------------------------- 5. tmax
+def test_tmax_bounds_the_primary_ray(committed):
+    c = committed("S4")
+    ro, rd, base = c.base()
+    o, om, _ = oracle_for(c.sd)
+    t_ref = o.rayint(om[c.sd.root], ro.astype(np.float64), rd.astype(np.float64))["t"]
+    hit = t_ref >= 0
+    assert hit.sum() > 1000
+    ro, rd, t_ref = ro[hit], rd[hit], t_ref[hit].astype(np.float32)
+    short = c.sc.trace(ro, rd, c.lights, tmax=0.5 * t_ref, want_hit=True)
+    assert np.all(rgbad(short) == np.array([0, 0, 0, 0, 1e6], np.float32)) and np.all(short["prim"] == -1) and np.all(short["t"] == -1)
+    far = c.sc.trace(ro, rd, c.lights, tmax=2 * t_ref, want_hit=True)
+    assert np.array_equal(far["prim"], base["prim"][hit])
+    e = (np.abs(far["rgba"].astype(np.float64) - base["rgba"][hit]) / np.maximum(1.0, np.abs(base["rgba"][hit]))).max(axis=1)
+    assert (e > 1e-4).sum() <= 2, int((e > 1e-4).sum())
+
+
+# ---------------------------------------------------------------- 6. device pointers
+@pytest.mark.parametrize("name", ["S1", "nested"])
+def test_device_pointer_form_equals_the_host_form(gpu_ctx, committed, name):
+    import torch
+    c = committed(name)
+    ro, rd, base = c.base()
+    n = len(ro)
+    dev = torch.device("cuda:0")
+    cols = [torch.tensor(np.ascontiguousarray(a), device=dev) for a in (ro[:, 0], ro[:, 1], ro[:, 2], rd[:, 0], rd[:, 1], rd[:, 2])]
+    out = torch.zeros((n, 5), dtype=torch.float32, device=dev)
+    t = torch.zeros(n, dtype=torch.float32, device=dev)
+    prim = torch.zeros(n, dtype=torch.int32, device=dev)
+    tex = torch.zeros((n, 8), dtype=torch.int32, device=dev)
+    torch.cuda.synchronize()
+    ptrs = [x.data_ptr() for x in cols] + [None]
+    # asynchronous without statistics: the results are there after the context's synchronize
+    assert c.sc.trace_dev(n, ptrs, c.lights, api.trace_params(maxdepth=3), out.data_ptr(), [t.data_ptr(), prim.data_ptr(), None, None, None, tex.data_ptr()], want_stats=False) is None
+    gpu_ctx.synchronize()
+    assert np.array_equal(out.cpu().numpy(), rgbad(base))
+    assert np.array_equal(t.cpu().numpy(), base["t"]) and np.array_equal(prim.cpu().numpy(), base["prim"]) and np.array_equal(tex.cpu().numpy(), base["tex"])
+    # with statistics, and an explicit tmax stream of infinities: the same rows and the host form's ray counts
+    out.zero_()
+    tm = torch.full((n,), 1e6, dtype=torch.float32, device=dev)
+    torch.cuda.synchronize()
+    st = c.sc.trace_dev(n, ptrs[:6] + [tm.data_ptr()], c.lights, api.trace_params(maxdepth=3), out.data_ptr())
+    assert np.array_equal(out.cpu().numpy(), rgbad(base))
+    assert all(st[k] == base["stats"][k] for k in ("rays_primary", "rays_shadow", "rays_secondary", "n_tiles", "n_pixels")) and st["rays_primary"] == n
+
+
+# ---------------------------------------------------------------- 7. refusals
+def test_refused_arguments_fail_with_a_status(gpu_ctx, committed):
+    """Decided on the host: nothing is launched, nothing is written."""
+    c = committed("S1")
+    ro, rd, _ = c.base()
+    for md in (0, 9):
+        with pytest.raises(api.GlomeError, match=r"status -5"):
+            c.sc.trace(ro[:64], rd[:64], c.lights, params=api.trace_params(maxdepth=md))
+        rc, out, *_ = _trace_into_sentinels(c, ro, rd, 64, api.trace_params(maxdepth=md))
+        assert rc == L.E_LIMIT and "maxdepth" in gpu_ctx.err() and np.all(out == -7.5)
+    with pytest.raises(api.GlomeError, match=r"status -5"):
+        c.sc.trace(ro[:64], rd[:64], [c.lights[0]] * 17)
+    cols = [np.ascontiguousarray(a[:64]) for a in (ro[:, 0], ro[:, 1], ro[:, 2], rd[:, 0], rd[:, 1], rd[:, 2])]
+    out = np.full((65, 5), -7.5, np.float32)
+    la = (L.Light * len(c.lights))(*c.lights)
+    P = api.trace_params()
+    lib, fp = c.sc.lib, lambda a: a.ctypes.data_as(L.c_fp)
+    for k in range(6):  # a null ray stream
+        args = [fp(a) for a in cols]
+        args[k] = None
+        assert lib.glome_trace_batch(c.sc.h, 64, *args, None, la, len(c.lights), C.byref(P), fp(out), None, None, None, None, None, None, None) == L.E_INVALID
+    assert lib.glome_trace_batch(c.sc.h, 64, *[fp(a) for a in cols], None, la, len(c.lights), C.byref(P), None, None, None, None, None, None, None, None) == L.E_INVALID  # no rgbad
+    assert lib.glome_trace_batch(c.sc.h, 64, *[fp(a) for a in cols], None, la, len(c.lights), None, fp(out), None, None, None, None, None, None, None) == L.E_INVALID  # no params
+    assert lib.glome_trace_batch(c.sc.h, 64, *[fp(a) for a in cols], None, None, 1, C.byref(P), fp(out), None, None, None, None, None, None, None) == L.E_INVALID  # lights
+    assert lib.glome_trace_batch(c.sc.h, 64, *[fp(a) for a in cols], None, la, -1, C.byref(P), fp(out), None, None, None, None, None, None, None) == L.E_INVALID
+    # n = 0: success, nothing touched (not even the null streams)
+    assert lib.glome_trace_batch(c.sc.h, 0, None, None, None, None, None, None, None, la, len(c.lights), C.byref(P), fp(out), None, None, None, None, None, None, None) == 0
+    assert lib.glome_trace_batch_dev(c.sc.h, 0, None, None, None, None, None, None, None, la, len(c.lights), C.byref(P), None, None, None, None, None, None, None, None) == 0
+    assert np.all(out == -7.5)
+    gpu_ctx.synchronize()
+
+
+@pytest.mark.parametrize("name", ["S1", "nested"])
+def test_directions_that_are_not_unit_length_need_faithful(gpu_ctx, committed, name):
+    """One contract on both tiers: without `faithful` a direction that is not unit length fails the call (an ordinary flag in the slot's
+    error word, no fault); with it the reference's own traversal takes any direction -- a ray twice as long hits the same thing at half
+    the distance."""
+    c = committed(name)
+    ro, rd, base = c.base()
+    # The ray that is doubled.  The reference's rayint is not homogeneous in the direction on every primitive: rayint_sphere
+    # (Sphere.hs:20-41) is written for unit directions, and a ray twice as long may hit another sphere altogether (ray 0 on S1: the fp64
+    # oracle answers primitive 74 at 17.09 for the unit ray, primitive 96 at 4.64 for the doubled one).  So the ray is the first one for
+    # which the fp64 oracle itself shows the property -- the same primitive at half the distance.
+    oc, om, _ = oracle_for(c.sd)
+    o64, d64 = ro[:128].astype(np.float64), rd[:128].astype(np.float64)
+    unit, twice = oc.rayint(om[c.sd.root], o64, d64), oc.rayint(om[c.sd.root], o64, 2 * d64)
+    i = int(np.flatnonzero((unit["t"] >= 0) & (twice["prim"] == unit["prim"]) & (np.abs(twice["t"] - 0.5 * unit["t"]) <= 1e-9 * unit["t"]))[0])
+    assert base["t"][i] >= 0
+    o, d = ro[:128].copy(), rd[:128].copy()
+    o[0] = o[1] = ro[i]
+    d[0] = rd[i]; d[1] = rd[i] * np.float32(2)
+    with pytest.raises(api.GlomeError, match="faithful") as ei:
+        c.sc.trace(o, d, c.lights)
+    assert "status -1" in str(ei.value)
+    gpu_ctx.synchronize()  # (the flag was read and cleared with the failing call)
+    ok = c.sc.trace(o[[0] + list(range(2, 128))], d[[0] + list(range(2, 128))], c.lights, want_hit=True)  # the unit ones alone: as ever
+    assert np.array_equal(ok["t"][0], base["t"][i]) and np.array_equal(ok["prim"][1:], base["prim"][2:128])
+    r = c.sc.trace(o, d, c.lights, params=api.trace_params(faithful=1), want_hit=True)
+    assert r["t"][0] > 0 and r["prim"][1] == r["prim"][0] == base["prim"][i]
+    assert abs(r["t"][1] - 0.5 * r["t"][0]) <= 1e-4 * 0.5 * r["t"][0]
+    # the device-pointer form without statistics reports the refusal at the next synchronize
+    import torch
+    dev = torch.device("cuda:0")
+    cols = [torch.tensor(np.ascontiguousarray(a), device=dev) for a in (o[:, 0], o[:, 1], o[:, 2], d[:, 0], d[:, 1], d[:, 2])]
+    out = torch.zeros((128, 5), dtype=torch.float32, device=dev)
+    torch.cuda.synchronize()
+    c.sc.trace_dev(128, [x.data_ptr() for x in cols] + [None], c.lights, api.trace_params(), out.data_ptr(), want_stats=False)
+    with pytest.raises(api.GlomeError, match="faithful"):
+        gpu_ctx.synchronize()
+    gpu_ctx.synchronize()
