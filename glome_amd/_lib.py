@@ -150,6 +150,7 @@ SYMBOLS = [
     ("glome_kernel_choice", C.c_int64, [C.c_int64, C.POINTER(C.c_int64), c_ip]),
     ("glome_sb_scene_traits", C.c_int, [vp, C.c_int32, C.POINTER(C.c_int64)]),
     ("glome_ctx_coord_tables", C.c_int, [vp, C.c_int, C.c_int, c_fp, c_fp, C.c_int]),
+    ("glome_ctx_last_cull", C.c_int, [vp, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     ("glome_tiles_pack_dev", C.c_int, [vp, C.POINTER(RenderParams), vp, vp]),
     ("glome_tiles_blit_dev", C.c_int, [vp, C.POINTER(RenderParams), C.c_int, C.c_int, vp, vp, vp]),
     ("glome_tiles_blit_all_dev", C.c_int, [vp, C.POINTER(RenderParams), C.c_int, vp, C.c_int64, vp, vp]),

@@ -15,7 +15,8 @@
 //   k_ss_frame_flat / k_ss_frame_generic  the adaptive sampler (renderTileSubsample, Glome.hs:226-323): five passes per
 //                                       tile, one launch per frame or batch of frames
 //   k_rayint_batch / k_shadow_batch / k_inside_batch   the `Solid` method seams on SoA ray streams (the generic tier's: kernel_parts.hip)
-//   (runtime.hip: k_tiles_pack / k_tiles_blit / k_tiles_blit_packed, Tile payload <-> frame; bih_build_device.hpp: k_bb_* / k_mb_*, the tree builders)
+//   (runtime.hip: k_tiles_pack / k_tiles_blit / k_tiles_blit_packed, Tile payload <-> frame; bih_build_device.hpp: k_bb_* / k_mb_*, the tree builders;
+//   cull_kernels.hpp: k_cull_items, the cull pass in front of the flagship instance of k_render_flat, which leaves that launch's ticket list)
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -193,8 +194,10 @@ struct TicketQueue {
       shard = (shard + 1) % kQueueShards;
     }
   }
-  // The lean loop's take: the ticket the atomic returns is handed out on the spot (inext / left / cur are then dead: two scalar registers
-  // fewer through both walks of the flagship instance).
+  // The flagship loop's take: the ticket the atomic returns is handed out on the spot (inext / left / cur are then dead: two scalar registers
+  // fewer through both walks of the flagship instance).  Its queue runs over the positions of the launch's ticket list (cull_kernels.hpp):
+  // head h's ticket i is position ticket_item(i, h), which grows with i, so the head is dry from the first position at or past the list's
+  // length -- a word of device memory the cull pass wrote, read here, beside the atomic, and dead before the walks.
   __device__ __forceinline__ uint32_t take_direct(const DRenderArgs& A) {
     constexpr uint32_t kAll = (1u << kQueueShards) - 1u;
     for (;;) {
@@ -203,7 +206,8 @@ struct TicketQueue {
         uint32_t i = 0;
         if (LaneStack::lane() == 0) i = atomicAdd(&A.counters->heads[shard * kQueueHeadStride], 1u);
         i = uni(i);
-        if (i < A.shard_cap) return ticket_item(i, shard);
+        const uint32_t t = ticket_item(i, shard);
+        if (t < ld_word_u(&A.counters->list_len, 0)) return t;
         mark_dry(A);
       }
       shard = (shard + 1) % kQueueShards;
@@ -245,23 +249,25 @@ __device__ __forceinline__ void render_loop(const DRenderArgs& A_, TIER& Tk) {
     else { if (LaneStack::lane() == 0) w = Q.take(A); w = __shfl(w, 0, 64); }
     if (w == kNoTicket) break;
     uint32_t frame;  // wave-uniform
-    if (A.chunks_per_frame) {
+    if constexpr (ITEMS) {
+      // the ticket is a position of the launch's ticket list: the live items in the launch's order, every entry a frame and an item of
+      // its plan -- no padding, no division (the cull pass decoded the position: cull_kernels.hpp queue_position)
+      const uint32_t e = ld_word_u(A.list, w);
+      frame = e >> kListFrameShift;
+      w = e & ((1u << kListFrameShift) - 1u);
+    } else if (A.chunks_per_frame) {
       // chunk by chunk through all frames: the same 64x64 work tile of every view one after the other (neighbouring views walk the
       // same part of the tree), and what a launch ends with is the last chunks of ALL its frames, not the whole of its last frame
       const uint32_t g = w / kQueueChunk, nf = (uint32_t)A.nframes;
       if (g >= A.chunks_per_frame * nf) continue;  // padding of the last round of chunks
-      // (lean: the quotient by the launch's multiplier -- s_mul_hi_u32 -- instead of two emulated 32-bit divisions of ~25 instructions each)
-      const uint32_t q = ITEMS ? __umulhi(g, A.nframes_rcp) : g / nf;
+      const uint32_t q = g / nf;
       frame = g - q * nf;
       w = q * kQueueChunk + (w % kQueueChunk);
       if (w >= A.total_waves) continue;            // padding of a frame's last chunk
     } else {
       if (w >= A.total_waves * (uint32_t)A.nframes) continue;  // padding of the last round of chunks
-      frame = 0;
-      if (!ITEMS || w >= A.total_waves) {  // (a launch of one frame never divides)
-        frame = w / A.total_waves;
-        w -= frame * A.total_waves;
-      }
+      frame = w / A.total_waves;
+      w -= frame * A.total_waves;
     }
     int px = 0, py = 0;
     size_t dense_off = 0;
@@ -295,15 +301,7 @@ __device__ __forceinline__ void render_loop(const DRenderArgs& A_, TIER& Tk) {
       px = 0; py = 0; dense_off = 0;
       (void)item_pixel(it, A.tiles, (int)LaneStack::lane(), px, py, dense_off);
     } else if constexpr (LEAN) { px = 0; py = 0; dense_off = 0; (void)work_to_pixel(A, w, (int)LaneStack::lane(), px, py, dense_off); }
-    float depth = h.hit ? h.t : kInf;      // ridepth
-    float r = c.r;
-    if (A.fog) r = r + (depth / 400);      // renderTile's debug fog (Glome.hs:174, Q20)
-    size_t o = (A.dense ? dense_off : (size_t)py * A.width + px) + (size_t)frame * A.frame_stride;
-    if (A.out5) {
-      float* out = A.out5 + o * 5;
-      out[0] = r; out[1] = c.g; out[2] = c.b; out[3] = c.a; out[4] = depth;
-    }
-    if (A.packed) A.packed[o] = rgbf(r * c.a, c.g * c.a, c.b * c.a);  // blitTile (Glome.hs:353-358)
+    store_pixel(A, frame, px, py, dense_off, c, h.hit ? h.t : kInf);  // (ridepth)
   }
   Q.leave(A_);
 }

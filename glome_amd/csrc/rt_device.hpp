@@ -116,6 +116,10 @@ GD DItem ld_item_u(const DItem* p, uint32_t i) {  // (a frame is at most 2^30 pi
   u32x4 v = *(const u32x4 __attribute__((address_space(4)))*)(b + (uint32_t)(uni(i) << 4));
   DItem r; r.x = v.x; r.y = v.y; r.off = v.z; r.pitch = v.w; return r;
 }
+GD uint32_t ld_word_u(const uint32_t* p, uint32_t i) {  // one word at a wave-uniform index (the ticket list: < 2^30 entries): s_load_dword
+  const char __attribute__((address_space(4)))* b = (const char __attribute__((address_space(4)))*)(uintptr_t)p;
+  return *(const uint32_t __attribute__((address_space(4)))*)(b + (uint32_t)(uni(i) << 2));
+}
 typedef float f32x4_a4 __attribute__((ext_vector_type(4), aligned(4)));  // (the cameras sit at 4-byte aligned offsets of the argument segment; s_load_dwordx4 needs no more)
 GD DCamera ld_camera_u(const void __attribute__((address_space(4)))* base, uint32_t byte_off) {  // both wave-uniform
   const f32x4_a4 __attribute__((address_space(4)))* q = (const f32x4_a4 __attribute__((address_space(4)))*)((const char __attribute__((address_space(4)))*)base + byte_off);
@@ -889,6 +893,14 @@ GD PacketResult bih_tri_packet_hw(const F4* nodes, uint32_t nbytes, const float*
 }
 #endif
 
+// What a packet walk starts with, shared with the cull pass of the flagship launch (cull_kernels.hpp), which must decide exactly as the
+// walk does: the ray's interval in the tree's bounds (header words h0, h1) clipped to d, and whether a lane enters the root branch.
+GD void bih_root_interval(const Ray& r, const F4& h0, const F4& h1, float d, float& nearv, float& farv) {
+  bbclip_ub(r, v3(h0), v3(h1), nearv, farv);
+  farv = gminf(d, farv);  // `traverse root near (fmin d far)`, Bih.hs:368
+}
+GD bool bih_root_enters(bool valid, float nearv, float farv) { return valid && !(nearv > farv); }
+
 template <int MODE, bool COUNT, int LEAFK = 0, class STK>
 GD bool bih_tri_wave(const DScene& S, uint32_t hdr, const Ray& r, float d, bool valid, STK& stk, Cnt& cnt, float& best_t, uint32_t& best_rec) {
   hdr = uni(hdr);
@@ -900,8 +912,7 @@ GD bool bih_tri_wave(const DScene& S, uint32_t hdr, const Ray& r, float d, bool 
   const uint32_t ref = uni(as_u(h0.w));
   const V3 rcp = v3(dir_rcp(r.d.x), dir_rcp(r.d.y), dir_rcp(r.d.z));
   float nearv, farv;
-  bbclip_ub(r, v3(h0), v3(h1), nearv, farv);
-  farv = gminf(d, farv);  // `traverse root near (fmin d far)`, Bih.hs:368
+  bih_root_interval(r, h0, h1, d, nearv, farv);
   if (ref & BREF_LEAF) {
     // A one-leaf tree: `rayint [s] r far` over its items (Bih.hs:339), per lane.  Nothing is pushed -- the kernels that
     // keep only two stack rows per entry (lane_stack<TWO_ROWS>) rely on that; bih_tri's continuation entries for leaves
@@ -927,7 +938,7 @@ GD bool bih_tri_wave(const DScene& S, uint32_t hdr, const Ray& r, float d, bool 
   // `am`: the lanes whose ray has a non-empty interval in the current node.  Their (near, far) are live; the other
   // lanes' are don't-cares, so no sentinel values are needed and plain min / max serve (a NaN plane distance only
   // arises on a lane that fails the activity test of that child).
-  LaneMask todo = wave_ballot(valid && !(nearv > farv));
+  LaneMask todo = wave_ballot(bih_root_enters(valid, nearv, farv));
   bool occ = false;
   while (todo != 0) {
     const uint32_t fwdbits = uni(first_lane_value(todo, oct));  // per axis: do the rays of this walk run towards +axis
@@ -1951,6 +1962,19 @@ GD float cap1(float x) { return x >= 1 ? 1 - kDel : x; }  // Glome.hs:98-101
 GD uint32_t rgbf(float r, float g, float b) {            // Glome.hs:107-110 (wraps like Word32 arithmetic)
   int ri = (int)floorf(cap1(r) * 256), gi = (int)floorf(cap1(g) * 256), bi = (int)floorf(cap1(b) * 256);
   return (uint32_t)ri * 65536u + (uint32_t)gi * 256u + (uint32_t)bi;
+}
+
+// A pixel of a renderTile frame goes out: the tail of the render loop, and what the cull pass writes for the pixels of a dead item
+// (c = ca(0, 0, 0, 0), depth = kInf).  frame: the launch's frame; dense_off: the pixel's place in a dense tile payload.
+GD void store_pixel(const DRenderArgs& A, uint32_t frame, int px, int py, size_t dense_off, const CA& c, float depth) {
+  float r = c.r;
+  if (A.fog) r = r + (depth / 400);      // renderTile's debug fog (Glome.hs:174, Q20)
+  size_t o = (A.dense ? dense_off : (size_t)py * A.width + px) + (size_t)frame * A.frame_stride;
+  if (A.out5) {
+    float* out = A.out5 + o * 5;
+    out[0] = r; out[1] = c.g; out[2] = c.b; out[3] = c.a; out[4] = depth;
+  }
+  if (A.packed) A.packed[o] = rgbf(r * c.a, c.g * c.a, c.b * c.a);  // blitTile (Glome.hs:353-358)
 }
 
 

@@ -149,6 +149,9 @@ struct DCounters {  // device-side atomics, one block per launch slot
   unsigned int done_pad[31];
   unsigned int done;       // waves of the running launch that have left the queue (the last one resets the heads)
   unsigned int error;      // sticky: kErr* bits, set when a device-side limit was hit (stack overflow guard, CSG cap) or a trace launch refused a ray; reset_counters stops short of it
+  // the flagship launch's cull pass (cull_kernels.hpp); past `error`, so reset_counters leaves them alone
+  unsigned int list_len;   // live work items of the launch = entries of the slot's ticket list: written by the cull pass, read by every take of the render kernel
+  unsigned int cull_done;  // blocks of the running cull pass that have stored their chunk's mask (the last one scans and puts it back to zero)
 };
 constexpr unsigned int kErrLimit = 1u;    // a device-side limit (what every kernel reports)
 constexpr unsigned int kErrNonUnit = 2u;  // a trace launch without `faithful` met a direction that is not unit length (trace_kernels.hpp; no other kernel sets it)
@@ -187,11 +190,13 @@ struct DRenderArgs {
   uint32_t chunks_per_frame;  // > 0: the frames of the launch are interleaved in the queue chunk by chunk (chunk c of every frame, then chunk
                               // c + 1 of every frame ...; a chunk = kQueueChunk items of ONE frame), chunks_per_frame = ceil(total_waves / kQueueChunk);
                               // 0: frame after frame
-  uint32_t nframes_rcp;   // m = floor(2^32 / nframes) + 1 (nframes >= 2): chunk / nframes = mulhi(chunk, m).  m * nframes = 2^32 + e with 0 < e <= nframes,
-                          // so the quotient is exact while chunk * e < 2^32, that is for chunk < 2^32 / nframes; a chunk index is < 2^32 / kQueueChunk (static_assert below)
   int32_t want_counters;  // 0: nobody will read the ray / work counters of this launch -- the waves skip the flush
   DCamera more_cams[kMaxBatchFrames - 1];
+  const uint32_t* list;   // the flagship launch's ticket list (the slot's; kListFrameShift): counters->list_len entries, the live items in the launch's order
 };
+// an entry of the ticket list: frame << kListFrameShift | item of the frame's plan (a frame is at most 2^24 items, a launch at most 32 frames)
+constexpr uint32_t kListFrameShift = 24;
+static_assert(kMaxBatchFrames <= (1 << (32 - kListFrameShift)), "a ticket list entry holds the frame in its top bits");
 
 // The arguments of a trace launch (trace_kernels.hpp: Trace.trace over a caller's SoA ray streams).  No frame, no tile, item or
 // coordinate table: work item w is rays 64 w .. 64 w + 63.
@@ -209,6 +214,5 @@ struct DTraceArgs {
   float* t; int32_t* prim; float *nx, *ny, *nz; int32_t* tex8;  // the trace's own Rayint, as the rayint seam writes it; any may be null
   DCounters* counters;
 };
-static_assert(kMaxBatchFrames <= (int)kQueueChunk, "DRenderArgs::nframes_rcp: chunk indices (< 2^32 / kQueueChunk) must stay below 2^32 / nframes");
 
 }  // namespace glome

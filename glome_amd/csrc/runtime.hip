@@ -1,8 +1,8 @@
 // runtime.hip -- the device half of the C ABI (include/glome_hip.h): context, slots, tile and coordinate caches, scene commit / upload,
 // the whole-frame render, the per-ray batch seams, tile transport and the multi-GPU driver.  Compiled once.  It launches the render,
 // sampler and batch kernels through kernel_launch.hpp (the instances live in kernel_parts.hip, chosen by instances.hpp) and holds
-// only the light kernels: the kernel-argument self-test, the coordinate tables, tile transport and the tree builders
-// (bih_build_device.hpp).
+// only the light kernels: the kernel-argument self-test, the coordinate tables, tile transport, the tree builders
+// (bih_build_device.hpp) and the flagship launch's cull pass (cull_kernels.hpp).
 #include <hip/hip_runtime.h>
 
 #include <cstdio>
@@ -21,6 +21,7 @@
 #include "instances.hpp"
 #include "kernel_launch.hpp"
 #include "bih_build_device.hpp"
+#include "cull_kernels.hpp"
 
 using namespace glome;
 
@@ -116,6 +117,9 @@ struct glome_ctx {
     size_t ovf_bytes = 0;
     float* d_scratch = nullptr;  // adaptive sampler working buffer
     size_t scratch_bytes = 0;
+    uint32_t* d_list = nullptr;  // the flagship launch's ticket list, then its cull pass's chunk masks (cull_kernels.hpp)
+    size_t list_items = 0;       // ... sized for this many work items (ensure_list)
+    uint32_t cull_total = 0;     // work items of the slot's last flagship launch (its live ones: DCounters::list_len)
     bool launched = false;  // a launch went out on this slot since its error word was last polled
     hipStream_t launched_on = nullptr;  // ... on this stream (a caller's own stream is the caller's to synchronise)
   };
@@ -287,6 +291,7 @@ void glome_ctx_destroy(glome_ctx* c) {
     if (sl.d_counters) (void)hipFree(sl.d_counters);
     if (sl.d_ovf) (void)hipFree(sl.d_ovf);
     if (sl.d_scratch) (void)hipFree(sl.d_scratch);
+    if (sl.d_list) (void)hipFree(sl.d_list);
   }
   if (c->ev0) (void)hipEventDestroy(c->ev0);
   if (c->ev1) (void)hipEventDestroy(c->ev1);
@@ -315,6 +320,15 @@ int glome_ctx_use_slot(glome_ctx* c, void* stream, int slot) {
 int glome_ctx_set_grid_per_cu(glome_ctx* c, int waves_per_cu) {
   if (!c || waves_per_cu < 0 || waves_per_cu > 32) return GLOME_E_INVALID;
   c->grid_per_cu = waves_per_cu;
+  return 0;
+}
+int glome_ctx_last_cull(glome_ctx* c, int64_t* live, int64_t* total) {
+  if (!c || !live || !total) return GLOME_E_INVALID;
+  HIPCHK(c, hipSetDevice(c->device));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  unsigned int n = 0;
+  if (c->slot().cull_total) HIPCHK(c, hipMemcpy(&n, &c->slot().d_counters->list_len, sizeof(n), hipMemcpyDeviceToHost));
+  *live = (int64_t)n; *total = (int64_t)c->slot().cull_total;
   return 0;
 }
 int glome_ctx_timing_begin(glome_ctx* c, int max_launches) {
@@ -560,6 +574,18 @@ static int ensure_scratch(glome_ctx* ctx, size_t need) {
   sl.scratch_bytes = need;
   return 0;
 }
+// The ticket list of a flagship launch and, behind it, the two mask words per chunk of its cull pass: room for a launch of kMaxBatchFrames
+// frames of the plan (`per_frame` items, chunked per frame), so a slot allocates once per frame size.
+static size_t list_chunks(size_t items) { return (items + kQueueChunk - 1) / kQueueChunk + kMaxBatchFrames; }
+static int ensure_list(glome_ctx* ctx, uint32_t per_frame) {
+  glome_ctx::Slot& sl = ctx->slot();
+  const size_t need = (size_t)per_frame * kMaxBatchFrames;
+  if (need <= sl.list_items) return 0;
+  if (sl.d_list) { HIPCHK(ctx, hipStreamSynchronize(ctx->stream)); HIPCHK(ctx, hipFree(sl.d_list)); sl.d_list = nullptr; sl.list_items = 0; }
+  HIPCHK(ctx, hipMalloc((void**)&sl.d_list, (need + 2 * list_chunks(need)) * sizeof(uint32_t)));
+  sl.list_items = need;
+  return 0;
+}
 // The device-side error word is sticky: kernels only ever OR into it, the counter reset leaves it alone, and it is read --
 // and cleared -- where the host waits anyway (statistics, the host-buffer seams, glome_ctx_synchronize).  So a launch
 // that nobody asked statistics of (the pipelined frame path) still reports a CSG-advance or frame-pool limit, at the
@@ -649,7 +675,6 @@ static int render_impl(glome_scene* s, const glome_camera* cam, const glome_ligh
     if ((rc = get_coord_tables(ctx, P->width, P->height, &ct))) return rc;
     A.xc_tab = ct; A.yc_tab = ct + P->width;
   }
-  A.nframes_rcp = nframes > 1 ? (uint32_t)((1ull << 32) / (uint64_t)nframes) + 1u : 0u;
   {  // tickets per queue head: the launch's chunks dealt round-robin over the heads, the last round padded
     A.chunks_per_frame = (nframes > 1 && P->mode == GLOME_MODE_TILE) ? (A.total_waves + kQueueChunk - 1) / kQueueChunk : 0u;
     const uint32_t tickets = A.chunks_per_frame ? A.chunks_per_frame * kQueueChunk * (uint32_t)nframes : A.total_waves * (uint32_t)nframes, round = kQueueChunk * kQueueShards;
@@ -708,8 +733,21 @@ static int render_impl(glome_scene* s, const glome_camera* cam, const glome_ligh
     const size_t lds = ch.generic ? 0 : flat_lds_bytes(s->tr.stack_cap, ch.two_rows);
     const int grid = persistent_grid(ctx, lds, items, waves_per_cu(ch), grid_floor(s));
     if (!ch.generic && (rc = ensure_overflow(ctx, grid, 1, s->ovf_cap))) return rc;
+    if (ch.two_rows) {  // the flagship instance: its queue runs over the ticket list the cull pass leaves
+      if (A.total_waves > (1u << kListFrameShift)) { ctx->err = "frame too large"; return GLOME_E_INVALID; }
+      if ((rc = ensure_list(ctx, A.total_waves))) return rc;
+      A.list = ctx->slot().d_list;
+    }
     const bool pooled = launch_events(ctx, ev_start, ev_stop), timed = stats || pooled;
     if (timed) HIPCHK(ctx, hipEventRecord(ev_start, ctx->stream));
+    if (ch.two_rows) {
+      // one block per chunk of the launch's item order (padding chunks of the last round of heads hold nothing and are not visited)
+      const uint32_t nchunks = A.chunks_per_frame ? A.chunks_per_frame * (uint32_t)nframes : (items + kQueueChunk - 1) / kQueueChunk;
+      glome_ctx::Slot& sl = ctx->slot();
+      hipLaunchKernelGGL(k_cull_items, dim3(nchunks), dim3(kCullThreads), 0, ctx->stream, A, sl.d_list, sl.d_list + sl.list_items, nchunks);
+      HIPCHK(ctx, hipGetLastError());
+      sl.cull_total = items;
+    }
     if ((rc = launch_chosen(s, ch, KIND_RENDER, grid, lds, A))) return rc;
     if (timed) HIPCHK(ctx, hipEventRecord(ev_stop, ctx->stream));
   }

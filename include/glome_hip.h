@@ -372,6 +372,10 @@ int glome_sb_scene_traits(glome_sb*, int32_t root, int64_t* out11);
 /* The lean render loop's pixel-coordinate tables of a frame size (xc[width], yc[height]; made on the device, once per context), or with
  * direct != 0 the same values evaluated per pixel by the coordinate function itself. */
 int glome_ctx_coord_tables(glome_ctx*, int width, int height, float* xc, float* yc, int direct);
+/* What the cull pass of the last flagship launch on the current slot found (the launches glome_kernel_choice reports two_rows for; their
+ * work items whose rays all miss the scene's root bounds are finished before the render kernel and never queued): `total` work items of
+ * the launch (all its frames), `live` of them queued.  Synchronizes the context's stream.  0 / 0 before the slot's first such launch. */
+int glome_ctx_last_cull(glome_ctx*, int64_t* live, int64_t* total);
 int glome_tiles_pack_dev(glome_ctx*, const glome_render_params*, const float* rgbad_dev, float* payload_dev);
 int glome_tiles_blit_dev(glome_ctx*, const glome_render_params*, int tile_first, int tile_stride,
                          const float* payload_dev, float* rgbad_dev, uint32_t* packed_dev);
