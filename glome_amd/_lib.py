@@ -138,6 +138,9 @@ SYMBOLS = [
     ("glome_trace_batch", C.c_int, [vp, C.c_size_t] + [c_fp] * 7 + [C.POINTER(Light), C.c_int, C.POINTER(TraceParams), c_fp, c_fp, c_ip, c_fp, c_fp, c_fp, c_ip,
                                     C.POINTER(Stats)]),
     ("glome_trace_batch_dev", C.c_int, [vp, C.c_size_t] + [vp] * 7 + [C.POINTER(Light), C.c_int, C.POINTER(TraceParams)] + [vp] * 7 + [C.POINTER(Stats)]),
+    ("glome_work_words", C.c_int, []),
+    ("glome_trace_work_batch", C.c_int, [vp, C.c_size_t] + [c_fp] * 7 + [C.POINTER(Light), C.c_int, C.POINTER(TraceParams), c_fp, c_up, C.POINTER(Stats)]),
+    ("glome_trace_work_batch_dev", C.c_int, [vp, C.c_size_t] + [vp] * 7 + [C.POINTER(Light), C.c_int, C.POINTER(TraceParams), vp, vp, C.POINTER(Stats)]),
     ("glome_trace_kernel_choice", C.c_int64, [C.c_int64, C.POINTER(C.c_int64), c_ip]),
     ("glome_camera_lookat", C.c_int, [c_dp, c_dp, c_dp, C.c_double, C.POINTER(Camera)]),
     ("glome_render_params_default", None, [C.POINTER(RenderParams)]),

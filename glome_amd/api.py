@@ -111,6 +111,26 @@ def render_params(width=720, height=480, mode=0, blocksize=65, maxdepth=3, fog=0
     return p
 
 
+def frame_rays(cam, w, h):
+    """The primary rays of a w x h frame of `cam` (an L.Camera), as (o, d) float32 arrays of w * h rows, row major: get_coordsf and
+    get_rayint (Glome.hs:27-33, 119-140) evaluated in float64, rounded to float32 and renormalised -- the render kernels' own rays to an
+    ulp.  What Scene.cost_image traces; a host with a sampler of its own starts from here."""
+    x, y = np.meshgrid(np.arange(w, dtype=np.float64), np.arange(h, dtype=np.float64))
+    xc = ((x / w) * 2 - 1) * (w / h)
+    yc = -((y / h) * 2 - 1)
+    pos, fwd, up, right = (np.array(list(v), np.float64) for v in (cam.pos, cam.fwd, cam.up, cam.right))
+    d = fwd + right * (-xc[..., None]) + up * yc[..., None]
+    d = (d / np.linalg.norm(d, axis=-1, keepdims=True)).reshape(-1, 3).astype(np.float32)
+    d = (d / np.linalg.norm(d.astype(np.float64), axis=1, keepdims=True)).astype(np.float32)
+    o = np.broadcast_to(pos.astype(np.float32), d.shape).copy()
+    return o, d
+
+
+# a work record's words (GLOME_WORK_*, include/glome_hip.h)
+WORK_BIH_NODES, WORK_MESH_NODES, WORK_PRIM_TESTS, WORK_RAYS_SHADOW, WORK_RAYS_SECONDARY = 0, 1, 2, 3, 4
+WORK_PRIMARY_BIH_NODES, WORK_PRIMARY_MESH_NODES, WORK_PRIMARY_PRIM_TESTS = 5, 6, 7
+
+
 def trace_params(maxdepth=3, faithful=0, count_work=0):
     """glome_trace_params: faithful=1 is required when ray directions are not unit length (include/glome_hip.h, the trace seam)."""
     lib = L.load()
@@ -442,6 +462,41 @@ class Scene:
         self._chk(self.lib.glome_trace_batch_dev(self.h, int(n), *[vp(p) for p in ray_ptrs7], la, len(lights), C.byref(params), vp(rgbad_ptr),
                                                  *[vp(p) for p in hit], C.byref(st) if want_stats else None), "glome_trace_batch_dev")
         return _stats_dict(st) if want_stats else None
+
+    def trace_work(self, o, d, lights, tmax=None, params=None):
+        """Trace.trace_debug over a batch of rays (Trace.hs:84-109): `trace` with a record of each ray's work.  Returns dict work (n x 8
+        uint32, the words WORK_* name), rgba, depth, stats.  params.count_work is implied."""
+        o = np.asarray(o, dtype=np.float32).reshape(-1, 3)
+        d = np.asarray(d, dtype=np.float32).reshape(-1, 3)
+        n = o.shape[0]
+        cols = [_f32(o[:, 0]), _f32(o[:, 1]), _f32(o[:, 2]), _f32(d[:, 0]), _f32(d[:, 1]), _f32(d[:, 2])]
+        tm = None if tmax is None else _f32(np.broadcast_to(np.asarray(tmax, dtype=np.float32), (n,)))
+        params = trace_params() if params is None else params
+        out = np.zeros((n, 5), np.float32)
+        work = np.zeros((n, self.lib.glome_work_words()), np.uint32)
+        la = (L.Light * max(1, len(lights)))(*lights)
+        st = L.Stats()
+        self._chk(self.lib.glome_trace_work_batch(self.h, n, *[c.ctypes.data_as(L.c_fp) for c in cols], tm.ctypes.data_as(L.c_fp) if tm is not None else None,
+                                                  la, len(lights), C.byref(params), out.ctypes.data_as(L.c_fp), work.ctypes.data_as(L.c_up), C.byref(st)),
+                  "glome_trace_work_batch")
+        return {"work": work, "rgba": out[:, :4], "depth": out[:, 4], "stats": _stats_dict(st)}
+
+    def trace_work_dev(self, n, ray_ptrs7, lights, params, work_ptr, rgbad_ptr=None, want_stats=True):
+        """Device-pointer trace_work: ray_ptrs7 as trace_dev takes them; work_ptr: n * 8 uint32, 16-byte aligned; rgbad_ptr may be None / 0
+        (no colour is stored); asynchronous on the context's stream unless want_stats."""
+        vp = lambda p: C.c_void_p(p) if p else None
+        la = (L.Light * max(1, len(lights)))(*lights)
+        st = L.Stats()
+        self._chk(self.lib.glome_trace_work_batch_dev(self.h, int(n), *[vp(p) for p in ray_ptrs7], la, len(lights), C.byref(params), vp(rgbad_ptr),
+                                                      vp(work_ptr), C.byref(st) if want_stats else None), "glome_trace_work_batch_dev")
+        return _stats_dict(st) if want_stats else None
+
+    def cost_image(self, cam, lights, width, height, maxdepth=3, faithful=0):
+        """A frame's work records, (height, width, 8) uint32: the frame's primary rays (frame_rays) through trace_work.  Word 5 is what
+        GlomeView's debug view tints a pixel with (get_color_debug, Glome.hs:35-41)."""
+        o, d = frame_rays(cam, width, height)
+        r = self.trace_work(o, d, lights, params=trace_params(maxdepth=maxdepth, faithful=faithful))
+        return r["work"].reshape(height, width, -1)
 
     def render(self, cam, lights, params, want_packed=True, init=None):
         """renderTiles (Glome.hs:379-386): returns (rgbad[h,w,5] float32, packed[h,w] uint32 or None, stats dict)."""

@@ -77,6 +77,8 @@ int glome_camera_lookat(const double pos[3], const double at[3], const double up
 }
 
 int glome_tex_words(void) { return GLOME_TEX_WORDS; }  // int32 words per ray of glome_rayint_batch's texture-stack output
+static_assert(GLOME_WORK_WORDS == kWorkWords && GLOME_WORK_PRIMARY_PRIM_TESTS == kWorkWords - 1, "the header's work record is the kernels' (rt_types.h, trace_kernels.hpp)");
+int glome_work_words(void) { return GLOME_WORK_WORDS; }  // uint32 words per ray of glome_trace_work_batch's records
 
 glome_sb* glome_sb_new(void) { return new glome_sb(); }
 void glome_sb_free(glome_sb* sb) { delete sb; }

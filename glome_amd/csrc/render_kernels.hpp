@@ -28,9 +28,10 @@
 // FAITHFUL = the reference's exact node-visit order (no ordered early-out, Bih.hs:332-368); COUNT = node / primitive
 // work counters.  They back the `faithful` / `count_work` render params (byte-model measurement, parity tests).
 // The production variant traverses with early-out and counts rays only.
-template <bool FAITHFUL, bool COUNT, bool FULL_, int CLS = CLS_ALL>
+template <bool FAITHFUL, bool COUNT_, bool FULL_, int CLS = CLS_ALL>
 struct FlatTier {
   static constexpr bool FULL = FULL_;  // false: lean kernel (no secondary rays, no Blend / Layers)
+  static constexpr bool COUNT = COUNT_;  // (rt_device.hpp tier_counts: a counting tier counts every ray per lane and keeps the primary ray's snapshot)
   static constexpr bool WARP = false;  // scenes with a Warp material (traces over other roots, Shader.hs:157-175) render on the generic tier
   const DScene& S;
   const DLight* lights;
@@ -38,6 +39,7 @@ struct FlatTier {
   LaneStack stk;
   Cnt cnt;
   unsigned int err = 0;  // a CSG item ran into the advance / frame cap (kernels with CLS_CSG)
+  PrimarySnap<COUNT_> snap = {};
   // the same tier over another copy of the launch's arguments (render_loop: the kernarg segment, re-read per work item), and back
   __device__ __forceinline__ FlatTier rebound(const DRenderArgs& A) const { return FlatTier{A.S, A.lights, A.nlights, stk, cnt, err}; }
   __device__ __forceinline__ void absorb(const FlatTier& t) { cnt = t.cnt; err = t.err; }
@@ -67,9 +69,10 @@ struct FlatTier {
 // PKMIN: lanes that must wait before the packet service walks (rt_generic.hpp vm_run).  COUNT: bih_nodes / prim_tests are counted -- asked for by
 // glome_render_params.count_work; the instances that do not count are 4 % (renderTile) and 2 % (sampler) faster on GlomeView's default scene
 // (profiles/r04_probes/generic_tier_no_count_ab.txt), like the flat tier's lean instances.
-template <int PKMIN = kPkMinLanes, bool COUNT = true>
+template <int PKMIN = kPkMinLanes, bool COUNT_ = true>
 struct GenericTierT {
   static constexpr bool FULL = true;
+  static constexpr bool COUNT = COUNT_;
   static constexpr bool WARP = true;
   // What the out-of-line interpreter calls take the address of -- counters, error flag, frame memory -- are locals of the kernel,
   // referred to from here, and S refers to the kernel-argument segment itself (kernel_args): this struct then never needs an
@@ -83,6 +86,7 @@ struct GenericTierT {
   unsigned int& err;
   uint32_t* vm;  // the interpreter's frames: one word stack of kVmWords per lane for the whole kernel (scratch)
   LaneStack pk;  // the wave's LDS stack for packet walks of sphere BIHs inside the interpreter (cap 0: the scene has none)
+  PrimarySnap<COUNT_> snap = {};
   __device__ __forceinline__ GenericTierT rebound(const DRenderArgs&) const { return *this; }  // (already reads the kernarg segment: kernel_args<>())
   __device__ __forceinline__ void absorb(const GenericTierT&) {}
   // `root`: the record the trace runs over -- the scene's, or the frame / scene of a Warp material

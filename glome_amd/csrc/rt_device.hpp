@@ -145,12 +145,29 @@ struct Cnt {  // per-lane work counters (only live when COUNT)
   uint32_t w_primary = 0, w_shadow = 0;  // rays counted once per WAVE where the wave acts together (scalar registers: a per-lane counter is a vector register
                                          // alive through the whole kernel); flush_counters adds both kinds
 };
+// bih / mesh / prim of a lane's Cnt as they stood when its last primary ray's closest hit returned (rayint_debug's count, Solid.hs:155: what
+// Trace.trace_debug returns).  A member of the counting tiers only -- the others carry the empty form, so their kernels are the same
+// kernels with or without it -- written by trace_primary, read by the trace seam's work records (trace_kernels.hpp).
+template <bool COUNT> struct PrimarySnap {};
+template <> struct PrimarySnap<true> { uint32_t p_bih = 0, p_mesh = 0, p_prim = 0; };
+// does the tier count work?  (a tier without a COUNT member -- the host build's -- does not ask for what only counting instances do)
+template <class TIER, class = void> struct tier_counts { static constexpr bool value = false; };
+template <class TIER> struct tier_counts<TIER, decltype((void)TIER::COUNT)> { static constexpr bool value = TIER::COUNT; };
 // `p` rays of a wave-wide step: one scalar add on the device (the host build's "wave" is one lane: its per-lane counter)
 #if defined(__HIP_DEVICE_COMPILE__) && !defined(GLOME_RB_OLD_COUNT)
 GD void count_wave(uint32_t&, uint32_t& per_wave, bool p) { per_wave += (uint32_t)__builtin_popcountll(__builtin_amdgcn_ballot_w64(p)); }
 #else
 GD void count_wave(uint32_t& per_lane, uint32_t&, bool p) { if (p) per_lane++; }
 #endif
+// the same for a tier: its counting instances count per lane -- a work record (trace_kernels.hpp) is a lane's own counters -- and the totals
+// flush_counters adds up are the same either way
+template <class TIER> GD void count_rays(TIER&, uint32_t& per_lane, uint32_t& per_wave, bool p) {
+  if constexpr (tier_counts<TIER>::value) { if (p) per_lane++; }
+  else count_wave(per_lane, per_wave, p);
+}
+template <class TIER> GD void snapshot_primary(TIER& T) {  // the primary ray's closest hit has just returned
+  if constexpr (tier_counts<TIER>::value) { T.snap.p_bih = T.cnt.bih; T.snap.p_mesh = T.cnt.mesh; T.snap.p_prim = T.cnt.prim; }
+}
 
 // 1 / (a ray direction component), the ONE way everywhere a slab or a split plane is clipped: a box that ends on a BIH split
 // plane (or on its tree's bounds) must leave at bit-identical distances on both paths -- box_shadow's `far > d` (Box.hs:56-62)
@@ -1665,7 +1682,7 @@ GD uint32_t preshade_wave(TIER& T, const HitCore& h, bool want) {
     V3 ldir = lvec * (1.0f / llen);
     bool lit = want && !(vdot(lvec, h.n) < 0) && !(llen > L.rad);
     if (L.shadow) {
-      count_wave(T.cnt.shadow, T.cnt.w_shadow, lit);
+      count_rays(T, T.cnt.shadow, T.cnt.w_shadow, lit);
       Ray sr; sr.o = vscaleadd(h.p, h.n, kDel); sr.d = ldir;
       bool occ = T.occluded_wave(sr, llen - (2 * kDel), lit);
       lit = lit && !occ;
@@ -1776,7 +1793,7 @@ GD CA shade_vm(TIER& T, const Ray& ray0, float tmax, int maxdepth, bool valid, H
     if (wave_any(wh)) {
       const Ray r = wh ? tr[tl].ray : ray0;
       const HitG h = T.closest_wave(r, wh ? tr[tl].tmax : tmax, wh, wh ? tr[tl].root : S.root_rec);
-      if (wh) { tr[tl].h = h; if constexpr (TIER::WARP) { tr[tl].lo = h.lo; tr[tl].ld = h.ld; } if (tl == 0) *hout = h; st = S_HIT; }
+      if (wh) { tr[tl].h = h; if constexpr (TIER::WARP) { tr[tl].lo = h.lo; tr[tl].ld = h.ld; } if (tl == 0) { *hout = h; snapshot_primary(T); } st = S_HIT; }
     }
     const bool wl = st == S_NEED_LIGHTS;
     if (wave_any(wl)) {
@@ -1921,6 +1938,7 @@ template <class TIER> GD CA trace_primary(TIER& T, const Ray& ray, float tmax, i
     if (maxdepth <= 0) { *hout = hit_miss(); return ca(0, 0, 0, 0); }
     HitG h = T.closest_wave(ray, tmax, valid);
     *hout = h;
+    snapshot_primary(T);
     LightCache lc; lc.done = false; lc.mask = 0;
     bool eager = false;
     if (valid && h.hit) {

@@ -213,6 +213,11 @@ struct DTraceArgs {
   float* rgbad;           // n * 5: (r, g, b, a, depth)
   float* t; int32_t* prim; float *nx, *ny, *nz; int32_t* tex8;  // the trace's own Rayint, as the rayint seam writes it; any may be null
   DCounters* counters;
+  uint32_t* work;         // n * kWorkWords, 16-byte aligned: a work record per ray (glome_trace_work_batch), or null.  Read by the counting instances
+                          // only; with it, rgbad may be null
+  uint64_t work_pad;      // (the struct grows by a whole 16 bytes: the kernel arguments behind it keep their alignment, and with it the
+                          // instances that never read `work` the scalar loads -- and the registers -- they had)
 };
+constexpr int kWorkWords = 8;  // GLOME_WORK_WORDS: bih, mesh, prim, shadow rays, secondary rays of a ray's whole trace; bih, mesh, prim of its primary ray's closest hit
 
 }  // namespace glome

@@ -959,14 +959,19 @@ int glome_inside_batch(glome_scene* s, size_t n, const float* px, const float* p
 }
 
 // ---- the trace seam: Trace.trace over a caller's ray streams (trace_kernels.hpp) ----
-int glome_trace_batch_dev(glome_scene* s, size_t n, const float* ox, const float* oy, const float* oz, const float* dx, const float* dy,
-                          const float* dz, const float* tmax, const glome_light* lights, int nlights, const glome_trace_params* P,
-                          float* rgbad, float* t, int32_t* prim, float* nx, float* ny, float* nz, int32_t* tex8, glome_stats* stats) {
+// One launch for both forms.  with_work: glome_trace_work_batch_dev -- `work` receives a record per ray, rgbad may be null, and the launch
+// takes the counting instance whatever count_work says; else `work` is null and rgbad is required.
+static int trace_launch(glome_scene* s, size_t n, const float* ox, const float* oy, const float* oz, const float* dx, const float* dy,
+                        const float* dz, const float* tmax, const glome_light* lights, int nlights, const glome_trace_params* P,
+                        float* rgbad, float* t, int32_t* prim, float* nx, float* ny, float* nz, int32_t* tex8, bool with_work, uint32_t* work,
+                        glome_stats* stats) {
   if (!s) return GLOME_E_INVALID;
   glome_ctx* ctx = s->ctx;
   if (n == 0) return 0;
   if (!ox || !oy || !oz || !dx || !dy || !dz) { ctx->err = "null ray stream"; return GLOME_E_INVALID; }
-  if (!rgbad || !P || nlights < 0 || (nlights > 0 && !lights)) { ctx->err = "bad argument"; return GLOME_E_INVALID; }
+  if ((!rgbad && !with_work) || !P || nlights < 0 || (nlights > 0 && !lights)) { ctx->err = "bad argument"; return GLOME_E_INVALID; }
+  if (with_work && !work) { ctx->err = "null work buffer"; return GLOME_E_INVALID; }
+  if (with_work && ((uintptr_t)work & 15u)) { ctx->err = "the work buffer must be 16-byte aligned"; return GLOME_E_INVALID; }
   if (nlights > kMaxLights) { ctx->err = "too many lights"; return GLOME_E_LIMIT; }
   if (P->maxdepth < 1 || P->maxdepth > kMaxTraceDepth) { ctx->err = "maxdepth must be in 1.." + std::to_string(kMaxTraceDepth); return GLOME_E_LIMIT; }
   if (n > ((size_t)1 << 31)) { ctx->err = "a trace launch carries at most 2^31 rays"; return GLOME_E_LIMIT; }
@@ -983,11 +988,12 @@ int glome_trace_batch_dev(glome_scene* s, size_t n, const float* ox, const float
   A.want_counters = stats ? 1 : 0;
   A.ox = ox; A.oy = oy; A.oz = oz; A.dx = dx; A.dy = dy; A.dz = dz; A.tmax = tmax;
   A.rgbad = rgbad; A.t = t; A.prim = prim; A.nx = nx; A.ny = ny; A.nz = nz; A.tex8 = tex8;
+  A.work = with_work ? work : nullptr;
   A.counters = ctx->slot().d_counters;
   int rc;
   if (stats && (rc = reset_counters(ctx))) return rc;  // (nobody reads the counters of a launch without `stats`, and a trace launch has no queue heads)
   const uint32_t items = (uint32_t)((n + 63) / 64);
-  const Choice ch = choose_trace(s->tr, P->faithful != 0, P->count_work != 0, P->maxdepth);
+  const Choice ch = choose_trace(s->tr, P->faithful != 0, with_work || P->count_work != 0, P->maxdepth);  // (only the counting instances read A.work)
   const size_t lds = ch.generic ? flat_lds_bytes((int)s->dev.pk_generic_cap) : flat_lds_bytes(s->tr.stack_cap);
   // four blocks per wave slot the kernel can hold: the items are dealt statically, and the dispatcher evens out what they cost (trace_batch_loop)
   const int grid = (int)std::min<uint64_t>(items, (uint64_t)persistent_grid(ctx, lds, 0x7fffffff, waves_per_cu(ch)) * 4);
@@ -1019,6 +1025,46 @@ int glome_trace_batch_dev(glome_scene* s, size_t n, const float* ox, const float
   }
   return 0;
 }
+int glome_trace_batch_dev(glome_scene* s, size_t n, const float* ox, const float* oy, const float* oz, const float* dx, const float* dy,
+                          const float* dz, const float* tmax, const glome_light* lights, int nlights, const glome_trace_params* P,
+                          float* rgbad, float* t, int32_t* prim, float* nx, float* ny, float* nz, int32_t* tex8, glome_stats* stats) {
+  return trace_launch(s, n, ox, oy, oz, dx, dy, dz, tmax, lights, nlights, P, rgbad, t, prim, nx, ny, nz, tex8, false, nullptr, stats);
+}
+int glome_trace_work_batch_dev(glome_scene* s, size_t n, const float* ox, const float* oy, const float* oz, const float* dx, const float* dy,
+                               const float* dz, const float* tmax, const glome_light* lights, int nlights, const glome_trace_params* P,
+                               float* rgbad, uint32_t* work, glome_stats* stats) {
+  return trace_launch(s, n, ox, oy, oz, dx, dy, dz, tmax, lights, nlights, P, rgbad, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, true, work, stats);
+}
+// the rays of a host-buffer trace call, staged: din[6] stays null without tmax
+static int stage_rays(glome_ctx* ctx, Staging& st, size_t n, const float* const h[7], float* din[7]) {
+  for (int k = 0; k < (h[6] ? 7 : 6); k++) if (!(din[k] = st.in(h[k], n))) { ctx->err = "staging allocation failed"; return GLOME_E_HIP; }
+  return 0;
+}
+int glome_trace_work_batch(glome_scene* s, size_t n, const float* ox, const float* oy, const float* oz, const float* dx, const float* dy,
+                           const float* dz, const float* tmax, const glome_light* lights, int nlights, const glome_trace_params* P,
+                           float* rgbad, uint32_t* work, glome_stats* stats) {
+  if (!s) return GLOME_E_INVALID;
+  glome_ctx* ctx = s->ctx;
+  if (n == 0) return 0;
+  if (!ox || !oy || !oz || !dx || !dy || !dz) { ctx->err = "null ray stream"; return GLOME_E_INVALID; }
+  if (!P) { ctx->err = "bad argument"; return GLOME_E_INVALID; }
+  if (!work) { ctx->err = "null work buffer"; return GLOME_E_INVALID; }
+  if (n > ((size_t)1 << 31)) { ctx->err = "a trace launch carries at most 2^31 rays"; return GLOME_E_LIMIT; }
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  Staging st{ctx, {}};
+  float* din[7] = {};
+  const float* const h[7] = {ox, oy, oz, dx, dy, dz, tmax};
+  if (int rcs = stage_rays(ctx, st, n, h, din)) return rcs;
+  float* d5 = rgbad ? st.in<float>(nullptr, n * 5) : nullptr;
+  uint32_t* dwork = st.in<uint32_t>(nullptr, n * kWorkWords);  // (a device allocation: aligned far beyond 16 bytes)
+  if ((rgbad && !d5) || !dwork) { ctx->err = "staging allocation failed"; return GLOME_E_HIP; }
+  glome_stats local;
+  int rc = glome_trace_work_batch_dev(s, n, din[0], din[1], din[2], din[3], din[4], din[5], din[6], lights, nlights, P, d5, dwork, stats ? stats : &local);
+  if (rc) return rc;
+  if (rgbad) HIPCHK(ctx, hipMemcpy(rgbad, d5, n * 20, hipMemcpyDeviceToHost));
+  HIPCHK(ctx, hipMemcpy(work, dwork, n * kWorkWords * 4, hipMemcpyDeviceToHost));
+  return 0;
+}
 int glome_trace_batch(glome_scene* s, size_t n, const float* ox, const float* oy, const float* oz, const float* dx, const float* dy,
                       const float* dz, const float* tmax, const glome_light* lights, int nlights, const glome_trace_params* P,
                       float* rgbad, float* t, int32_t* prim, float* nx, float* ny, float* nz, int32_t* tex8, glome_stats* stats) {
@@ -1031,10 +1077,8 @@ int glome_trace_batch(glome_scene* s, size_t n, const float* ox, const float* oy
   HIPCHK(ctx, hipSetDevice(ctx->device));
   Staging st{ctx, {}};
   float* din[7] = {};
-  {
-    const float* const h[7] = {ox, oy, oz, dx, dy, dz, tmax};
-    for (int k = 0; k < (tmax ? 7 : 6); k++) if (!(din[k] = st.in(h[k], n))) { ctx->err = "staging allocation failed"; return GLOME_E_HIP; }
-  }
+  const float* const h[7] = {ox, oy, oz, dx, dy, dz, tmax};
+  if (int rcs = stage_rays(ctx, st, n, h, din)) return rcs;
   float* d5 = st.in<float>(nullptr, n * 5);
   float* dt = t ? st.in<float>(nullptr, n) : nullptr;
   int32_t* dprim = prim ? st.in<int32_t>(nullptr, n) : nullptr;

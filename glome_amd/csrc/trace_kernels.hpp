@@ -33,9 +33,22 @@ __device__ __forceinline__ void trace_batch_loop(const DTraceArgs& A, TIER& T, b
       if (CHECK && check && !unit_length(ray.d)) { bad = 1; valid = false; }
     }
     count_wave(T.cnt.primary, T.cnt.w_primary, valid);
+    // a counting instance keeps what this ray's trace adds to the lane's counters (they run on across the items a block takes): the work
+    // record.  The primary ray's part is the snapshot trace_primary leaves in the tier's `snap`; a lane it never traces keeps zeros there.
+    Cnt c0;
+    if constexpr (tier_counts<TIER>::value) { c0 = T.cnt; T.snap.p_bih = c0.bih; T.snap.p_mesh = c0.mesh; T.snap.p_prim = c0.prim; }
     HitG h;
     const CA c = trace_primary(T, ray, tmax, A.maxdepth, valid, &h);
     if (!valid) continue;
+    if constexpr (tier_counts<TIER>::value) {
+      if (A.work) {  // two 16-byte stores per lane: a wave writes 2 KB contiguously
+        const Cnt& c1 = T.cnt;
+        uint4* w = reinterpret_cast<uint4*>(A.work + (size_t)i * kWorkWords);
+        w[0] = make_uint4(c1.bih - c0.bih, c1.mesh - c0.mesh, c1.prim - c0.prim, c1.shadow - c0.shadow);
+        w[1] = make_uint4(c1.secondary - c0.secondary, T.snap.p_bih - c0.bih, T.snap.p_mesh - c0.mesh, T.snap.p_prim - c0.prim);
+        if (!A.rgbad) continue;  // (a work launch may leave the colour out; it has no hit streams)
+      }
+    }
     float* out = A.rgbad + (size_t)i * 5;
     out[0] = c.r; out[1] = c.g; out[2] = c.b; out[3] = c.a; out[4] = h.hit ? h.t : kInf;  // (ridepth: what glome_render stores with fog = 0)
     store_hit(HitStream{A.t, A.prim, A.nx, A.ny, A.nz, A.tex8}, i, h, (int)A.S.tex_bits);

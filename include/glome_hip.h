@@ -269,7 +269,7 @@ int glome_render_tiles_dev(glome_scene*, const glome_camera*, const glome_light*
 int glome_render_tiles_packed_dev(glome_scene*, const glome_camera*, const glome_light* lights, int nlights,
                                   const glome_render_params*, uint32_t* payload_dev, glome_stats*);
 /* Several independent frames in ONE launch (an animation's next views: same scene and lights, cams[0..nframes), at
- * most 8).  Frame f's pixels land frame_stride_pixels words after frame f-1's: rows of a dense tile payload
+ * most 32).  Frame f's pixels land frame_stride_pixels words after frame f-1's: rows of a dense tile payload
  * (..._tiles_packed_batch_dev; stride >= this rank's payload size) or whole packed framebuffers (..._packed_batch_dev;
  * stride >= width*height).  A rank's share of one frame is a few thousand work items -- too little to fill the GPU
  * beyond its slowest item; a batch restores long launches.  Both render modes (the adaptive sampler of a batch of 4 or
@@ -306,6 +306,28 @@ int glome_trace_batch(glome_scene*, size_t n, const float* ox, const float* oy, 
 int glome_trace_batch_dev(glome_scene*, size_t n, const float* ox, const float* oy, const float* oz, const float* dx, const float* dy,
                           const float* dz, const float* tmax, const glome_light* lights, int nlights, const glome_trace_params*,
                           float* rgbad, float* t, int32_t* prim, float* nx, float* ny, float* nz, int32_t* tex8, glome_stats*);
+/* ---- per-ray work records (Trace.trace_debug, Trace.hs:84-109; rayint_debug, Solid.hs:155,205, Bih.hs:376-412) ----
+ * glome_trace_batch again, but every ray also leaves a record of the work its trace did: what glome_stats counts for a whole launch,
+ * for that ray alone -- GLOME_WORK_WORDS (8) uint32 PER RAY, ray i at work[8 i ..] (glome_work_words() returns what the loaded library
+ * writes).  Words 0..2: BIH nodes, Mesh nodes and primitive tests of everything the ray's trace walked -- its closest hit, its shadow
+ * rays, its reflection / refraction / Warp rays; words 3, 4: the shadow and secondary rays it spawned; words 5..7: words 0..2 as they
+ * stood when the primary ray's closest hit returned, before mpreshade -- word 5 is the Int of trace_debug for a scene without Bound, the
+ * number GlomeView tints a pixel with (get_color_debug, Glome.hs:35-41).  Over a launch words 0..4 sum to its glome_stats exactly.
+ * The contract is glome_trace_batch's -- validation, the unit-length rule, tmax == NULL, n == 0, the asynchronous _dev form, timing --
+ * but: `work` is required, and work_dev must be 16-byte aligned (else GLOME_E_INVALID); rgbad may be NULL, and then no colour is stored;
+ * there are no hit streams; count_work is implied (the launch takes the counting kernel instance) and ignored, faithful is honoured.
+ * A launch that fails leaves the records unspecified, as it leaves rgbad.  It costs what a count_work launch costs plus 32 bytes
+ * stored per ray. */
+#define GLOME_WORK_WORDS 8
+enum { GLOME_WORK_BIH_NODES = 0, GLOME_WORK_MESH_NODES = 1, GLOME_WORK_PRIM_TESTS = 2, GLOME_WORK_RAYS_SHADOW = 3, GLOME_WORK_RAYS_SECONDARY = 4,
+       GLOME_WORK_PRIMARY_BIH_NODES = 5, GLOME_WORK_PRIMARY_MESH_NODES = 6, GLOME_WORK_PRIMARY_PRIM_TESTS = 7 };
+int glome_work_words(void);
+int glome_trace_work_batch(glome_scene*, size_t n, const float* ox, const float* oy, const float* oz, const float* dx, const float* dy,
+                           const float* dz, const float* tmax, const glome_light* lights, int nlights, const glome_trace_params*,
+                           float* rgbad, uint32_t* work, glome_stats*);
+int glome_trace_work_batch_dev(glome_scene*, size_t n, const float* ox, const float* oy, const float* oz, const float* dx, const float* dy,
+                               const float* dz, const float* tmax, const glome_light* lights, int nlights, const glome_trace_params*,
+                               float* rgbad_dev, uint32_t* work_dev, glome_stats*);
 /* Host-only, no device: the kernel instance a trace launch gets (choose_trace, glome_amd/csrc/instances.hpp).  n rows of 11 inputs -- the
  * eight scene traits of glome_sb_scene_traits, then faithful, count_work, maxdepth -- give n rows of 3 outputs: the instance (a flat-tier
  * key with the bits glome_kernel_choice describes, TWO_ROWS never set; -1 / -2: the generic tier's kernel that counts work / does not),
