@@ -43,6 +43,11 @@ class TraceParams(C.Structure):  # glome_trace_params
     _fields_ = [("maxdepth", C.c_int32), ("faithful", C.c_int32), ("count_work", C.c_int32)]
 
 
+class RaygenParams(C.Structure):  # glome_raygen_params
+    _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("lens", C.c_int32), ("samples", C.c_int32), ("jitter", C.c_int32),
+                ("seed", C.c_uint32), ("aperture", C.c_float), ("focus_dist", C.c_float)]
+
+
 class SceneInfo(C.Structure):  # glome_scene_info
     _fields_ = [("tier", C.c_int32), ("nesting_depth", C.c_int32), ("n_records", C.c_int64), ("n_bih_nodes", C.c_int64),
                 ("n_mesh_nodes", C.c_int64), ("n_triangles", C.c_int64), ("n_spheres", C.c_int64),
@@ -142,6 +147,17 @@ SYMBOLS = [
     ("glome_trace_work_batch", C.c_int, [vp, C.c_size_t] + [c_fp] * 7 + [C.POINTER(Light), C.c_int, C.POINTER(TraceParams), c_fp, c_up, C.POINTER(Stats)]),
     ("glome_trace_work_batch_dev", C.c_int, [vp, C.c_size_t] + [vp] * 7 + [C.POINTER(Light), C.c_int, C.POINTER(TraceParams), vp, vp, C.POINTER(Stats)]),
     ("glome_trace_kernel_choice", C.c_int64, [C.c_int64, C.POINTER(C.c_int64), c_ip]),
+    ("glome_raygen_params_default", None, [C.POINTER(RaygenParams)]),
+    ("glome_raygen_params_size", C.c_size_t, []),
+    ("glome_raygen_count", C.c_int64, [C.POINTER(RaygenParams)]),
+    ("glome_raygen_sample", C.c_uint32, [C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32]),
+    ("glome_camera_rays_dev", C.c_int, [vp, C.POINTER(Camera), C.POINTER(RaygenParams), C.c_int64, C.c_int64] + [vp] * 6),
+    ("glome_camera_rays", C.c_int, [vp, C.POINTER(Camera), C.POINTER(RaygenParams), C.c_int64, C.c_int64] + [c_fp] * 6),
+    ("glome_resolve_dev", C.c_int, [vp, C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_int64, vp, vp, vp]),
+    ("glome_render_lens", C.c_int, [vp, C.POINTER(Camera), C.POINTER(RaygenParams), C.POINTER(Light), C.c_int, C.POINTER(TraceParams), C.c_int64, c_fp, c_up,
+                                    C.POINTER(Stats)]),
+    ("glome_render_lens_dev", C.c_int, [vp, C.POINTER(Camera), C.POINTER(RaygenParams), C.POINTER(Light), C.c_int, C.POINTER(TraceParams), C.c_int64, vp, vp,
+                                        C.POINTER(Stats)]),
     ("glome_camera_lookat", C.c_int, [c_dp, c_dp, c_dp, C.c_double, C.POINTER(Camera)]),
     ("glome_render_params_default", None, [C.POINTER(RenderParams)]),
     ("glome_render", C.c_int, [vp, C.POINTER(Camera), C.POINTER(Light), C.c_int, C.POINTER(RenderParams), c_fp, c_up, C.POINTER(Stats)]),

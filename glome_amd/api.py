@@ -114,7 +114,9 @@ def render_params(width=720, height=480, mode=0, blocksize=65, maxdepth=3, fog=0
 def frame_rays(cam, w, h):
     """The primary rays of a w x h frame of `cam` (an L.Camera), as (o, d) float32 arrays of w * h rows, row major: get_coordsf and
     get_rayint (Glome.hs:27-33, 119-140) evaluated in float64, rounded to float32 and renormalised -- the render kernels' own rays to an
-    ulp.  What Scene.cost_image traces; a host with a sampler of its own starts from here."""
+    ulp.  What Scene.cost_image traces.  The device form is Context.camera_rays / camera_rays_dev (glome_camera_rays: the render
+    kernels' own rays bit for bit, three lens models, jitter), and Scene.render_lens a whole frame from them without the rays ever
+    leaving the GPU; this host form stays for small streams and as a formula to read."""
     x, y = np.meshgrid(np.arange(w, dtype=np.float64), np.arange(h, dtype=np.float64))
     xc = ((x / w) * 2 - 1) * (w / h)
     yc = -((y / h) * 2 - 1)
@@ -138,6 +140,24 @@ def trace_params(maxdepth=3, faithful=0, count_work=0):
     lib.glome_trace_params_default(C.byref(p))
     p.maxdepth, p.faithful, p.count_work = maxdepth, faithful, count_work
     return p
+
+
+LENS_PINHOLE, LENS_THIN, LENS_LATLONG = 0, 1, 2  # GLOME_LENS_*
+
+
+def raygen_params(width=720, height=480, lens=LENS_PINHOLE, samples=1, jitter=0, seed=0, aperture=0.0, focus_dist=1.0):
+    """glome_raygen_params: the frame, the lens model and the sampling of Context.camera_rays and Scene.render_lens."""
+    lib = L.load()
+    p = L.RaygenParams()
+    lib.glome_raygen_params_default(C.byref(p))
+    p.width, p.height, p.lens, p.samples, p.jitter, p.seed = width, height, lens, samples, jitter, seed
+    p.aperture, p.focus_dist = float(aperture), float(focus_dist)
+    return p
+
+
+def raygen_sample(seed, pixel, s, dim):
+    """The 32-bit word behind sample dimension `dim` of sample s of pixel y * width + x (glome_raygen_sample): u = (word >> 8) * 2^-24."""
+    return int(L.load().glome_raygen_sample(seed & 0xffffffff, pixel & 0xffffffff, s & 0xffffffff, dim & 0xffffffff))
 
 
 # ---------------------------------------------------------------- scene builder
@@ -338,6 +358,30 @@ class Context:
         self.lib.glome_ctx_device_info(self.h, name, 256, C.byref(cu), C.byref(ws))
         return name.value.decode(), cu.value, ws.value
 
+    def _chk(self, rc, what):
+        if rc != 0:
+            raise GlomeError(f"{what}: {self.err()} (status {rc})")
+
+    def camera_rays(self, cam, params, first_ray=0, n_rays=None):
+        """The rays of `cam` under params' lens, made on the device (glome_camera_rays): (o, d) float32 arrays of n_rays rows, in the
+        frame's order (y * width + x) * samples + s; the whole frame by default."""
+        n = int(self.lib.glome_raygen_count(C.byref(params))) - first_ray if n_rays is None else int(n_rays)
+        cols = [np.zeros(max(n, 0), np.float32) for _ in range(6)]
+        self._chk(self.lib.glome_camera_rays(self.h, C.byref(cam), C.byref(params), int(first_ray), n, *[c.ctypes.data_as(L.c_fp) for c in cols]), "glome_camera_rays")
+        return np.stack(cols[:3], 1), np.stack(cols[3:], 1)
+
+    def camera_rays_dev(self, cam, params, first_ray, n_rays, ray_ptrs6):
+        """Device-pointer raygen: ray_ptrs6 = ox, oy, oz, dx, dy, dz, n_rays floats each; asynchronous on the context's stream."""
+        self._chk(self.lib.glome_camera_rays_dev(self.h, C.byref(cam), C.byref(params), int(first_ray), int(n_rays), *[C.c_void_p(p) if p else None for p in ray_ptrs6]),
+                  "glome_camera_rays_dev")
+
+    def resolve_dev(self, width, height, samples, first_pixel, n_pixels, samples_ptr, rgbad_ptr=None, packed_ptr=None):
+        """Device-pointer resolve: samples_ptr = the n_pixels * samples * 5 floats a trace wrote for the range's rays; rgbad_ptr / packed_ptr
+        = whole frames, either may be None / 0; asynchronous on the context's stream."""
+        vp = lambda p: C.c_void_p(p) if p else None
+        self._chk(self.lib.glome_resolve_dev(self.h, int(width), int(height), int(samples), int(first_pixel), int(n_pixels), vp(samples_ptr), vp(rgbad_ptr), vp(packed_ptr)),
+                  "glome_resolve_dev")
+
     def bih(self, builder, ids):
         """`bih ids` built on this context's GPU (glome_sb_bih_dev): the node glome_sb_bih makes, tree bit for bit.
         Returns (node, device milliseconds)."""
@@ -497,6 +541,28 @@ class Scene:
         o, d = frame_rays(cam, width, height)
         r = self.trace_work(o, d, lights, params=trace_params(maxdepth=maxdepth, faithful=faithful))
         return r["work"].reshape(height, width, -1)
+
+    def render_lens(self, cam, lights, raygen, trace=None, rays_per_pass=0, want_packed=True):
+        """A frame of `cam` under raygen's lens through the trace seam, rays made and samples resolved on the device (glome_render_lens):
+        returns (rgbad[h,w,5] float32, packed[h,w] uint32 or None, stats dict), like render."""
+        w, h = raygen.width, raygen.height
+        img = np.zeros((max(h, 0), max(w, 0), 5), np.float32)
+        packed = np.zeros((max(h, 0), max(w, 0)), np.uint32) if want_packed else None
+        trace = trace_params() if trace is None else trace
+        la = (L.Light * max(1, len(lights)))(*lights)
+        st = L.Stats()
+        self._chk(self.lib.glome_render_lens(self.h, C.byref(cam), C.byref(raygen), la, len(lights), C.byref(trace), int(rays_per_pass), img.ctypes.data_as(L.c_fp),
+                                             packed.ctypes.data_as(L.c_up) if want_packed else None, C.byref(st)), "glome_render_lens")
+        return img, packed, _stats_dict(st)
+
+    def render_lens_dev(self, cam, lights, raygen, trace, rgbad_ptr, packed_ptr=None, rays_per_pass=0, want_stats=True):
+        """Device-pointer render_lens (whole frames; either pointer may be None / 0); asynchronous unless want_stats."""
+        la = (L.Light * max(1, len(lights)))(*lights)
+        st = L.Stats()
+        self._chk(self.lib.glome_render_lens_dev(self.h, C.byref(cam), C.byref(raygen), la, len(lights), C.byref(trace), int(rays_per_pass),
+                                                 C.c_void_p(rgbad_ptr) if rgbad_ptr else None, C.c_void_p(packed_ptr) if packed_ptr else None,
+                                                 C.byref(st) if want_stats else None), "glome_render_lens_dev")
+        return _stats_dict(st) if want_stats else None
 
     def render(self, cam, lights, params, want_packed=True, init=None):
         """renderTiles (Glome.hs:379-386): returns (rgbad[h,w,5] float32, packed[h,w] uint32 or None, stats dict)."""

@@ -1,7 +1,7 @@
 """Build libglome_hip.so in-tree: the host half with g++, the HIP half with hipcc for gfx950 only.
 
-The HIP half is fifteen objects, built in parallel: runtime.hip (the host runtime and its light kernels) once, and kernel_parts.hip
-once per PART (-DGLOME_PART=k, k = 1..14: the kernel instances instances.hpp lists for that part, which are what takes the time).
+The HIP half is sixteen objects, built in parallel: runtime.hip (the host runtime and its light kernels) once, and kernel_parts.hip
+once per PART (-DGLOME_PART=k, k = 1..15: the kernel instances instances.hpp lists for that part, which are what takes the time).
 An object is stale against its own source and the headers only, so an edit of runtime.hip recompiles one object and relinks."""
 import hashlib
 import os

@@ -55,6 +55,23 @@ void glome_trace_params_default(glome_trace_params* p) {
   p->maxdepth = 3;  // Glome.hs:25
 }
 
+// ---- the lens stages' host-only entries (the rest: runtime.hip) ----
+static_assert((int)GLOME_LENS_PINHOLE == (int)LENS_PINHOLE && (int)GLOME_LENS_THIN == (int)LENS_THIN && (int)GLOME_LENS_LATLONG == (int)LENS_LATLONG, "the header's lenses are the kernels' (rt_types.h)");
+void glome_raygen_params_default(glome_raygen_params* p) {
+  if (!p) return;
+  memset(p, 0, sizeof(*p));
+  p->width = 720; p->height = 480;  // Glome.hs:112-113
+  p->lens = GLOME_LENS_PINHOLE;
+  p->samples = 1;
+  p->focus_dist = 1.0f;
+}
+size_t glome_raygen_params_size(void) { return sizeof(glome_raygen_params); }
+int64_t glome_raygen_count(const glome_raygen_params* p) {
+  if (raygen_params_error(p)) return GLOME_E_INVALID;
+  return (int64_t)p->width * p->height * p->samples;
+}
+uint32_t glome_raygen_sample(uint32_t seed, uint32_t pixel, uint32_t s, uint32_t dim) { return raygen_word(seed, pixel, s, dim); }
+
 int glome_xfm_translate(const double v[3], double out[24]) { return xguard([&] { xf_to(xf_translate(d3(v)), out); }); }
 int glome_xfm_scale(const double v[3], double out[24]) { return xguard([&] { xf_to(xf_scale(d3(v)), out); }); }
 int glome_xfm_rotate(const double axis[3], double angle, double out[24]) { return xguard([&] { xf_to(xf_rotate(d3(axis), angle), out); }); }

@@ -1,8 +1,10 @@
 // capi_shared.hpp -- what the host half (capi_host.cpp) and the device half (runtime.hip) of the C ABI share: the scene builder's
-// handle and what a commit derives from a flattened scene for the choice of kernel instances.
+// handle, what a commit derives from a flattened scene for the choice of kernel instances, and the check of a set of raygen params.
 #pragma once
+#include <cmath>
 #include <string>
 
+#include "../../include/glome_hip.h"
 #include "flatten.hpp"
 #include "host_graph.hpp"
 #include "instances.hpp"
@@ -28,4 +30,17 @@ inline CommitRules commit_rules(const glome::Graph& G, const glome::FlatScene& F
     if (m.kind == glome::MAT_LAYERS || m.kind == glome::MAT_BLEND) t.has_nested_mats = true;
   }
   return R;
+}
+
+// What every lens entry refuses of its raygen params (glome_raygen_count on the host half, the raygen / resolve / render_lens entries on
+// the device half): the reason, or null when they are fine.
+inline const char* raygen_params_error(const glome_raygen_params* p) {
+  if (!p) return "null raygen params";
+  if (p->width < 1 || p->height < 1) return "width and height must be at least 1";
+  if ((int64_t)p->width * p->height > (1ll << 30)) return "frame too large";
+  if (p->samples < 1 || p->samples > glome::kMaxLensSamples) return "samples must be in 1..64";
+  if (p->lens != GLOME_LENS_PINHOLE && p->lens != GLOME_LENS_THIN && p->lens != GLOME_LENS_LATLONG) return "unknown lens";
+  if (!std::isfinite(p->aperture) || !std::isfinite(p->focus_dist)) return "aperture and focus_dist must be finite";
+  if (p->lens == GLOME_LENS_THIN && (p->focus_dist <= 0 || p->aperture < 0)) return "a thin lens needs focus_dist > 0 and aperture >= 0";
+  return nullptr;
 }

@@ -53,7 +53,7 @@ constexpr int ss_flat_key(bool U, int CLS, int LB, bool TWO, bool F) { return (F
 #define GLOME_TRACE_FLAT_P14(X) /* faithful / counting */                                                                   \
   X(true, true, true, CLS_EVERY, 1) X(true, true, false, CLS_EVERY, 1) X(false, true, true, CLS_EVERY, 1) X(false, true, false, CLS_EVERY, 1)
 // the units of the device half: 0 is runtime.hip, 1..kParts-1 are kernel_parts.hip with -DGLOME_PART=k (glome_amd/build.py reads the count from here)
-#define GLOME_NPARTS 15
+#define GLOME_NPARTS 16
 constexpr int kParts = GLOME_NPARTS;
 
 // is `key` one of the listed instances (the lists the launchers of kernel_parts.hip are made from)

@@ -70,3 +70,8 @@ bool launch_trace_flat_p13(int key, const FlatLaunch& L, const DTraceArgs& A);
 bool launch_trace_flat_p14(int key, const FlatLaunch& L, const DTraceArgs& A);
 void launch_trace_generic(int grid, hipStream_t st, const DTraceArgs& A);       // counts bih_nodes / prim_tests (part 14)
 void launch_trace_generic_lean(int grid, hipStream_t st, const DTraceArgs& A);  // does not (part 13)
+// the lens stages of the trace seam (lens_kernels.hpp; part 15): k_camera_rays, and k_resolve staging kResolveSamplesInLds samples per pixel
+// in LDS at a time -- 64 * (16 * 5 + 1) words = 20.25 KB a wave, seven waves per CU
+constexpr int kResolveSamplesInLds = 16;
+void launch_camera_rays(int grid, hipStream_t st, const DLensArgs& A);
+void launch_resolve(int grid, hipStream_t st, const DResolveArgs& A);

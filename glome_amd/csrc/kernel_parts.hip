@@ -1,8 +1,9 @@
 // kernel_parts.hip -- the kernel instances of the library, cut into parts that compile in parallel: -DGLOME_PART=k (k = 1..kParts-1,
 // glome_amd/build.py) keeps the instances instances.hpp lists for part k and defines the launcher that knows them (kernel_launch.hpp).
-// The device code itself is render_kernels.hpp and trace_kernels.hpp; the host runtime (runtime.hip) is a unit of its own and holds none of it.
+// The device code itself is render_kernels.hpp, trace_kernels.hpp and lens_kernels.hpp; the host runtime (runtime.hip) is a unit of its own and holds none of it.
 #include "render_kernels.hpp"
 #include "trace_kernels.hpp"
+#include "lens_kernels.hpp"
 
 #if !defined(GLOME_PART) || GLOME_PART < 1 || GLOME_PART >= GLOME_NPARTS
 #error "kernel_parts.hip is compiled once per part: -DGLOME_PART=k with k = 1..GLOME_NPARTS-1 (instances.hpp)"
@@ -110,4 +111,9 @@ void launch_trace_generic_lean(int grid, hipStream_t st, const DTraceArgs& A) { 
 #if GLOME_IN_PART(14)
 bool launch_trace_flat_p14(int key, const FlatLaunch& L, const DTraceArgs& A) { GLOME_TRACE_FLAT_P14(GLOME_TRY_TRACE_FLAT) return false; }
 void launch_trace_generic(int grid, hipStream_t st, const DTraceArgs& A) { hipLaunchKernelGGL(k_trace_batch_generic<true>, dim3(grid), dim3(64), flat_lds_bytes((int)A.S.pk_generic_cap), st, A); }
+#endif
+// the lens stages of the trace seam (lens_kernels.hpp): plain grids, the arguments by value
+#if GLOME_IN_PART(15)
+void launch_camera_rays(int grid, hipStream_t st, const DLensArgs& A) { hipLaunchKernelGGL(k_camera_rays<>, dim3(grid), dim3(64), 0, st, A); }
+void launch_resolve(int grid, hipStream_t st, const DResolveArgs& A) { hipLaunchKernelGGL(k_resolve<kResolveSamplesInLds>, dim3(grid), dim3(64), 0, st, A); }
 #endif

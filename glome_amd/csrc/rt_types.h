@@ -218,6 +218,39 @@ struct DTraceArgs {
   uint64_t work_pad;      // (the struct grows by a whole 16 bytes: the kernel arguments behind it keep their alignment, and with it the
                           // instances that never read `work` the scalar loads -- and the registers -- they had)
 };
+// ---- the lens stages of the trace seam (lens_kernels.hpp: k_camera_rays before a trace launch, k_resolve after it)
+// The word behind sample dimension `dim` of sample `s` of pixel `pixel` (glome_raygen_sample; u = (word >> 8) * 2^-24): three rounds of a
+// 32-bit mixer, uint32 arithmetic throughout.  One definition for the host entry and the kernel: they must agree to the bit.
+constexpr uint32_t raygen_mix(uint32_t x) {
+  x ^= x >> 16; x *= 0x7feb352du; x ^= x >> 15; x *= 0x846ca68bu; x ^= x >> 16;
+  return x;
+}
+constexpr uint32_t raygen_word(uint32_t seed, uint32_t pixel, uint32_t s, uint32_t dim) {
+  return raygen_mix(raygen_mix(raygen_mix(seed + 0x9e3779b9u * (pixel + 1u)) + s) + dim);
+}
+enum DLens : int32_t { LENS_PINHOLE = 0, LENS_THIN = 1, LENS_LATLONG = 2 };  // GLOME_LENS_*
+constexpr int kMaxLensSamples = 64;  // samples per pixel of a raygen / resolve launch
+// The arguments of a raygen launch: ray first_ray + j of the frame's order (y * width + x) * samples + s goes to element j of the streams.
+struct DLensArgs {
+  DCamera cam;
+  float fhat[3], rhat[3], uhat[3];  // the camera's fwd, right and up normalised (in double on the host, rounded once); THIN and LATLONG
+  int32_t width, height, lens, samples, jitter;
+  uint32_t seed;
+  float aperture, focus_dist;
+  uint32_t first_pixel, first_s;    // first_ray = first_pixel * samples + first_s, divided once on the host
+  uint32_t n;                       // rays of the launch (<= 2^31: a ray's offset in the launch fits 32 bits)
+  float *ox, *oy, *oz, *dx, *dy, *dz;
+};
+// The arguments of a resolve launch: samples_in holds the n_pixels * samples tuples of pixels first_pixel .. first_pixel + n_pixels - 1,
+// rgbad / packed are whole frames (either may be null).
+struct DResolveArgs {
+  const float* samples_in;
+  float* rgbad;
+  uint32_t* packed;
+  uint32_t first_pixel, n_pixels;
+  int32_t samples;
+  int32_t vec;  // 1: samples_in is 16-byte aligned (a wave's block then is: it starts a multiple of 1280 bytes further on)
+};
 constexpr int kWorkWords = 8;  // GLOME_WORK_WORDS: bih, mesh, prim, shadow rays, secondary rays of a ray's whole trace; bih, mesh, prim of its primary ray's closest hit
 
 }  // namespace glome

@@ -5,6 +5,7 @@
 // (bih_build_device.hpp) and the flagship launch's cull pass (cull_kernels.hpp).
 #include <hip/hip_runtime.h>
 
+#include <cmath>
 #include <cstdio>
 #include <cstring>
 #include <map>
@@ -108,6 +109,7 @@ struct glome_ctx {
   bool timing = false;
   int timing_stride = 1, timing_seen = 0;  // every timing_stride-th launch is timed
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
+  hipEvent_t ev2 = nullptr, ev3 = nullptr;  // glome_render_lens with statistics: its raygen and resolve stages (a trace launch in between records ev0 / ev1)
   hipDeviceProp_t prop;
   // Per-slot launch state, so several frames can be in flight on different streams (their work queues, counters and
   // workspaces must not be shared): slot 0 is the default.
@@ -120,6 +122,8 @@ struct glome_ctx {
     uint32_t* d_list = nullptr;  // the flagship launch's ticket list, then its cull pass's chunk masks (cull_kernels.hpp)
     size_t list_items = 0;       // ... sized for this many work items (ensure_list)
     uint32_t cull_total = 0;     // work items of the slot's last flagship launch (its live ones: DCounters::list_len)
+    float* d_lens = nullptr;     // glome_render_lens: a pass's six ray streams, then its n * 5 results (grown on demand)
+    size_t lens_bytes = 0;
     bool launched = false;  // a launch went out on this slot since its error word was last polled
     hipStream_t launched_on = nullptr;  // ... on this stream (a caller's own stream is the caller's to synchronise)
   };
@@ -258,6 +262,7 @@ glome_ctx* glome_ctx_create(int device_ordinal) {
   c->own_stream = c->stream;
   if ((e = hipEventCreate(&c->ev0)) != hipSuccess) return fail("hipEventCreate", e);
   if ((e = hipEventCreate(&c->ev1)) != hipSuccess) return fail("hipEventCreate", e);
+  if ((e = hipEventCreate(&c->ev2)) != hipSuccess || (e = hipEventCreate(&c->ev3)) != hipSuccess) return fail("hipEventCreate", e);
   for (int k = 0; k < glome_ctx::kSlots; k++)
     if ((e = hipMalloc((void**)&c->slots[k].d_counters, sizeof(DCounters))) != hipSuccess || (e = hipMemset(c->slots[k].d_counters, 0, sizeof(DCounters))) != hipSuccess) return fail("hipMalloc", e);
   {  // kernel_args<>()'s assumption about the kernarg segment, checked once per process on the first context
@@ -292,9 +297,12 @@ void glome_ctx_destroy(glome_ctx* c) {
     if (sl.d_ovf) (void)hipFree(sl.d_ovf);
     if (sl.d_scratch) (void)hipFree(sl.d_scratch);
     if (sl.d_list) (void)hipFree(sl.d_list);
+    if (sl.d_lens) (void)hipFree(sl.d_lens);
   }
   if (c->ev0) (void)hipEventDestroy(c->ev0);
   if (c->ev1) (void)hipEventDestroy(c->ev1);
+  if (c->ev2) (void)hipEventDestroy(c->ev2);
+  if (c->ev3) (void)hipEventDestroy(c->ev3);
   for (hipEvent_t ev : c->pool) (void)hipEventDestroy(ev);
   if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
   delete c;
@@ -1097,6 +1105,189 @@ int glome_trace_batch(glome_scene* s, size_t n, const float* ox, const float* oy
   if (ny) HIPCHK(ctx, hipMemcpy(ny, dny, n * 4, hipMemcpyDeviceToHost));
   if (nz) HIPCHK(ctx, hipMemcpy(nz, dnz, n * 4, hipMemcpyDeviceToHost));
   if (tex8) HIPCHK(ctx, hipMemcpy(tex8, dtex, n * 32, hipMemcpyDeviceToHost));
+  return 0;
+}
+
+// ---- frames through the trace seam: raygen and resolve (lens_kernels.hpp), and the pass loop that chains them around a trace launch ----
+// Everything a raygen launch is refused for, decided before anything is launched; fills the launch's arguments but for the streams.
+static int lens_args(glome_ctx* ctx, const glome_camera* cam, const glome_raygen_params* P, int64_t first_ray, int64_t n_rays, DLensArgs& A) {
+  if (const char* why = raygen_params_error(P)) { ctx->err = why; return GLOME_E_INVALID; }
+  if (!cam) { ctx->err = "null camera"; return GLOME_E_INVALID; }
+  const float* c = cam->pos;  // (pos, fwd, up, right: twelve floats)
+  for (int k = 0; k < 12; k++) if (!std::isfinite(c[k])) { ctx->err = "a camera component is not finite"; return GLOME_E_INVALID; }
+  const int64_t total = (int64_t)P->width * P->height * P->samples;
+  if (first_ray < 0 || n_rays < 0 || first_ray > total || n_rays > total - first_ray) { ctx->err = "ray range outside the frame"; return GLOME_E_INVALID; }
+  if (n_rays > (1ll << 31)) { ctx->err = "a raygen launch makes at most 2^31 rays"; return GLOME_E_INVALID; }
+  memset(&A, 0, sizeof(A));
+  static_assert(sizeof(DCamera) == sizeof(glome_camera), "glome_camera is DCamera");
+  memcpy(&A.cam, cam, sizeof(DCamera));
+  const float* axis[3] = {cam->fwd, cam->right, cam->up};
+  float* hat[3] = {A.fhat, A.rhat, A.uhat};
+  for (int k = 0; k < 3; k++) {
+    const double x = axis[k][0], y = axis[k][1], z = axis[k][2], len = std::sqrt(x * x + y * y + z * z);
+    if (len > 0) { hat[k][0] = (float)(x / len); hat[k][1] = (float)(y / len); hat[k][2] = (float)(z / len); }
+    else if (P->lens != GLOME_LENS_PINHOLE) { ctx->err = "the camera's fwd, right and up must not be zero for this lens"; return GLOME_E_INVALID; }
+  }
+  A.width = P->width; A.height = P->height; A.lens = P->lens; A.samples = P->samples; A.jitter = P->jitter ? 1 : 0;
+  A.seed = P->seed; A.aperture = P->aperture; A.focus_dist = P->focus_dist;
+  A.first_pixel = (uint32_t)(first_ray / P->samples); A.first_s = (uint32_t)(first_ray % P->samples);
+  A.n = (uint32_t)n_rays;
+  return 0;
+}
+static int resolve_check(glome_ctx* ctx, int32_t width, int32_t height, int32_t samples, int64_t first_pixel, int64_t n_pixels) {
+  if (width < 1 || height < 1) { ctx->err = "width and height must be at least 1"; return GLOME_E_INVALID; }
+  if ((int64_t)width * height > (1ll << 30)) { ctx->err = "frame too large"; return GLOME_E_INVALID; }
+  if (samples < 1 || samples > kMaxLensSamples) { ctx->err = "samples must be in 1..64"; return GLOME_E_INVALID; }
+  const int64_t total = (int64_t)width * height;
+  if (first_pixel < 0 || n_pixels < 0 || first_pixel > total || n_pixels > total - first_pixel) { ctx->err = "pixel range outside the frame"; return GLOME_E_INVALID; }
+  return 0;
+}
+// the two launches (arguments checked; both take part in glome_ctx_timing_begin / _end like a render launch)
+static int lens_launch_rays(glome_ctx* ctx, const DLensArgs& A) {
+  if (A.n == 0) return 0;
+  hipEvent_t e0, e1;
+  const bool pooled = ctx->timing && launch_events(ctx, e0, e1);
+  if (pooled) HIPCHK(ctx, hipEventRecord(e0, ctx->stream));
+  const uint32_t items = (A.n + 63u) >> 6;
+  launch_camera_rays((int)std::min<uint32_t>(items, (uint32_t)ctx->prop.multiProcessorCount * 32u * 4u), ctx->stream, A);
+  HIPCHK(ctx, hipGetLastError());
+  if (pooled) HIPCHK(ctx, hipEventRecord(e1, ctx->stream));
+  return 0;
+}
+static int lens_launch_resolve(glome_ctx* ctx, int32_t samples, int64_t first_pixel, int64_t n_pixels, const float* in, float* rgbad, uint32_t* packed) {
+  if (n_pixels == 0) return 0;
+  DResolveArgs A;
+  A.samples_in = in; A.rgbad = rgbad; A.packed = packed;
+  A.first_pixel = (uint32_t)first_pixel; A.n_pixels = (uint32_t)n_pixels; A.samples = samples;
+  A.vec = ((uintptr_t)in & 15u) == 0 ? 1 : 0;
+  hipEvent_t e0, e1;
+  const bool pooled = ctx->timing && launch_events(ctx, e0, e1);
+  if (pooled) HIPCHK(ctx, hipEventRecord(e0, ctx->stream));
+  launch_resolve((int)((n_pixels + 63) / 64), ctx->stream, A);  // (a wave per 64 pixels: at most 2^24 blocks)
+  HIPCHK(ctx, hipGetLastError());
+  if (pooled) HIPCHK(ctx, hipEventRecord(e1, ctx->stream));
+  return 0;
+}
+int glome_camera_rays_dev(glome_ctx* ctx, const glome_camera* cam, const glome_raygen_params* P, int64_t first_ray, int64_t n_rays,
+                          float* ox, float* oy, float* oz, float* dx, float* dy, float* dz) {
+  if (!ctx) return GLOME_E_INVALID;
+  DLensArgs A;
+  if (int rc = lens_args(ctx, cam, P, first_ray, n_rays, A)) return rc;
+  if (!ox || !oy || !oz || !dx || !dy || !dz) { ctx->err = "null ray stream"; return GLOME_E_INVALID; }
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  A.ox = ox; A.oy = oy; A.oz = oz; A.dx = dx; A.dy = dy; A.dz = dz;
+  return lens_launch_rays(ctx, A);
+}
+int glome_camera_rays(glome_ctx* ctx, const glome_camera* cam, const glome_raygen_params* P, int64_t first_ray, int64_t n_rays,
+                      float* ox, float* oy, float* oz, float* dx, float* dy, float* dz) {
+  if (!ctx) return GLOME_E_INVALID;
+  DLensArgs A;
+  if (int rc = lens_args(ctx, cam, P, first_ray, n_rays, A)) return rc;
+  if (!ox || !oy || !oz || !dx || !dy || !dz) { ctx->err = "null ray stream"; return GLOME_E_INVALID; }
+  if (n_rays == 0) return 0;
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  Staging st{ctx, {}};
+  float* h[6] = {ox, oy, oz, dx, dy, dz};
+  float* d[6];
+  for (int k = 0; k < 6; k++) if (!(d[k] = st.in<float>(nullptr, (size_t)n_rays))) { ctx->err = "staging allocation failed"; return GLOME_E_HIP; }
+  A.ox = d[0]; A.oy = d[1]; A.oz = d[2]; A.dx = d[3]; A.dy = d[4]; A.dz = d[5];
+  if (int rc = lens_launch_rays(ctx, A)) return rc;
+  HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+  for (int k = 0; k < 6; k++) HIPCHK(ctx, hipMemcpy(h[k], d[k], (size_t)n_rays * sizeof(float), hipMemcpyDeviceToHost));
+  return 0;
+}
+int glome_resolve_dev(glome_ctx* ctx, int32_t width, int32_t height, int32_t samples, int64_t first_pixel, int64_t n_pixels,
+                      const float* rgbad_samples, float* rgbad, uint32_t* packed) {
+  if (!ctx) return GLOME_E_INVALID;
+  if (int rc = resolve_check(ctx, width, height, samples, first_pixel, n_pixels)) return rc;
+  if (!rgbad_samples) { ctx->err = "null sample buffer"; return GLOME_E_INVALID; }
+  if (!rgbad && !packed) { ctx->err = "a resolve needs a frame to write: rgbad, packed or both"; return GLOME_E_INVALID; }
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  return lens_launch_resolve(ctx, samples, first_pixel, n_pixels, rgbad_samples, rgbad, packed);
+}
+// The pass's workspace: six streams of `rays` floats, each starting a multiple of 256 bytes in, then the results.
+static size_t lens_stream_floats(size_t rays) { return (rays + 63) & ~(size_t)63; }
+static int ensure_lens(glome_ctx* ctx, size_t rays) {
+  glome_ctx::Slot& sl = ctx->slot();
+  const size_t need = (lens_stream_floats(rays) * 6 + rays * 5) * sizeof(float);
+  if (need <= sl.lens_bytes) return 0;
+  if (sl.d_lens) { HIPCHK(ctx, hipStreamSynchronize(ctx->stream)); HIPCHK(ctx, hipFree(sl.d_lens)); sl.d_lens = nullptr; sl.lens_bytes = 0; }
+  HIPCHK(ctx, hipMalloc((void**)&sl.d_lens, need));
+  sl.lens_bytes = need;
+  return 0;
+}
+constexpr int64_t kLensRaysPerPass = 1ll << 22;  // 4M rays, 176 MiB of workspace: a first guess, not a measured optimum (include/glome_hip.h)
+// everything glome_render_lens is refused for -- its own arguments, and what a pass's raygen, trace or resolve launch would refuse --
+// asked before the first launch and before a frame is allocated; fills the raygen arguments but for the streams and the range
+static int render_lens_check(glome_ctx* ctx, const glome_camera* cam, const glome_raygen_params* RP, const glome_light* lights, int nlights,
+                             const glome_trace_params* TP, int64_t rays_per_pass, const void* rgbad, const void* packed, DLensArgs& A) {
+  if (int rc = lens_args(ctx, cam, RP, 0, 0, A)) return rc;
+  if (!rgbad && !packed) { ctx->err = "a frame needs somewhere to go: rgbad, packed or both"; return GLOME_E_INVALID; }
+  if (!TP || nlights < 0 || (nlights > 0 && !lights) || rays_per_pass < 0) { ctx->err = "bad argument"; return GLOME_E_INVALID; }
+  if ((int64_t)RP->width * RP->height * RP->samples > (1ll << 31)) { ctx->err = "glome_render_lens renders at most 2^31 rays per frame"; return GLOME_E_INVALID; }
+  if (nlights > kMaxLights) { ctx->err = "too many lights"; return GLOME_E_LIMIT; }
+  if (TP->maxdepth < 1 || TP->maxdepth > kMaxTraceDepth) { ctx->err = "maxdepth must be in 1.." + std::to_string(kMaxTraceDepth); return GLOME_E_LIMIT; }
+  return 0;
+}
+int glome_render_lens_dev(glome_scene* s, const glome_camera* cam, const glome_raygen_params* RP, const glome_light* lights, int nlights,
+                          const glome_trace_params* TP, int64_t rays_per_pass, float* rgbad_dev, uint32_t* packed_dev, glome_stats* stats) {
+  if (!s) return GLOME_E_INVALID;
+  glome_ctx* ctx = s->ctx;
+  DLensArgs A;
+  if (int rc = render_lens_check(ctx, cam, RP, lights, nlights, TP, rays_per_pass, rgbad_dev, packed_dev, A)) return rc;
+  const int64_t pixels = (int64_t)RP->width * RP->height, samples = RP->samples;
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  const int64_t per_pass = std::min<int64_t>(pixels, std::max<int64_t>(1, (rays_per_pass ? rays_per_pass : kLensRaysPerPass) / samples));  // pixels
+  if (int rc = ensure_lens(ctx, (size_t)(per_pass * samples))) return rc;
+  const size_t sf = lens_stream_floats((size_t)(per_pass * samples));
+  float* w = ctx->slot().d_lens;
+  A.ox = w; A.oy = w + sf; A.oz = w + 2 * sf; A.dx = w + 3 * sf; A.dy = w + 4 * sf; A.dz = w + 5 * sf;
+  float* results = w + 6 * sf;
+  if (stats) memset(stats, 0, sizeof(*stats));
+  for (int64_t p0 = 0; p0 < pixels; p0 += per_pass) {
+    const int64_t np = std::min(per_pass, pixels - p0), n = np * samples;
+    A.first_pixel = (uint32_t)p0; A.first_s = 0; A.n = (uint32_t)n;
+    float ms_rays = 0, ms_resolve = 0;
+    glome_stats ps;
+    if (stats) HIPCHK(ctx, hipEventRecord(ctx->ev2, ctx->stream));
+    if (int rc = lens_launch_rays(ctx, A)) return rc;
+    if (stats) HIPCHK(ctx, hipEventRecord(ctx->ev3, ctx->stream));
+    if (int rc = glome_trace_batch_dev(s, (size_t)n, A.ox, A.oy, A.oz, A.dx, A.dy, A.dz, nullptr, lights, nlights, TP, results, nullptr, nullptr, nullptr, nullptr,
+                                       nullptr, nullptr, stats ? &ps : nullptr)) return rc;
+    if (stats) {  // (the trace launch has synchronised the stream: the raygen pair is complete)
+      HIPCHK(ctx, hipEventElapsedTime(&ms_rays, ctx->ev2, ctx->ev3));
+      HIPCHK(ctx, hipEventRecord(ctx->ev2, ctx->stream));
+    }
+    if (int rc = lens_launch_resolve(ctx, (int32_t)samples, p0, np, results, rgbad_dev, packed_dev)) return rc;
+    if (stats) {
+      HIPCHK(ctx, hipEventRecord(ctx->ev3, ctx->stream));
+      HIPCHK(ctx, hipEventSynchronize(ctx->ev3));
+      HIPCHK(ctx, hipEventElapsedTime(&ms_resolve, ctx->ev2, ctx->ev3));
+      stats->rays_primary += ps.rays_primary; stats->rays_shadow += ps.rays_shadow; stats->rays_secondary += ps.rays_secondary;
+      stats->bih_nodes += ps.bih_nodes; stats->mesh_nodes += ps.mesh_nodes; stats->prim_tests += ps.prim_tests;
+      stats->kernel_ms += ms_rays + ps.kernel_ms + ms_resolve;
+      stats->n_tiles += ps.n_tiles;
+    }
+  }
+  if (stats) stats->n_pixels = (int32_t)pixels;
+  return 0;
+}
+int glome_render_lens(glome_scene* s, const glome_camera* cam, const glome_raygen_params* RP, const glome_light* lights, int nlights,
+                      const glome_trace_params* TP, int64_t rays_per_pass, float* rgbad, uint32_t* packed, glome_stats* stats) {
+  if (!s) return GLOME_E_INVALID;
+  glome_ctx* ctx = s->ctx;
+  DLensArgs A;
+  if (int rc = render_lens_check(ctx, cam, RP, lights, nlights, TP, rays_per_pass, rgbad, packed, A)) return rc;
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  const size_t np = (size_t)RP->width * RP->height;
+  Staging st{ctx, {}};
+  float* d5 = rgbad ? st.in<float>(nullptr, np * 5) : nullptr;
+  uint32_t* dp = packed ? st.in<uint32_t>(nullptr, np) : nullptr;
+  if ((rgbad && !d5) || (packed && !dp)) { ctx->err = "staging allocation failed"; return GLOME_E_HIP; }
+  glome_stats local;
+  if (int rc = glome_render_lens_dev(s, cam, RP, lights, nlights, TP, rays_per_pass, d5, dp, stats ? stats : &local)) return rc;
+  if (rgbad) HIPCHK(ctx, hipMemcpy(rgbad, d5, np * 5 * sizeof(float), hipMemcpyDeviceToHost));
+  if (packed) HIPCHK(ctx, hipMemcpy(packed, dp, np * sizeof(uint32_t), hipMemcpyDeviceToHost));
   return 0;
 }
 

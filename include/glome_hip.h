@@ -328,6 +328,74 @@ int glome_trace_work_batch(glome_scene*, size_t n, const float* ox, const float*
 int glome_trace_work_batch_dev(glome_scene*, size_t n, const float* ox, const float* oy, const float* oz, const float* dx, const float* dy,
                                const float* dz, const float* tmax, const glome_light* lights, int nlights, const glome_trace_params*,
                                float* rgbad_dev, uint32_t* work_dev, glome_stats*);
+/* ---- frames through the trace seam: camera rays made on the device, and the per-pixel resolve of their results ----
+ * The two stages a host with a lens of its own needs around glome_trace_batch_dev so that a frame's rays never cross the bus: raygen
+ * stands where GlomeView makes a pixel's ray (getCoords / get_coords + get_rayint, Glome.hs:27-33, 119-140), resolve where it averages
+ * a pixel's samples and pokes the word into the framebuffer (cAvg + blitTile, Glome.hs:191-197, 353-358).  The reference has one lens,
+ * the pinhole of get_rayint; THIN and LATLONG have no counterpart there.
+ * A frame's rays are ordered (y * width + x) * samples + s: a pixel's samples are consecutive.
+ *   PINHOLE  get_rayint of the pixel's coordinates: with samples = 1, jitter = 0 the rays glome_render traces, bit for bit.
+ *   THIN     thin lens: with dp the pinhole direction and f, r, u the camera's fwd, right and up normalised, the ray from the lens point
+ *            L = pos + aperture sqrt(u2) (cos(2 pi u3) r + sin(2 pi u3) u) through the focal-plane point P = pos + dp focus_dist / (dp . f).
+ *   LATLONG  light probe / panorama: longitude pi (2 (x + jx) / width - 1), latitude (pi / 2) yc (yc: get_coords' y, +1 at the top row);
+ *            d = cos(lat) (cos(lon) f - sin(lon) r) + sin(lat) u, o = pos.  Every pixel has a ray.
+ * (jx, jy) = (u0, u1) when jitter is set, else 0; every direction is normalised last, so the streams are legal for glome_trace_batch
+ * with faithful = 0.  u_dim = (glome_raygen_sample(seed, y * width + x, s, dim) >> 8) * 2^-24, in [0, 1): dims 0, 1 the jitter, 2, 3 the
+ * lens point.  With mix(x): x ^= x >> 16; x *= 0x7feb352d; x ^= x >> 15; x *= 0x846ca68b; x ^= x >> 16 (uint32 arithmetic), the word is
+ * mix(mix(mix(seed + 0x9e3779b9 * (pixel + 1)) + s) + dim); the device computes the same word. */
+enum { GLOME_LENS_PINHOLE = 0, GLOME_LENS_THIN = 1, GLOME_LENS_LATLONG = 2 };
+typedef struct glome_raygen_params {
+  int32_t width, height;
+  int32_t lens;        /* GLOME_LENS_* */
+  int32_t samples;     /* per pixel, 1..64 */
+  int32_t jitter;      /* 0: every sample at the pixel's own coordinates (getCoords, Glome.hs:119-128); 1: + (u0, u1) in [0,1)^2 */
+  uint32_t seed;
+  float aperture;      /* THIN: lens radius, scene units (0 = a pinhole's rays up to rounding) */
+  float focus_dist;    /* THIN: distance of the focal plane along the normalised fwd, > 0 */
+} glome_raygen_params;
+void glome_raygen_params_default(glome_raygen_params*);  /* 720x480 (Glome.hs:112-113), PINHOLE, 1 sample, no jitter, seed 0, aperture 0, focus 1 */
+size_t glome_raygen_params_size(void);                   /* sizeof(glome_raygen_params) of the loaded library, for a binding to check */
+/* Host-only.  What every entry below refuses, as GLOME_E_INVALID: a null pointer, width or height < 1, width * height > 2^30 (the limit
+ * of glome_render), samples outside 1..64, an unknown lens, aperture or focus_dist not finite, THIN with focus_dist <= 0 or aperture < 0.
+ * glome_raygen_count: width * height * samples, or GLOME_E_INVALID. */
+int64_t glome_raygen_count(const glome_raygen_params*);
+uint32_t glome_raygen_sample(uint32_t seed, uint32_t pixel, uint32_t s, uint32_t dim);  /* host-only: the word behind u_dim */
+/* Rays first_ray .. first_ray + n_rays - 1 of the frame's order into elements 0 .. n_rays - 1 of the six streams.  The range need not be
+ * a multiple of 64 nor start at a pixel's first sample; a call makes at most 2^31 rays (what one trace launch takes).  GLOME_E_INVALID,
+ * before anything is launched or written: the params as above, a null context, camera or stream, a camera with a component that is not
+ * finite, for THIN and LATLONG a fwd, right or up of length 0, a range that is negative or reaches past glome_raygen_count.  n_rays = 0
+ * succeeds.  The _dev form is asynchronous on the context's stream and takes part in glome_ctx_timing_begin / _end like a render launch;
+ * the host form stages the streams through device memory and is there for tests and small streams. */
+int glome_camera_rays_dev(glome_ctx*, const glome_camera*, const glome_raygen_params*, int64_t first_ray, int64_t n_rays,
+                          float* ox, float* oy, float* oz, float* dx, float* dy, float* dz);
+int glome_camera_rays(glome_ctx*, const glome_camera*, const glome_raygen_params*, int64_t first_ray, int64_t n_rays,
+                      float* ox, float* oy, float* oz, float* dx, float* dy, float* dz);
+/* Pixels first_pixel .. first_pixel + n_pixels - 1 (row major) of a width x height frame from rgbad_samples, the n_pixels * samples
+ * (r, g, b, a, depth) tuples glome_trace_batch wrote for those pixels' rays.  Per pixel r, g, b, a are each summed over s = 0 .. samples - 1
+ * in that order -- fp32 additions starting from sample 0 -- and the sum is divided once by (float)samples, correctly rounded; depth is the
+ * least of the samples' depths.  The order is part of the contract: a host reproduces the frame bit for bit.  rgbad (width * height * 5) and
+ * packed (width * height words) are whole frames, and pixels outside the range are left untouched; packed gets the word glome_render
+ * stores for a pixel with that (r, g, b, a) (rgbf of the premultiplied colour); samples = 1 copies the tuples.  Either output may be NULL,
+ * not both.  GLOME_E_INVALID: a null context or input, both outputs null, width or height < 1, width * height > 2^30, samples outside
+ * 1..64, a range that is negative or reaches past the frame.  Asynchronous; timed like glome_camera_rays_dev. */
+int glome_resolve_dev(glome_ctx*, int32_t width, int32_t height, int32_t samples, int64_t first_pixel, int64_t n_pixels,
+                      const float* rgbad_samples, float* rgbad, uint32_t* packed);
+/* A frame of `cam` under the lens of the raygen params, in one call: for each pass of at most rays_per_pass rays (rounded down to whole
+ * pixels, at least one pixel) raygen -> glome_trace_batch_dev -> resolve, all on the scene's context, its current stream and slot.  The
+ * pass's rays and results live in a workspace the slot owns and grows on demand: 44 bytes per ray (six streams and the five-float
+ * result; tmax is not needed).  rays_per_pass = 0 takes the default, 4M rays = 176 MiB -- a first guess (large enough that a pass fills
+ * the GPU many times over, small enough to sit beside a scene), not a measured optimum.  The frame does not depend on rays_per_pass, bit
+ * for bit, and equals the three stages called by hand.  rgbad and packed as glome_render's (either may be NULL, not both); faithful and
+ * count_work of the trace params are passed through.  stats are summed over the passes, n_pixels = width * height, n_tiles = the trace
+ * launches' 64-ray work items, kernel_ms = the HIP-event time of all three stages.  GLOME_E_INVALID, before anything is launched: what
+ * glome_camera_rays_dev and glome_resolve_dev refuse, null trace params, bad lights, rays_per_pass < 0, and width * height * samples >
+ * 2^31 -- a limit of this entry's bookkeeping, not of its passes, which are far below it; GLOME_E_LIMIT: maxdepth or the light count, as
+ * glome_trace_batch.  The host form allocates and copies the frame like glome_render; the _dev form takes device frame pointers and is
+ * asynchronous unless stats != NULL (a unit-length refusal cannot occur: raygen normalises). */
+int glome_render_lens(glome_scene*, const glome_camera*, const glome_raygen_params*, const glome_light* lights, int nlights,
+                      const glome_trace_params*, int64_t rays_per_pass, float* rgbad, uint32_t* packed, glome_stats*);
+int glome_render_lens_dev(glome_scene*, const glome_camera*, const glome_raygen_params*, const glome_light* lights, int nlights,
+                          const glome_trace_params*, int64_t rays_per_pass, float* rgbad_dev, uint32_t* packed_dev, glome_stats*);
 /* Host-only, no device: the kernel instance a trace launch gets (choose_trace, glome_amd/csrc/instances.hpp).  n rows of 11 inputs -- the
  * eight scene traits of glome_sb_scene_traits, then faithful, count_work, maxdepth -- give n rows of 3 outputs: the instance (a flat-tier
  * key with the bits glome_kernel_choice describes, TWO_ROWS never set; -1 / -2: the generic tier's kernel that counts work / does not),
