@@ -105,11 +105,15 @@ def test_frame_rays_traced_as_a_batch_give_the_oracle_frame(committed, name):
 # (0-12 per scene and seed); hit / miss flips <= 2 (the fp32 oracle: 0; parity.MISMATCH_MAX allows 1e-4); depth beyond 1e-4 relative on
 # rays both sides hit <= 4 (the fp32 oracle: 0-1).  The GPU's own counts on an MI355X, per scene and seed: beyond
 # 1e-4 0-13 (S1 0 / 0, S4 2 / 11, materials 7 / 10, nested 0 / 0, portal 1 / 3, textures 13 / 10), flips 0, depth 0.
+# The triangle-BIH class (S3small: one tree of 1,152 triangles under a matte material, walked as packets by the hand-written walk) has caps
+# of its own, each twice the fp32 oracle's worst count on its rays: that oracle moves no ray of either seed beyond 1e-4, flips none and
+# moves no depth, so all three caps are 0.  The GPU's own counts on an MI355X: beyond 1e-4 0 / 0, flips 0, depth 0.
 AWAY_MAX, FLIP_MAX, DEPTH_MAX = 24, 2, 4
+CAPS_OF = {"S3small": (0, 0, 0)}  # (away, flips, depth) where a scene has caps of its own
 
 
 @pytest.mark.parametrize("seed", [11, 29])
-@pytest.mark.parametrize("name", ["S1", "S4", "materials", "nested", "portal", "textures"])
+@pytest.mark.parametrize("name", ["S1", "S3small", "S4", "materials", "nested", "portal", "textures"])
 def test_arbitrary_rays_against_the_oracle_ray_by_ray(committed, name, seed):
     c = committed(name)
     ro, rd, r = c.base(seed)
@@ -123,9 +127,10 @@ def test_arbitrary_rays_against_the_oracle_ray_by_ray(committed, name, seed):
     drel = np.abs(got[both, 4] - ref[both, 4]) / np.maximum(1.0, ref[both, 4])
     levels = {"away": int((e > 1e-4).sum()), "flips": int((hit_g != hit_r).sum()), "depth": int((drel > 1e-4).sum()), "hit_frac": float(hit_r.mean())}
     print("trace_vs_oracle", name, seed, levels)
-    assert levels["away"] <= AWAY_MAX, levels
-    assert levels["flips"] <= FLIP_MAX, levels
-    assert levels["depth"] <= DEPTH_MAX, levels
+    away_max, flip_max, depth_max = CAPS_OF.get(name, (AWAY_MAX, FLIP_MAX, DEPTH_MAX))
+    assert levels["away"] <= away_max, levels
+    assert levels["flips"] <= flip_max, levels
+    assert levels["depth"] <= depth_max, levels
 
 
 # ---------------------------------------------------------------- 3. tail and order
