@@ -237,6 +237,13 @@ class Builder:
         return self._chk(self.lib.glome_sb_mesh(self.h, v.ctypes.data_as(L.c_dp), v.shape[0], n.ctypes.data_as(L.c_dp), n.shape[0],
                                                 t.ctypes.data_as(L.c_ip), t.shape[0], m.ctypes.data_as(L.c_ip), m.shape[0]), "glome_sb_mesh")
 
+    def mesh_set_vertices(self, node, verts, norms=None):
+        """Same tree, new vertices (glome_sb_mesh_set_vertices): the mesh's boxes are made again from `verts`, its topology stays."""
+        v = np.ascontiguousarray(np.asarray(verts, dtype=np.float64).reshape(-1, 3))
+        n = None if norms is None else np.ascontiguousarray(np.asarray(norms, dtype=np.float64).reshape(-1, 3))
+        self._chk(self.lib.glome_sb_mesh_set_vertices(self.h, int(node), v.ctypes.data_as(L.c_dp), v.shape[0], n.ctypes.data_as(L.c_dp) if n is not None and n.shape[0] else None,
+                                                      0 if n is None else n.shape[0]), "glome_sb_mesh_set_vertices")
+
     def tex(self, node, material): return self._chk(self.lib.glome_sb_tex(self.h, int(node), int(material)), "glome_sb_tex")
     def tag(self, node, _tag=None): return self._chk(self.lib.glome_sb_tag(self.h, int(node)), "glome_sb_tag")
     def noshadow(self, node): return self._chk(self.lib.glome_sb_noshadow(self.h, int(node)), "glome_sb_noshadow")
@@ -437,6 +444,29 @@ class Scene:
     def _chk(self, rc, what):
         if rc != 0:
             raise GlomeError(f"{what}: {self.ctx.err()} (status {rc})")
+
+    def mesh_update(self, mesh_id, verts, norms=None):
+        """New vertices for a committed Mesh, its BVH refitted on the GPU (glome_scene_mesh_update): the scene a commit after
+        Builder.mesh_set_vertices would have made.  NumPy arrays (or anything array-like) take the host form, which returns the device
+        milliseconds of the finished update; CUDA torch.float64 tensors take the device form, asynchronous on the context's stream
+        (returns None; the tensors must stay alive until it has run)."""
+        if hasattr(verts, "data_ptr"):  # torch tensors: the device form
+            def dev(t, what):
+                if t is None:
+                    return None, 0
+                if not t.is_cuda or str(t.dtype) != "torch.float64" or not t.is_contiguous() or t.numel() % 3:
+                    raise GlomeError(f"mesh_update: {what} must be a contiguous CUDA torch.float64 tensor of 3 values per row")
+                return (C.c_void_p(t.data_ptr()) if t.numel() else None), t.numel() // 3
+            pv, nv = dev(verts, "verts")
+            pn, nn = dev(norms, "norms")
+            self._chk(self.lib.glome_scene_mesh_update_dev(self.h, int(mesh_id), pv, nv, pn, nn), "glome_scene_mesh_update_dev")
+            return None
+        v = np.ascontiguousarray(np.asarray(verts, dtype=np.float64).reshape(-1, 3))
+        n = None if norms is None else np.ascontiguousarray(np.asarray(norms, dtype=np.float64).reshape(-1, 3))
+        ms = C.c_float(0)
+        self._chk(self.lib.glome_scene_mesh_update(self.h, int(mesh_id), v.ctypes.data_as(L.c_dp), v.shape[0], n.ctypes.data_as(L.c_dp) if n is not None and n.shape[0] else None,
+                                                   0 if n is None else n.shape[0], C.byref(ms)), "glome_scene_mesh_update")
+        return ms.value
 
     def _rays(self, o, d, tmax):
         o = np.asarray(o, dtype=np.float32).reshape(-1, 3)

@@ -136,6 +136,16 @@ int32_t glome_sb_mesh(glome_sb* sb, const double* verts, int nv, const double* n
     return sb->graph.mesh(std::move(V), std::move(N), std::move(T), std::vector<int>(mats, mats + nm));
   });
 }
+int glome_sb_mesh_set_vertices(glome_sb* sb, int32_t mesh_id, const double* verts, int nv, const double* norms, int nn) {
+  return guard(sb, [&] {
+    if (nv < 0 || nn < 0 || (nv && !verts) || (nn && !norms)) throw std::invalid_argument("mesh_set_vertices: bad vertex / normal arrays");
+    std::vector<D3> V, N;
+    for (int k = 0; k < nv; k++) V.push_back(d3(verts + 3 * k));
+    for (int k = 0; k < nn; k++) N.push_back(d3(norms + 3 * k));
+    sb->graph.mesh_set_vertices(mesh_id, std::move(V), std::move(N));
+    return 0;
+  });
+}
 int32_t glome_sb_tex(glome_sb* sb, int32_t id, int32_t material) { return guard(sb, [&] { return sb->graph.wrap(K_TEX, id, material); }); }
 int32_t glome_sb_tag(glome_sb* sb, int32_t id) { return guard(sb, [&] { return sb->graph.wrap(K_TAG, id); }); }
 int32_t glome_sb_noshadow(glome_sb* sb, int32_t id) { return guard(sb, [&] { return sb->graph.wrap(K_NOSHADOW, id); }); }

@@ -12,6 +12,22 @@
 
 namespace glome {
 
+// What an update of a committed Mesh's vertices needs (glome_scene_mesh_update; mesh_update_kernels.hpp), recorded per emitted mesh and
+// kept beside the scene, outside DScene.  Record j of the mesh is mtris record first_tri + j; its index row is rows[8 j ..]:
+// a b c na nb nc, the triangle's first trinorms word or -1, a spare word.  The placeholder record of an empty leaf has a = -1.
+struct MeshUpdateInfo {
+  int node = -1;                  // the mesh's builder id
+  int nv = 0, nn = 0;
+  uint32_t hdr = 0;               // meshhdr index
+  uint32_t first_node = 0, n_nodes = 0;  // its branch nodes (meshnodes index, count)
+  uint32_t first_tri = 0, n_tris = 0;    // its mtris records (placeholders included)
+  std::vector<int32_t> rows;
+  std::vector<uint32_t> level_nodes;  // its branch nodes, deepest tree level first ...
+  std::vector<uint32_t> level_off;    // ... level l is level_nodes[level_off[l] .. level_off[l + 1])
+  bool updatable = true;          // false: a path from the committed root to the mesh passes through a Bih, whose planes and root box were
+  std::string why_not;            // built from the mesh's bound (Bih.hs:309-324) -- the reason, naming that bih
+};
+
 struct FlatScene {
   std::vector<U4> recs;
   std::vector<F4> spheres, tris, trinorms, boxes, planes, discs, quadrics, xfms, bihhdr, bihnodes, meshhdr, meshnodes, mtris, mats, wlights;
@@ -27,6 +43,7 @@ struct FlatScene {
   int64_t n_other_prims = 0;
   std::string why_generic;  // why the flat tier was not chosen
   bool pk_all = true;       // every triangle BIH has the packet walk's node form (emit_bih)
+  std::vector<MeshUpdateInfo> mesh_updates;  // one per emitted mesh (emit_mesh), in emission order
 };
 
 inline float f32(double d) { return (float)d; }
@@ -34,8 +51,9 @@ inline float as_float_bits(uint32_t u) { float f; std::memcpy(&f, &u, 4); return
 inline F4 mk4(double x, double y, double z, double w) { return F4{f32(x), f32(y), f32(z), f32(w)}; }
 inline F4 mk4u(double x, double y, double z, uint32_t w) { return F4{f32(x), f32(y), f32(z), as_float_bits(w)}; }
 // split planes are rounded outward so that an fp32 plane never cuts into the objects it bounds
-inline float round_up(double d) { float f = (float)d; return ((double)f < d) ? std::nextafterf(f, INFINITY) : f; }
-inline float round_down(double d) { float f = (float)d; return ((double)f > d) ? std::nextafterf(f, -INFINITY) : f; }
+// (host and device: the mesh update's kernels round with these very functions, mesh_update_kernels.hpp)
+GLOME_HD float round_up(double d) { float f = (float)d; return ((double)f < d) ? nextafterf(f, INFINITY) : f; }
+GLOME_HD float round_down(double d) { float f = (float)d; return ((double)f > d) ? nextafterf(f, -INFINITY) : f; }
 
 constexpr uint32_t BREF_LEAF_BIT = 1u << 29, BREF_FIRST_LIMIT = 1u << 26;  // child references, see rt_device.hpp
 
@@ -68,6 +86,7 @@ class Flattener {
     // the generic tier walks BIHs / Mesh BVHs with a fixed scratch stack per level: a deeper tree is refused, not truncated
     if (F.tier != 0 && F.max_mesh_depth > kGenericStack)
       throw limit_error("Mesh tree deeper than the device traversal stack (" + std::to_string(F.max_mesh_depth) + " > " + std::to_string(kGenericStack) + ")");
+    mark_updatable(root);
     pad();
   }
 
@@ -272,6 +291,45 @@ class Flattener {
     return d;
   }
 
+  // Which emitted meshes may have their vertices replaced in the committed scene (MeshUpdateInfo::updatable): every one that no Bih
+  // lies above, on any path from the root or from a Warp material's frame / scene.  Of the composites, only a Bih keeps something derived
+  // from a child's bound -- its planes and its root box.  A list, an Instance, a Difference, an Intersection and the Tex / Tag / shadow
+  // wrappers emit no box at all (emit, below), and the bounding solid of a Bound / InnerBound is the caller's own object.
+  void mark_updatable(int root) {
+    if (F.mesh_updates.empty()) return;
+    std::unordered_map<int, size_t> slot_of;
+    for (size_t k = 0; k < F.mesh_updates.size(); k++) slot_of[F.mesh_updates[k].node] = k;
+    std::unordered_map<int, int> seen;  // node -> 1: visited with no Bih above, 2: with one, 3: both
+    struct Item { int id, bih; };
+    std::vector<Item> stack{{root, -1}};
+    for (const Mat& m : G.mats) if (m.kind == MAT_WARP) { stack.push_back({m.wframe, -1}); if (m.wscene >= 0) stack.push_back({m.wscene, -1}); }
+    while (!stack.empty()) {
+      Item it = stack.back();
+      stack.pop_back();
+      int& sn = seen[it.id];
+      const int bit = it.bih < 0 ? 1 : 2;
+      if (sn & bit) continue;
+      sn |= bit;
+      const Node& n = G.at(it.id);
+      switch (n.kind) {
+        case K_LIST: case K_ISECT: for (int k : n.kids) stack.push_back({k, it.bih}); break;
+        case K_DIFF: case K_BOUND: case K_INNERBOUND: stack.push_back({n.a, it.bih}); stack.push_back({n.b, it.bih}); break;
+        case K_INSTANCE: case K_TEX: case K_TAG: case K_NOSHADOW: case K_ONLYSHADOW: stack.push_back({n.a, it.bih}); break;
+        case K_BIH: for (auto& bn : n.bih->nodes) for (int k : bn.items) stack.push_back({k, it.bih < 0 ? it.id : it.bih}); break;
+        case K_MESH: {
+          auto sl = slot_of.find(it.id);
+          if (it.bih >= 0 && sl != slot_of.end() && F.mesh_updates[sl->second].updatable) {
+            MeshUpdateInfo& U = F.mesh_updates[sl->second];
+            U.updatable = false;
+            U.why_not = "mesh " + std::to_string(it.id) + " lies inside bih " + std::to_string(it.bih) + ", whose planes and root box were built from the mesh's bound";
+          }
+          break;
+        }
+        default: break;
+      }
+    }
+  }
+
   // ---- primitive pools ----
   uint32_t emit_tri(const double* p) {  // (p1, e1, e2, n) evaluated in double, rounded once
     D3 p1{p[0], p[1], p[2]}, p2{p[3], p[4], p[5]}, p3{p[6], p[7], p[8]};
@@ -408,7 +466,7 @@ class Flattener {
         break;
       }
       case K_BIH: r = emit_bih(n); break;
-      case K_MESH: r = emit_mesh(n); break;
+      case K_MESH: r = emit_mesh(n, id); break;
     }
     memo[id] = r;
     return r;
@@ -561,11 +619,13 @@ class Flattener {
     return U4{R_BIH, hdr, 0, (uint32_t)n.uid};
   }
 
-  U4 emit_mesh(const Node& n) {
+  U4 emit_mesh(const Node& n, int id) {
     const MeshData& M = *n.mesh;
     F.max_mesh_depth = std::max(F.max_mesh_depth, M.depth);
     uint32_t hdr = (uint32_t)(F.meshhdr.size() / 2);
     uint32_t nbase = (uint32_t)(F.meshnodes.size() / 4);
+    MeshUpdateInfo U;
+    U.node = id; U.nv = (int)M.verts.size(); U.nn = (int)M.norms.size(); U.hdr = hdr; U.first_node = nbase; U.first_tri = (uint32_t)(F.mtris.size() / 3);
     // node index remap: branches only (leaves are encoded in the parent's ref)
     std::vector<uint32_t> bidx(M.nodes.size(), 0);
     uint32_t nb = 0;
@@ -586,6 +646,8 @@ class Flattener {
         F.mtris.push_back(mk4(e1.x, e1.y, e1.z, nn.y));
         F.mtris.push_back(mk4(e2.x, e2.y, e2.z, nn.z));
         U4 meta{0, 0, q == 0 ? count : 0u, 0};
+        const int32_t row[8] = {t.a, t.b, t.c, t.na, t.nb, t.nc, t.na != -1 ? (int32_t)F.trinorms.size() : -1, 0};
+        U.rows.insert(U.rows.end(), row, row + 8);
         if (t.na != -1) {
           meta.x = (uint32_t)F.trinorms.size() + 1;
           for (int ni : {t.na, t.nb, t.nc}) F.trinorms.push_back(mk4(M.norms[ni].x, M.norms[ni].y, M.norms[ni].z, 0));
@@ -593,7 +655,11 @@ class Flattener {
         if (t.tex != -1) meta.y = (uint32_t)M.mats[t.tex] + 1;
         F.mtrimeta.push_back(meta);
       }
-      if (count == 0) { F.mtrimeta.push_back(U4{0, 0, 0, 0}); for (int q = 0; q < 3; q++) F.mtris.push_back(F4{0, 0, 0, 0}); }  // keep `first` addressable
+      if (count == 0) {  // keep `first` addressable
+        F.mtrimeta.push_back(U4{0, 0, 0, 0}); for (int q = 0; q < 3; q++) F.mtris.push_back(F4{0, 0, 0, 0});
+        const int32_t row[8] = {-1, -1, -1, -1, -1, -1, -1, 0};
+        U.rows.insert(U.rows.end(), row, row + 8);
+      }
       ref[k] = 0x80000000u | ((count >= 15 ? 15u : count) << 27) | first;
     }
     for (size_t k = 0; k < M.nodes.size(); k++) {
@@ -608,6 +674,26 @@ class Flattener {
     }
     F.meshhdr.push_back(mk4u(round_down(M.bb.lo.x), round_down(M.bb.lo.y), round_down(M.bb.lo.z), ref[0]));
     F.meshhdr.push_back(mk4(round_up(M.bb.hi.x), round_up(M.bb.hi.y), round_up(M.bb.hi.z), 0));
+    U.n_nodes = nb; U.n_tris = (uint32_t)(F.mtris.size() / 3) - U.first_tri;
+    if (nb) {  // the branch nodes by tree level, deepest first: a level's children were refitted by the launch before it
+      std::vector<int> depth(M.nodes.size(), 0);
+      std::vector<int> order{0};  // (a parent before its children, whatever the numbering)
+      for (size_t q = 0; q < order.size(); q++) {
+        const MeshData::Node& mn = M.nodes[(size_t)order[q]];
+        if (mn.leaf) continue;
+        for (int c : {mn.left, mn.right}) { depth[(size_t)c] = depth[(size_t)order[q]] + 1; order.push_back(c); }
+      }
+      int deepest = 0;
+      for (int k : order) if (!M.nodes[(size_t)k].leaf) deepest = std::max(deepest, depth[(size_t)k]);
+      std::vector<uint32_t> per_level((size_t)deepest + 2, 0);
+      for (int k : order) if (!M.nodes[(size_t)k].leaf) per_level[(size_t)(deepest - depth[(size_t)k]) + 1]++;
+      for (size_t l = 1; l < per_level.size(); l++) per_level[l] += per_level[l - 1];
+      U.level_off = per_level;
+      U.level_nodes.resize(nb);
+      std::vector<uint32_t> fill(per_level.begin(), per_level.end() - 1);
+      for (int k : order) if (!M.nodes[(size_t)k].leaf) U.level_nodes[fill[(size_t)(deepest - depth[(size_t)k])]++] = bidx[(size_t)k];
+    }
+    F.mesh_updates.push_back(std::move(U));
     return U4{R_MESH, hdr, 0, (uint32_t)n.uid};
   }
 

@@ -552,6 +552,37 @@ struct Graph {
     B2.rec(all, M->bb, 0);
     return mesh_node(M);
   }
+  // Same tree, new vertices (glome_sb_mesh_set_vertices): what `mesh` derives from the vertex arrays is made again -- the
+  // triangles' boxes (Mesh.hs:119-121), every branch's two boxes as the true unions MeshBuild::join makes of the triangles
+  // below them, the mesh's box over ALL vertices (Mesh.hs:55) -- and what build_tree decided (nodes, leaf lists, depth)
+  // stays.  The reference has no such call (`mesh` is a pure constructor): this is the mesh the reference would print for
+  // the same tree with the new arrays.  Nothing is touched unless everything is valid.
+  void mesh_set_vertices(int id, std::vector<D3> verts, std::vector<D3> norms) {
+    if (at(id).kind != K_MESH) throw std::invalid_argument(std::string("mesh_set_vertices: node ") + std::to_string(id) + " is a " + kind_name(at(id).kind) + ", not a Mesh");
+    MeshData& M = *nodes[(size_t)id].mesh;
+    if (verts.size() != M.verts.size()) throw std::invalid_argument("mesh_set_vertices: the mesh has " + std::to_string(M.verts.size()) + " vertices, not " + std::to_string(verts.size()));
+    if (norms.size() != M.norms.size()) throw std::invalid_argument("mesh_set_vertices: the mesh has " + std::to_string(M.norms.size()) + " normals, not " + std::to_string(norms.size()));
+    for (const std::vector<D3>* a : {&verts, &norms})
+      for (const D3& v : *a) if (!(std::isfinite(v.x) && std::isfinite(v.y) && std::isfinite(v.z))) throw std::invalid_argument("mesh_set_vertices: a coordinate is not finite");
+    M.verts = std::move(verts); M.norms = std::move(norms);
+    M.bb = box_of_points(M.verts.data(), M.verts.size());
+    std::vector<Box3> tbb;
+    for (auto& t : M.tris) { D3 pts[3] = {M.verts[t.a], M.verts[t.b], M.verts[t.c]}; tbb.push_back(box_of_points(pts, 3)); }
+    if (M.nodes.empty()) return;
+    // bottom-up over an explicit stack (deep trees): a node's box is known once both subtrees' are
+    std::vector<Box3> sub(M.nodes.size(), box_empty());
+    struct Item { int node; bool done; };
+    std::vector<Item> stack{{0, false}};
+    while (!stack.empty()) {
+      Item it = stack.back();
+      stack.pop_back();
+      MeshData::Node& n = M.nodes[(size_t)it.node];
+      if (n.leaf) { for (int t : n.tris) sub[(size_t)it.node] = box_join(sub[(size_t)it.node], tbb[(size_t)t]); continue; }
+      if (!it.done) { stack.push_back({it.node, true}); stack.push_back({n.right, false}); stack.push_back({n.left, false}); continue; }
+      n.lbb = sub[(size_t)n.left]; n.rbb = sub[(size_t)n.right];
+      sub[(size_t)it.node] = box_join(n.lbb, n.rbb);
+    }
+  }
 
   // ---------------- materials ----------------
   int add_mat(Mat m) { mats.push_back(std::move(m)); return (int)mats.size() - 1; }

@@ -29,6 +29,12 @@
 #pragma once
 #include <stdint.h>
 
+#if defined(__HIPCC__)
+#define GLOME_HD __host__ __device__ inline
+#else
+#define GLOME_HD inline
+#endif
+
 namespace glome {
 
 enum RecKind : uint32_t {
@@ -155,6 +161,7 @@ struct DCounters {  // device-side atomics, one block per launch slot
 };
 constexpr unsigned int kErrLimit = 1u;    // a device-side limit (what every kernel reports)
 constexpr unsigned int kErrNonUnit = 2u;  // a trace launch without `faithful` met a direction that is not unit length (trace_kernels.hpp; no other kernel sets it)
+constexpr unsigned int kErrBadVertex = 4u;  // a mesh update met a vertex coordinate that is not finite (mesh_update_kernels.hpp; no other kernel sets it)
 
 struct DRenderArgs {
   DScene S;

@@ -2,7 +2,7 @@
 // the whole-frame render, the per-ray batch seams, tile transport and the multi-GPU driver.  Compiled once.  It launches the render,
 // sampler and batch kernels through kernel_launch.hpp (the instances live in kernel_parts.hip, chosen by instances.hpp) and holds
 // only the light kernels: the kernel-argument self-test, the coordinate tables, tile transport, the tree builders
-// (bih_build_device.hpp) and the flagship launch's cull pass (cull_kernels.hpp).
+// (bih_build_device.hpp), the flagship launch's cull pass (cull_kernels.hpp) and the update of a committed Mesh (mesh_update_kernels.hpp).
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -23,6 +23,7 @@
 #include "kernel_launch.hpp"
 #include "bih_build_device.hpp"
 #include "cull_kernels.hpp"
+#include "mesh_update_kernels.hpp"
 
 using namespace glome;
 
@@ -147,6 +148,15 @@ struct glome_scene {
   std::vector<void*> allocs;
   glome_scene_info info{};
   SceneTraits tr;   // what the choice of a kernel instance looks at (instances.hpp; tr.stack_cap: stack entries per lane in LDS)
+  // what glome_scene_mesh_update needs of every Mesh of the scene, by its builder id (flatten.hpp MeshUpdateInfo; the index rows and the
+  // level list live on the device, in `allocs`); outside DScene: no render, sampler or trace kernel sees any of it
+  struct MeshUpd {
+    MeshUpdateInfo info;               // (rows and level_nodes emptied once uploaded)
+    const int32_t* d_rows = nullptr;
+    const uint32_t* d_levels = nullptr;
+    float4* d_ws = nullptr;            // two words per record, then the bound's partial boxes: allocated at the first update
+  };
+  std::map<int, MeshUpd> meshes;
 };
 
 static std::string g_global_error;
@@ -510,6 +520,12 @@ glome_scene* glome_scene_commit(glome_ctx* ctx, glome_sb* sb, int32_t root) {
   I.max_bih_depth = F.max_bih_depth; I.max_mesh_depth = F.max_mesh_depth;
   s->tr = R.traits;
   s->ovf_cap = R.caps.ovf_cap;
+  for (MeshUpdateInfo& U : F.mesh_updates) {
+    glome_scene::MeshUpd& m = s->meshes[U.node];
+    if (upload(s, U.rows, &m.d_rows) || (!U.level_nodes.empty() && upload(s, U.level_nodes, &m.d_levels))) { glome_scene_release(s); return nullptr; }
+    U.rows = {}; U.level_nodes = {};
+    m.info = std::move(U);
+  }
   return s;
 }
 void glome_scene_release(glome_scene* s) {
@@ -602,6 +618,10 @@ static int ensure_list(glome_ctx* ctx, uint32_t per_frame) {
 static int device_error_status(glome_ctx* ctx, unsigned int e) {
   if (e & kErrNonUnit) {  // (only a trace launch sets it)
     ctx->err = "a ray direction is not unit length: set glome_trace_params.faithful to trace such rays (the reference's own traversal)";
+    return GLOME_E_INVALID;
+  }
+  if (e & kErrBadVertex) {  // (only a mesh update sets it)
+    ctx->err = "a mesh update met a vertex coordinate that is not finite: the scene's mesh is unspecified until a valid update";
     return GLOME_E_INVALID;
   }
   ctx->err = "device-side limit hit (traversal stack or CSG advance cap)";
@@ -964,6 +984,94 @@ int glome_inside_batch(glome_scene* s, size_t n, const float* px, const float* p
   if (rc) return rc;
   HIPCHK(ctx, hipMemcpy(inside, din, n, hipMemcpyDeviceToHost));
   return 0;
+}
+
+// ---- new vertices for a committed Mesh (mesh_update_kernels.hpp) ----
+// what both forms refuse before anything is launched; *out = the mesh's tables
+static int mesh_update_check(glome_scene* s, int32_t mesh_id, const void* verts, int nv, const void* norms, int nn, glome_scene::MeshUpd** out) {
+  glome_ctx* ctx = s->ctx;
+  auto it = s->meshes.find(mesh_id);
+  if (it == s->meshes.end()) { ctx->err = "mesh update: node " + std::to_string(mesh_id) + " is not a mesh of this scene"; return GLOME_E_INVALID; }
+  const MeshUpdateInfo& U = it->second.info;
+  if (nv != U.nv) { ctx->err = "mesh update: the mesh has " + std::to_string(U.nv) + " vertices, not " + std::to_string(nv); return GLOME_E_INVALID; }
+  if (nn != U.nn) { ctx->err = "mesh update: the mesh has " + std::to_string(U.nn) + " normals, not " + std::to_string(nn); return GLOME_E_INVALID; }
+  if ((nv && !verts) || (nn && !norms)) { ctx->err = "mesh update: null vertex / normal array"; return GLOME_E_INVALID; }
+  if (!U.updatable) { ctx->err = "mesh update refused: " + U.why_not; return GLOME_E_INVALID; }
+  *out = &it->second;
+  return 0;
+}
+int glome_scene_mesh_update_dev(glome_scene* s, int32_t mesh_id, const double* verts_dev, int nv, const double* norms_dev, int nn) {
+  if (!s) return GLOME_E_INVALID;
+  glome_ctx* ctx = s->ctx;
+  glome_scene::MeshUpd* m = nullptr;
+  if (int rc = mesh_update_check(s, mesh_id, verts_dev, nv, norms_dev, nn, &m)) return rc;
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  const MeshUpdateInfo& U = m->info;
+  if (!m->d_ws) {  // 32 bytes per record and the bound's partial boxes: kept until glome_scene_release
+    void* d = nullptr;
+    HIPCHK(ctx, hipMalloc(&d, ((size_t)U.n_tris + meshupd::kBoundMaxBlocks) * 2 * sizeof(float4)));
+    s->allocs.push_back(d);
+    m->d_ws = (float4*)d;
+  }
+  hipStream_t st = ctx->stream;
+  const uint32_t max_items = (uint32_t)ctx->prop.multiProcessorCount * 32u * 4u;
+  // one event pair per update while timing is on; with GLOME_DEBUG_MESH_UPDATE_SPLIT one per stage -- records, levels, bound -- (tools/probe/mesh_update_rate.py)
+  const bool split = getenv("GLOME_DEBUG_MESH_UPDATE_SPLIT") != nullptr;
+  hipEvent_t e0 = nullptr, e1 = nullptr;
+  auto begin = [&]() -> hipError_t { return ctx->timing && launch_events(ctx, e0, e1) ? hipEventRecord(e0, st) : (e1 = nullptr, hipSuccess); };
+  auto end = [&]() -> hipError_t { return e1 ? hipEventRecord(e1, st) : hipSuccess; };
+  HIPCHK(ctx, begin());
+  {
+    meshupd::DTrisArgs A;
+    A.verts = verts_dev; A.norms = norms_dev; A.rows = (const int4*)m->d_rows;
+    A.mtris = (float4*)s->dev.mtris + 3 * (size_t)U.first_tri; A.trinorms = (float4*)s->dev.trinorms; A.ws = m->d_ws; A.n = U.n_tris;
+    hipLaunchKernelGGL(meshupd::k_mesh_tris, dim3(std::min<uint32_t>((U.n_tris + 63u) >> 6, max_items)), dim3(64), 0, st, A);
+  }
+  if (split) { HIPCHK(ctx, end()); HIPCHK(ctx, begin()); }
+  for (size_t l = 0; l + 1 < U.level_off.size(); l++) {
+    meshupd::DLevelArgs A;
+    A.nodes = m->d_levels + U.level_off[l]; A.n = U.level_off[l + 1] - U.level_off[l];
+    A.meshnodes = (float4*)s->dev.meshnodes; A.mtrimeta = (const uint4*)s->dev.mtrimeta; A.ws = m->d_ws; A.first_tri = U.first_tri;
+    hipLaunchKernelGGL(meshupd::k_mesh_refit_level, dim3(std::min<uint32_t>((A.n + 63u) >> 6, max_items)), dim3(64), 0, st, A);
+  }
+  if (split) { HIPCHK(ctx, end()); HIPCHK(ctx, begin()); }
+  if (nv > 0) {
+    const uint32_t blocks = std::min<uint32_t>(((uint32_t)nv + meshupd::kBoundBlock - 1) / meshupd::kBoundBlock, (uint32_t)meshupd::kBoundMaxBlocks);
+    float4* part = m->d_ws + 2 * (size_t)U.n_tris;
+    meshupd::DBoundArgs A;
+    A.verts = verts_dev; A.nv = (uint32_t)nv; A.part = part; A.error = &ctx->slot().d_counters->error;
+    hipLaunchKernelGGL(meshupd::k_mesh_bound, dim3(blocks), dim3(meshupd::kBoundBlock), 0, st, A);
+    hipLaunchKernelGGL(meshupd::k_mesh_bound_store, dim3(1), dim3(64), 0, st, (const float4*)part, blocks, (float4*)s->dev.meshhdr + 2 * (size_t)U.hdr);
+  }
+  HIPCHK(ctx, hipGetLastError());
+  HIPCHK(ctx, end());
+  ctx->slot().launched = true; ctx->slot().launched_on = ctx->stream;  // (a vertex that is not finite is reported at the next synchronize)
+  return 0;
+}
+int glome_scene_mesh_update(glome_scene* s, int32_t mesh_id, const double* verts, int nv, const double* norms, int nn, float* gpu_ms) {
+  if (!s) return GLOME_E_INVALID;
+  glome_ctx* ctx = s->ctx;
+  if (gpu_ms) *gpu_ms = 0;
+  glome_scene::MeshUpd* m = nullptr;
+  if (int rc = mesh_update_check(s, mesh_id, verts, nv, norms, nn, &m)) return rc;
+  for (size_t k = 0; k < 3 * (size_t)nv; k++) if (!std::isfinite(verts[k])) { ctx->err = "mesh update: a vertex coordinate is not finite"; return GLOME_E_INVALID; }
+  for (size_t k = 0; k < 3 * (size_t)nn; k++) if (!std::isfinite(norms[k])) { ctx->err = "mesh update: a normal coordinate is not finite"; return GLOME_E_INVALID; }
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  // every slot of the context may have a launch in flight that reads the pools about to be written
+  HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+  for (auto& sl : ctx->slots)
+    if (sl.launched_on && sl.launched_on != ctx->stream) (void)hipStreamSynchronize(sl.launched_on);
+  (void)hipGetLastError();  // (a stream its owner has destroyed since must not be this call's error: other_slots_busy)
+  Staging stg{ctx, {}};
+  double* dv = stg.in<double>(verts, 3 * (size_t)nv);
+  double* dn = nn ? stg.in<double>(norms, 3 * (size_t)nn) : nullptr;
+  if (!dv || (nn && !dn)) { ctx->err = "staging allocation failed"; return GLOME_E_HIP; }
+  if (gpu_ms) HIPCHK(ctx, hipEventRecord(ctx->ev0, ctx->stream));
+  if (int rc = glome_scene_mesh_update_dev(s, mesh_id, dv, nv, dn, nn)) return rc;
+  if (gpu_ms) HIPCHK(ctx, hipEventRecord(ctx->ev1, ctx->stream));
+  HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+  if (gpu_ms) HIPCHK(ctx, hipEventElapsedTime(gpu_ms, ctx->ev0, ctx->ev1));
+  return check_device_error(ctx);
 }
 
 // ---- the trace seam: Trace.trace over a caller's ray streams (trace_kernels.hpp) ----

@@ -6,12 +6,6 @@
 
 #include "rt_types.h"
 
-#if defined(__HIPCC__)
-#define GLOME_HD __host__ __device__ inline
-#else
-#define GLOME_HD inline
-#endif
-
 namespace glome {
 
 inline std::vector<std::pair<int, int>> chunk(int size, int blocksize) {  // Glome.hs:371-377: the last chunk is the remainder

@@ -18,7 +18,8 @@
  *     fp32.  Ray / hit / framebuffer arrays are caller-owned fp32 SoA buffers, valid for the call.
  *   - `_dev` variants take DEVICE pointers and run asynchronously on the context's HIP stream.
  *   - A glome_ctx owns one device + one stream and is single-threaded; distinct contexts may be
- *     driven from distinct threads.  A glome_scene is immutable after commit.
+ *     driven from distinct threads.  A glome_scene is immutable after commit, but for the vertices of its
+ *     meshes (glome_scene_mesh_update).
  *   - There is NO CPU fallback: every compute entry point fails with GLOME_E_NO_DEVICE when no
  *     gfx950 device is usable.  Builder and flatten-inspection calls are host-only.
  */
@@ -102,6 +103,16 @@ int32_t glome_sb_bih(glome_sb*, const int32_t* ids, int n);                     
 /* tris: 8 ints per triangle = a b c na nb nc tex tag (-1 = none), Mesh.hs:27-29; mats = the mesh's texture vector */
 int32_t glome_sb_mesh(glome_sb*, const double* verts, int nv, const double* norms, int nn,
                       const int32_t* tris, int nt, const int32_t* mats, int nm);                 /* Mesh.hs:50-55 */
+/* Same tree, new vertices.  mesh_id names a Mesh node, whoever made it (glome_sb_mesh, glome_sb_mesh_dev, glome_sb_load_show); nv and
+ * nn are the mesh's own counts; norms may be NULL when nn == 0; every coordinate is finite.  Replaces the mesh's vertex and normal
+ * arrays and makes again what `mesh` derives from them: every triangle's box (Mesh.hs:119-121), every branch's two boxes as the true
+ * unions of the triangle boxes below them (Mesh.hs:89-96), and the mesh's box over ALL vertices, unreferenced ones included
+ * (Mesh.hs:55).  What build_tree decided -- nodes, leaf lists, depth -- stays: no triangle changes leaf, so a tree built for one pose
+ * serves the next one less well the further the vertices move (glome_sb_mesh again re-splits).  glome_sb_bound, glome_sb_show and a later
+ * commit see the new mesh; a `bih` built over the mesh earlier keeps the planes it was built with.  The reference has no such call
+ * (`mesh` is a pure constructor); the result is the Mesh the reference would print for the same tree with the new arrays.  Anything
+ * else is GLOME_E_INVALID with a message, and the mesh is left untouched.  Host only; the specification of glome_scene_mesh_update. */
+int glome_sb_mesh_set_vertices(glome_sb*, int32_t mesh_id, const double* verts, int nv, const double* norms, int nn);
 int32_t glome_sb_tex(glome_sb*, int32_t id, int32_t material);                                   /* Tex.hs:33-34 */
 int32_t glome_sb_tag(glome_sb*, int32_t id);                                                     /* Tex.hs:38-39 (tags feed picking only) */
 int32_t glome_sb_noshadow(glome_sb*, int32_t id);                                                /* Tex.hs:43 */
@@ -191,6 +202,30 @@ typedef struct glome_scene_info {
   int64_t device_bytes;
 } glome_scene_info;
 int glome_scene_get_info(const glome_scene*, glome_scene_info* out);
+
+/* ---- animate a committed Mesh: new vertices, its BVH refitted on the GPU ----
+ * After an update the committed scene is, bit for bit, the scene glome_scene_commit would have made had glome_sb_mesh_set_vertices
+ * been called with the same arrays first: the mesh's triangle records and vertex normals, every box of its BVH, its own box.  The tree's
+ * topology stays (see glome_sb_mesh_set_vertices); nothing else of the scene is read or written, and one update moves every Instance
+ * of the mesh.  (One deviation from "bit for bit": a component whose fp32 value would be subnormal is stored as zero -- which is how
+ * every kernel reads it anyway.)  The builder is not touched: a host that also wants the new mesh there calls both.
+ *   mesh_id  the builder id of a Mesh that is part of this scene; nv, nn its own vertex / normal counts; norms NULL when nn == 0.
+ *   Refused with GLOME_E_INVALID before anything is launched, the scene untouched: an id that is not a mesh of this scene, a count
+ *   mismatch, a missing array, and a mesh with a `bih` above it on any path from the committed root (or from a Warp material's frame
+ *   / scene) -- that tree's planes and root box were built from the mesh's bound; the message names the bih.  Every other composite
+ *   keeps nothing of its children's bounds, and the bounding solid of a Bound / InnerBound is the caller's own object, as in the
+ *   reference: it must still contain the moved mesh.
+ * glome_scene_mesh_update takes host arrays, checks that every coordinate is finite, waits for every launch of the context (all
+ * slots), stages the arrays, updates and returns when the update is complete; *gpu_ms (may be NULL) = HIP-event time of its kernels.
+ * glome_scene_mesh_update_dev takes DEVICE pointers (fp64, 3 per vertex) and is asynchronous on the context's current stream and
+ * slot, like glome_rayint_batch_dev: launches enqueued after it on that stream see the new mesh, and the arrays must stay valid until
+ * it has run.  Launches still in flight on OTHER slots / streams read the same pools: ordering an update against them is the
+ * caller's responsibility (the pools are not double-buffered).  It takes part in glome_ctx_timing_begin / _end (one event pair per
+ * update).  A coordinate that is not finite is found on the device: the next glome_ctx_synchronize returns GLOME_E_INVALID, and the
+ * mesh is unspecified -- though never out of bounds -- until a valid update (as rgbad is after a failed trace).
+ * The first update of a mesh allocates its workspace (32 bytes per triangle), kept until glome_scene_release. */
+int glome_scene_mesh_update(glome_scene*, int32_t mesh_id, const double* verts, int nv, const double* norms, int nn, float* gpu_ms);
+int glome_scene_mesh_update_dev(glome_scene*, int32_t mesh_id, const double* verts_dev, int nv, const double* norms_dev, int nn);
 
 /* ---- per-ray seams (Solid.hs:146-166), host buffers ---- */
 /* closest hit: t < 0 marks a miss (RayMiss); prim = builder id of the primitive hit; tex8 = the hit's
