@@ -244,6 +244,19 @@ class Builder:
         self._chk(self.lib.glome_sb_mesh_set_vertices(self.h, int(node), v.ctypes.data_as(L.c_dp), v.shape[0], n.ctypes.data_as(L.c_dp) if n is not None and n.shape[0] else None,
                                                       0 if n is None else n.shape[0]), "glome_sb_mesh_set_vertices")
 
+    def bih_set_triangles(self, node, pts9):
+        """Same tree, new triangles (glome_sb_bih_set_triangles): nine values per item in update order (bih_items); the bih's planes and
+        box are made again, its topology stays."""
+        p = np.ascontiguousarray(np.asarray(pts9, dtype=np.float64).reshape(-1, 9))
+        self._chk(self.lib.glome_sb_bih_set_triangles(self.h, int(node), p.ctypes.data_as(L.c_dp) if p.shape[0] else None, p.shape[0]), "glome_sb_bih_set_triangles")
+
+    def bih_items(self, node):
+        """the item ids of a Bih in update order (glome_sb_bih_items)"""
+        n = self._chk(self.lib.glome_sb_bih_items(self.h, int(node), None, 0), "glome_sb_bih_items")
+        out = np.zeros(max(1, n), np.int32)
+        self._chk(self.lib.glome_sb_bih_items(self.h, int(node), out.ctypes.data_as(L.c_ip), n), "glome_sb_bih_items")
+        return [int(x) for x in out[:n]]
+
     def tex(self, node, material): return self._chk(self.lib.glome_sb_tex(self.h, int(node), int(material)), "glome_sb_tex")
     def tag(self, node, _tag=None): return self._chk(self.lib.glome_sb_tag(self.h, int(node)), "glome_sb_tag")
     def noshadow(self, node): return self._chk(self.lib.glome_sb_noshadow(self.h, int(node)), "glome_sb_noshadow")
@@ -466,6 +479,22 @@ class Scene:
         ms = C.c_float(0)
         self._chk(self.lib.glome_scene_mesh_update(self.h, int(mesh_id), v.ctypes.data_as(L.c_dp), v.shape[0], n.ctypes.data_as(L.c_dp) if n is not None and n.shape[0] else None,
                                                    0 if n is None else n.shape[0], C.byref(ms)), "glome_scene_mesh_update")
+        return ms.value
+
+    def bih_update(self, bih_id, pts9):
+        """New triangles for a committed triangle bih, its planes refitted on the GPU (glome_scene_bih_update): the scene a commit after
+        Builder.bih_set_triangles would have made.  NumPy arrays (or anything array-like) take the host form, which returns the device
+        milliseconds of the finished update; a CUDA torch.float64 tensor takes the device form, asynchronous on the context's stream
+        (returns None; the tensor must stay alive until it has run)."""
+        if hasattr(pts9, "data_ptr"):  # a torch tensor: the device form
+            t = pts9
+            if not t.is_cuda or str(t.dtype) != "torch.float64" or not t.is_contiguous() or t.numel() % 9:
+                raise GlomeError("bih_update: pts9 must be a contiguous CUDA torch.float64 tensor of 9 values per row")
+            self._chk(self.lib.glome_scene_bih_update_dev(self.h, int(bih_id), C.c_void_p(t.data_ptr()) if t.numel() else None, t.numel() // 9), "glome_scene_bih_update_dev")
+            return None
+        p = np.ascontiguousarray(np.asarray(pts9, dtype=np.float64).reshape(-1, 9))
+        ms = C.c_float(0)
+        self._chk(self.lib.glome_scene_bih_update(self.h, int(bih_id), p.ctypes.data_as(L.c_dp) if p.shape[0] else None, p.shape[0], C.byref(ms)), "glome_scene_bih_update")
         return ms.value
 
     def _rays(self, o, d, tmax):

@@ -125,6 +125,24 @@ int32_t glome_sb_difference(glome_sb* sb, int32_t a, int32_t b) { return guard(s
 int32_t glome_sb_difference_retexture(glome_sb* sb, int32_t a, int32_t b) { return guard(sb, [&] { return sb->graph.difference(a, b, true); }); }
 int32_t glome_sb_intersection(glome_sb* sb, const int32_t* ids, int n) { return guard(sb, [&] { return sb->graph.intersection(ids_of(ids, n)); }); }
 int32_t glome_sb_bih(glome_sb* sb, const int32_t* ids, int n) { return guard(sb, [&] { return sb->graph.bih(ids_of(ids, n)); }); }
+int glome_sb_bih_set_triangles(glome_sb* sb, int32_t bih_id, const double* pts9, int n) {
+  return guard(sb, [&] {
+    if (n < 0 || (n && !pts9)) throw std::invalid_argument("bih_set_triangles: null triangle array");
+    std::vector<D3> P;
+    for (size_t k = 0; k < 3 * (size_t)n; k++) P.push_back(d3(pts9 + 3 * k));
+    sb->graph.bih_set_triangles(bih_id, P);
+    return 0;
+  });
+}
+int32_t glome_sb_bih_items(glome_sb* sb, int32_t bih_id, int32_t* out, int32_t cap) {
+  return guard(sb, [&] {
+    const Node& n = sb->graph.at(bih_id);
+    if (n.kind != K_BIH) throw std::invalid_argument(std::string("bih_items: node ") + std::to_string(bih_id) + " is a " + kind_name(n.kind) + ", not a Bih");
+    const std::vector<int> items = n.bih->update_order();
+    for (size_t k = 0; k < items.size() && (int32_t)k < cap && out; k++) out[k] = items[k];
+    return (int)items.size();
+  });
+}
 int32_t glome_sb_mesh(glome_sb* sb, const double* verts, int nv, const double* norms, int nn, const int32_t* tris, int nt, const int32_t* mats, int nm) {
   return guard(sb, [&] {
     if (nv < 0 || nn < 0 || nt < 0 || nm < 0 || (nv && !verts) || (nn && !norms) || (nt && !tris) || (nm && !mats)) throw std::invalid_argument("bad mesh arrays");

@@ -28,6 +28,27 @@ struct MeshUpdateInfo {
   std::string why_not;            // built from the mesh's bound (Bih.hs:309-324) -- the reason, naming that bih
 };
 
+// What an update of a committed triangle bih's triangles needs (glome_scene_bih_update; bih_update_kernels.hpp), recorded per emitted bih
+// of class BC_TRI and kept beside the scene, outside DScene.  The tree's leaves are emitted in preorder with nothing in between, so
+// record j of the tree is `recs` record first_rec + j and `tris` record first_tri + j.  rows[2 j] is the record's item (its index in
+// BihTree::update_order), rows[2 j + 1] where its words go in `tripairs`: the pair record's first word (a float index), kPairHalfB when
+// it is the record's second triangle, kPairBoth when it is an odd last one that is paired with itself; kNoPair when the tree has no
+// packet form.  A branch's two child references are read from its node, whose .zw words an update never writes.
+struct BihUpdateInfo {
+  static constexpr uint32_t kPairHalfB = 1u << 29, kPairBoth = 1u << 30, kNoPair = 0xffffffffu;
+  int node = -1;                  // the bih's builder id
+  int n_items = 0;
+  uint32_t hdr = 0;               // bihhdr index
+  uint32_t first_slot = 0, n_slots = 0;  // its node slots (bihnodes index, count; unused slots included)
+  uint32_t first_tri = 0, first_rec = 0, n_tris = 0;
+  bool pk = false;                // the tree has the packet form: pknodes and tripairs follow
+  std::vector<uint32_t> rows;
+  std::vector<uint32_t> level_nodes;  // its branch slots (bihnodes indices), deepest tree level first ...
+  std::vector<uint32_t> level_off;    // ... level l is level_nodes[level_off[l] .. level_off[l + 1])
+  bool updatable = true;          // false: another Bih lies above it, or the scene holds another copy of one of its triangles -- the reason
+  std::string why_not;
+};
+
 struct FlatScene {
   std::vector<U4> recs;
   std::vector<F4> spheres, tris, trinorms, boxes, planes, discs, quadrics, xfms, bihhdr, bihnodes, meshhdr, meshnodes, mtris, mats, wlights;
@@ -44,6 +65,7 @@ struct FlatScene {
   std::string why_generic;  // why the flat tier was not chosen
   bool pk_all = true;       // every triangle BIH has the packet walk's node form (emit_bih)
   std::vector<MeshUpdateInfo> mesh_updates;  // one per emitted mesh (emit_mesh), in emission order
+  std::vector<BihUpdateInfo> bih_updates;    // one per emitted triangle bih (emit_bih), in emission order
 };
 
 inline float f32(double d) { return (float)d; }
@@ -295,27 +317,46 @@ class Flattener {
   // lies above, on any path from the root or from a Warp material's frame / scene.  Of the composites, only a Bih keeps something derived
   // from a child's bound -- its planes and its root box.  A list, an Instance, a Difference, an Intersection and the Tex / Tag / shadow
   // wrappers emit no box at all (emit, below), and the bounding solid of a Bound / InnerBound is the caller's own object.
+  // And which triangle bihs may have their triangles replaced (BihUpdateInfo::updatable): every one that no OTHER Bih lies above -- for
+  // the same reason -- and whose item triangles the scene reaches through this bih alone: a triangle node that is also in a group beside
+  // the bih, or in another bih, has a record of its own there, which an update of this bih could not move.
   void mark_updatable(int root) {
-    if (F.mesh_updates.empty()) return;
-    std::unordered_map<int, size_t> slot_of;
+    if (F.mesh_updates.empty() && F.bih_updates.empty()) return;
+    std::unordered_map<int, size_t> slot_of, bslot_of;
     for (size_t k = 0; k < F.mesh_updates.size(); k++) slot_of[F.mesh_updates[k].node] = k;
-    std::unordered_map<int, int> seen;  // node -> 1: visited with no Bih above, 2: with one, 3: both
-    struct Item { int id, bih; };
-    std::vector<Item> stack{{root, -1}};
-    for (const Mat& m : G.mats) if (m.kind == MAT_WARP) { stack.push_back({m.wframe, -1}); if (m.wscene >= 0) stack.push_back({m.wscene, -1}); }
+    for (size_t k = 0; k < F.bih_updates.size(); k++) bslot_of[F.bih_updates[k].node] = k;
+    // per Triangle node, the innermost Bih it was reached under: kUnseen, a bih's id, -1 for none, kMixed once two of those differ
+    constexpr int kUnseen = -3, kMixed = -2;
+    std::vector<int> tri_under(F.bih_updates.empty() ? 0 : G.nodes.size(), kUnseen);
+    struct Item { int id, bih, inner; };  // bih: the outermost Bih above, inner: the innermost (-1: none)
+    std::unordered_map<int, std::vector<std::pair<int, int>>> seen;  // composites and wrappers only (a primitive has nothing below it): the (bih, inner) pairs a node was visited with
+    std::vector<Item> stack{{root, -1, -1}};
+    for (const Mat& m : G.mats) if (m.kind == MAT_WARP) { stack.push_back({m.wframe, -1, -1}); if (m.wscene >= 0) stack.push_back({m.wscene, -1, -1}); }
     while (!stack.empty()) {
       Item it = stack.back();
       stack.pop_back();
-      int& sn = seen[it.id];
-      const int bit = it.bih < 0 ? 1 : 2;
-      if (sn & bit) continue;
-      sn |= bit;
       const Node& n = G.at(it.id);
+      if (is_prim(n.kind) || n.kind == K_VOID) {
+        if (n.kind == K_TRI && !tri_under.empty()) { int& u = tri_under[(size_t)it.id]; u = (u == kUnseen || u == it.inner) ? it.inner : kMixed; }
+        continue;
+      }
+      std::vector<std::pair<int, int>>& sn = seen[it.id];
+      if (std::find(sn.begin(), sn.end(), std::make_pair(it.bih, it.inner)) != sn.end()) continue;
+      sn.push_back({it.bih, it.inner});
       switch (n.kind) {
-        case K_LIST: case K_ISECT: for (int k : n.kids) stack.push_back({k, it.bih}); break;
-        case K_DIFF: case K_BOUND: case K_INNERBOUND: stack.push_back({n.a, it.bih}); stack.push_back({n.b, it.bih}); break;
-        case K_INSTANCE: case K_TEX: case K_TAG: case K_NOSHADOW: case K_ONLYSHADOW: stack.push_back({n.a, it.bih}); break;
-        case K_BIH: for (auto& bn : n.bih->nodes) for (int k : bn.items) stack.push_back({k, it.bih < 0 ? it.id : it.bih}); break;
+        case K_LIST: case K_ISECT: for (int k : n.kids) stack.push_back({k, it.bih, it.inner}); break;
+        case K_DIFF: case K_BOUND: case K_INNERBOUND: stack.push_back({n.a, it.bih, it.inner}); stack.push_back({n.b, it.bih, it.inner}); break;
+        case K_INSTANCE: case K_TEX: case K_TAG: case K_NOSHADOW: case K_ONLYSHADOW: stack.push_back({n.a, it.bih, it.inner}); break;
+        case K_BIH: {
+          auto sl = bslot_of.find(it.id);
+          if (it.bih >= 0 && sl != bslot_of.end() && F.bih_updates[sl->second].updatable) {
+            BihUpdateInfo& U = F.bih_updates[sl->second];
+            U.updatable = false;
+            U.why_not = "bih " + std::to_string(it.id) + " lies inside bih " + std::to_string(it.bih) + ", whose planes and root box were built from its bound";
+          }
+          for (auto& bn : n.bih->nodes) for (int k : bn.items) stack.push_back({k, it.bih < 0 ? it.id : it.bih, it.id});
+          break;
+        }
         case K_MESH: {
           auto sl = slot_of.find(it.id);
           if (it.bih >= 0 && sl != slot_of.end() && F.mesh_updates[sl->second].updatable) {
@@ -326,6 +367,20 @@ class Flattener {
           break;
         }
         default: break;
+      }
+    }
+    for (BihUpdateInfo& U : F.bih_updates) {
+      if (!U.updatable) continue;
+      for (const BihTree::Node& bn : G.at(U.node).bih->nodes) {
+        for (int item : bn.items) {
+          const int t = G.peel_wrappers(item);
+          const int u = tri_under[(size_t)t];
+          if (u == U.node || u == kUnseen) continue;  // (kUnseen: the bih itself is not reachable from the root -- nothing renders it)
+          U.updatable = false;
+          U.why_not = "triangle " + std::to_string(t) + " of bih " + std::to_string(U.node) + " is also part of the scene outside that bih, as a copy an update could not move";
+          break;
+        }
+        if (!U.updatable) break;
       }
     }
   }
@@ -465,7 +520,7 @@ class Flattener {
         r.y = slot(a); r.z = slot(b);
         break;
       }
-      case K_BIH: r = emit_bih(n); break;
+      case K_BIH: r = emit_bih(n, id); break;
       case K_MESH: r = emit_mesh(n, id); break;
     }
     memo[id] = r;
@@ -489,7 +544,7 @@ class Flattener {
 
   // BIH: nodes in preorder; leaf items become consecutive records, and (for homogeneous leaves) consecutive pool
   // entries, so a leaf is one contiguous run of 48-byte triangles / 16-byte spheres.
-  U4 emit_bih(const Node& n) {
+  U4 emit_bih(const Node& n, int id) {
     const BihTree& T = *n.bih;
     F.max_bih_depth = std::max(F.max_bih_depth, T.depth);
     // classify
@@ -550,6 +605,23 @@ class Flattener {
     uint32_t delta = 0;
     bool have_delta = false;
     bool in_place = cls != BC_TRI && cls != BC_SPHERE;  // (those two have their own packet walk)
+    BihUpdateInfo U;
+    std::vector<uint32_t> item_of;  // a triangle bih: item node id -> its index in the update order (BihTree::update_order, whichever way the tree was made)
+    if (cls == BC_TRI) {
+      U.node = id; U.hdr = hdr; U.first_slot = base; U.n_slots = nslots;
+      const std::vector<int> order = T.update_order();
+      U.n_items = (int)order.size();
+      item_of.assign(G.nodes.size(), 0xffffffffu);
+      std::vector<char> tri_seen(G.nodes.size(), 0);  // an item, or a triangle under two items, that the tree holds twice has two records: one row cannot name both
+      for (size_t k = 0; k < order.size(); k++) {
+        const int t = G.peel_wrappers(order[k]);
+        if ((item_of[(size_t)order[k]] != 0xffffffffu || tri_seen[(size_t)t]) && U.updatable) {
+          U.updatable = false;
+          U.why_not = "bih " + std::to_string(id) + " holds triangle " + std::to_string(t) + " more than once";
+        }
+        item_of[(size_t)order[k]] = (uint32_t)k; tri_seen[(size_t)t] = 1;
+      }
+    }
     for (size_t k = 0; k < T.nodes.size(); k++) {
       const BihTree::Node& bn = T.nodes[k];
       if (!bn.leaf) { ref[k] = base + slot[k]; continue; }
@@ -577,9 +649,18 @@ class Flattener {
         if (have_delta && dl != delta) throw scene_error("internal: BIH leaf pools are not contiguous");
         delta = dl; have_delta = true;
       }
+      bool paired = false;
       if (cls == BC_TRI && count && pk) {
         if (((uint64_t)F.tripairs.size() + (uint64_t)count * kPairWords) * 4 >= (1ull << 31)) pk = false;  // (a pair record's byte offset is a reference)
-        else pkleaf[k] = emit_pairs(first_prim, count, first_rec) | 3u;
+        else { pkleaf[k] = emit_pairs(first_prim, count, first_rec) | 3u; paired = true; }
+      }
+      if (cls == BC_TRI && count) {
+        if (U.rows.empty()) { U.first_tri = first_prim; U.first_rec = first_rec; }
+        for (uint32_t q = 0; q < count; q++) {
+          const uint32_t pair = (pkleaf[k] & ~3u) / 4u + (q / 2u) * kPairWords;  // (a float index: below 2^29)
+          U.rows.push_back(item_of[(size_t)bn.items[q]]);
+          U.rows.push_back(!paired ? BihUpdateInfo::kNoPair : (pair | (q & 1u ? BihUpdateInfo::kPairHalfB : 0u) | (q + 1 == count && !(q & 1u) ? BihUpdateInfo::kPairBoth : 0u)));
+        }
       }
       if (count == 0) ref[k] = BREF_LEAF_BIT;
       else if (count <= 6) ref[k] = BREF_LEAF_BIT | (count << 26) | first_rec;
@@ -616,6 +697,28 @@ class Flattener {
     in_place = in_place && !T.nodes.empty() && !T.nodes[0].leaf;
     F.bihhdr[3 * hdr + 2] = F4{as_float_bits(delta), as_float_bits(pkroot), as_float_bits(pk ? 1u : 0u), as_float_bits((uint32_t)T.depth | (in_place ? kBihItemsInPlace : 0u))};
     if (cls == BC_SPHERE || cls == BC_TRI || in_place) F.max_sphere_bih_depth = std::max(F.max_sphere_bih_depth, T.depth);
+    if (cls == BC_TRI) {
+      U.n_tris = (uint32_t)(U.rows.size() / 2); U.pk = pk;
+      if (!pk) for (size_t j = 0; j < U.n_tris; j++) U.rows[2 * j + 1] = BihUpdateInfo::kNoPair;  // (the packet form was given up part way)
+      if (!T.nodes.empty() && !T.nodes[0].leaf) {  // the branch slots by tree level, deepest first: a level's children were refitted before it
+        std::vector<int> depth(T.nodes.size(), 0), order{0};  // (a parent before its children, whatever the numbering)
+        for (size_t q = 0; q < order.size(); q++) {
+          const BihTree::Node& bn = T.nodes[(size_t)order[q]];
+          if (bn.leaf) continue;
+          for (int c : {bn.left, bn.right}) { depth[(size_t)c] = depth[(size_t)order[q]] + 1; order.push_back(c); }
+        }
+        int deepest = 0;
+        for (int k : order) if (!T.nodes[(size_t)k].leaf) deepest = std::max(deepest, depth[(size_t)k]);
+        std::vector<uint32_t> per_level((size_t)deepest + 2, 0);
+        for (int k : order) if (!T.nodes[(size_t)k].leaf) per_level[(size_t)(deepest - depth[(size_t)k]) + 1]++;
+        for (size_t l = 1; l < per_level.size(); l++) per_level[l] += per_level[l - 1];
+        U.level_off = per_level;
+        U.level_nodes.resize(per_level.back());
+        std::vector<uint32_t> fill(per_level.begin(), per_level.end() - 1);
+        for (int k : order) if (!T.nodes[(size_t)k].leaf) U.level_nodes[fill[(size_t)(deepest - depth[(size_t)k])]++] = base + slot[(size_t)k];
+      }
+      F.bih_updates.push_back(std::move(U));
+    }
     return U4{R_BIH, hdr, 0, (uint32_t)n.uid};
   }
 

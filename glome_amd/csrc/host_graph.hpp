@@ -147,6 +147,18 @@ struct BihTree {  // Bih bb root, Bih.hs:51-57, as preorder arrays
   Box3 bb;
   std::vector<Node> nodes;  // nodes[0] = root
   int depth = 0;
+  std::vector<int> order;   // the ids `bih` was given, in the caller's order; empty (a tree read from a `show` text): the leaf items in preorder
+  std::vector<int> update_order() const {  // item k of glome_sb_bih_set_triangles / glome_scene_bih_update
+    if (!order.empty() || nodes.empty()) return order;
+    std::vector<int> out, st{0};
+    while (!st.empty()) {  // preorder, left before right
+      const Node& n = nodes[(size_t)st.back()];
+      st.pop_back();
+      if (n.leaf) out.insert(out.end(), n.items.begin(), n.items.end());
+      else { st.push_back(n.right); st.push_back(n.left); }
+    }
+    return out;
+  }
 };
 struct MeshTri { int a, b, c, na, nb, nc, tex, tag; };  // Tri, Mesh.hs:29
 struct MeshData {                                       // Mesh, Mesh.hs:42
@@ -475,12 +487,69 @@ struct Graph {
       throw scene_error("bih: infinite bounding box");
     auto T = std::make_shared<BihTree>();
     T->bb = bb;
+    T->order = ids;
     std::vector<int> all(ids.size());
     for (size_t k = 0; k < all.size(); k++) all[k] = (int)k;
     BihBuild B{boxes, ids, *T};
     B.rec(all, bb, box_mid(bb), 0);
     Node n; n.kind = K_BIH; n.bih = T;
     return add(n);
+  }
+
+  // Same tree, new triangles (glome_sb_bih_set_triangles): item k of the tree (BihTree::update_order), a Triangle under any number of
+  // Tex / Tag / shadow wrappers, gets the vertices pts[3 k ..], and what `bih` derives from its items' bounds is made again by the
+  // builder's own definitions -- a branch's lsplit = (max of the left subtree's box hi[axis], from -kInfinity) + kDelta, rsplit = (min
+  // of the right subtree's lo[axis], from kInfinity) - kDelta (BihBuild::rec), the tree's box the join of the items' boxes -- while
+  // what the builder decided (nodes, axes, leaf lists, depth) stays.  The walk enters a child when the ray's interval reaches the
+  // half-space below lsplit / above rsplit, and the interval starts from the tree's box: so the tree stays correct whichever item sits
+  // in which leaf, and only its quality degrades as the items move.  The reference has no such call (`bih` is a pure constructor).
+  // Nothing is touched unless everything is valid.
+  int peel_wrappers(int id) const {
+    for (;;) {
+      const Node& n = at(id);
+      if (n.kind != K_TEX && n.kind != K_TAG && n.kind != K_NOSHADOW && n.kind != K_ONLYSHADOW) return id;
+      id = n.a;
+    }
+  }
+  void bih_set_triangles(int id, const std::vector<D3>& pts) {
+    if (at(id).kind != K_BIH) throw std::invalid_argument(std::string("bih_set_triangles: node ") + std::to_string(id) + " is a " + kind_name(at(id).kind) + ", not a Bih");
+    BihTree& T = *nodes[(size_t)id].bih;
+    const std::vector<int> order = T.update_order();
+    if (pts.size() != 3 * order.size()) throw std::invalid_argument("bih_set_triangles: the bih has " + std::to_string(order.size()) + " items, not " + std::to_string(pts.size() / 3));
+    for (const D3& v : pts) if (!(std::isfinite(v.x) && std::isfinite(v.y) && std::isfinite(v.z))) throw std::invalid_argument("bih_set_triangles: a coordinate is not finite");
+    std::vector<int> tri(order.size());
+    {
+      std::vector<int> sorted;
+      for (size_t k = 0; k < order.size(); k++) {
+        tri[k] = peel_wrappers(order[k]);
+        if (at(tri[k]).kind != K_TRI) throw std::invalid_argument("bih_set_triangles: item " + std::to_string(k) + " (node " + std::to_string(order[k]) + ") is a " + kind_name(at(tri[k]).kind) + ", not a plain Triangle");
+        sorted.push_back(tri[k]);
+      }
+      std::sort(sorted.begin(), sorted.end());
+      auto dup = std::adjacent_find(sorted.begin(), sorted.end());
+      if (dup != sorted.end()) throw std::invalid_argument("bih_set_triangles: triangle " + std::to_string(*dup) + " is an item of the bih more than once");
+    }
+    for (size_t k = 0; k < order.size(); k++) {
+      double* p = nodes[(size_t)tri[k]].p;
+      for (int q = 0; q < 3; q++) { p[3 * q] = pts[3 * k + q].x; p[3 * q + 1] = pts[3 * k + q].y; p[3 * q + 2] = pts[3 * k + q].z; }
+    }
+    T.bb = box_empty();
+    for (int it : order) T.bb = box_join(T.bb, bound(it));
+    if (T.nodes.empty()) return;
+    // bottom-up over an explicit stack (deep trees): a branch's planes are known once both subtrees' boxes are
+    std::vector<Box3> sub(T.nodes.size(), box_empty());
+    struct Item { int node; bool done; };
+    std::vector<Item> stack{{0, false}};
+    while (!stack.empty()) {
+      Item it = stack.back();
+      stack.pop_back();
+      BihTree::Node& n = T.nodes[(size_t)it.node];
+      if (n.leaf) { for (int i : n.items) sub[(size_t)it.node] = box_join(sub[(size_t)it.node], bound(i)); continue; }
+      if (!it.done) { stack.push_back({it.node, true}); stack.push_back({n.right, false}); stack.push_back({n.left, false}); continue; }
+      n.lsplit = comp(sub[(size_t)n.left].hi, n.axis) + kDelta;
+      n.rsplit = comp(sub[(size_t)n.right].lo, n.axis) - kDelta;
+      sub[(size_t)it.node] = box_join(sub[(size_t)n.left], sub[(size_t)n.right]);
+    }
   }
 
   // ---------------- Mesh builder, Mesh.hs:50-134 (Q12) ----------------

@@ -55,6 +55,20 @@ __device__ __forceinline__ void box_add(const double p[3], float lo[3], float hi
   for (int a = 0; a < 3; a++) { lo[a] = fminf(lo[a], round_down(__dsub_rn(p[a], kDelta))); hi[a] = fmaxf(hi[a], round_up(__dadd_rn(p[a], kDelta))); }
 }
 
+// A triangle's record (p1, n.x) (e1, n.y) (e2, n.z) from its vertices: emit_mesh's and emit_tri's expression (flatten.hpp), in the host's
+// order, rounded once.  Shared with the triangle bih's update (bih_update_kernels.hpp).
+__device__ __forceinline__ void tri_record(const double a[3], const double b[3], const double c[3], float4 rec[3]) {
+  double e1[3], e2[3], n[3];
+  for (int k = 0; k < 3; k++) { e1[k] = __dsub_rn(b[k], a[k]); e2[k] = __dsub_rn(c[k], a[k]); }
+  n[0] = __dsub_rn(__dmul_rn(e1[1], e2[2]), __dmul_rn(e1[2], e2[1]));  // cross, host_graph.hpp
+  n[1] = __dsub_rn(__dmul_rn(e1[2], e2[0]), __dmul_rn(e1[0], e2[2]));
+  n[2] = __dsub_rn(__dmul_rn(e1[0], e2[1]), __dmul_rn(e1[1], e2[0]));
+  const double inv = __ddiv_rn(1.0, __dsqrt_rn(__dadd_rn(__dadd_rn(__dmul_rn(n[0], n[0]), __dmul_rn(n[1], n[1])), __dmul_rn(n[2], n[2]))));  // normalize
+  rec[0] = make_float4((float)a[0], (float)a[1], (float)a[2], (float)__dmul_rn(n[0], inv));
+  rec[1] = make_float4((float)e1[0], (float)e1[1], (float)e1[2], (float)__dmul_rn(n[1], inv));
+  rec[2] = make_float4((float)e2[0], (float)e2[1], (float)e2[2], (float)__dmul_rn(n[2], inv));
+}
+
 // Grid-stride over 64-record items, like k_camera_rays.
 __global__ void __launch_bounds__(64) k_mesh_tris(DTrisArgs A) {
   const uint32_t items = (A.n + 63u) >> 6;
@@ -63,17 +77,12 @@ __global__ void __launch_bounds__(64) k_mesh_tris(DTrisArgs A) {
     if (j >= A.n) continue;
     const int4 r0 = A.rows[2 * (size_t)j], r1 = A.rows[2 * (size_t)j + 1];
     if (r0.x < 0) continue;  // the placeholder of an empty leaf: no triangle, and no leaf folds its box
-    double a[3], b[3], c[3], e1[3], e2[3], n[3];
+    double a[3], b[3], c[3];
     d3_load(A.verts, r0.x, a); d3_load(A.verts, r0.y, b); d3_load(A.verts, r0.z, c);
-    for (int k = 0; k < 3; k++) { e1[k] = __dsub_rn(b[k], a[k]); e2[k] = __dsub_rn(c[k], a[k]); }
-    n[0] = __dsub_rn(__dmul_rn(e1[1], e2[2]), __dmul_rn(e1[2], e2[1]));  // cross, host_graph.hpp
-    n[1] = __dsub_rn(__dmul_rn(e1[2], e2[0]), __dmul_rn(e1[0], e2[2]));
-    n[2] = __dsub_rn(__dmul_rn(e1[0], e2[1]), __dmul_rn(e1[1], e2[0]));
-    const double inv = __ddiv_rn(1.0, __dsqrt_rn(__dadd_rn(__dadd_rn(__dmul_rn(n[0], n[0]), __dmul_rn(n[1], n[1])), __dmul_rn(n[2], n[2]))));  // normalize
+    float4 rec[3];
+    tri_record(a, b, c, rec);
     float4* o = A.mtris + 3 * (size_t)j;
-    o[0] = make_float4((float)a[0], (float)a[1], (float)a[2], (float)__dmul_rn(n[0], inv));
-    o[1] = make_float4((float)e1[0], (float)e1[1], (float)e1[2], (float)__dmul_rn(n[1], inv));
-    o[2] = make_float4((float)e2[0], (float)e2[1], (float)e2[2], (float)__dmul_rn(n[2], inv));
+    o[0] = rec[0]; o[1] = rec[1]; o[2] = rec[2];
     if (r1.z >= 0) {
       const int ni[3] = {r0.w, r1.x, r1.y};
       for (int k = 0; k < 3; k++) { double v[3]; d3_load(A.norms, ni[k], v); A.trinorms[(size_t)r1.z + k] = make_float4((float)v[0], (float)v[1], (float)v[2], 0.0f); }

@@ -2,7 +2,8 @@
 // the whole-frame render, the per-ray batch seams, tile transport and the multi-GPU driver.  Compiled once.  It launches the render,
 // sampler and batch kernels through kernel_launch.hpp (the instances live in kernel_parts.hip, chosen by instances.hpp) and holds
 // only the light kernels: the kernel-argument self-test, the coordinate tables, tile transport, the tree builders
-// (bih_build_device.hpp), the flagship launch's cull pass (cull_kernels.hpp) and the update of a committed Mesh (mesh_update_kernels.hpp).
+// (bih_build_device.hpp), the flagship launch's cull pass (cull_kernels.hpp) and the updates of a committed Mesh (mesh_update_kernels.hpp)
+// and of a committed triangle bih (bih_update_kernels.hpp).
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -24,6 +25,7 @@
 #include "bih_build_device.hpp"
 #include "cull_kernels.hpp"
 #include "mesh_update_kernels.hpp"
+#include "bih_update_kernels.hpp"
 
 using namespace glome;
 
@@ -157,6 +159,15 @@ struct glome_scene {
     float4* d_ws = nullptr;            // two words per record, then the bound's partial boxes: allocated at the first update
   };
   std::map<int, MeshUpd> meshes;
+  // the same for glome_scene_bih_update, of every triangle bih of the scene (flatten.hpp BihUpdateInfo)
+  struct BihUpd {
+    BihUpdateInfo info;                // (rows and level_nodes emptied once uploaded)
+    const uint32_t* d_rows = nullptr;
+    const uint32_t* d_levels = nullptr;
+    const uint32_t* d_level_off = nullptr;
+    float4* d_ws = nullptr;            // two words per record, two per node slot, then the bound's partial boxes: allocated at the first update
+  };
+  std::map<int, BihUpd> bihs;
 };
 
 static std::string g_global_error;
@@ -455,6 +466,7 @@ int32_t glome_sb_bih_dev(glome_ctx* ctx, glome_sb* sb, const int32_t* ids, int32
     auto T = std::make_shared<BihTree>();
     std::string err;
     if (!bihdev::build(boxes, v, bb, *T, ctx->stream, err, gpu_ms)) { ctx->err = sb->err = err; return GLOME_E_LIMIT; }
+    T->order = v;
     Node nd; nd.kind = K_BIH; nd.bih = T;
     return G.add(nd);
   } catch (const scene_error& e) { ctx->err = sb->err = e.what(); return GLOME_E_SCENE; }
@@ -523,6 +535,12 @@ glome_scene* glome_scene_commit(glome_ctx* ctx, glome_sb* sb, int32_t root) {
   for (MeshUpdateInfo& U : F.mesh_updates) {
     glome_scene::MeshUpd& m = s->meshes[U.node];
     if (upload(s, U.rows, &m.d_rows) || (!U.level_nodes.empty() && upload(s, U.level_nodes, &m.d_levels))) { glome_scene_release(s); return nullptr; }
+    U.rows = {}; U.level_nodes = {};
+    m.info = std::move(U);
+  }
+  for (BihUpdateInfo& U : F.bih_updates) {
+    glome_scene::BihUpd& m = s->bihs[U.node];
+    if ((!U.rows.empty() && upload(s, U.rows, &m.d_rows)) || (!U.level_nodes.empty() && (upload(s, U.level_nodes, &m.d_levels) || upload(s, U.level_off, &m.d_level_off)))) { glome_scene_release(s); return nullptr; }
     U.rows = {}; U.level_nodes = {};
     m.info = std::move(U);
   }
@@ -620,8 +638,9 @@ static int device_error_status(glome_ctx* ctx, unsigned int e) {
     ctx->err = "a ray direction is not unit length: set glome_trace_params.faithful to trace such rays (the reference's own traversal)";
     return GLOME_E_INVALID;
   }
-  if (e & kErrBadVertex) {  // (only a mesh update sets it)
-    ctx->err = "a mesh update met a vertex coordinate that is not finite: the scene's mesh is unspecified until a valid update";
+  if (e & kErrBadVertex) {  // (only a mesh update and a bih update set it; the word does not say which)
+    ctx->err = "a mesh update met a vertex coordinate that is not finite: the scene's mesh is unspecified until a valid update"
+               " (or a bih update, glome_scene_bih_update: then the bih is)";
     return GLOME_E_INVALID;
   }
   ctx->err = "device-side limit hit (traversal stack or CSG advance cap)";
@@ -1068,6 +1087,106 @@ int glome_scene_mesh_update(glome_scene* s, int32_t mesh_id, const double* verts
   if (!dv || (nn && !dn)) { ctx->err = "staging allocation failed"; return GLOME_E_HIP; }
   if (gpu_ms) HIPCHK(ctx, hipEventRecord(ctx->ev0, ctx->stream));
   if (int rc = glome_scene_mesh_update_dev(s, mesh_id, dv, nv, dn, nn)) return rc;
+  if (gpu_ms) HIPCHK(ctx, hipEventRecord(ctx->ev1, ctx->stream));
+  HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+  if (gpu_ms) HIPCHK(ctx, hipEventElapsedTime(gpu_ms, ctx->ev0, ctx->ev1));
+  return check_device_error(ctx);
+}
+
+// ---- new triangles for a committed triangle bih (bih_update_kernels.hpp) ----
+// what both forms refuse before anything is launched; *out = the bih's tables
+static int bih_update_check(glome_scene* s, int32_t bih_id, const void* pts9, int n, glome_scene::BihUpd** out) {
+  glome_ctx* ctx = s->ctx;
+  auto it = s->bihs.find(bih_id);
+  if (it == s->bihs.end()) { ctx->err = "bih update: node " + std::to_string(bih_id) + " is not a bih of plain triangles of this scene"; return GLOME_E_INVALID; }
+  const BihUpdateInfo& U = it->second.info;
+  if (n != U.n_items) { ctx->err = "bih update: the bih has " + std::to_string(U.n_items) + " items, not " + std::to_string(n); return GLOME_E_INVALID; }
+  if (n && !pts9) { ctx->err = "bih update: null triangle array"; return GLOME_E_INVALID; }
+  if (!U.updatable) { ctx->err = "bih update refused: " + U.why_not; return GLOME_E_INVALID; }
+  *out = &it->second;
+  return 0;
+}
+int glome_scene_bih_update_dev(glome_scene* s, int32_t bih_id, const double* pts9_dev, int n) {
+  if (!s) return GLOME_E_INVALID;
+  glome_ctx* ctx = s->ctx;
+  glome_scene::BihUpd* m = nullptr;
+  if (int rc = bih_update_check(s, bih_id, pts9_dev, n, &m)) return rc;
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  const BihUpdateInfo& U = m->info;
+  if (!m->d_ws) {  // 32 bytes per record and per node slot, and the bound's partial boxes: kept until glome_scene_release
+    void* d = nullptr;
+    HIPCHK(ctx, hipMalloc(&d, ((size_t)U.n_tris + U.n_slots + meshupd::kBoundMaxBlocks) * 2 * sizeof(float4)));
+    s->allocs.push_back(d);
+    m->d_ws = (float4*)d;
+  }
+  hipStream_t st = ctx->stream;
+  const uint32_t max_items = (uint32_t)ctx->prop.multiProcessorCount * 32u * 4u;
+  // one event pair per update while timing is on; with GLOME_DEBUG_BIH_UPDATE_SPLIT one per stage -- records, levels, bound.  The levels run
+  // a launch each: the merged launch of the narrow levels (k_bih_levels_merged) stays behind GLOME_DEBUG_BIH_UPDATE_MERGED until
+  // tools/probe/bih_update_rate.py has shown on the hardware that it wins beyond the run-to-run spread
+  const bool split = getenv("GLOME_DEBUG_BIH_UPDATE_SPLIT") != nullptr, per_level = getenv("GLOME_DEBUG_BIH_UPDATE_MERGED") == nullptr;
+  hipEvent_t e0 = nullptr, e1 = nullptr;
+  auto begin = [&]() -> hipError_t { return ctx->timing && launch_events(ctx, e0, e1) ? hipEventRecord(e0, st) : (e1 = nullptr, hipSuccess); };
+  auto end = [&]() -> hipError_t { return e1 ? hipEventRecord(e1, st) : hipSuccess; };
+  HIPCHK(ctx, begin());
+  if (U.n_tris) {
+    bihupd::DTrisArgs A;
+    A.pts9 = pts9_dev; A.rows = (const uint2*)m->d_rows; A.tris = (float4*)s->dev.tris + 3 * (size_t)U.first_tri; A.tripairs = (float*)s->dev.tripairs;
+    A.ws = m->d_ws; A.n = U.n_tris;
+    hipLaunchKernelGGL(bihupd::k_bih_tris, dim3(std::min<uint32_t>((U.n_tris + 63u) >> 6, max_items)), dim3(64), 0, st, A);
+  }
+  if (split) { HIPCHK(ctx, end()); HIPCHK(ctx, begin()); }
+  {
+    bihupd::DLevelArgs A;
+    A.nodes = m->d_levels; A.bihnodes = (float4*)s->dev.bihnodes; A.pknodes = U.pk ? (float4*)s->dev.pknodes : nullptr;
+    A.ws_tri = m->d_ws; A.ws_node = m->d_ws + 2 * (size_t)U.n_tris; A.first_rec = U.first_rec; A.first_slot = U.first_slot;
+    const size_t levels = U.level_off.empty() ? 0 : U.level_off.size() - 1;
+    auto width = [&](size_t l) { return U.level_off[l + 1] - U.level_off[l]; };
+    for (size_t l = 0; l < levels;) {
+      size_t e = l;
+      while (!per_level && e < levels && width(e) <= (uint32_t)bihupd::kMergeBlock) e++;
+      if (e > l + 1) {  // a run of narrow levels: one block
+        hipLaunchKernelGGL(bihupd::k_bih_levels_merged, dim3(1), dim3(bihupd::kMergeBlock), 0, st, A, m->d_level_off, (uint32_t)l, (uint32_t)e);
+        l = e;
+      } else {
+        hipLaunchKernelGGL(bihupd::k_bih_level, dim3(std::min<uint32_t>((width(l) + 63u) >> 6, max_items)), dim3(64), 0, st, A, U.level_off[l], width(l));
+        l++;
+      }
+    }
+  }
+  if (split) { HIPCHK(ctx, end()); HIPCHK(ctx, begin()); }
+  {
+    const uint32_t nv = 3u * (uint32_t)n;
+    const uint32_t blocks = std::max<uint32_t>(1u, std::min<uint32_t>((nv + meshupd::kBoundBlock - 1) / meshupd::kBoundBlock, (uint32_t)meshupd::kBoundMaxBlocks));
+    float4* part = m->d_ws + 2 * ((size_t)U.n_tris + U.n_slots);
+    meshupd::DBoundArgs A;
+    A.verts = pts9_dev; A.nv = nv; A.part = part; A.error = &ctx->slot().d_counters->error;
+    hipLaunchKernelGGL(meshupd::k_mesh_bound, dim3(blocks), dim3(meshupd::kBoundBlock), 0, st, A);
+    hipLaunchKernelGGL(bihupd::k_bih_bound_store, dim3(1), dim3(64), 0, st, (const float4*)part, blocks, (float4*)s->dev.bihhdr + 3 * (size_t)U.hdr);
+  }
+  HIPCHK(ctx, hipGetLastError());
+  HIPCHK(ctx, end());
+  ctx->slot().launched = true; ctx->slot().launched_on = ctx->stream;  // (a coordinate that is not finite is reported at the next synchronize)
+  return 0;
+}
+int glome_scene_bih_update(glome_scene* s, int32_t bih_id, const double* pts9, int n, float* gpu_ms) {
+  if (!s) return GLOME_E_INVALID;
+  glome_ctx* ctx = s->ctx;
+  if (gpu_ms) *gpu_ms = 0;
+  glome_scene::BihUpd* m = nullptr;
+  if (int rc = bih_update_check(s, bih_id, pts9, n, &m)) return rc;
+  for (size_t k = 0; k < 9 * (size_t)n; k++) if (!std::isfinite(pts9[k])) { ctx->err = "bih update: a vertex coordinate is not finite"; return GLOME_E_INVALID; }
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  // every slot of the context may have a launch in flight that reads the pools about to be written
+  HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+  for (auto& sl : ctx->slots)
+    if (sl.launched_on && sl.launched_on != ctx->stream) (void)hipStreamSynchronize(sl.launched_on);
+  (void)hipGetLastError();  // (a stream its owner has destroyed since must not be this call's error: other_slots_busy)
+  Staging stg{ctx, {}};
+  double* dp = stg.in<double>(pts9, 9 * (size_t)n);
+  if (!dp) { ctx->err = "staging allocation failed"; return GLOME_E_HIP; }
+  if (gpu_ms) HIPCHK(ctx, hipEventRecord(ctx->ev0, ctx->stream));
+  if (int rc = glome_scene_bih_update_dev(s, bih_id, dp, n)) return rc;
   if (gpu_ms) HIPCHK(ctx, hipEventRecord(ctx->ev1, ctx->stream));
   HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
   if (gpu_ms) HIPCHK(ctx, hipEventElapsedTime(gpu_ms, ctx->ev0, ctx->ev1));

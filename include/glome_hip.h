@@ -19,7 +19,7 @@
  *   - `_dev` variants take DEVICE pointers and run asynchronously on the context's HIP stream.
  *   - A glome_ctx owns one device + one stream and is single-threaded; distinct contexts may be
  *     driven from distinct threads.  A glome_scene is immutable after commit, but for the vertices of its
- *     meshes (glome_scene_mesh_update).
+ *     meshes (glome_scene_mesh_update) and the triangles of its triangle bihs (glome_scene_bih_update).
  *   - There is NO CPU fallback: every compute entry point fails with GLOME_E_NO_DEVICE when no
  *     gfx950 device is usable.  Builder and flatten-inspection calls are host-only.
  */
@@ -113,6 +113,23 @@ int32_t glome_sb_mesh(glome_sb*, const double* verts, int nv, const double* norm
  * (`mesh` is a pure constructor); the result is the Mesh the reference would print for the same tree with the new arrays.  Anything
  * else is GLOME_E_INVALID with a message, and the mesh is left untouched.  Host only; the specification of glome_scene_mesh_update. */
 int glome_sb_mesh_set_vertices(glome_sb*, int32_t mesh_id, const double* verts, int nv, const double* norms, int nn);
+/* Same tree, new triangles.  bih_id names a Bih node, whoever made it (glome_sb_bih, glome_sb_bih_dev, glome_sb_load_show, glome_sb_load_nff);
+ * n is its item count and pts9 holds nine doubles per item, p1 p2 p3, every one finite.  Item k is the k-th id of the list the bih was
+ * built from; for a tree read by glome_sb_load_show, the k-th leaf item in preorder (glome_sb_bih_items returns the ids in this order).
+ * Every item must be a Triangle under any number of Tex / Tag / NoShadow / OnlyShadow wrappers, and no Triangle node may be an item
+ * twice.  Sets the item triangles' vertices (a Triangle node that is also used elsewhere in the builder moves there too) and makes again
+ * what `bih` derives from its items' bounds: every branch's lsplit = (max over the left subtree of the items' box hi[axis]) + delta and
+ * rsplit = (min over the right subtree of lo[axis]) - delta (Bih.hs:243-250, 285), and the tree's box.  What the builder decided -- nodes,
+ * axes, leaf lists, depth -- stays.  The tree stays correct: the traversal enters a child when the ray's interval, which starts from the
+ * tree's box, reaches the half-space below lsplit / above rsplit, whichever item sits in which leaf; only its quality degrades the
+ * further the triangles move (glome_sb_bih again re-splits).  glome_sb_bound, glome_sb_show, glome_sb_bih_dump and a later commit see the
+ * new tree; a `bih` built earlier over this one keeps the planes it was built with.  The reference has no such call (`bih` is a pure
+ * constructor); the result is the Bih the reference would print for the same tree with the new triangles.  Anything else is
+ * GLOME_E_INVALID with a message (an item that is not a plain triangle is named), and nothing is touched.  Host only; the specification
+ * of glome_scene_bih_update. */
+int glome_sb_bih_set_triangles(glome_sb*, int32_t bih_id, const double* pts9, int n);
+/* the item ids of a Bih in update order: returns their number and fills out[0 .. min(number, cap)) (out may be NULL: count first) */
+int32_t glome_sb_bih_items(glome_sb*, int32_t bih_id, int32_t* out, int32_t cap);
 int32_t glome_sb_tex(glome_sb*, int32_t id, int32_t material);                                   /* Tex.hs:33-34 */
 int32_t glome_sb_tag(glome_sb*, int32_t id);                                                     /* Tex.hs:38-39 (tags feed picking only) */
 int32_t glome_sb_noshadow(glome_sb*, int32_t id);                                                /* Tex.hs:43 */
@@ -227,8 +244,37 @@ int glome_scene_get_info(const glome_scene*, glome_scene_info* out);
 int glome_scene_mesh_update(glome_scene*, int32_t mesh_id, const double* verts, int nv, const double* norms, int nn, float* gpu_ms);
 int glome_scene_mesh_update_dev(glome_scene*, int32_t mesh_id, const double* verts_dev, int nv, const double* norms_dev, int nn);
 
+/* ---- animate a committed triangle bih: new triangles, its planes refitted on the GPU ----
+ * A triangle bih is a Bih whose items are all plain Triangles (under Tex / Tag wrappers, at most two Tex levels): the flagship's
+ * `tex (bih (map triangle ...))`.  After an update the committed scene is, bit for bit, the scene glome_scene_commit would have made had
+ * glome_sb_bih_set_triangles been called with the same array first: the triangle records, the pair records of the packet walk, every
+ * branch's two planes in both node pools, the tree's box.  The tree's topology stays (see glome_sb_bih_set_triangles); nothing else of
+ * the scene is read or written, and one update moves every Instance of the bih.  (One deviation from "bit for bit", as for the mesh: a
+ * component whose fp32 value would be subnormal is stored as zero -- which is how every kernel reads it anyway.)  The builder is not
+ * touched: a host that also wants the new tree there calls both.
+ *   bih_id  the builder id of a triangle bih that is part of this scene; n its item count; pts9 nine doubles per item in update order.
+ *   Refused with GLOME_E_INVALID before anything is launched, the scene untouched: an id that is not a triangle bih of this scene, a
+ *   count mismatch, a missing array, a bih with another `bih` above it on any path from the committed root (or from a Warp material's
+ *   frame / scene) -- that tree's planes were built from this one's bound; the message names it --, a bih one of whose triangles the
+ *   scene also reaches outside it (in a group beside it, say: that copy could not be moved; the message names the triangle), and a bih
+ *   that holds a triangle twice.  The bounding solid of a Bound / InnerBound above is the caller's own object, as in the reference: it
+ *   must still contain the moved triangles.
+ * glome_scene_bih_update takes a host array, checks that every coordinate is finite, waits for every launch of the context (all slots),
+ * stages the array, updates and returns when the update is complete; *gpu_ms (may be NULL) = HIP-event time of its kernels.
+ * glome_scene_bih_update_dev takes a DEVICE pointer (fp64) and is asynchronous on the context's current stream and slot, like
+ * glome_scene_mesh_update_dev: launches enqueued after it on that stream see the new triangles, and the array must stay valid until it
+ * has run.  Launches still in flight on OTHER slots / streams read the same pools: ordering an update against them is the caller's
+ * responsibility (the pools are not double-buffered).  It takes part in glome_ctx_timing_begin / _end (one event pair per update).  A
+ * coordinate that is not finite is found on the device: the next glome_ctx_synchronize returns GLOME_E_INVALID (the error word is the mesh
+ * update's: the message names both calls, a context cannot tell which one raised it), and the tree is unspecified -- though never out
+ * of bounds -- until a valid update.
+ * The first update of a bih allocates its workspace (32 bytes per triangle and per node), kept until glome_scene_release. */
+int glome_scene_bih_update(glome_scene*, int32_t bih_id, const double* pts9, int n, float* gpu_ms);
+int glome_scene_bih_update_dev(glome_scene*, int32_t bih_id, const double* pts9_dev, int n);
+
 /* ---- per-ray seams (Solid.hs:146-166), host buffers ---- */
-/* closest hit: t < 0 marks a miss (RayMiss); prim = builder id of the primitive hit; tex8 = the hit's
+/* closest hit: t < 0 marks a miss (RayMiss), and then prim is -1, tex8 all -1 and the normal UNSPECIFIED (whatever the traversal
+ * left: it may differ between two commits of one builder); prim = builder id of the primitive hit; tex8 = the hit's
  * texture stack (the ids of glome_sb_material), innermost first, -1 padded: GLOME_TEX_WORDS (8) int32 PER RAY -- the buffer is
  * n * GLOME_TEX_WORDS words (until round 3 it was 4 per ray: a caller built against that header must be rebuilt; glome_tex_words()
  * returns what the loaded library writes, for a binding that wants to check at run time).  Any output pointer may be NULL. */
