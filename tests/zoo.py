@@ -297,6 +297,74 @@ def mirror_terrain(N=24):
 ALL["mirror_terrain"] = mirror_terrain
 
 
+# Scenes for tests/instance_ledger.py: each selects kernel instances no scene above does (mirror_terrain and every random_flat scene
+# hold a Refract material, so from maxdepth 2 they run on the faithful instance).  Not in ALL; seen from above, so that most pixels hit.
+def _bowl(pts, k):
+    """points (rows of x, y, z, one or three to a row) lifted by k * (x^2 + z^2): the gentle heightfield bent into a bowl, so that seen from
+    above a mirror on one slope shows the slope across (flat, its mirrors show the sky alone and a secondary ray never hits)"""
+    p = np.array(pts, np.float64).reshape(-1, 3)
+    p[:, 1] += k * (p[:, 0] ** 2 + p[:, 2] ** 2)
+    return p.reshape(np.shape(pts))
+
+
+def mirror_tri(N=24):
+    """Two triangle BIHs and nothing else, one of mirrors and one matte, no Refract: the triangle-class instances with secondary rays
+    (the full TRI render / sampler / trace instances at maxdepth 3) and, at maxdepth 1, the lean TRI instances without the two-row form
+    (a Reflect material in the scene rules the two-row flagship out).  The two trees are halves of one heightfield, in four stripes:
+    with a material edge per triangle the frame holds so many mirrored edges that the oracle's own fp32 frame comes near the caps."""
+    sd = SceneDesc()
+    m = scenes.materials(sd)
+    tri = _bowl(scenes.heightfield_triangles(N) * np.array([0.6, 1.0, 0.6] * 3), 0.08)
+    stripe = (np.arange(len(tri)) // (2 * N * (N // 4))) % 2 == 0  # four stripes along x, every other one of mirrors: halves of the triangles
+    mirrors = sd.tex(sd.bih(sd.triangles_bulk(tri[stripe])), m["mirror"])
+    slopes = sd.tex(sd.bih(sd.triangles_bulk(tri[~stripe])), scenes.matte(sd, (0.8, 0.5, 0.4)))
+    _finish(sd, sd.group([mirrors, slopes]))
+    sd.set_camera((8.0, 7.0, 6.0), (0.0, 0.0, 0.0), (0, 1, 0), 45)
+    return sd
+
+
+def mirror_mesh():
+    """mesh_scene's Mesh alone (no sphere beside it), bent into a bowl, one of its two per-triangle materials a mirror (in stripes, as
+    in mirror_tri): the Mesh-class instances with secondary rays.  The vertex normals follow the bowl: a mirror whose interpolated
+    normal leans away from its triangle sends reflected rays back through the surface, and those pixels fall either way in fp32."""
+    sd = SceneDesc()
+    m = scenes.materials(sd)
+    N = 12
+    V = _bowl(scenes.heightfield_vertices(N).reshape(-1, 3) * np.array([0.5, 1.0, 0.5]), 0.1)
+    idx = np.arange((N + 1) * (N + 1)).reshape(N + 1, N + 1)
+    a, b, c, d = idx[:-1, :-1], idx[:-1, 1:], idx[1:, :-1], idx[1:, 1:]
+    tri = np.stack([np.stack([a, b, c], -1), np.stack([c, b, d], -1)], axis=2).reshape(-1, 3)
+    nrm = np.stack([0.3 * np.sin(V[:, 0]) - 0.2 * V[:, 0], np.ones(len(V)), 0.3 * np.cos(V[:, 2]) - 0.2 * V[:, 2]], -1)  # (the bowl's own slope and a small tilt)
+    nrm /= np.linalg.norm(nrm, axis=1, keepdims=True)
+    tris = np.full((len(tri), 8), -1, np.int32)
+    tris[:, :3] = tri
+    smooth = np.arange(len(tri)) % 3 == 0
+    tris[smooth, 3:6] = tri[smooth]
+    tris[:, 6] = (np.arange(len(tri)) // (2 * N * (N // 4))) % 2  # four stripes along x: matte, mirror, matte, mirror
+    tris[::7, 6] = -1  # some triangles carry no texture of their own
+    me = sd.tex(sd.mesh(V, nrm, tris, [scenes.matte(sd, (0.8, 0.5, 0.4)), m["mirror"]]), scenes.matte(sd, (0.3, 0.3, 0.3)))
+    _finish(sd, me)
+    sd.set_camera((0.5, 5.0, 7.0), (0.0, 0.0, 0.0), (0, 1, 0), 45)
+    return sd
+
+
+def every_class():
+    """Flat tier, every entry class side by side and no Refract: a triangle BIH of mirrors, a Tex'd Difference (the CSG class), a BIH of
+    spheres and a cone -- the production every-class instances (two waves per SIMD), lean at maxdepth 1 and full at maxdepth 3.  The
+    spheres are large and the eye is near: rayint_sphere (Sphere.hs:20-41) cancels digits with the distance, and with spheres 0.6 across
+    seen from 15 away the oracle's own fp32 frame had 3e-3 of its pixels beyond 1e-4 relative (the cap is 5e-3); now 9e-4."""
+    sd = SceneDesc()
+    m = scenes.materials(sd)
+    tri = scenes.heightfield_triangles(12) * np.array([0.6, 1.0, 0.6] * 3)
+    terrain = sd.tex(sd.bih(sd.triangles_bulk(tri)), m["mirror"])
+    cut = sd.tex(sd.difference(sd.box((-3.5, 1.8, -1.5), (-1.5, 3.8, 0.5)), sd.sphere((-2.1, 3.9, 0.7), 1.1)), m["shiny_red"])
+    balls = sd.bih([sd.tex(sd.sphere((float(x), 2.5, float(z)), 0.85), scenes.matte(sd, (0.9, 0.3 + 0.1 * x, 0.2))) for x in (1, 3) for z in (-2, 1)])
+    cone = sd.tex(sd.cone((-0.5, 1.7, 3.0), 0.9, (-0.3, 3.4, 3.0), 0.1), scenes.matte(sd, (0.2, 0.3, 0.9)))
+    _finish(sd, sd.group([terrain, cut, balls, cone]))
+    sd.set_camera((0.5, 8.0, 5.0), (0.0, 1.0, 0.0), (0, 1, 0), 55)
+    return sd
+
+
 def portal():
     """The portal of TestScene.hs:152-181: a door frame (a Difference of boxes) and, filling it, a box textured with
     `Warp frame scene lights xfm` (Shader.hs:47-50, 157-175) -- a hit traces the frame through the hit's own local ray
