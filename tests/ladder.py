@@ -58,15 +58,17 @@ def rung_rect(j):
     return cv - RUNG_HALF * W, cv + RUNG_HALF * W, cw - RUNG_HALF * W, cw + RUNG_HALF * W
 
 
-def rung_triangles(j):
+def rung_triangles(j, k=None, ndup=None, dup_at_end=None):
     """the cluster of rung j in ladder coordinates: k triangles (P1, P2_i, P3_i) that each touch the six faces of the box
-    [u - THICK, u] x [v0, v1] x [w0, w1] -- P1 its low corner, P2_i on the far face's v1 edge, P3_i on the w1 face -- facing the far end"""
-    k, u = CLUSTER[j], rung_u(j)
+    [u - THICK, u] x [v0, v1] x [w0, w1] -- P1 its low corner, P2_i on the far face's v1 edge, P3_i on the w1 face -- facing the far end.
+    k, ndup, dup_at_end: the ladder's own tables (CLUSTER, DUPLICATES, DUP_AT_END) unless given (tests/mesh_ladder.py has its own)"""
+    k, u = CLUSTER[j] if k is None else k, rung_u(j)
     v0, v1, w0, w1 = rung_rect(j)
-    ndup = DUPLICATES.get(j, 1)
+    ndup = DUPLICATES.get(j, 1) if ndup is None else ndup
+    dup_at_end = j in DUP_AT_END if dup_at_end is None else dup_at_end
     tris = []
     for i in range(k):
-        m = min(i, k - ndup) if j in DUP_AT_END else max(0, i - (ndup - 1))  # which member of the cluster triangle i is
+        m = min(i, k - ndup) if dup_at_end else max(0, i - (ndup - 1))  # which member of the cluster triangle i is
         a, b, c = 0.27 * (m % 3), 0.05 + 0.22 * (m % 5), 0.13 * (m % 4)
         tris.append(((u - THICK, v0, w0), (u, v1, w0 + a * (w1 - w0)), (u - (1 - b) * THICK, v0 + c * (v1 - v0), w1)))
     return tris
