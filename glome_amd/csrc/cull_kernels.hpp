@@ -5,7 +5,7 @@
 // ticket, make its rays, fail bih_tri_wave's entry test and store 64 blank pixels: ~500 instructions and, above all, a turn at a queue
 // head.  The cull pass visits every (frame, item) of the launch once -- one block per chunk of kQueueChunk positions of the launch's
 // order, a wave per item -- makes the item's rays as the render loop makes them (item table, coordinate tables, the frame's camera,
-// primary_ray) and asks, for every root entry, what bih_tri_wave asks before it walks (bih_root_interval / bih_root_enters: the same
+// primary_ray) and asks, for every root entry, what bih_tri_wave asks before it walks (bih_root_interval / bih_clip_root_at_origin / bih_root_enters: the same
 // inline functions, not a restatement).  An item none of whose lanes enters any root is dead: its pixels are stored here, through the
 // render loop's own store (store_pixel), and it never reaches the queue.  The live items become the slot's ticket list, in the launch's
 // order: every block leaves its chunk's 64-bit live mask in device memory, and the last block to finish scans the masks and writes the
@@ -59,6 +59,7 @@ __device__ __forceinline__ bool item_live(const DScene& S, const Ray& r, bool va
     if (uni(as_u(h0.w)) & BREF_LEAF) return true;     // a root that is a single leaf is tested regardless of its interval (Bih.hs:339)
     float nearv, farv;
     bih_root_interval(r, h0, h1, kInf, nearv, farv);
+    bih_clip_root_at_origin(nearv);  // as the launch's walk does (never a faithful or counting instance): bounds that only the line behind the camera crosses are missed
     if (wave_ballot(bih_root_enters(valid, nearv, farv)) != 0) return true;
   }
   return false;

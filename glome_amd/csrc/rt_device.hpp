@@ -14,6 +14,7 @@
 #pragma once
 #include "rt_types.h"
 
+#include <cfloat>
 #include <type_traits>
 #if defined(__HIPCC__)
 #include <hip/hip_runtime.h>
@@ -658,6 +659,35 @@ GD void bih_traverse(const DScene& S, uint32_t hdr, const Ray& r, float d, STK& 
   }
 }
 
+// What a packet walk starts with, shared with the cull pass of the flagship launch (cull_kernels.hpp), which must decide exactly as the
+// walk does: the ray's interval in the tree's bounds (header words h0, h1) clipped to d, and whether a lane enters the root branch.
+GD void bih_root_interval(const Ray& r, const F4& h0, const F4& h1, float d, float& nearv, float& farv) {
+  bbclip_ub(r, v3(h0), v3(h1), nearv, farv);
+  farv = gminf(d, farv);  // `traverse root near (fmin d far)`, Bih.hs:368
+}
+GD bool bih_root_enters(bool valid, float nearv, float farv) { return valid && !(nearv > farv); }
+// The production walks (MODE != 0, !COUNT) of a BIH of triangles or spheres start at the ray's origin, not at the point where its backward
+// extension enters the bounds: near = max(near, -FLT_MIN).  The reference does not clip (`traverse root near (fmin d far)`, Bih.hs:368); for a
+// ray that starts inside the bounds -- every shadow ray that leaves a terrain -- it then descends into every node along the line BEHIND the
+// origin and tests their items, and every one of those tests fails on t < 0.  Why no result can change:
+//   * every leaf test of these walks accepts a hit only with 0 <= t <= far, far being the node's interval end: tri_test by !(lo < 0) with
+//     lo = min(b1, b2, t) and !(t > dist) (the hand-written walk by v_cmpx_ngt 0, lo and v_cmpx_ngt t, far), sphere_test / sphere_shadow by
+//     rejecting hitdist < 0 || hitdist > dist.  For finite inputs t is never NaN (a zero or flushed divisor is rejected first);
+//   * a child that is no longer entered has its plane at t <= -FLT_MIN: its interval ENDS below zero, the reference enters it with far < 0 and
+//     accepts nothing there;
+//   * a child whose interval ends at exactly +-0 is still entered, -FLT_MIN < +-0: an origin exactly on a split plane, where a triangle
+//     through the origin is hit at t = 0.  (Clipping to 0 itself would lose that case.  -FLT_MIN is the largest negative float there is
+//     here: subnormals are flushed.);
+//   * `near` is never read by a leaf test; the far child's near = max(t2, near) and the filters at a pop only get tighter; MODE 1's
+//     invariant far <= best_t is untouched; a tree that is one leaf is tested regardless of its interval, as before.
+// Not clipped: MODE 0 and every COUNT instance (their counters are pinned to the oracle's, and count_work keeps meaning the reference's
+// interval), bih_traverse (cylinders and cones answer by tmax in ways the argument does not cover), the Mesh walks and the generic tier (its
+// packet service calls bih_tri_wave without ORIGIN_CLIP).
+// The cull pass calls this too (its launch is never a faithful or counting one): it must decide as the walk does.
+// (The operands in this order: the compare-select keeps a NaN `near` -- bbclip_ub's for a direction component of -0 with the origin exactly on
+// that face of the bounds, Q1 -- as it is, and the walk then goes on deciding as the reference does: a NaN near enters no near child.)
+GD void bih_clip_root_at_origin(float& nearv) { nearv = gmaxf(-FLT_MIN, nearv); }
+
 // ------------------------------------------------------------------ BIH of triangles (the `Bih Triangle` SPECIALIZE, Bih.hs:370-374)
 // Same traversal as bih_traverse, shaped for a 64-lane wave: every loop iteration a lane takes ONE step -- a branch
 // step or one triangle of the leaf it stands on (the leaf reference itself is the cursor: first record + remaining
@@ -681,6 +711,7 @@ GD bool bih_tri(const DScene& S, uint32_t hdr, const Ray& r, float d, STK& stk, 
   float nearv, farv;
   bbclip_ub(r, v3(h0), v3(h1), nearv, farv);
   farv = gminf(d, farv);  // `traverse root near (fmin d far)`, Bih.hs:368
+  if (MODE != 0 && !COUNT) bih_clip_root_at_origin(nearv);
   const V3 rcp = v3(dir_rcp(r.d.x), dir_rcp(r.d.y), dir_rcp(r.d.z));
   uint32_t ref = as_u(h0.w);
   const int cap = stk.total_cap();
@@ -910,15 +941,9 @@ GD PacketResult bih_tri_packet_hw(const F4* nodes, uint32_t nbytes, const float*
 }
 #endif
 
-// What a packet walk starts with, shared with the cull pass of the flagship launch (cull_kernels.hpp), which must decide exactly as the
-// walk does: the ray's interval in the tree's bounds (header words h0, h1) clipped to d, and whether a lane enters the root branch.
-GD void bih_root_interval(const Ray& r, const F4& h0, const F4& h1, float d, float& nearv, float& farv) {
-  bbclip_ub(r, v3(h0), v3(h1), nearv, farv);
-  farv = gminf(d, farv);  // `traverse root near (fmin d far)`, Bih.hs:368
-}
-GD bool bih_root_enters(bool valid, float nearv, float farv) { return valid && !(nearv > farv); }
-
-template <int MODE, bool COUNT, int LEAFK = 0, class STK>
+// ORIGIN_CLIP: the caller is a flat-tier kernel, whose production walks start at the ray's origin (bih_clip_root_at_origin).  The generic tier's
+// packet service (rt_generic.hpp) does not ask for it yet and keeps the reference's interval.
+template <int MODE, bool COUNT, int LEAFK = 0, bool ORIGIN_CLIP = false, class STK>
 GD bool bih_tri_wave(const DScene& S, uint32_t hdr, const Ray& r, float d, bool valid, STK& stk, Cnt& cnt, float& best_t, uint32_t& best_rec) {
   hdr = uni(hdr);
   F4 h0 = ld4u(S.bihhdr, 3 * hdr), h1 = ld4u(S.bihhdr, 3 * hdr + 1);
@@ -930,6 +955,7 @@ GD bool bih_tri_wave(const DScene& S, uint32_t hdr, const Ray& r, float d, bool 
   const V3 rcp = v3(dir_rcp(r.d.x), dir_rcp(r.d.y), dir_rcp(r.d.z));
   float nearv, farv;
   bih_root_interval(r, h0, h1, d, nearv, farv);
+  if (ORIGIN_CLIP && MODE != 0 && !COUNT) bih_clip_root_at_origin(nearv);  // (both packet walks below start from this interval)
   if (ref & BREF_LEAF) {
     // A one-leaf tree: `rayint [s] r far` over its items (Bih.hs:339), per lane.  Nothing is pushed -- the kernels that
     // keep only two stack rows per entry (lane_stack<TWO_ROWS>) rely on that; bih_tri's continuation entries for leaves
@@ -1422,13 +1448,13 @@ GD Cand closest_flat(const DScene& S, const Ray& r, float d, STK& stk, Cnt& cnt,
       if (tri_bih) {
         float bt = best.id == CAND_NONE ? kNoBest : best.t;
         uint32_t brec = CAND_NONE;
-        if (WAVE) bih_tri_wave<FAITHFUL ? 0 : 1, COUNT>(S, rec.y, r, dd, valid, stk, cnt, bt, brec);
+        if (WAVE) bih_tri_wave<FAITHFUL ? 0 : 1, COUNT, 0, true>(S, rec.y, r, dd, valid, stk, cnt, bt, brec);
         else bih_tri<FAITHFUL ? 0 : 1, COUNT>(S, rec.y, r, dd, stk, cnt, bt, brec);
         if (brec != CAND_NONE) { best.t = bt; best.id = brec; best.aux = e; }
       } else if (sph_bih) {
         float bt = best.id == CAND_NONE ? kNoBest : best.t;
         uint32_t brec = CAND_NONE;
-        if (WAVE) bih_tri_wave<FAITHFUL ? 0 : 1, COUNT, 1>(S, rec.y, r, dd, valid, stk, cnt, bt, brec);
+        if (WAVE) bih_tri_wave<FAITHFUL ? 0 : 1, COUNT, 1, true>(S, rec.y, r, dd, valid, stk, cnt, bt, brec);
         else bih_tri<FAITHFUL ? 0 : 1, COUNT, 1>(S, rec.y, r, dd, stk, cnt, bt, brec);
         if (brec != CAND_NONE) { best.t = bt; best.id = brec; best.aux = e; }
       } else if ((CLS & CLS_CSG) && cls == BC_CSG) {  // primitives and CSG over primitives: every item evaluated in full
@@ -1535,11 +1561,11 @@ GD bool occluded_flat(const DScene& S, const Ray& r, float d, STK& stk, Cnt& cnt
       auto nobest = [&]() { return 0.0f; };
       if (tri_bih) {
         float bt = kNoBest; uint32_t brec = CAND_NONE;
-        if (WAVE) occ = bih_tri_wave<2, COUNT>(S, rec.y, r, d, valid, stk, cnt, bt, brec);
+        if (WAVE) occ = bih_tri_wave<2, COUNT, 0, true>(S, rec.y, r, d, valid, stk, cnt, bt, brec);
         else occ = bih_tri<2, COUNT>(S, rec.y, r, d, stk, cnt, bt, brec);
       } else if (sph_bih) {
         float bt = kNoBest; uint32_t brec = CAND_NONE;
-        if (WAVE) occ = bih_tri_wave<2, COUNT, 1>(S, rec.y, r, d, valid, stk, cnt, bt, brec);
+        if (WAVE) occ = bih_tri_wave<2, COUNT, 1, true>(S, rec.y, r, d, valid, stk, cnt, bt, brec);
         else occ = bih_tri<2, COUNT, 1>(S, rec.y, r, d, stk, cnt, bt, brec);
       } else if ((CLS & CLS_CSG) && cls == BC_CSG) {
         bih_traverse<2, COUNT>(S, rec.y, r, d, stk, stk.total_cap(), cnt,

@@ -7,9 +7,13 @@
 //   slab_b   + every node carries the true extent of its subtree along ONE fixed axis b (the tree's "thin" axis); a ray's interval
 //            is clipped with it on entry
 //   aabb     + every node carries the true box of its subtree (what a BVH has)
+//   origin   the walk as it is, but the root interval starts at the ray's origin: near = max(near, -FLT_MIN) (bih_clip_root_at_origin,
+//            rt_device.hpp) -- in the closest-hit walk and in the any-hit walk.  Every shadow result is compared with the unclipped walk's.
 // A cull only ever drops nodes in which nothing can be hit: results are unchanged (checked: same hits).
 //
-//   g++ -O2 -std=c++17 -I glome_amd/csrc -I include tools/probe/bih_cull_study.cpp -o /tmp/bih_cull_study && /tmp/bih_cull_study 224 8
+//   g++ -O2 -std=c++17 -I glome_amd/csrc -I include tools/probe/bih_cull_study.cpp -o /tmp/bih_cull_study && /tmp/bih_cull_study 224 8 3
+//   (S5: 708 8 3 -- N > 300 selects the 3840 x 2160 frame)
+#include <cfloat>
 #include <cmath>
 #include <cstdint>
 #include <cstdio>
@@ -30,6 +34,8 @@ struct Study {
   std::vector<Box3> nbox;           // true box of every node's subtree
   long steps = 0, tests = 0;
   int variant = 0, baxis = 1;
+  bool origin_clip = false;         // variant `origin`
+  long pushes = 0;
   std::vector<int>* visited = nullptr;  // when set: every branch node entered is appended
   bool tri_hit(const Tri& t, D3 o, D3 d, double tmax, double& tt) const {
     D3 s1 = cross(d, t.e2);
@@ -71,6 +77,7 @@ struct Study {
         tn = std::max(tn, t0); tf = std::min(tf, t1);
       }
       nearv = tn; farv = std::min(dmax, tf);
+      if (origin_clip) nearv = std::max(nearv, -(double)FLT_MIN);
       if (nearv > farv) return -1;
     }
     struct E { int k; double n, f; };
@@ -102,7 +109,7 @@ struct Study {
           bool e1 = T->nodes[c1].leaf && T->nodes[c1].items.empty(), e2 = T->nodes[c2].leaf && T->nodes[c2].items.empty();
           bool go1 = nearv < t1 && !e1, go2 = t2 < farv && !e2;
           if (go1) {
-            if (go2) st.push_back({c2, std::max(t2, nearv), farv});
+            if (go2) { st.push_back({c2, std::max(t2, nearv), farv}); pushes++; }
             k = c1; farv = std::min(t1, farv); pop = false;
           } else if (go2) { k = c2; nearv = std::max(t2, nearv); pop = false; }
         }
@@ -155,18 +162,20 @@ int main(int argc, char** argv) {
   D3 fwd = normalize(at - pos), right = normalize(cross(up, fwd)), up_ = normalize(cross(fwd, right));
   double cs = std::tan((M_PI / 180) * 22.5);
   up_ = up_ * cs; right = right * cs;
-  const char* names[3] = {"none", "slab_y", "aabb"};
+  const char* names[4] = {"none", "slab_y", "aabb", "origin"};
   std::vector<double> ref_t;
-  for (int v = 0; v < 3; v++) {
-    S.variant = v; S.baxis = 1;
-    long psteps = 0, ptests = 0, ssteps = 0, stests = 0, nprim = 0, nshadow = 0, nocc = 0;
-    size_t idx = 0;
+  std::vector<char> ref_occ;
+  for (int v = 0; v < 4; v++) {
+    S.variant = v == 3 ? 0 : v; S.baxis = 1; S.origin_clip = v == 3;
+    long psteps = 0, ptests = 0, ssteps = 0, stests = 0, nprim = 0, nshadow = 0, nocc = 0, ppush = 0, spush = 0, occ_diff = 0;
+    unsigned long long occ_sum = 1469598103934665603ull;  // FNV-1a over the shadow results in ray order
+    size_t idx = 0, sidx = 0;
     for (int py = STRIDE / 2; py < H; py += STRIDE) for (int px = STRIDE / 2; px < W; px += STRIDE) {
       double xc = ((double(px) / W) * 2 - 1) * (double(W) / H), yc = -((double(py) / H) * 2 - 1);
       D3 d = normalize(fwd + right * (-xc) + up_ * yc);
-      S.steps = S.tests = 0;
+      S.steps = S.tests = S.pushes = 0;
       double t = S.walk(pos, d, 1e6, 1);
-      psteps += S.steps; ptests += S.tests; nprim++;
+      psteps += S.steps; ptests += S.tests; ppush += S.pushes; nprim++;
       if (v == 0) ref_t.push_back(t); else if (ref_t[idx] != t) { printf("MISMATCH at %d %d: %g vs %g\n", px, py, ref_t[idx], t); }
       idx++;
       if (t >= 0) {
@@ -177,19 +186,23 @@ int main(int argc, char** argv) {
         D3 lv = light - p;
         double ll = std::sqrt(dot(lv, lv));
         D3 ld = lv * (1.0 / ll);
-        S.steps = S.tests = 0;
+        S.steps = S.tests = S.pushes = 0;
         double ts = S.walk(p + n * 1e-4, ld, ll - 2e-4, 2);
-        ssteps += S.steps; stests += S.tests; nshadow++; nocc += ts >= 0;
+        ssteps += S.steps; stests += S.tests; spush += S.pushes; nshadow++; nocc += ts >= 0;
+        occ_sum = (occ_sum ^ (unsigned long long)(ts >= 0)) * 1099511628211ull;
+        if (v == 0) ref_occ.push_back(ts >= 0); else occ_diff += ref_occ[sidx] != (char)(ts >= 0);
+        sidx++;
       }
     }
     printf("%-7s primary: %ld rays, %.1f steps %.1f tests per ray | shadow: %ld rays (%ld occluded), %.1f steps %.1f tests per ray | all: %.1f steps %.1f tests per ray\n", names[v], nprim,
            double(psteps) / nprim, double(ptests) / nprim, nshadow, nocc, double(ssteps) / std::max(1L, nshadow), double(stests) / std::max(1L, nshadow),
            double(psteps + ssteps) / (nprim + nshadow), double(ptests + stests) / (nprim + nshadow));
+    printf("        pushes per ray: primary %.1f shadow %.1f | shadow results: checksum %016llx, %ld differ from `none`\n", double(ppush) / nprim, double(spush) / std::max(1L, nshadow), occ_sum, occ_diff);
   }
   // ---- per PACKET (one 8x8 pixel block = one work item): branch nodes entered by any of its 64 rays (what the wave-wide walk steps
   // through), primary walk and shadow walk, over every BSTRIDE-th block of the frame
-  {
-    S.variant = 0;
+  for (int clipped = 0; clipped < 2; clipped++) {
+    S.variant = 0; S.origin_clip = clipped != 0;
     const int BSTRIDE = argc > 3 ? atoi(argv[3]) : 3;
     std::vector<long> pu, su, ptot;
     std::vector<int> vis, all;
@@ -222,8 +235,8 @@ int main(int argc, char** argv) {
     S.visited = nullptr;
     auto q = [](std::vector<long> v, double f) { std::sort(v.begin(), v.end()); return v[(size_t)(f * (v.size() - 1))]; };
     auto mean = [](const std::vector<long>& v) { double s = 0; for (long x : v) s += x; return s / v.size(); };
-    printf("packets (%zu sampled): branch steps per item  primary walk mean %.0f p50 %ld p99 %ld max %ld | shadow walk mean %.0f p50 %ld p90 %ld p99 %ld p999 %ld max %ld | item mean %.0f p50 %ld p99 %ld max %ld (max / mean %.1f)\n",
-           pu.size(), mean(pu), q(pu, .5), q(pu, .99), q(pu, 1.0), mean(su), q(su, .5), q(su, .9), q(su, .99), q(su, .999), q(su, 1.0), mean(ptot), q(ptot, .5), q(ptot, .99), q(ptot, 1.0), q(ptot, 1.0) / mean(ptot));
+    printf("%-7s packets (%zu sampled): branch steps per item  primary walk mean %.0f p50 %ld p99 %ld max %ld | shadow walk mean %.0f p50 %ld p90 %ld p99 %ld p999 %ld max %ld | item mean %.0f p50 %ld p99 %ld max %ld (max / mean %.1f)\n",
+           clipped ? "origin" : "none", pu.size(), mean(pu), q(pu, .5), q(pu, .99), q(pu, 1.0), mean(su), q(su, .5), q(su, .9), q(su, .99), q(su, .999), q(su, 1.0), mean(ptot), q(ptot, .5), q(ptot, .99), q(ptot, 1.0), q(ptot, 1.0) / mean(ptot));
   }
   return 0;
 }
