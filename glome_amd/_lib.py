@@ -107,6 +107,7 @@ SYMBOLS = [
     ("glome_sb_bih", C.c_int32, [vp, c_ip, C.c_int]),
     ("glome_sb_mesh", C.c_int32, [vp, c_dp, C.c_int, c_dp, C.c_int, c_ip, C.c_int, c_ip, C.c_int]),
     ("glome_sb_bih_set_triangles", C.c_int, [vp, C.c_int32, c_dp, C.c_int]),
+    ("glome_sb_instance_set_transforms", C.c_int, [vp, c_ip, c_dp, C.c_int]),
     ("glome_sb_bih_items", C.c_int32, [vp, C.c_int32, c_ip, C.c_int32]),
     ("glome_sb_mesh_set_vertices", C.c_int, [vp, C.c_int32, c_dp, C.c_int, c_dp, C.c_int]),
     ("glome_sb_tex", C.c_int32, [vp, C.c_int32, C.c_int32]),
@@ -141,6 +142,8 @@ SYMBOLS = [
     ("glome_scene_mesh_update_dev", C.c_int, [vp, C.c_int32, vp, C.c_int, vp, C.c_int]),
     ("glome_scene_bih_update", C.c_int, [vp, C.c_int32, c_dp, C.c_int, C.POINTER(C.c_float)]),
     ("glome_scene_bih_update_dev", C.c_int, [vp, C.c_int32, vp, C.c_int]),
+    ("glome_scene_instance_update", C.c_int, [vp, c_ip, c_dp, C.c_int, C.POINTER(C.c_float)]),
+    ("glome_scene_instance_update_dev", C.c_int, [vp, c_ip, vp, C.c_int]),
     ("glome_rayint_batch", C.c_int, [vp, C.c_size_t] + [c_fp] * 7 + [c_fp, c_ip, c_fp, c_fp, c_fp, c_ip]),
     ("glome_shadow_batch", C.c_int, [vp, C.c_size_t] + [c_fp] * 7 + [c_bp]),
     ("glome_inside_batch", C.c_int, [vp, C.c_size_t, c_fp, c_fp, c_fp, c_bp]),

@@ -250,6 +250,15 @@ class Builder:
         p = np.ascontiguousarray(np.asarray(pts9, dtype=np.float64).reshape(-1, 9))
         self._chk(self.lib.glome_sb_bih_set_triangles(self.h, int(node), p.ctypes.data_as(L.c_dp) if p.shape[0] else None, p.shape[0]), "glome_sb_bih_set_triangles")
 
+    def instance_set_transforms(self, ids, xfms):
+        """New matrices for Instances (glome_sb_instance_set_transforms): xfms holds 24 values per id (api.translate / rotate / compose ...);
+        every bih that holds one of them as an item has its planes and box made again, its topology stays."""
+        i, pi = L.ivec(ids)
+        x = np.ascontiguousarray(np.asarray(xfms, dtype=np.float64).reshape(-1, 24))
+        if x.shape[0] != len(i):
+            raise GlomeError(f"instance_set_transforms: {len(i)} ids but {x.shape[0]} matrices")
+        self._chk(self.lib.glome_sb_instance_set_transforms(self.h, pi if len(i) else None, x.ctypes.data_as(L.c_dp) if len(i) else None, len(i)), "glome_sb_instance_set_transforms")
+
     def bih_items(self, node):
         """the item ids of a Bih in update order (glome_sb_bih_items)"""
         n = self._chk(self.lib.glome_sb_bih_items(self.h, int(node), None, 0), "glome_sb_bih_items")
@@ -496,6 +505,27 @@ class Scene:
         ms = C.c_float(0)
         self._chk(self.lib.glome_scene_bih_update(self.h, int(bih_id), p.ctypes.data_as(L.c_dp) if p.shape[0] else None, p.shape[0], C.byref(ms)), "glome_scene_bih_update")
         return ms.value
+
+    def instance_update(self, ids, xfms):
+        """New matrices for committed Instances, the bih that holds them refitted on the GPU (glome_scene_instance_update): the scene a
+        commit after Builder.instance_set_transforms would have made.  xfms: 24 values per id.  The host form; returns the device
+        milliseconds of the finished update."""
+        i, pi = L.ivec(ids)
+        x = np.ascontiguousarray(np.asarray(xfms, dtype=np.float64).reshape(-1, 24))
+        if x.shape[0] != len(i):
+            raise GlomeError(f"instance_update: {len(i)} ids but {x.shape[0]} matrices")
+        ms = C.c_float(0)
+        self._chk(self.lib.glome_scene_instance_update(self.h, pi if len(i) else None, x.ctypes.data_as(L.c_dp) if len(i) else None, len(i), C.byref(ms)), "glome_scene_instance_update")
+        return ms.value
+
+    def instance_update_dev(self, ids, tensor):
+        """The device form (glome_scene_instance_update_dev): ids a host list, `tensor` a contiguous CUDA torch.float64 tensor of 24 values
+        per id; asynchronous on the context's stream (the tensor must stay alive until it has run)."""
+        i, pi = L.ivec(ids)
+        t = tensor
+        if not hasattr(t, "data_ptr") or not t.is_cuda or str(t.dtype) != "torch.float64" or not t.is_contiguous() or t.numel() != 24 * len(i):
+            raise GlomeError("instance_update_dev: the matrices must be a contiguous CUDA torch.float64 tensor of 24 values per id")
+        self._chk(self.lib.glome_scene_instance_update_dev(self.h, pi if len(i) else None, C.c_void_p(t.data_ptr()) if len(i) else None, len(i)), "glome_scene_instance_update_dev")
 
     def _rays(self, o, d, tmax):
         o = np.asarray(o, dtype=np.float32).reshape(-1, 3)

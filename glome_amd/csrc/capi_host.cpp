@@ -134,6 +134,15 @@ int glome_sb_bih_set_triangles(glome_sb* sb, int32_t bih_id, const double* pts9,
     return 0;
   });
 }
+int glome_sb_instance_set_transforms(glome_sb* sb, const int32_t* ids, const double* xfms, int n) {
+  return guard(sb, [&] {
+    if (n < 0 || (n && (!ids || !xfms))) throw std::invalid_argument("instance_set_transforms: bad count or null array");
+    std::vector<Xf> X;
+    for (int k = 0; k < n; k++) X.push_back(xf_from(xfms + 24 * (size_t)k));
+    sb->graph.instance_set_transforms(std::vector<int>(ids, ids + n), X);
+    return 0;
+  });
+}
 int32_t glome_sb_bih_items(glome_sb* sb, int32_t bih_id, int32_t* out, int32_t cap) {
   return guard(sb, [&] {
     const Node& n = sb->graph.at(bih_id);

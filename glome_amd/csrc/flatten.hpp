@@ -49,6 +49,37 @@ struct BihUpdateInfo {
   std::string why_not;
 };
 
+// What an update of committed Instances' matrices needs (glome_scene_instance_update; instance_update_kernels.hpp), kept beside the
+// scene, outside DScene.  Per emitted Instance node: its slots in the `xfms` pool (emit memoises a node's record, so today a node has
+// exactly one however many parents hold it; the list is what the update walks), and -- when it is an item of a bih -- which bih and which
+// of that bih's items.
+struct InstanceUpdateInfo {
+  int node = -1;                  // the Instance's builder id
+  std::vector<uint32_t> slots;    // xfm indices (six float4 each)
+  int bih = -1;                   // the bih it is an item of (builder id), -1: of none
+  uint32_t item = 0;              // ... and its item there (an index into InstBihInfo's per-item arrays)
+  bool updatable = true;          // false: see Flattener::mark_updatable -- the reason
+  std::string why_not;
+};
+// Per emitted bih, of class BC_CSG or BC_GENERIC (no other class can hold one), with at least one Instance item.  Its items are its leaf
+// records in emission order; item j's record is recs[first_rec + rec_off[j]] -- the leaves' runs are NOT adjacent here: an item's own
+// records (an Instance's child slot, a list's members) lie between them.  rows: per item two fp32 boxes as the host derives them from the
+// fp64 bound(item) -- the plane form, round_down((lo - kDelta)) / round_up((hi + kDelta)) (a branch's plane is one more pad beyond the
+// item's box; bih_update_kernels.hpp plane_add), then the box form, round_down(lo) / round_up(hi) (what the header's box is the fold of):
+// four F4 per item, (plane lo, plane hi, box lo, box hi).  child_bound: per item the six doubles of bound(child) when the item is an
+// Instance (lo, hi), zeros otherwise.
+struct InstBihInfo {
+  int node = -1;                  // the bih's builder id
+  uint32_t hdr = 0;               // bihhdr index
+  uint32_t first_slot = 0, n_slots = 0;  // its node slots (bihnodes index, count)
+  uint32_t first_rec = 0, rec_span = 0;  // its leaf records lie in recs[first_rec .. first_rec + rec_span)
+  std::vector<uint32_t> rec_off;
+  std::vector<F4> rows;
+  std::vector<double> child_bound;
+  std::vector<uint32_t> level_nodes;  // its branch slots (bihnodes indices), deepest tree level first ...
+  std::vector<uint32_t> level_off;    // ... level l is level_nodes[level_off[l] .. level_off[l + 1])
+};
+
 struct FlatScene {
   std::vector<U4> recs;
   std::vector<F4> spheres, tris, trinorms, boxes, planes, discs, quadrics, xfms, bihhdr, bihnodes, meshhdr, meshnodes, mtris, mats, wlights;
@@ -66,6 +97,8 @@ struct FlatScene {
   bool pk_all = true;       // every triangle BIH has the packet walk's node form (emit_bih)
   std::vector<MeshUpdateInfo> mesh_updates;  // one per emitted mesh (emit_mesh), in emission order
   std::vector<BihUpdateInfo> bih_updates;    // one per emitted triangle bih (emit_bih), in emission order
+  std::vector<InstanceUpdateInfo> inst_updates;  // one per emitted Instance node (emit), in emission order
+  std::vector<InstBihInfo> inst_bihs;        // one per emitted bih that holds an Instance as an item (emit_bih), in emission order
 };
 
 inline float f32(double d) { return (float)d; }
@@ -320,18 +353,34 @@ class Flattener {
   // And which triangle bihs may have their triangles replaced (BihUpdateInfo::updatable): every one that no OTHER Bih lies above -- for
   // the same reason -- and whose item triangles the scene reaches through this bih alone: a triangle node that is also in a group beside
   // the bih, or in another bih, has a record of its own there, which an update of this bih could not move.
+  // And which Instances may have their matrices replaced (InstanceUpdateInfo::updatable).  An Instance's matrix is read from its xfm
+  // slots alone, so one with no Bih above it on any path is a write of those slots.  One that IS an item of a bih (wrappers only in
+  // between), that bih having no other above it, also moves the item's box: that tree's planes and box are refitted from the tables of
+  // emit_bih.  Refused: an Instance that lies deeper inside an item (the item's box depends on it through a list, a CSG node, a Bound or
+  // another Instance, which the update does not recompute), one with two or more bihs above it on some path (the outer tree's item box is
+  // the inner tree's box), and one that is an item more than once (a single table entry could not name both).
   void mark_updatable(int root) {
-    if (F.mesh_updates.empty() && F.bih_updates.empty()) return;
-    std::unordered_map<int, size_t> slot_of, bslot_of;
+    if (F.mesh_updates.empty() && F.bih_updates.empty() && F.inst_updates.empty()) return;
+    std::unordered_map<int, size_t> slot_of, bslot_of, islot_of;
     for (size_t k = 0; k < F.mesh_updates.size(); k++) slot_of[F.mesh_updates[k].node] = k;
     for (size_t k = 0; k < F.bih_updates.size(); k++) bslot_of[F.bih_updates[k].node] = k;
+    for (size_t k = 0; k < F.inst_updates.size(); k++) islot_of[F.inst_updates[k].node] = k;
+    for (const InstItem& I : inst_items) {
+      InstanceUpdateInfo& U = F.inst_updates[islot_of.at(I.inst)];
+      if (U.bih >= 0 && U.updatable) {
+        U.updatable = false;
+        U.why_not = "instance " + std::to_string(I.inst) + " is an item of a bih more than once (bih " + std::to_string(U.bih) + " and bih " + std::to_string(I.bih) + ")";
+      }
+      U.bih = I.bih; U.item = I.item;
+    }
     // per Triangle node, the innermost Bih it was reached under: kUnseen, a bih's id, -1 for none, kMixed once two of those differ
     constexpr int kUnseen = -3, kMixed = -2;
     std::vector<int> tri_under(F.bih_updates.empty() ? 0 : G.nodes.size(), kUnseen);
-    struct Item { int id, bih, inner; };  // bih: the outermost Bih above, inner: the innermost (-1: none)
-    std::unordered_map<int, std::vector<std::pair<int, int>>> seen;  // composites and wrappers only (a primitive has nothing below it): the (bih, inner) pairs a node was visited with
-    std::vector<Item> stack{{root, -1, -1}};
-    for (const Mat& m : G.mats) if (m.kind == MAT_WARP) { stack.push_back({m.wframe, -1, -1}); if (m.wscene >= 0) stack.push_back({m.wscene, -1, -1}); }
+    struct Item { int id, bih, inner, direct; };  // bih: the outermost Bih above, inner: the innermost (-1: none), direct: only wrappers since that bih's item list
+    struct Seen { int bih, inner, direct; bool operator==(const Seen& o) const { return bih == o.bih && inner == o.inner && direct == o.direct; } };
+    std::unordered_map<int, std::vector<Seen>> seen;  // composites and wrappers only (a primitive has nothing below it): the states a node was visited with
+    std::vector<Item> stack{{root, -1, -1, 0}};
+    for (const Mat& m : G.mats) if (m.kind == MAT_WARP) { stack.push_back({m.wframe, -1, -1, 0}); if (m.wscene >= 0) stack.push_back({m.wscene, -1, -1, 0}); }
     while (!stack.empty()) {
       Item it = stack.back();
       stack.pop_back();
@@ -340,13 +389,28 @@ class Flattener {
         if (n.kind == K_TRI && !tri_under.empty()) { int& u = tri_under[(size_t)it.id]; u = (u == kUnseen || u == it.inner) ? it.inner : kMixed; }
         continue;
       }
-      std::vector<std::pair<int, int>>& sn = seen[it.id];
-      if (std::find(sn.begin(), sn.end(), std::make_pair(it.bih, it.inner)) != sn.end()) continue;
-      sn.push_back({it.bih, it.inner});
+      std::vector<Seen>& sn = seen[it.id];
+      if (std::find(sn.begin(), sn.end(), Seen{it.bih, it.inner, it.direct}) != sn.end()) continue;
+      sn.push_back({it.bih, it.inner, it.direct});
       switch (n.kind) {
-        case K_LIST: case K_ISECT: for (int k : n.kids) stack.push_back({k, it.bih, it.inner}); break;
-        case K_DIFF: case K_BOUND: case K_INNERBOUND: stack.push_back({n.a, it.bih, it.inner}); stack.push_back({n.b, it.bih, it.inner}); break;
-        case K_INSTANCE: case K_TEX: case K_TAG: case K_NOSHADOW: case K_ONLYSHADOW: stack.push_back({n.a, it.bih, it.inner}); break;
+        case K_LIST: case K_ISECT: for (int k : n.kids) stack.push_back({k, it.bih, it.inner, 0}); break;
+        case K_DIFF: case K_BOUND: case K_INNERBOUND: stack.push_back({n.a, it.bih, it.inner, 0}); stack.push_back({n.b, it.bih, it.inner, 0}); break;
+        case K_INSTANCE: {
+          auto sl = islot_of.find(it.id);
+          if (sl != islot_of.end() && F.inst_updates[sl->second].updatable && it.bih >= 0) {
+            InstanceUpdateInfo& U = F.inst_updates[sl->second];
+            if (it.bih != it.inner) {
+              U.updatable = false;
+              U.why_not = "instance " + std::to_string(it.id) + " lies under bih " + std::to_string(it.inner) + " inside bih " + std::to_string(it.bih) + ", whose planes and root box were built from the inner tree's bound";
+            } else if (!it.direct) {
+              U.updatable = false;
+              U.why_not = "instance " + std::to_string(it.id) + " lies inside an item of bih " + std::to_string(it.inner) + " rather than being the item: that item's box depends on it through a list, CSG, Bound or Instance, which an update does not recompute";
+            }
+          }
+          stack.push_back({n.a, it.bih, it.inner, 0});
+          break;
+        }
+        case K_TEX: case K_TAG: case K_NOSHADOW: case K_ONLYSHADOW: stack.push_back({n.a, it.bih, it.inner, it.direct}); break;
         case K_BIH: {
           auto sl = bslot_of.find(it.id);
           if (it.bih >= 0 && sl != bslot_of.end() && F.bih_updates[sl->second].updatable) {
@@ -354,7 +418,7 @@ class Flattener {
             U.updatable = false;
             U.why_not = "bih " + std::to_string(it.id) + " lies inside bih " + std::to_string(it.bih) + ", whose planes and root box were built from its bound";
           }
-          for (auto& bn : n.bih->nodes) for (int k : bn.items) stack.push_back({k, it.bih < 0 ? it.id : it.bih, it.id});
+          for (auto& bn : n.bih->nodes) for (int k : bn.items) stack.push_back({k, it.bih < 0 ? it.id : it.bih, it.id, 1});
           break;
         }
         case K_MESH: {
@@ -507,6 +571,9 @@ class Flattener {
         r.x = R_INSTANCE; r.y = slot(child); r.z = (uint32_t)(F.xfms.size() / 6);
         for (int k = 0; k < 3; k++) F.xfms.push_back(mk4(n.xf.f.m[4 * k], n.xf.f.m[4 * k + 1], n.xf.f.m[4 * k + 2], n.xf.f.m[4 * k + 3]));
         for (int k = 0; k < 3; k++) F.xfms.push_back(mk4(n.xf.i.m[4 * k], n.xf.i.m[4 * k + 1], n.xf.i.m[4 * k + 2], n.xf.i.m[4 * k + 3]));
+        InstanceUpdateInfo U;
+        U.node = id; U.slots.push_back(r.z);
+        F.inst_updates.push_back(std::move(U));
         break;
       }
       case K_DIFF: case K_BOUND: case K_INNERBOUND: {
@@ -540,6 +607,27 @@ class Flattener {
     while ((c.x & RF_KINDMASK) == R_TEX) c = F.recs[c.y];
     k = c.x & RF_KINDMASK;
     return (k >= R_SPHERE && k <= R_CONE) || (k == R_LIST && (c.x & RF_PRIMLIST) != 0);
+  }
+
+  // A tree's branch slots by tree level, deepest first (a level's children were refitted before it): what the triangle bih's update and
+  // the Instance update launch k_bih_level over.  Nothing for a tree whose root is a leaf.
+  static void bih_levels(const BihTree& T, uint32_t base, const std::vector<uint32_t>& slot, std::vector<uint32_t>& level_nodes, std::vector<uint32_t>& level_off) {
+    if (T.nodes.empty() || T.nodes[0].leaf) return;
+    std::vector<int> depth(T.nodes.size(), 0), order{0};  // (a parent before its children, whatever the numbering)
+    for (size_t q = 0; q < order.size(); q++) {
+      const BihTree::Node& bn = T.nodes[(size_t)order[q]];
+      if (bn.leaf) continue;
+      for (int c : {bn.left, bn.right}) { depth[(size_t)c] = depth[(size_t)order[q]] + 1; order.push_back(c); }
+    }
+    int deepest = 0;
+    for (int k : order) if (!T.nodes[(size_t)k].leaf) deepest = std::max(deepest, depth[(size_t)k]);
+    std::vector<uint32_t> per_level((size_t)deepest + 2, 0);
+    for (int k : order) if (!T.nodes[(size_t)k].leaf) per_level[(size_t)(deepest - depth[(size_t)k]) + 1]++;
+    for (size_t l = 1; l < per_level.size(); l++) per_level[l] += per_level[l - 1];
+    level_off = per_level;
+    level_nodes.resize(per_level.back());
+    std::vector<uint32_t> fill(per_level.begin(), per_level.end() - 1);
+    for (int k : order) if (!T.nodes[(size_t)k].leaf) level_nodes[fill[(size_t)(deepest - depth[(size_t)k])]++] = base + slot[(size_t)k];
   }
 
   // BIH: nodes in preorder; leaf items become consecutive records, and (for homogeneous leaves) consecutive pool
@@ -598,14 +686,19 @@ class Flattener {
     if (base + nslots >= BREF_FIRST_LIMIT) throw limit_error("too many BIH nodes");
     bool pk = cls == BC_TRI && base + nslots < (1u << 27);  // (a node's byte offset is a reference: 31 bits)
     F.pknodes.resize(F.bihnodes.size(), F4{0, 0, 0, 0});
-    // pass 1: leaves -- emit the items fresh (no memo) so records and pool entries are consecutive, and build the
-    // child reference that describes each leaf (rt_device.hpp: BREF_*)
+    // pass 1: leaves -- a leaf's item records are consecutive, and so the child reference that describes each leaf is built here
+    // (rt_device.hpp: BREF_*).  The primitive classes (BC_TRI, BC_SPHERE, BC_SIMPLE) emit their items fresh, without the memo, so their
+    // pool entries are consecutive too and leaf follows leaf; the items of BC_CSG / BC_GENERIC go through the memoising emit(): a node
+    // shared with another parent keeps one record value (an Instance: one xfm slot), and an item's own records lie between the leaves
     std::vector<uint32_t> ref(T.nodes.size(), 0);
     std::vector<uint32_t> pkleaf(T.nodes.size(), 3u);  // a leaf as the packet walk refers to it: byte offset of its first pair record | 3
     uint32_t delta = 0;
     bool have_delta = false;
     bool in_place = cls != BC_TRI && cls != BC_SPHERE;  // (those two have their own packet walk)
     BihUpdateInfo U;
+    std::vector<int> item_ids;        // a bih of class BC_CSG / BC_GENERIC: its items in emission order, and their records
+    std::vector<uint32_t> item_recs;
+    bool has_inst = false;            // ... one of them is an Instance (under wrappers): the tree gets an InstBihInfo
     std::vector<uint32_t> item_of;  // a triangle bih: item node id -> its index in the update order (BihTree::update_order, whichever way the tree was made)
     if (cls == BC_TRI) {
       U.node = id; U.hdr = hdr; U.first_slot = base; U.n_slots = nslots;
@@ -642,6 +735,10 @@ class Flattener {
       }
       uint32_t first_rec = (uint32_t)F.recs.size();
       F.recs.insert(F.recs.end(), items.begin(), items.end());
+      if (cls == BC_GENERIC || cls == BC_CSG) for (size_t q = 0; q < bn.items.size(); q++) {
+        item_ids.push_back(bn.items[q]); item_recs.push_back(first_rec + (uint32_t)q);
+        has_inst = has_inst || G.at(G.peel_wrappers(bn.items[q])).kind == K_INSTANCE;
+      }
       if (first_rec + items.size() >= BREF_FIRST_LIMIT) throw limit_error("too many records for the BIH leaf references");
       uint32_t count = (uint32_t)items.size();
       if (count && (cls == BC_TRI || cls == BC_SPHERE)) {
@@ -700,27 +797,35 @@ class Flattener {
     if (cls == BC_TRI) {
       U.n_tris = (uint32_t)(U.rows.size() / 2); U.pk = pk;
       if (!pk) for (size_t j = 0; j < U.n_tris; j++) U.rows[2 * j + 1] = BihUpdateInfo::kNoPair;  // (the packet form was given up part way)
-      if (!T.nodes.empty() && !T.nodes[0].leaf) {  // the branch slots by tree level, deepest first: a level's children were refitted before it
-        std::vector<int> depth(T.nodes.size(), 0), order{0};  // (a parent before its children, whatever the numbering)
-        for (size_t q = 0; q < order.size(); q++) {
-          const BihTree::Node& bn = T.nodes[(size_t)order[q]];
-          if (bn.leaf) continue;
-          for (int c : {bn.left, bn.right}) { depth[(size_t)c] = depth[(size_t)order[q]] + 1; order.push_back(c); }
-        }
-        int deepest = 0;
-        for (int k : order) if (!T.nodes[(size_t)k].leaf) deepest = std::max(deepest, depth[(size_t)k]);
-        std::vector<uint32_t> per_level((size_t)deepest + 2, 0);
-        for (int k : order) if (!T.nodes[(size_t)k].leaf) per_level[(size_t)(deepest - depth[(size_t)k]) + 1]++;
-        for (size_t l = 1; l < per_level.size(); l++) per_level[l] += per_level[l - 1];
-        U.level_off = per_level;
-        U.level_nodes.resize(per_level.back());
-        std::vector<uint32_t> fill(per_level.begin(), per_level.end() - 1);
-        for (int k : order) if (!T.nodes[(size_t)k].leaf) U.level_nodes[fill[(size_t)(deepest - depth[(size_t)k])]++] = base + slot[(size_t)k];
-      }
+      bih_levels(T, base, slot, U.level_nodes, U.level_off);
       F.bih_updates.push_back(std::move(U));
+    }
+    if (has_inst) {
+      InstBihInfo B;
+      B.node = id; B.hdr = hdr; B.first_slot = base; B.n_slots = nslots;
+      B.first_rec = item_recs.front(); B.rec_span = item_recs.back() + 1u - B.first_rec;  // (records only ever grow: the first item's is the lowest)
+      B.child_bound.assign(6 * item_ids.size(), 0.0);
+      for (size_t j = 0; j < item_ids.size(); j++) {
+        B.rec_off.push_back(item_recs[j] - B.first_rec);
+        const Box3 b = G.bound(item_ids[j]);
+        B.rows.push_back(F4{round_down((b.lo.x - kDelta)), round_down((b.lo.y - kDelta)), round_down((b.lo.z - kDelta)), 0.0f});
+        B.rows.push_back(F4{round_up((b.hi.x + kDelta)), round_up((b.hi.y + kDelta)), round_up((b.hi.z + kDelta)), 0.0f});
+        B.rows.push_back(F4{round_down(b.lo.x), round_down(b.lo.y), round_down(b.lo.z), 0.0f});
+        B.rows.push_back(F4{round_up(b.hi.x), round_up(b.hi.y), round_up(b.hi.z), 0.0f});
+        const int inst = G.peel_wrappers(item_ids[j]);
+        if (G.at(inst).kind != K_INSTANCE) continue;
+        const Box3 cb = G.bound(G.at(inst).a);
+        const double c6[6] = {cb.lo.x, cb.lo.y, cb.lo.z, cb.hi.x, cb.hi.y, cb.hi.z};
+        std::copy(c6, c6 + 6, B.child_bound.begin() + 6 * (ptrdiff_t)j);
+        inst_items.push_back({inst, id, (uint32_t)j});
+      }
+      bih_levels(T, base, slot, B.level_nodes, B.level_off);
+      F.inst_bihs.push_back(std::move(B));
     }
     return U4{R_BIH, hdr, 0, (uint32_t)n.uid};
   }
+  struct InstItem { int inst, bih; uint32_t item; };
+  std::vector<InstItem> inst_items;  // every (Instance, bih, item) emit_bih met: bound to F.inst_updates by mark_updatable
 
   U4 emit_mesh(const Node& n, int id) {
     const MeshData& M = *n.mesh;

@@ -533,6 +533,13 @@ struct Graph {
       double* p = nodes[(size_t)tri[k]].p;
       for (int q = 0; q < 3; q++) { p[3 * q] = pts[3 * k + q].x; p[3 * q + 1] = pts[3 * k + q].y; p[3 * q + 2] = pts[3 * k + q].z; }
     }
+    bih_refit(id);
+  }
+  // What `bih` derives from its items' bounds, made again for the tree as it stands (the pass both bih_set_triangles and
+  // instance_set_transforms end with): the tree's box and every branch's two planes, by the definitions quoted above.
+  void bih_refit(int id) {
+    BihTree& T = *nodes[(size_t)id].bih;
+    const std::vector<int> order = T.update_order();
     T.bb = box_empty();
     for (int it : order) T.bb = box_join(T.bb, bound(it));
     if (T.nodes.empty()) return;
@@ -550,6 +557,45 @@ struct Graph {
       n.rsplit = comp(sub[(size_t)n.right].lo, n.axis) - kDelta;
       sub[(size_t)it.node] = box_join(sub[(size_t)n.left], sub[(size_t)n.right]);
     }
+  }
+
+  // New matrices for Instances (glome_sb_instance_set_transforms): ids[k], a K_INSTANCE node whoever made it -- `transform`, `cylinder` /
+  // `cone`, flatten_transform, a `show` text --, gets xfs[k], and every Bih of the builder that holds one of them AS AN ITEM (under any
+  // number of Tex / Tag / shadow wrappers) has its planes and box made again from its items' current bounds (bih_refit): an item's box is
+  // the eight transformed corners of bound(child) (`bound`, K_INSTANCE).  A bih that holds the Instance deeper inside an item (through a
+  // list, CSG, Bound or another Instance), and a bih above a refitted bih, keep their old planes and box: moving such an Instance out of
+  // them is the caller's error, as moving a mesh out of the bih above it is.  The reference has no such call; the result is what the
+  // reference would print for the same trees with the new matrices.  Nothing is touched unless everything is valid.
+  void instance_set_transforms(const std::vector<int>& ids, const std::vector<Xf>& xfs) {
+    std::vector<char> named(nodes.size(), 0);
+    for (size_t k = 0; k < ids.size(); k++) {
+      const int id = ids[k];
+      if (id < 0 || id >= (int)nodes.size()) throw std::invalid_argument("instance_set_transforms: no node " + std::to_string(id));
+      if (nodes[(size_t)id].kind != K_INSTANCE) throw std::invalid_argument("instance_set_transforms: node " + std::to_string(id) + " is a " + kind_name(nodes[(size_t)id].kind) + ", not an Instance");
+      if (named[(size_t)id]) throw std::invalid_argument("instance_set_transforms: node " + std::to_string(id) + " is named more than once");
+      named[(size_t)id] = 1;
+      for (int q = 0; q < 12; q++)
+        if (!(std::isfinite(xfs[k].f.m[q]) && std::isfinite(xfs[k].i.m[q]))) throw std::invalid_argument("instance_set_transforms: a matrix entry of node " + std::to_string(id) + " is not finite");
+      try { xf_check(xfs[k]); } catch (const scene_error& e) { throw scene_error("instance_set_transforms: node " + std::to_string(id) + ": " + e.what()); }
+    }
+    std::vector<int> refit;  // the bihs that hold a named Instance as an item
+    for (size_t b = 0; b < nodes.size(); b++) {
+      if (nodes[b].kind != K_BIH) continue;
+      bool holds = false;
+      for (const BihTree::Node& bn : nodes[b].bih->nodes) { for (int it : bn.items) if (named[(size_t)peel_wrappers(it)]) { holds = true; break; } if (holds) break; }
+      if (holds) refit.push_back((int)b);
+    }
+    std::vector<Xf> old(ids.size());
+    for (size_t k = 0; k < ids.size(); k++) { old[k] = nodes[(size_t)ids[k]].xf; nodes[(size_t)ids[k]].xf = xfs[k]; }
+    for (int b : refit) {  // the constructor's own refusal (`bih`), before any tree is touched
+      Box3 bb = box_empty();
+      for (int it : nodes[(size_t)b].bih->update_order()) bb = box_join(bb, bound(it));
+      if (bb.lo.x == -kInfinity || bb.lo.y == -kInfinity || bb.lo.z == -kInfinity || bb.hi.x == kInfinity || bb.hi.y == kInfinity || bb.hi.z == kInfinity) {
+        for (size_t k = 0; k < ids.size(); k++) nodes[(size_t)ids[k]].xf = old[k];
+        throw scene_error("instance_set_transforms: bih " + std::to_string(b) + ": bih: infinite bounding box");
+      }
+    }
+    for (int b : refit) bih_refit(b);
   }
 
   // ---------------- Mesh builder, Mesh.hs:50-134 (Q12) ----------------

@@ -3,7 +3,7 @@
 // sampler and batch kernels through kernel_launch.hpp (the instances live in kernel_parts.hip, chosen by instances.hpp) and holds
 // only the light kernels: the kernel-argument self-test, the coordinate tables, tile transport, the tree builders
 // (bih_build_device.hpp), the flagship launch's cull pass (cull_kernels.hpp) and the updates of a committed Mesh (mesh_update_kernels.hpp)
-// and of a committed triangle bih (bih_update_kernels.hpp).
+// and of a committed triangle bih (bih_update_kernels.hpp), and of committed Instances' matrices (instance_update_kernels.hpp).
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -26,6 +26,7 @@
 #include "cull_kernels.hpp"
 #include "mesh_update_kernels.hpp"
 #include "bih_update_kernels.hpp"
+#include "instance_update_kernels.hpp"
 
 using namespace glome;
 
@@ -168,6 +169,28 @@ struct glome_scene {
     float4* d_ws = nullptr;            // two words per record, two per node slot, then the bound's partial boxes: allocated at the first update
   };
   std::map<int, BihUpd> bihs;
+  // and for glome_scene_instance_update: every Instance of the scene by its builder id, and every bih that holds one as an item
+  // (flatten.hpp InstanceUpdateInfo, InstBihInfo)
+  std::map<int, InstanceUpdateInfo> insts;
+  struct InstBih {
+    InstBihInfo info;                  // (level_nodes emptied once uploaded; rows once the workspace holds them)
+    const uint32_t* d_levels = nullptr;
+    const uint32_t* d_rec_off = nullptr;
+    const double* d_bounds = nullptr;
+    // two words per record of the tree's span (plane-form rows), two per node slot, two per item (box-form rows), then the bound's partial
+    // boxes: allocated, and filled with the commit-time rows, at the first update that touches the tree
+    float4* d_ws = nullptr;
+  };
+  std::map<int, InstBih> ibihs;
+  // an update's own tables (which matrix goes to which slot / item) travel through pinned buffers, so that the device form stays
+  // asynchronous: a small ring, a buffer reused once the copy out of it has run.  The ring protects the PINNED side only: the one device
+  // table d_inst_rows is rewritten by every call, which is safe because a call's copy into it is ordered, on the stream, after the
+  // kernels of the call before it -- calls on other streams are the caller's to order, as for the pools themselves
+  struct RowStage { uint2* h = nullptr; size_t cap = 0; hipEvent_t ev = nullptr; bool pending = false; };
+  RowStage inst_stage[4];
+  int inst_stage_next = 0;
+  uint2* d_inst_rows = nullptr;
+  size_t inst_rows_cap = 0;
 };
 
 static std::string g_global_error;
@@ -544,12 +567,21 @@ glome_scene* glome_scene_commit(glome_ctx* ctx, glome_sb* sb, int32_t root) {
     U.rows = {}; U.level_nodes = {};
     m.info = std::move(U);
   }
+  for (InstBihInfo& B : F.inst_bihs) {
+    glome_scene::InstBih& m = s->ibihs[B.node];
+    if ((!B.level_nodes.empty() && upload(s, B.level_nodes, &m.d_levels)) || upload(s, B.rec_off, &m.d_rec_off) || upload(s, B.child_bound, &m.d_bounds)) { glome_scene_release(s); return nullptr; }
+    B.level_nodes = {};
+    m.info = std::move(B);
+  }
+  for (InstanceUpdateInfo& U : F.inst_updates) { const int node = U.node; s->insts[node] = std::move(U); }
   return s;
 }
 void glome_scene_release(glome_scene* s) {
   if (!s) return;
   (void)hipSetDevice(s->ctx->device);
   for (void* p : s->allocs) (void)hipFree(p);
+  for (auto& st : s->inst_stage) { if (st.h) (void)hipHostFree(st.h); if (st.ev) (void)hipEventDestroy(st.ev); }
+  if (s->d_inst_rows) (void)hipFree(s->d_inst_rows);
   delete s;
 }
 int glome_scene_get_info(const glome_scene* s, glome_scene_info* out) {
@@ -638,9 +670,10 @@ static int device_error_status(glome_ctx* ctx, unsigned int e) {
     ctx->err = "a ray direction is not unit length: set glome_trace_params.faithful to trace such rays (the reference's own traversal)";
     return GLOME_E_INVALID;
   }
-  if (e & kErrBadVertex) {  // (only a mesh update and a bih update set it; the word does not say which)
+  if (e & kErrBadVertex) {  // (only the three updates set it; the word does not say which)
     ctx->err = "a mesh update met a vertex coordinate that is not finite: the scene's mesh is unspecified until a valid update"
-               " (or a bih update, glome_scene_bih_update: then the bih is)";
+               " (or a bih update, glome_scene_bih_update: then the bih is; or an Instance update, glome_scene_instance_update, met a matrix"
+               " entry that is not finite or a bih item box that reaches infinity: then those Instances and the bih that holds them are)";
     return GLOME_E_INVALID;
   }
   ctx->err = "device-side limit hit (traversal stack or CSG advance cap)";
@@ -1187,6 +1220,166 @@ int glome_scene_bih_update(glome_scene* s, int32_t bih_id, const double* pts9, i
   if (!dp) { ctx->err = "staging allocation failed"; return GLOME_E_HIP; }
   if (gpu_ms) HIPCHK(ctx, hipEventRecord(ctx->ev0, ctx->stream));
   if (int rc = glome_scene_bih_update_dev(s, bih_id, dp, n)) return rc;
+  if (gpu_ms) HIPCHK(ctx, hipEventRecord(ctx->ev1, ctx->stream));
+  HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+  if (gpu_ms) HIPCHK(ctx, hipEventElapsedTime(gpu_ms, ctx->ev0, ctx->ev1));
+  return check_device_error(ctx);
+}
+
+// ---- new matrices for committed Instances (instance_update_kernels.hpp) ----
+// what both forms refuse before anything is launched; out[k] = the tables of ids[k]
+static int instance_update_check(glome_scene* s, const int32_t* ids, const void* xfms, int n, std::vector<const InstanceUpdateInfo*>& out) {
+  glome_ctx* ctx = s->ctx;
+  if (n < 0 || (n && (!ids || !xfms))) { ctx->err = "instance update: bad count or null array"; return GLOME_E_INVALID; }
+  out.clear();
+  for (int k = 0; k < n; k++) {
+    auto it = s->insts.find(ids[k]);
+    if (it == s->insts.end()) { ctx->err = "instance update: node " + std::to_string(ids[k]) + " is not an Instance of this scene"; return GLOME_E_INVALID; }
+    if (!it->second.updatable) { ctx->err = "instance update refused: " + it->second.why_not; return GLOME_E_INVALID; }
+    out.push_back(&it->second);
+  }
+  std::vector<int32_t> sorted(ids, ids + n);
+  std::sort(sorted.begin(), sorted.end());
+  auto dup = std::adjacent_find(sorted.begin(), sorted.end());
+  if (dup != sorted.end()) { ctx->err = "instance update: node " + std::to_string(*dup) + " is named more than once"; return GLOME_E_INVALID; }
+  return 0;
+}
+int glome_scene_instance_update_dev(glome_scene* s, const int32_t* ids, const double* xfms_dev, int n) {
+  if (!s) return GLOME_E_INVALID;
+  glome_ctx* ctx = s->ctx;
+  std::vector<const InstanceUpdateInfo*> U;
+  if (int rc = instance_update_check(s, ids, xfms_dev, n, U)) return rc;
+  if (n == 0) return 0;
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  hipStream_t st = ctx->stream;
+  // this call's rows: (matrix, xfm slot) of every slot, then per bih (matrix, item) of its named items
+  std::vector<uint2> rows;
+  std::map<int, std::vector<uint2>> per_bih;
+  for (int k = 0; k < n; k++) {
+    for (uint32_t slot : U[(size_t)k]->slots) rows.push_back(make_uint2((uint32_t)k, slot));
+    if (U[(size_t)k]->bih >= 0) per_bih[U[(size_t)k]->bih].push_back(make_uint2((uint32_t)k, U[(size_t)k]->item));
+  }
+  const uint32_t n_xfm = (uint32_t)rows.size();
+  for (auto& pb : per_bih) rows.insert(rows.end(), pb.second.begin(), pb.second.end());
+  if (rows.size() > s->inst_rows_cap) {
+    if (s->d_inst_rows) { HIPCHK(ctx, hipStreamSynchronize(st)); HIPCHK(ctx, hipFree(s->d_inst_rows)); s->d_inst_rows = nullptr; s->inst_rows_cap = 0; }
+    HIPCHK(ctx, hipMalloc((void**)&s->d_inst_rows, rows.size() * sizeof(uint2)));
+    s->inst_rows_cap = rows.size();
+  }
+  glome_scene::RowStage& stage = s->inst_stage[s->inst_stage_next];
+  s->inst_stage_next = (s->inst_stage_next + 1) % 4;
+  if (stage.pending) { HIPCHK(ctx, hipEventSynchronize(stage.ev)); stage.pending = false; }
+  if (rows.size() > stage.cap) {
+    if (stage.h) { HIPCHK(ctx, hipHostFree(stage.h)); stage.h = nullptr; stage.cap = 0; }
+    HIPCHK(ctx, hipHostMalloc((void**)&stage.h, rows.size() * sizeof(uint2), hipHostMallocDefault));
+    stage.cap = rows.size();
+  }
+  if (!stage.ev) HIPCHK(ctx, hipEventCreateWithFlags(&stage.ev, hipEventDisableTiming));
+  std::copy(rows.begin(), rows.end(), stage.h);
+  // the workspaces of the bihs this call refits, allocated and given the commit-time rows of all their items at their first update
+  for (auto& pb : per_bih) {
+    glome_scene::InstBih& m = s->ibihs.at(pb.first);
+    if (m.d_ws) continue;
+    const InstBihInfo& B = m.info;
+    const size_t n_items = B.rows.size() / 4, words = 2 * ((size_t)B.rec_span + B.n_slots + n_items + meshupd::kBoundMaxBlocks);
+    std::vector<float4> init(words, make_float4(0.0f, 0.0f, 0.0f, 0.0f));
+    float4* box = init.data() + 2 * ((size_t)B.rec_span + B.n_slots);
+    for (size_t j = 0; j < n_items; j++) {
+      const F4* r = &B.rows[4 * j];
+      float4* plane = init.data() + 2 * (size_t)m.info.rec_off[j];
+      plane[0] = make_float4(r[0].x, r[0].y, r[0].z, 0.0f); plane[1] = make_float4(r[1].x, r[1].y, r[1].z, 0.0f);
+      box[2 * j] = make_float4(r[2].x, r[2].y, r[2].z, 0.0f); box[2 * j + 1] = make_float4(r[3].x, r[3].y, r[3].z, 0.0f);
+    }
+    void* d = nullptr;
+    HIPCHK(ctx, hipMalloc(&d, words * sizeof(float4)));
+    s->allocs.push_back(d);
+    HIPCHK(ctx, hipMemcpy(d, init.data(), words * sizeof(float4), hipMemcpyHostToDevice));  // (nothing has read the workspace yet, and the launches below follow the copy)
+    m.d_ws = (float4*)d;
+    m.info.rows = {};
+  }
+  const uint32_t max_items = (uint32_t)ctx->prop.multiProcessorCount * 32u * 4u;
+  auto grid = [&](uint32_t lanes) { return dim3(std::max<uint32_t>(1u, std::min<uint32_t>((lanes + 63u) >> 6, max_items))); };
+  // one event pair per update while timing is on
+  hipEvent_t e0 = nullptr, e1 = nullptr;
+  if (ctx->timing && launch_events(ctx, e0, e1)) HIPCHK(ctx, hipEventRecord(e0, st)); else e1 = nullptr;
+  HIPCHK(ctx, hipMemcpyAsync(s->d_inst_rows, stage.h, rows.size() * sizeof(uint2), hipMemcpyHostToDevice, st));
+  HIPCHK(ctx, hipEventRecord(stage.ev, st));
+  stage.pending = true;
+  unsigned int* err = &ctx->slot().d_counters->error;
+  {
+    instupd::DXfmArgs A;
+    A.xfms = xfms_dev; A.rows = s->d_inst_rows; A.pool = (float4*)s->dev.xfms; A.n = n_xfm; A.error = err;
+    hipLaunchKernelGGL(instupd::k_inst_xfm, grid(n_xfm), dim3(64), 0, st, A);
+  }
+  uint32_t at = n_xfm;
+  for (auto& pb : per_bih) {
+    glome_scene::InstBih& m = s->ibihs.at(pb.first);
+    const InstBihInfo& B = m.info;
+    const uint32_t n_named = (uint32_t)pb.second.size(), n_items = (uint32_t)(B.child_bound.size() / 6);
+    float4* ws_plane = m.d_ws;
+    float4* ws_node = ws_plane + 2 * (size_t)B.rec_span;
+    float4* ws_box = ws_node + 2 * (size_t)B.n_slots;
+    float4* part = ws_box + 2 * (size_t)n_items;
+    {
+      instupd::DItemArgs A;
+      A.xfms = xfms_dev; A.rows = s->d_inst_rows + at; A.bounds = m.d_bounds; A.rec_off = m.d_rec_off; A.ws_plane = ws_plane; A.ws_box = ws_box; A.n = n_named; A.error = err;
+      hipLaunchKernelGGL(instupd::k_inst_item_box, grid(n_named), dim3(64), 0, st, A);
+    }
+    at += n_named;
+    {  // the planes, a launch per tree level, deepest first: the triangle bih's own kernel over the plane-form rows
+      bihupd::DLevelArgs A;
+      A.nodes = m.d_levels; A.bihnodes = (float4*)s->dev.bihnodes; A.pknodes = nullptr;
+      A.ws_tri = ws_plane; A.ws_node = ws_node; A.first_rec = B.first_rec; A.first_slot = B.first_slot;
+      for (size_t l = 0; l + 1 < B.level_off.size(); l++) {
+        const uint32_t width = B.level_off[l + 1] - B.level_off[l];
+        hipLaunchKernelGGL(bihupd::k_bih_level, grid(width), dim3(64), 0, st, A, B.level_off[l], width);
+      }
+    }
+    const uint32_t blocks = std::max<uint32_t>(1u, std::min<uint32_t>((n_items + 63u) >> 6, (uint32_t)meshupd::kBoundMaxBlocks));
+    hipLaunchKernelGGL(instupd::k_inst_box_fold, dim3(blocks), dim3(64), 0, st, (const float4*)ws_box, n_items, part);
+    hipLaunchKernelGGL(bihupd::k_bih_bound_store, dim3(1), dim3(64), 0, st, (const float4*)part, blocks, (float4*)s->dev.bihhdr + 3 * (size_t)B.hdr);
+  }
+  HIPCHK(ctx, hipGetLastError());
+  if (e1) HIPCHK(ctx, hipEventRecord(e1, st));
+  ctx->slot().launched = true; ctx->slot().launched_on = ctx->stream;  // (a matrix entry that is not finite is reported at the next synchronize)
+  return 0;
+}
+int glome_scene_instance_update(glome_scene* s, const int32_t* ids, const double* xfms, int n, float* gpu_ms) {
+  if (!s) return GLOME_E_INVALID;
+  glome_ctx* ctx = s->ctx;
+  if (gpu_ms) *gpu_ms = 0;
+  std::vector<const InstanceUpdateInfo*> U;
+  if (int rc = instance_update_check(s, ids, xfms, n, U)) return rc;
+  for (int k = 0; k < n; k++) {
+    const double* m = xfms + 24 * (size_t)k;
+    for (int q = 0; q < 24; q++) if (!std::isfinite(m[q])) { ctx->err = "instance update: a matrix entry of node " + std::to_string(ids[k]) + " is not finite"; return GLOME_E_INVALID; }
+    Xf x;
+    for (int q = 0; q < 12; q++) { x.f.m[q] = m[q]; x.i.m[q] = m[12 + q]; }
+    try { xf_check(x); } catch (const scene_error& e) { ctx->err = "instance update: node " + std::to_string(ids[k]) + ": " + e.what(); return GLOME_E_INVALID; }
+    if (U[(size_t)k]->bih < 0) continue;
+    // the item's new box, as `bound` makes it: `bih` refuses one that reaches the reference's infinity
+    const double* cb = &s->ibihs.at(U[(size_t)k]->bih).info.child_bound[6 * (size_t)U[(size_t)k]->item];
+    D3 pts[8];
+    int q = 0;
+    for (double px : {cb[0], cb[3]}) for (double py : {cb[1], cb[4]}) for (double pz : {cb[2], cb[5]}) pts[q++] = xf_point(x, D3{px, py, pz});
+    const Box3 b = box_of_points(pts, 8);
+    if (b.lo.x == -kInfinity || b.lo.y == -kInfinity || b.lo.z == -kInfinity || b.hi.x == kInfinity || b.hi.y == kInfinity || b.hi.z == kInfinity) {
+      ctx->err = "instance update: node " + std::to_string(ids[k]) + " in bih " + std::to_string(U[(size_t)k]->bih) + ": bih: infinite bounding box";
+      return GLOME_E_SCENE;
+    }
+  }
+  if (n == 0) return 0;
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  // every slot of the context may have a launch in flight that reads the pools about to be written
+  HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+  for (auto& sl : ctx->slots)
+    if (sl.launched_on && sl.launched_on != ctx->stream) (void)hipStreamSynchronize(sl.launched_on);
+  (void)hipGetLastError();  // (a stream its owner has destroyed since must not be this call's error: other_slots_busy)
+  Staging stg{ctx, {}};
+  double* dx = stg.in<double>(xfms, 24 * (size_t)n);
+  if (!dx) { ctx->err = "staging allocation failed"; return GLOME_E_HIP; }
+  if (gpu_ms) HIPCHK(ctx, hipEventRecord(ctx->ev0, ctx->stream));
+  if (int rc = glome_scene_instance_update_dev(s, ids, dx, n)) return rc;
   if (gpu_ms) HIPCHK(ctx, hipEventRecord(ctx->ev1, ctx->stream));
   HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
   if (gpu_ms) HIPCHK(ctx, hipEventElapsedTime(gpu_ms, ctx->ev0, ctx->ev1));

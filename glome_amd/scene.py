@@ -26,6 +26,7 @@ class SceneDesc:
         self.root = None
         self.lights = []  # (pos, color, rad, shadow)
         self.cam = None   # (pos, at, up, angle)
+        self.updates = []  # (number of ops made before it, ids, xfms): instance_set_transforms calls, kept apart from `ops`
 
     def _q(self, x):
         return r32(x) if self.round32 else np.asarray(x, dtype=np.float64).tolist()
@@ -91,6 +92,16 @@ class SceneDesc:
         ls = [(self._q(l[0]), self._q(l[1]), float(l[2]) if len(l) > 2 else 1000000.0, bool(l[3]) if len(l) > 3 else True) for l in lights]
         return self._mat("material_warp", frame, scene, ls, np.asarray(xfm, dtype=np.float64).ravel().copy())
 
+    def instance_set_transforms(self, ids, xfms):
+        """New matrices for Instance nodes made earlier in this description (Builder.instance_set_transforms), replayed at this place among
+        the constructors.  xfms: 24 values per id, taken as they are like `transform`'s matrices (round32 rounds scene constants, not
+        matrices).  Kept in `updates`, not in `ops`: every reader of `ops` takes an entry for a constructor.  Only replay() honours it, and
+        replay() refuses a backend without the call (the checkers have none: describe the moved scene with `transform` for them)."""
+        ids = [int(i) for i in ids]
+        if any(i < 0 or i >= self.n_nodes for i in ids):
+            raise ValueError("instance_set_transforms: an id is not a node of this description")
+        self.updates.append((len(self.ops), ids, np.asarray(xfms, dtype=np.float64).reshape(len(ids), 24).copy()))
+
     def set_root(self, node): self.root = node
     def add_light(self, pos, color, rad=1000000.0, shadow=True): self.lights.append((self._q(pos), self._q(color), float(rad), bool(shadow)))
     def set_camera(self, pos, at, up, angle): self.cam = (self._q(pos), self._q(at), self._q(up), float(angle))
@@ -108,7 +119,16 @@ class SceneDesc:
         """Replay into `backend`; returns (node id map, material id map) from SceneDesc ids to backend ids."""
         nmap, mmap = [], []
         N = lambda i: nmap[i]
-        for kind, name, args in self.ops:
+        if self.updates and not hasattr(backend, "instance_set_transforms"):
+            raise TypeError(f"this description holds instance_set_transforms calls, which {type(backend).__name__} cannot replay")
+        pending = list(self.updates)
+
+        def updates_before(k):
+            while pending and pending[0][0] <= k:
+                _, ids, xfms = pending.pop(0)
+                backend.instance_set_transforms([N(i) for i in ids], xfms)
+        for k, (kind, name, args) in enumerate(self.ops):
+            updates_before(k)
             if kind == "m":
                 if name == "material_layers":
                     mmap.append(backend.material_layers([mmap[m] for m in args[0]]))
@@ -136,4 +156,5 @@ class SceneDesc:
                 nmap.append(backend.mesh(args[0], args[1], args[2], [mmap[m] for m in args[3]]))
             else:
                 nmap.append(getattr(backend, name)(*args))
+        updates_before(len(self.ops))
         return nmap, mmap

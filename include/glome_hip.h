@@ -130,6 +130,21 @@ int glome_sb_mesh_set_vertices(glome_sb*, int32_t mesh_id, const double* verts, 
 int glome_sb_bih_set_triangles(glome_sb*, int32_t bih_id, const double* pts9, int n);
 /* the item ids of a Bih in update order: returns their number and fills out[0 .. min(number, cap)) (out may be NULL: count first) */
 int32_t glome_sb_bih_items(glome_sb*, int32_t bih_id, int32_t* out, int32_t cap);
+/* New matrices for Instances.  Every id names an Instance node, whoever made it -- glome_sb_transform (of anything but a triangle, an
+ * Instance or Void, which it rewrites instead), glome_sb_cylinder / _cone (the node they return), glome_sb_flatten_transform, a `show`
+ * text --, no id twice; xfms holds 24 doubles per id (forward rows, inverse rows), every one finite, each matrix passing the reference's
+ * check_xfm (Vec.hs:466-477).  Sets the nodes' matrices and, for every Bih of the builder that holds one of these Instances AS AN ITEM
+ * (under any number of Tex / Tag / NoShadow / OnlyShadow wrappers), makes again what `bih` derives from its items' bounds, exactly as
+ * glome_sb_bih_set_triangles does: every branch's planes and the tree's box, an Instance item's box being the eight transformed corners
+ * of its child's bound padded by delta (Solid.hs:477-484).  What the builder decided -- nodes, axes, leaf lists, depth -- stays, and the
+ * tree stays correct for the reason given above.  A bih that holds the Instance deeper inside an item (in a group, a CSG node, a Bound,
+ * under another Instance), and a bih above a refitted bih, keep the planes and box they were built with: an Instance that leaves them is
+ * the caller's error.  glome_sb_bound, glome_sb_show, glome_sb_bih_dump and a later commit see the new matrices and trees.  The reference
+ * has no such call; the result is what the reference would print for the same trees with the new matrices.  All or nothing: GLOME_E_INVALID
+ * (not an Instance, an id twice, a bad count or pointer, an entry that is not finite) or GLOME_E_SCENE (check_xfm fails; a refitted tree's
+ * box would be infinite, as glome_sb_bih refuses it) with a message naming the node, and nothing is touched.  Host only; the
+ * specification of glome_scene_instance_update. */
+int glome_sb_instance_set_transforms(glome_sb*, const int32_t* ids, const double* xfms, int n);
 int32_t glome_sb_tex(glome_sb*, int32_t id, int32_t material);                                   /* Tex.hs:33-34 */
 int32_t glome_sb_tag(glome_sb*, int32_t id);                                                     /* Tex.hs:38-39 (tags feed picking only) */
 int32_t glome_sb_noshadow(glome_sb*, int32_t id);                                                /* Tex.hs:43 */
@@ -271,6 +286,45 @@ int glome_scene_mesh_update_dev(glome_scene*, int32_t mesh_id, const double* ver
  * The first update of a bih allocates its workspace (32 bytes per triangle and per node), kept until glome_scene_release. */
 int glome_scene_bih_update(glome_scene*, int32_t bih_id, const double* pts9, int n, float* gpu_ms);
 int glome_scene_bih_update_dev(glome_scene*, int32_t bih_id, const double* pts9_dev, int n);
+
+/* ---- animate committed Instances: new matrices, the bih that holds them refitted on the GPU ----
+ * Every `transform` that is not pushed down into a primitive is an Instance: a rigid object, and every `cylinder` and `cone`.  After an
+ * update the committed scene is, bit for bit, the scene glome_scene_commit would have made had glome_sb_instance_set_transforms been
+ * called with the same ids and matrices first: the six float4 of every xfm slot of every named Instance and, for a bih that holds a
+ * named Instance as an item, both planes of every branch and the header's box.  The tree's topology stays; one update moves everything
+ * below the Instance (a Mesh or a triangle bih under it keeps its own update call).  (The deviation of the two other updates holds: a
+ * component whose fp32 value would be subnormal is stored as zero.)  The builder is not touched: a host that also wants the new
+ * matrices there calls both.
+ *   ids   n builder ids of Instances that are part of this scene, a HOST array in both forms, no id twice; xfms 24 doubles per id
+ *         (forward rows, inverse rows: what glome_xfm_* writes).
+ *   Accepted: an Instance anywhere below lists, Instances, CSG, Bound / InnerBound and wrappers with no bih above it -- a write of its
+ *   slots and nothing else --, and an Instance that is an item of exactly one bih (under Tex / Tag / shadow wrappers), that bih below
+ *   anything but another bih.  The bounding solid of a Bound / InnerBound above is the caller's own object, as in the reference.
+ *   Refused with GLOME_E_INVALID before anything is launched, the scene untouched, the message naming the node: an id that is not an
+ *   Instance of this scene, an id named twice, a bad count or a null array, in the host form a matrix that is not finite or fails the
+ *   reference's check_xfm (forward * inverse = identity), an Instance that lies INSIDE an item of a bih rather than being the item (the
+ *   item's box depends on it through a list, CSG, Bound or Instance, which the update does not recompute), an Instance with two or more
+ *   bihs above it on any path from the committed root or from a Warp material's frame / scene (the items of the oak inside GlomeView's
+ *   default scene, whose root is itself a bih), and one that is an item of a bih more than once.  The host form also refuses, with
+ *   GLOME_E_SCENE and the constructor's "bih: infinite bounding box", an item whose new box reaches the reference's infinity (1e6) in a
+ *   component; it looks at the named items one by one, where glome_sb_instance_set_transforms looks at the joined box.
+ * glome_scene_instance_update takes a host array of matrices, checks it, waits for every launch of the context (all slots), stages it,
+ * updates and returns when the update is complete; *gpu_ms (may be NULL) = HIP-event time of its kernels.
+ * glome_scene_instance_update_dev takes the matrices as a DEVICE pointer (fp64, 24 per id) and is asynchronous on the context's current
+ * stream and slot, like the two other updates: launches enqueued after it on that stream see the new matrices, and the array must stay
+ * valid until it has run.  Launches still in flight on OTHER slots / streams read the same pools: ordering an update against them is
+ * the caller's responsibility.  It takes part in glome_ctx_timing_begin / _end (one event pair per call).  A matrix entry that is not
+ * finite, and an item box that reaches infinity, are found on the device: the next glome_ctx_synchronize returns GLOME_E_INVALID (the
+ * error word is the other updates': the message names all three calls), and the named Instances and the bih that holds them are
+ * unspecified -- though never out of bounds -- until a valid update.  A matrix that merely fails check_xfm is the caller's error there.
+ * The first update that touches a bih allocates its workspace (32 bytes per record the tree spans, per node and per item), kept until
+ * glome_scene_release, and gives it the commit-time boxes of all the tree's items; later updates rewrite only the named items' rows, so
+ * updating 3 of 2,047 items costs 3 boxes and the plane pass.  That first update is NOT asynchronous, in either form: it allocates and
+ * copies the workspace with blocking calls before it enqueues its kernels (once per bih; a host that cannot block mid-stream makes one
+ * update with the committed matrices right after the commit).  A call that names more Instances than any before it also waits for the
+ * stream once, to grow its table. */
+int glome_scene_instance_update(glome_scene*, const int32_t* ids, const double* xfms, int n, float* gpu_ms);
+int glome_scene_instance_update_dev(glome_scene*, const int32_t* ids, const double* xfms_dev, int n);
 
 /* ---- per-ray seams (Solid.hs:146-166), host buffers ---- */
 /* closest hit: t < 0 marks a miss (RayMiss), and then prim is -1, tex8 all -1 and the normal UNSPECIFIED (whatever the traversal
