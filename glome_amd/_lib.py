@@ -109,6 +109,8 @@ SYMBOLS = [
     ("glome_sb_bih_set_triangles", C.c_int, [vp, C.c_int32, c_dp, C.c_int]),
     ("glome_sb_instance_set_transforms", C.c_int, [vp, c_ip, c_dp, C.c_int]),
     ("glome_sb_bih_items", C.c_int32, [vp, C.c_int32, c_ip, C.c_int32]),
+    ("glome_sb_bih_refit", C.c_int, [vp, C.c_int32]),
+    ("glome_sb_bihs_above", C.c_int32, [vp, C.c_int32, C.c_int32, c_ip, C.c_int32]),
     ("glome_sb_mesh_set_vertices", C.c_int, [vp, C.c_int32, c_dp, C.c_int, c_dp, C.c_int]),
     ("glome_sb_tex", C.c_int32, [vp, C.c_int32, C.c_int32]),
     ("glome_sb_tag", C.c_int32, [vp, C.c_int32]),
@@ -144,6 +146,11 @@ SYMBOLS = [
     ("glome_scene_bih_update_dev", C.c_int, [vp, C.c_int32, vp, C.c_int]),
     ("glome_scene_instance_update", C.c_int, [vp, c_ip, c_dp, C.c_int, C.POINTER(C.c_float)]),
     ("glome_scene_instance_update_dev", C.c_int, [vp, c_ip, vp, C.c_int]),
+    ("glome_scene_nested_updates", C.c_int, [vp, C.c_int]),
+    ("glome_scene_bih_refit", C.c_int, [vp, C.c_int32, C.POINTER(C.c_float)]),
+    ("glome_scene_bih_refit_dev", C.c_int, [vp, C.c_int32]),
+    ("glome_scene_bihs_above", C.c_int32, [vp, C.c_int32, c_ip, C.c_int32]),
+    ("glome_scene_stale_bihs", C.c_int32, [vp, c_ip, C.c_int32]),
     ("glome_rayint_batch", C.c_int, [vp, C.c_size_t] + [c_fp] * 7 + [c_fp, c_ip, c_fp, c_fp, c_fp, c_ip]),
     ("glome_shadow_batch", C.c_int, [vp, C.c_size_t] + [c_fp] * 7 + [c_bp]),
     ("glome_inside_batch", C.c_int, [vp, C.c_size_t, c_fp, c_fp, c_fp, c_bp]),

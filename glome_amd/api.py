@@ -259,6 +259,19 @@ class Builder:
             raise GlomeError(f"instance_set_transforms: {len(i)} ids but {x.shape[0]} matrices")
         self._chk(self.lib.glome_sb_instance_set_transforms(self.h, pi if len(i) else None, x.ctypes.data_as(L.c_dp) if len(i) else None, len(i)), "glome_sb_instance_set_transforms")
 
+    def bih_refit(self, node):
+        """What `bih` derives from its items' bounds, made again for the tree as it stands (glome_sb_bih_refit): after mesh_set_vertices /
+        bih_set_triangles / instance_set_transforms of something below, call it for every bih above, inner trees first (bihs_above)."""
+        self._chk(self.lib.glome_sb_bih_refit(self.h, int(node)), "glome_sb_bih_refit")
+
+    def bihs_above(self, root, node):
+        """the bihs above `node` in the scene under `root`, in an order in which they can be refitted (glome_sb_bihs_above); raises with
+        the reason when an update of `node` would be refused even with nested updates on"""
+        n = self._chk(self.lib.glome_sb_bihs_above(self.h, int(root), int(node), None, 0), "glome_sb_bihs_above")
+        out = np.zeros(max(1, n), np.int32)
+        self._chk(self.lib.glome_sb_bihs_above(self.h, int(root), int(node), out.ctypes.data_as(L.c_ip), n), "glome_sb_bihs_above")
+        return [int(x) for x in out[:n]]
+
     def bih_items(self, node):
         """the item ids of a Bih in update order (glome_sb_bih_items)"""
         n = self._chk(self.lib.glome_sb_bih_items(self.h, int(node), None, 0), "glome_sb_bih_items")
@@ -526,6 +539,48 @@ class Scene:
         if not hasattr(t, "data_ptr") or not t.is_cuda or str(t.dtype) != "torch.float64" or not t.is_contiguous() or t.numel() != 24 * len(i):
             raise GlomeError("instance_update_dev: the matrices must be a contiguous CUDA torch.float64 tensor of 24 values per id")
         self._chk(self.lib.glome_scene_instance_update_dev(self.h, pi if len(i) else None, C.c_void_p(t.data_ptr()) if len(i) else None, len(i)), "glome_scene_instance_update_dev")
+
+    def nested_updates(self, on=True):
+        """The switch of glome_scene_nested_updates: with it on, the three updates accept objects that lie under bihs, leave the trees above
+        them stale, and bih_refit makes those trees again, one call per tree, inner trees first (refit_above does the walk)."""
+        self._chk(self.lib.glome_scene_nested_updates(self.h, 1 if on else 0), "glome_scene_nested_updates")
+
+    def bih_refit(self, bih_id):
+        """One tree refitted from the current bounds of the objects its items hang on (glome_scene_bih_refit, the host form): returns the
+        device milliseconds of the finished refit."""
+        ms = C.c_float(0)
+        self._chk(self.lib.glome_scene_bih_refit(self.h, int(bih_id), C.byref(ms)), "glome_scene_bih_refit")
+        return ms.value
+
+    def bih_refit_dev(self, bih_id):
+        """The device form (glome_scene_bih_refit_dev): asynchronous on the context's stream, after the updates enqueued before it."""
+        self._chk(self.lib.glome_scene_bih_refit_dev(self.h, int(bih_id)), "glome_scene_bih_refit_dev")
+
+    def _id_list(self, fn, what, *args):
+        n = fn(self.h, *args, None, 0)
+        if n < 0:
+            self._chk(n, what)
+        out = np.zeros(max(1, n), np.int32)
+        fn(self.h, *args, out.ctypes.data_as(L.c_ip), n)
+        return [int(x) for x in out[:n]]
+
+    def bihs_above(self, node):
+        """the bihs above `node` in this scene, in an order in which they can be refitted (glome_scene_bihs_above)"""
+        return self._id_list(self.lib.glome_scene_bihs_above, "glome_scene_bihs_above", int(node))
+
+    def stale_bihs(self):
+        """the bihs an update has left stale, in an order in which they can be refitted (glome_scene_stale_bihs)"""
+        return self._id_list(self.lib.glome_scene_stale_bihs, "glome_scene_stale_bihs")
+
+    def refit_above(self, node, dev=False):
+        """bih_refit of every bih above `node`, inner trees first; returns the summed device milliseconds (None in the device form)"""
+        total = 0.0
+        for b in self.bihs_above(node):
+            if dev:
+                self.bih_refit_dev(b)
+            else:
+                total += self.bih_refit(b)
+        return None if dev else total
 
     def _rays(self, o, d, tmax):
         o = np.asarray(o, dtype=np.float32).reshape(-1, 3)

@@ -143,6 +143,34 @@ int glome_sb_instance_set_transforms(glome_sb* sb, const int32_t* ids, const dou
     return 0;
   });
 }
+int glome_sb_bih_refit(glome_sb* sb, int32_t bih_id) {
+  return guard(sb, [&] {
+    Graph& G = sb->graph;
+    if (G.at(bih_id).kind != K_BIH) throw std::invalid_argument(std::string("bih_refit: node ") + std::to_string(bih_id) + " is a " + kind_name(G.at(bih_id).kind) + ", not a Bih");
+    Box3 bb = box_empty();  // the constructor's own refusal (`bih`), before the tree is touched
+    for (int it : G.at(bih_id).bih->update_order()) bb = box_join(bb, G.bound(it));
+    if (bb.lo.x == -kInfinity || bb.lo.y == -kInfinity || bb.lo.z == -kInfinity || bb.hi.x == kInfinity || bb.hi.y == kInfinity || bb.hi.z == kInfinity)
+      throw scene_error("bih_refit: bih " + std::to_string(bih_id) + ": bih: infinite bounding box");
+    G.bih_refit(bih_id);
+    return 0;
+  });
+}
+int32_t glome_sb_bihs_above(glome_sb* sb, int32_t root, int32_t node_id, int32_t* out, int32_t cap) {
+  return guard(sb, [&] {
+    FlatScene F;
+    Flattener fl(sb_graph(sb), F);
+    fl.run(root);
+    const NestedAnswer* A = nullptr;
+    for (const MeshUpdateInfo& U : F.mesh_updates) if (U.node == node_id) A = &U.nested;
+    for (const BihUpdateInfo& U : F.bih_updates) if (U.node == node_id) A = &U.nested;
+    for (const InstanceUpdateInfo& U : F.inst_updates) if (U.node == node_id) A = &U.nested;
+    for (const InstBihInfo& B : F.inst_bihs) if (B.node == node_id) A = &B.nested;
+    if (!A) throw std::invalid_argument("bihs_above: node " + std::to_string(node_id) + " is not a Mesh, a triangle bih, an Instance or a refittable bih of the scene under node " + std::to_string(root));
+    if (!A->ok) throw std::invalid_argument("bihs_above: " + A->why_not);
+    for (size_t k = 0; k < A->above.size() && (int32_t)k < cap && out; k++) out[k] = A->above[k];
+    return (int)A->above.size();
+  });
+}
 int32_t glome_sb_bih_items(glome_sb* sb, int32_t bih_id, int32_t* out, int32_t cap) {
   return guard(sb, [&] {
     const Node& n = sb->graph.at(bih_id);

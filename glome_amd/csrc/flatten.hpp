@@ -4,7 +4,9 @@
 #pragma once
 #include <limits>
 #include <cstring>
+#include <functional>
 #include <map>
+#include <set>
 #include <unordered_map>
 
 #include "host_graph.hpp"
@@ -15,6 +17,15 @@ namespace glome {
 // What an update of a committed Mesh's vertices needs (glome_scene_mesh_update; mesh_update_kernels.hpp), recorded per emitted mesh and
 // kept beside the scene, outside DScene.  Record j of the mesh is mtris record first_tri + j; its index row is rows[8 j ..]:
 // a b c na nb nc, the triangle's first trinorms word or -1, a spare word.  The placeholder record of an empty leaf has a = -1.
+// The second answer of mark_updatable, per Mesh, triangle bih and Instance: whether an update is accepted when the bihs above the object
+// are refitted after it (glome_scene_nested_updates, glome_scene_bih_refit), and those bihs in an order in which they can be refitted --
+// a tree after every tree below it.  `updatable` / `why_not` stay what they were: the answer with the switch off.
+struct NestedAnswer {
+  bool ok = true;
+  std::string why_not;
+  std::vector<int> above;
+};
+
 struct MeshUpdateInfo {
   int node = -1;                  // the mesh's builder id
   int nv = 0, nn = 0;
@@ -26,6 +37,8 @@ struct MeshUpdateInfo {
   std::vector<uint32_t> level_off;    // ... level l is level_nodes[level_off[l] .. level_off[l + 1])
   bool updatable = true;          // false: a path from the committed root to the mesh passes through a Bih, whose planes and root box were
   std::string why_not;            // built from the mesh's bound (Bih.hs:309-324) -- the reason, naming that bih
+  NestedAnswer nested;            // the answer with glome_scene_nested_updates on (Flattener::mark_nested)
+  double bound6[6] = {0, 0, 0, 0, 0, 0};  // bound(mesh) at commit: lo, hi
 };
 
 // What an update of a committed triangle bih's triangles needs (glome_scene_bih_update; bih_update_kernels.hpp), recorded per emitted bih
@@ -47,6 +60,8 @@ struct BihUpdateInfo {
   std::vector<uint32_t> level_off;    // ... level l is level_nodes[level_off[l] .. level_off[l + 1])
   bool updatable = true;          // false: another Bih lies above it, or the scene holds another copy of one of its triangles -- the reason
   std::string why_not;
+  NestedAnswer nested;
+  double bound6[6] = {0, 0, 0, 0, 0, 0};  // bound(bih) at commit
 };
 
 // What an update of committed Instances' matrices needs (glome_scene_instance_update; instance_update_kernels.hpp), kept beside the
@@ -60,15 +75,27 @@ struct InstanceUpdateInfo {
   uint32_t item = 0;              // ... and its item there (an index into InstBihInfo's per-item arrays)
   bool updatable = true;          // false: see Flattener::mark_updatable -- the reason
   std::string why_not;
+  NestedAnswer nested;
 };
-// Per emitted bih, of class BC_CSG or BC_GENERIC (no other class can hold one), with at least one Instance item.  Its items are its leaf
+// Per emitted bih, of class BC_CSG or BC_GENERIC (no other class can hold one), with at least one Instance item or one LIVE item: an
+// item that, Tex / Tag / shadow wrappers peeled off, is a Mesh or a Bih (a direct item) or an Instance of one under wrappers (an
+// instanced item) -- what glome_scene_bih_refit makes again from the object's fp64 bound.  Its items are its leaf
 // records in emission order; item j's record is recs[first_rec + rec_off[j]] -- the leaves' runs are NOT adjacent here: an item's own
 // records (an Instance's child slot, a list's members) lie between them.  rows: per item two fp32 boxes as the host derives them from the
 // fp64 bound(item) -- the plane form, round_down((lo - kDelta)) / round_up((hi + kDelta)) (a branch's plane is one more pad beyond the
 // item's box; bih_update_kernels.hpp plane_add), then the box form, round_down(lo) / round_up(hi) (what the header's box is the fold of):
 // four F4 per item, (plane lo, plane hi, box lo, box hi).  child_bound: per item the six doubles of bound(child) when the item is an
-// Instance (lo, hi), zeros otherwise.
+// Instance (lo, hi), zeros otherwise.  kind / live / box64 / live_xf: the tables of a refit -- per item its kind and the builder id of
+// the object it hangs on (-1: none), the six doubles of bound(item) at commit, and for the instanced items, in item order, the 24 doubles
+// of the Instance's matrix at commit (xf_at: which row).  An item over a Bih the scene cannot update (spheres, say) counts as static.
 struct InstBihInfo {
+  enum ItemKind : uint8_t { kStatic = 0, kInstance = 1, kDirectLive = 2, kInstancedLive = 3 };
+  std::vector<uint8_t> kind;
+  std::vector<int> live;
+  std::vector<double> box64, live_xf;
+  std::vector<int32_t> xf_at;     // per item: its row of live_xf, -1: none
+  NestedAnswer nested;            // of the bih itself, as a live object of the trees above it: ok = every tree above can be refitted after it
+  double bound6[6] = {0, 0, 0, 0, 0, 0};  // bound(bih) at commit
   int node = -1;                  // the bih's builder id
   uint32_t hdr = 0;               // bihhdr index
   uint32_t first_slot = 0, n_slots = 0;  // its node slots (bihnodes index, count)
@@ -142,6 +169,7 @@ class Flattener {
     if (F.tier != 0 && F.max_mesh_depth > kGenericStack)
       throw limit_error("Mesh tree deeper than the device traversal stack (" + std::to_string(F.max_mesh_depth) + " > " + std::to_string(kGenericStack) + ")");
     mark_updatable(root);
+    mark_nested(root);
     pad();
   }
 
@@ -449,6 +477,128 @@ class Flattener {
     }
   }
 
+  // The second answer (NestedAnswer), for glome_scene_nested_updates: an update of X -- a Mesh, a triangle bih, an Instance that is an
+  // item of a bih -- is accepted when every bih above it can be refitted from the tables of emit_bih, one tree after the other.  An item
+  // of a bih B is LIVE OVER Z when peeling its wrappers gives Z (a direct item) or an Instance whose child, peeled again, is Z (an
+  // instanced item).  X is ok when on every path from a root to X each bih B on the path holds, on that path, an item that is live over
+  // the next thing down the path: X, or the next bih.  (For an Instance X its own bih holds X as the item.)  Anything else between two
+  // trees -- a list, a CSG node, a Bound / InnerBound, a second Instance -- is refused with the node in the way named: its box is
+  // derived from the object's by something no kernel makes again.  One object under several items or several bihs is fine: every one
+  // of those rows is derived from the same bound.  The walk records, per Mesh, Bih and Instance, the states it was reached in
+  // (innermost bih, what lies between that bih's item list and the node); the answers are then resolved bih by bih, memoised.
+  void mark_nested(int root) {
+    if (F.mesh_updates.empty() && F.bih_updates.empty() && F.inst_updates.empty() && F.inst_bihs.empty()) return;
+    enum { kDirect = 0, kInst = 1, kBroken = 2 };
+    struct Edge { int bih, link, blocker, via; };   // blocker: the first list / CSG / Bound / second Instance since the item list; via: the Instance passed first (-1: none)
+    struct Item { int id, inner, link, blocker, via; };
+    constexpr int kUnseen = -3, kMixed = -2;
+    std::vector<int> tri_under(F.bih_updates.empty() ? 0 : G.nodes.size(), kUnseen);
+    std::unordered_map<int, std::vector<Edge>> edges;
+    std::unordered_map<int, std::vector<std::pair<int, int>>> seen;
+    std::vector<Item> stack{{root, -1, kDirect, -1, -1}};
+    for (const Mat& m : G.mats) if (m.kind == MAT_WARP) { stack.push_back({m.wframe, -1, kDirect, -1, -1}); if (m.wscene >= 0) stack.push_back({m.wscene, -1, kDirect, -1, -1}); }
+    while (!stack.empty()) {
+      const Item it = stack.back();
+      stack.pop_back();
+      const Node& n = G.at(it.id);
+      if (is_prim(n.kind) || n.kind == K_VOID) {
+        if (n.kind == K_TRI && !tri_under.empty()) { int& u = tri_under[(size_t)it.id]; u = (u == kUnseen || u == it.inner) ? it.inner : kMixed; }
+        continue;
+      }
+      std::vector<std::pair<int, int>>& sn = seen[it.id];
+      if (std::find(sn.begin(), sn.end(), std::make_pair(it.inner, it.link)) != sn.end()) continue;
+      sn.push_back({it.inner, it.link});
+      // below a node that is no wrapper: nothing is live any more (no bih above: nothing to keep track of)
+      const Item below{0, it.inner, it.inner < 0 ? kDirect : kBroken, it.inner < 0 ? -1 : (it.link == kBroken ? it.blocker : it.id), it.via};  // (the first node in the way is the one named)
+      switch (n.kind) {
+        case K_LIST: case K_ISECT: for (int k : n.kids) stack.push_back({k, below.inner, below.link, below.blocker, below.via}); break;
+        case K_DIFF: case K_BOUND: case K_INNERBOUND: stack.push_back({n.a, below.inner, below.link, below.blocker, below.via}); stack.push_back({n.b, below.inner, below.link, below.blocker, below.via}); break;
+        case K_INSTANCE:
+          edges[it.id].push_back({it.inner, it.link, it.blocker, it.via});
+          if (it.inner >= 0 && it.link == kDirect) stack.push_back({n.a, it.inner, kInst, -1, it.id});
+          else stack.push_back({n.a, below.inner, below.link, below.blocker, below.via});
+          break;
+        case K_TEX: case K_TAG: case K_NOSHADOW: case K_ONLYSHADOW: stack.push_back({n.a, it.inner, it.link, it.blocker, it.via}); break;
+        case K_BIH:
+          edges[it.id].push_back({it.inner, it.link, it.blocker, it.via});
+          for (auto& bn : n.bih->nodes) for (int k : bn.items) stack.push_back({k, it.id, kDirect, -1, -1});
+          break;
+        case K_MESH: edges[it.id].push_back({it.inner, it.link, it.blocker, it.via}); break;
+        default: break;
+      }
+    }
+    // a tree's height among the trees: the longest chain of bihs below it (what orders `above`)
+    std::unordered_map<int, std::vector<int>> kids_of;
+    for (auto& e : edges) if (G.at(e.first).kind == K_BIH) for (const Edge& ed : e.second) if (ed.bih >= 0) kids_of[ed.bih].push_back(e.first);
+    std::unordered_map<int, int> height_memo;
+    std::function<int(int)> height = [&](int b) {
+      auto f = height_memo.find(b);
+      if (f != height_memo.end()) return f->second;
+      int h = 0;
+      for (int c : kids_of[b]) h = std::max(h, height(c) + 1);
+      return height_memo[b] = h;
+    };
+    auto what = [&](int id) { const int k = G.at(id).kind; return std::string(k == K_MESH ? "mesh " : (k == K_BIH ? "bih " : "instance ")) + std::to_string(id); };
+    std::unordered_map<int, NestedAnswer> bih_memo;
+    std::function<NestedAnswer(int)> answer = [&](int x) {
+      const bool is_bih = G.at(x).kind == K_BIH, is_inst = G.at(x).kind == K_INSTANCE;
+      if (is_bih) { auto f = bih_memo.find(x); if (f != bih_memo.end()) return f->second; }
+      NestedAnswer A;
+      std::set<int> above;
+      auto f = edges.find(x);
+      if (f != edges.end()) for (const Edge& e : f->second) {
+        if (e.bih < 0) continue;
+        if (e.link == kBroken || (is_inst && e.link == kInst)) {
+          A.ok = false;
+          // for an Instance the first thing in the way is an Instance above it (it is then not the item); for a Mesh or Bih one Instance is fine
+          const int in_the_way = (is_inst && e.via >= 0) ? e.via : e.blocker;
+          A.why_not = what(x) + " lies inside an item of bih " + std::to_string(e.bih) + " under " + kind_name(G.at(in_the_way).kind) + " " + std::to_string(in_the_way) +
+                      ": that item's box depends on it through a list, CSG, Bound or second Instance, which a refit does not recompute";
+          break;
+        }
+        const NestedAnswer up = answer(e.bih);
+        if (!up.ok) { A.ok = false; A.why_not = up.why_not; break; }
+        above.insert(e.bih);
+        above.insert(up.above.begin(), up.above.end());
+      }
+      if (A.ok) {
+        A.above.assign(above.begin(), above.end());
+        std::stable_sort(A.above.begin(), A.above.end(), [&](int a, int b) { return height(a) < height(b); });
+      }
+      if (is_bih) bih_memo[x] = A;
+      return A;
+    };
+    for (MeshUpdateInfo& U : F.mesh_updates) U.nested = answer(U.node);
+    for (BihUpdateInfo& U : F.bih_updates) {
+      if (U.why_not.rfind("bih " + std::to_string(U.node) + " holds triangle", 0) == 0) { U.nested.ok = false; U.nested.why_not = U.why_not; continue; }  // (emit_bih's refusal)
+      U.nested = answer(U.node);
+      if (!U.nested.ok) continue;
+      for (const BihTree::Node& bn : G.at(U.node).bih->nodes) {
+        for (int item : bn.items) {
+          const int t = G.peel_wrappers(item);
+          const int u = tri_under[(size_t)t];
+          if (u == U.node || u == kUnseen) continue;
+          U.nested.ok = false;
+          U.nested.why_not = "triangle " + std::to_string(t) + " of bih " + std::to_string(U.node) + " is also part of the scene outside that bih, as a copy an update could not move";
+          break;
+        }
+        if (!U.nested.ok) break;
+      }
+    }
+    std::unordered_map<int, std::pair<int, int>> item_of_bih;  // Instance -> (its first bih, how often it is an item)
+    for (const InstItem& I : inst_items) { auto r = item_of_bih.insert({I.inst, {I.bih, 0}}); r.first->second.second++; }
+    for (InstanceUpdateInfo& U : F.inst_updates) {
+      auto f = item_of_bih.find(U.node);
+      if (f != item_of_bih.end() && f->second.second > 1) {
+        U.nested.ok = false;
+        U.nested.why_not = "instance " + std::to_string(U.node) + " is an item of a bih more than once (bih " + std::to_string(f->second.first) + " and bih " + std::to_string(U.bih) + ")";
+        continue;
+      }
+      U.nested = answer(U.node);
+    }
+    for (InstBihInfo& B : F.inst_bihs) B.nested = answer(B.node);
+  }
+
   // ---- primitive pools ----
   uint32_t emit_tri(const double* p) {  // (p1, e1, e2, n) evaluated in double, rounded once
     D3 p1{p[0], p[1], p[2]}, p2{p[3], p[4], p[5]}, p3{p[6], p[7], p[8]};
@@ -737,7 +887,8 @@ class Flattener {
       F.recs.insert(F.recs.end(), items.begin(), items.end());
       if (cls == BC_GENERIC || cls == BC_CSG) for (size_t q = 0; q < bn.items.size(); q++) {
         item_ids.push_back(bn.items[q]); item_recs.push_back(first_rec + (uint32_t)q);
-        has_inst = has_inst || G.at(G.peel_wrappers(bn.items[q])).kind == K_INSTANCE;
+        int live_obj;
+        has_inst = has_inst || item_kind(bn.items[q], live_obj) != InstBihInfo::kStatic;
       }
       if (first_rec + items.size() >= BREF_FIRST_LIMIT) throw limit_error("too many records for the BIH leaf references");
       uint32_t count = (uint32_t)items.size();
@@ -796,18 +947,28 @@ class Flattener {
     if (cls == BC_SPHERE || cls == BC_TRI || in_place) F.max_sphere_bih_depth = std::max(F.max_sphere_bih_depth, T.depth);
     if (cls == BC_TRI) {
       U.n_tris = (uint32_t)(U.rows.size() / 2); U.pk = pk;
+      box6(T.bb, U.bound6);
       if (!pk) for (size_t j = 0; j < U.n_tris; j++) U.rows[2 * j + 1] = BihUpdateInfo::kNoPair;  // (the packet form was given up part way)
       bih_levels(T, base, slot, U.level_nodes, U.level_off);
       F.bih_updates.push_back(std::move(U));
+      movable_bihs.insert(id);
     }
     if (has_inst) {
+      movable_bihs.insert(id);
       InstBihInfo B;
       B.node = id; B.hdr = hdr; B.first_slot = base; B.n_slots = nslots;
       B.first_rec = item_recs.front(); B.rec_span = item_recs.back() + 1u - B.first_rec;  // (records only ever grow: the first item's is the lowest)
       B.child_bound.assign(6 * item_ids.size(), 0.0);
+      box6(T.bb, B.bound6);
       for (size_t j = 0; j < item_ids.size(); j++) {
         B.rec_off.push_back(item_recs[j] - B.first_rec);
         const Box3 b = G.bound(item_ids[j]);
+        int live_obj = -1;
+        B.kind.push_back(item_kind(item_ids[j], live_obj));
+        B.live.push_back(live_obj);
+        B.xf_at.push_back(-1);
+        B.box64.resize(B.box64.size() + 6);
+        box6(b, &B.box64[B.box64.size() - 6]);
         B.rows.push_back(F4{round_down((b.lo.x - kDelta)), round_down((b.lo.y - kDelta)), round_down((b.lo.z - kDelta)), 0.0f});
         B.rows.push_back(F4{round_up((b.hi.x + kDelta)), round_up((b.hi.y + kDelta)), round_up((b.hi.z + kDelta)), 0.0f});
         B.rows.push_back(F4{round_down(b.lo.x), round_down(b.lo.y), round_down(b.lo.z), 0.0f});
@@ -818,12 +979,34 @@ class Flattener {
         const double c6[6] = {cb.lo.x, cb.lo.y, cb.lo.z, cb.hi.x, cb.hi.y, cb.hi.z};
         std::copy(c6, c6 + 6, B.child_bound.begin() + 6 * (ptrdiff_t)j);
         inst_items.push_back({inst, id, (uint32_t)j});
+        if (B.kind.back() == InstBihInfo::kInstancedLive) {
+          const Xf& x = G.at(inst).xf;
+          B.xf_at.back() = (int32_t)(B.live_xf.size() / 24);
+          B.live_xf.insert(B.live_xf.end(), x.f.m, x.f.m + 12);
+          B.live_xf.insert(B.live_xf.end(), x.i.m, x.i.m + 12);
+        }
       }
       bih_levels(T, base, slot, B.level_nodes, B.level_off);
       F.inst_bihs.push_back(std::move(B));
     }
     return U4{R_BIH, hdr, 0, (uint32_t)n.uid};
   }
+  static void box6(const Box3& b, double* o) { o[0] = b.lo.x; o[1] = b.lo.y; o[2] = b.lo.z; o[3] = b.hi.x; o[4] = b.hi.y; o[5] = b.hi.z; }
+  // An item of a bih by what a refit makes of it (InstBihInfo::ItemKind); live: the Mesh or Bih it hangs on
+  uint8_t item_kind(int item, int& live) const {
+    live = -1;
+    const int z = G.peel_wrappers(item);
+    const int k = G.at(z).kind;
+    if (can_move(z)) { live = z; return InstBihInfo::kDirectLive; }
+    if (k != K_INSTANCE) return InstBihInfo::kStatic;
+    const int c = G.peel_wrappers(G.at(z).a);
+    if (can_move(c)) { live = c; return InstBihInfo::kInstancedLive; }
+    return InstBihInfo::kInstance;
+  }
+  // a Mesh, or a Bih that has update tables of its own -- a triangle bih, a bih with Instance or live items -- which emit_bih has made
+  // by the time a parent asks (an item is emitted before its kind is looked at).  A bih of spheres, say, never changes: static.
+  bool can_move(int id) const { return G.at(id).kind == K_MESH || (G.at(id).kind == K_BIH && movable_bihs.count(id) != 0); }
+  std::set<int> movable_bihs;
   struct InstItem { int inst, bih; uint32_t item; };
   std::vector<InstItem> inst_items;  // every (Instance, bih, item) emit_bih met: bound to F.inst_updates by mark_updatable
 
@@ -883,6 +1066,7 @@ class Flattener {
     F.meshhdr.push_back(mk4u(round_down(M.bb.lo.x), round_down(M.bb.lo.y), round_down(M.bb.lo.z), ref[0]));
     F.meshhdr.push_back(mk4(round_up(M.bb.hi.x), round_up(M.bb.hi.y), round_up(M.bb.hi.z), 0));
     U.n_nodes = nb; U.n_tris = (uint32_t)(F.mtris.size() / 3) - U.first_tri;
+    box6(M.bb, U.bound6);
     if (nb) {  // the branch nodes by tree level, deepest first: a level's children were refitted by the launch before it
       std::vector<int> depth(M.nodes.size(), 0);
       std::vector<int> order{0};  // (a parent before its children, whatever the numbering)

@@ -3,13 +3,15 @@
 // sampler and batch kernels through kernel_launch.hpp (the instances live in kernel_parts.hip, chosen by instances.hpp) and holds
 // only the light kernels: the kernel-argument self-test, the coordinate tables, tile transport, the tree builders
 // (bih_build_device.hpp), the flagship launch's cull pass (cull_kernels.hpp) and the updates of a committed Mesh (mesh_update_kernels.hpp)
-// and of a committed triangle bih (bih_update_kernels.hpp), and of committed Instances' matrices (instance_update_kernels.hpp).
+// and of a committed triangle bih (bih_update_kernels.hpp), and of committed Instances' matrices (instance_update_kernels.hpp), and the
+// refit of the bihs above an updated object (nested_update_kernels.hpp).
 #include <hip/hip_runtime.h>
 
 #include <cmath>
 #include <cstdio>
 #include <cstring>
 #include <map>
+#include <set>
 #include <mutex>
 #include <string>
 #include <type_traits>
@@ -27,6 +29,7 @@
 #include "mesh_update_kernels.hpp"
 #include "bih_update_kernels.hpp"
 #include "instance_update_kernels.hpp"
+#include "nested_update_kernels.hpp"
 
 using namespace glome;
 
@@ -180,8 +183,25 @@ struct glome_scene {
     // two words per record of the tree's span (plane-form rows), two per node slot, two per item (box-form rows), then the bound's partial
     // boxes: allocated, and filled with the commit-time rows, at the first update that touches the tree
     float4* d_ws = nullptr;
+    // the refit's tables (nested_update_kernels.hpp), allocated and filled with the workspace: six doubles of bound(item) per item, then 24
+    // doubles of matrix per item (the commit's for an instanced live item, zeros until an update names the item otherwise); the live items
+    // as (item, the object's row of the bounds table | kInstancedBit); per item the row of its live child, kNoLive for none
+    double* d_box64 = nullptr;
+    double* d_xf = nullptr;
+    const uint2* d_live_items = nullptr;
+    const uint32_t* d_item_live = nullptr;
+    uint32_t n_live = 0;
   };
   std::map<int, InstBih> ibihs;
+  // glome_scene_nested_updates: the switch; every Mesh, triangle bih and table-holding bih has a row of six doubles in d_live, its fp64
+  // bound (live_bound0: the commit's, what the table is filled with when the switch is first turned on); d_live_part: the partial boxes
+  // of a bound's first stage; stale: the bihs whose planes and box no longer match an object below them
+  bool nested_on = false;
+  std::map<int, uint32_t> live_slot;
+  std::vector<double> live_bound0;
+  double* d_live = nullptr;
+  double* d_live_part = nullptr;
+  std::set<int> stale;
   // an update's own tables (which matrix goes to which slot / item) travel through pinned buffers, so that the device form stays
   // asynchronous: a small ring, a buffer reused once the copy out of it has run.  The ring protects the PINNED side only: the one device
   // table d_inst_rows is rewritten by every call, which is safe because a call's copy into it is ordered, on the stream, after the
@@ -574,6 +594,10 @@ glome_scene* glome_scene_commit(glome_ctx* ctx, glome_sb* sb, int32_t root) {
     m.info = std::move(B);
   }
   for (InstanceUpdateInfo& U : F.inst_updates) { const int node = U.node; s->insts[node] = std::move(U); }
+  auto live_row = [&](int node, const double* b6) { s->live_slot[node] = (uint32_t)(s->live_bound0.size() / 6); s->live_bound0.insert(s->live_bound0.end(), b6, b6 + 6); };
+  for (auto& m : s->meshes) live_row(m.first, m.second.info.bound6);
+  for (auto& m : s->bihs) live_row(m.first, m.second.info.bound6);
+  for (auto& m : s->ibihs) live_row(m.first, m.second.info.bound6);
   return s;
 }
 void glome_scene_release(glome_scene* s) {
@@ -673,7 +697,8 @@ static int device_error_status(glome_ctx* ctx, unsigned int e) {
   if (e & kErrBadVertex) {  // (only the three updates set it; the word does not say which)
     ctx->err = "a mesh update met a vertex coordinate that is not finite: the scene's mesh is unspecified until a valid update"
                " (or a bih update, glome_scene_bih_update: then the bih is; or an Instance update, glome_scene_instance_update, met a matrix"
-               " entry that is not finite or a bih item box that reaches infinity: then those Instances and the bih that holds them are)";
+               " entry that is not finite or a bih item box that reaches infinity: then those Instances and the bih that holds them are; or a"
+               " refit, glome_scene_bih_refit, met an item box or joined box that reaches infinity: then that bih and the bihs above it are)";
     return GLOME_E_INVALID;
   }
   ctx->err = "device-side limit hit (traversal stack or CSG advance cap)";
@@ -1038,6 +1063,56 @@ int glome_inside_batch(glome_scene* s, size_t n, const float* px, const float* p
   return 0;
 }
 
+// ---- objects under a bih (nested_update_kernels.hpp): the pieces the three updates share with glome_scene_bih_refit ----
+// An updated object's fp64 bound into its row of the bounds table -- two launches on the current stream -- and the trees above it stale.
+static void nested_points_bound(glome_scene* s, int node, const double* pts_dev, uint32_t n_pts, double start, const std::vector<int>& above) {
+  glome_ctx* ctx = s->ctx;
+  const uint32_t blocks = std::min<uint32_t>((n_pts + nestupd::kFoldBlock - 1) / nestupd::kFoldBlock, (uint32_t)nestupd::kPartMaxBlocks);
+  if (blocks) hipLaunchKernelGGL(nestupd::k_nest_points_part, dim3(blocks), dim3(nestupd::kFoldBlock), 0, ctx->stream, pts_dev, n_pts, s->d_live_part);
+  hipLaunchKernelGGL(nestupd::k_nest_fold_store, dim3(1), dim3(nestupd::kFoldBlock), 0, ctx->stream, (const double*)s->d_live_part, blocks, start,
+                     s->d_live + 6 * (size_t)s->live_slot.at(node), &ctx->slot().d_counters->error);
+  s->stale.insert(above.begin(), above.end());
+}
+// A tree's workspace and tables, allocated and given the commit-time rows of all its items at the first update or refit that touches it
+// (blocking calls: nothing has read them yet, and the launches that follow are ordered after the copies).
+static int ensure_tree_ws(glome_scene* s, glome_scene::InstBih& m) {
+  glome_ctx* ctx = s->ctx;
+  if (m.d_ws) return 0;
+  const InstBihInfo& B = m.info;
+  const size_t n_items = B.rows.size() / 4, words = 2 * ((size_t)B.rec_span + B.n_slots + n_items + meshupd::kBoundMaxBlocks);
+  std::vector<float4> init(words, make_float4(0.0f, 0.0f, 0.0f, 0.0f));
+  float4* box = init.data() + 2 * ((size_t)B.rec_span + B.n_slots);
+  for (size_t j = 0; j < n_items; j++) {
+    const F4* r = &B.rows[4 * j];
+    float4* plane = init.data() + 2 * (size_t)m.info.rec_off[j];
+    plane[0] = make_float4(r[0].x, r[0].y, r[0].z, 0.0f); plane[1] = make_float4(r[1].x, r[1].y, r[1].z, 0.0f);
+    box[2 * j] = make_float4(r[2].x, r[2].y, r[2].z, 0.0f); box[2 * j + 1] = make_float4(r[3].x, r[3].y, r[3].z, 0.0f);
+  }
+  std::vector<double> d64(30 * n_items, 0.0);  // box64, then the matrices
+  std::copy(B.box64.begin(), B.box64.end(), d64.begin());
+  std::vector<uint2> live;
+  std::vector<uint32_t> item_live(n_items, nestupd::kNoLive);
+  for (size_t j = 0; j < n_items; j++) {
+    if (B.xf_at[j] >= 0) std::copy(B.live_xf.begin() + 24 * (ptrdiff_t)B.xf_at[j], B.live_xf.begin() + 24 * (ptrdiff_t)B.xf_at[j] + 24, d64.begin() + 6 * (ptrdiff_t)n_items + 24 * (ptrdiff_t)j);
+    if (B.kind[j] != InstBihInfo::kDirectLive && B.kind[j] != InstBihInfo::kInstancedLive) continue;
+    const uint32_t row = s->live_slot.at(B.live[j]);
+    live.push_back(make_uint2((uint32_t)j, row | (B.kind[j] == InstBihInfo::kInstancedLive ? nestupd::kInstancedBit : 0u)));
+    if (B.kind[j] == InstBihInfo::kInstancedLive) item_live[j] = row;
+  }
+  void *d = nullptr, *d2 = nullptr;
+  HIPCHK(ctx, hipMalloc(&d, words * sizeof(float4)));
+  s->allocs.push_back(d);
+  HIPCHK(ctx, hipMemcpy(d, init.data(), words * sizeof(float4), hipMemcpyHostToDevice));
+  HIPCHK(ctx, hipMalloc(&d2, std::max<size_t>(1, d64.size()) * sizeof(double)));
+  s->allocs.push_back(d2);
+  if (!d64.empty()) HIPCHK(ctx, hipMemcpy(d2, d64.data(), d64.size() * sizeof(double), hipMemcpyHostToDevice));
+  if ((!live.empty() && upload(s, live, &m.d_live_items)) || upload(s, item_live, &m.d_item_live)) return GLOME_E_HIP;
+  m.d_box64 = (double*)d2; m.d_xf = (double*)d2 + 6 * n_items; m.n_live = (uint32_t)live.size();
+  m.d_ws = (float4*)d;
+  m.info.rows = {}; m.info.box64 = {}; m.info.live_xf = {};
+  return 0;
+}
+
 // ---- new vertices for a committed Mesh (mesh_update_kernels.hpp) ----
 // what both forms refuse before anything is launched; *out = the mesh's tables
 static int mesh_update_check(glome_scene* s, int32_t mesh_id, const void* verts, int nv, const void* norms, int nn, glome_scene::MeshUpd** out) {
@@ -1048,7 +1123,7 @@ static int mesh_update_check(glome_scene* s, int32_t mesh_id, const void* verts,
   if (nv != U.nv) { ctx->err = "mesh update: the mesh has " + std::to_string(U.nv) + " vertices, not " + std::to_string(nv); return GLOME_E_INVALID; }
   if (nn != U.nn) { ctx->err = "mesh update: the mesh has " + std::to_string(U.nn) + " normals, not " + std::to_string(nn); return GLOME_E_INVALID; }
   if ((nv && !verts) || (nn && !norms)) { ctx->err = "mesh update: null vertex / normal array"; return GLOME_E_INVALID; }
-  if (!U.updatable) { ctx->err = "mesh update refused: " + U.why_not; return GLOME_E_INVALID; }
+  if (!(s->nested_on ? U.nested.ok : U.updatable)) { ctx->err = "mesh update refused: " + (s->nested_on ? U.nested.why_not : U.why_not); return GLOME_E_INVALID; }
   *out = &it->second;
   return 0;
 }
@@ -1095,6 +1170,8 @@ int glome_scene_mesh_update_dev(glome_scene* s, int32_t mesh_id, const double* v
     hipLaunchKernelGGL(meshupd::k_mesh_bound, dim3(blocks), dim3(meshupd::kBoundBlock), 0, st, A);
     hipLaunchKernelGGL(meshupd::k_mesh_bound_store, dim3(1), dim3(64), 0, st, (const float4*)part, blocks, (float4*)s->dev.meshhdr + 2 * (size_t)U.hdr);
   }
+  // box_of_points starts from a vertex (real infinities); a mesh of no vertices keeps box_empty
+  if (s->nested_on && !U.nested.above.empty()) nested_points_bound(s, mesh_id, verts_dev, (uint32_t)nv, nv > 0 ? __builtin_huge_val() : kInfinity, U.nested.above);
   HIPCHK(ctx, hipGetLastError());
   HIPCHK(ctx, end());
   ctx->slot().launched = true; ctx->slot().launched_on = ctx->stream;  // (a vertex that is not finite is reported at the next synchronize)
@@ -1135,7 +1212,7 @@ static int bih_update_check(glome_scene* s, int32_t bih_id, const void* pts9, in
   const BihUpdateInfo& U = it->second.info;
   if (n != U.n_items) { ctx->err = "bih update: the bih has " + std::to_string(U.n_items) + " items, not " + std::to_string(n); return GLOME_E_INVALID; }
   if (n && !pts9) { ctx->err = "bih update: null triangle array"; return GLOME_E_INVALID; }
-  if (!U.updatable) { ctx->err = "bih update refused: " + U.why_not; return GLOME_E_INVALID; }
+  if (!(s->nested_on ? U.nested.ok : U.updatable)) { ctx->err = "bih update refused: " + (s->nested_on ? U.nested.why_not : U.why_not); return GLOME_E_INVALID; }
   *out = &it->second;
   return 0;
 }
@@ -1197,6 +1274,7 @@ int glome_scene_bih_update_dev(glome_scene* s, int32_t bih_id, const double* pts
     hipLaunchKernelGGL(meshupd::k_mesh_bound, dim3(blocks), dim3(meshupd::kBoundBlock), 0, st, A);
     hipLaunchKernelGGL(bihupd::k_bih_bound_store, dim3(1), dim3(64), 0, st, (const float4*)part, blocks, (float4*)s->dev.bihhdr + 3 * (size_t)U.hdr);
   }
+  if (s->nested_on && !U.nested.above.empty()) nested_points_bound(s, bih_id, pts9_dev, 3u * (uint32_t)n, kInfinity, U.nested.above);  // (the join of the triangles' boxes, from box_empty)
   HIPCHK(ctx, hipGetLastError());
   HIPCHK(ctx, end());
   ctx->slot().launched = true; ctx->slot().launched_on = ctx->stream;  // (a coordinate that is not finite is reported at the next synchronize)
@@ -1235,7 +1313,7 @@ static int instance_update_check(glome_scene* s, const int32_t* ids, const void*
   for (int k = 0; k < n; k++) {
     auto it = s->insts.find(ids[k]);
     if (it == s->insts.end()) { ctx->err = "instance update: node " + std::to_string(ids[k]) + " is not an Instance of this scene"; return GLOME_E_INVALID; }
-    if (!it->second.updatable) { ctx->err = "instance update refused: " + it->second.why_not; return GLOME_E_INVALID; }
+    if (!(s->nested_on ? it->second.nested.ok : it->second.updatable)) { ctx->err = "instance update refused: " + (s->nested_on ? it->second.nested.why_not : it->second.why_not); return GLOME_E_INVALID; }
     out.push_back(&it->second);
   }
   std::vector<int32_t> sorted(ids, ids + n);
@@ -1277,26 +1355,7 @@ int glome_scene_instance_update_dev(glome_scene* s, const int32_t* ids, const do
   if (!stage.ev) HIPCHK(ctx, hipEventCreateWithFlags(&stage.ev, hipEventDisableTiming));
   std::copy(rows.begin(), rows.end(), stage.h);
   // the workspaces of the bihs this call refits, allocated and given the commit-time rows of all their items at their first update
-  for (auto& pb : per_bih) {
-    glome_scene::InstBih& m = s->ibihs.at(pb.first);
-    if (m.d_ws) continue;
-    const InstBihInfo& B = m.info;
-    const size_t n_items = B.rows.size() / 4, words = 2 * ((size_t)B.rec_span + B.n_slots + n_items + meshupd::kBoundMaxBlocks);
-    std::vector<float4> init(words, make_float4(0.0f, 0.0f, 0.0f, 0.0f));
-    float4* box = init.data() + 2 * ((size_t)B.rec_span + B.n_slots);
-    for (size_t j = 0; j < n_items; j++) {
-      const F4* r = &B.rows[4 * j];
-      float4* plane = init.data() + 2 * (size_t)m.info.rec_off[j];
-      plane[0] = make_float4(r[0].x, r[0].y, r[0].z, 0.0f); plane[1] = make_float4(r[1].x, r[1].y, r[1].z, 0.0f);
-      box[2 * j] = make_float4(r[2].x, r[2].y, r[2].z, 0.0f); box[2 * j + 1] = make_float4(r[3].x, r[3].y, r[3].z, 0.0f);
-    }
-    void* d = nullptr;
-    HIPCHK(ctx, hipMalloc(&d, words * sizeof(float4)));
-    s->allocs.push_back(d);
-    HIPCHK(ctx, hipMemcpy(d, init.data(), words * sizeof(float4), hipMemcpyHostToDevice));  // (nothing has read the workspace yet, and the launches below follow the copy)
-    m.d_ws = (float4*)d;
-    m.info.rows = {};
-  }
+  for (auto& pb : per_bih) if (int rc = ensure_tree_ws(s, s->ibihs.at(pb.first))) return rc;
   const uint32_t max_items = (uint32_t)ctx->prop.multiProcessorCount * 32u * 4u;
   auto grid = [&](uint32_t lanes) { return dim3(std::max<uint32_t>(1u, std::min<uint32_t>((lanes + 63u) >> 6, max_items))); };
   // one event pair per update while timing is on
@@ -1320,7 +1379,18 @@ int glome_scene_instance_update_dev(glome_scene* s, const int32_t* ids, const do
     float4* ws_node = ws_plane + 2 * (size_t)B.rec_span;
     float4* ws_box = ws_node + 2 * (size_t)B.n_slots;
     float4* part = ws_box + 2 * (size_t)n_items;
-    {
+    // A tree whose items hang on objects that move keeps its matrices and fp64 boxes ALWAYS, switch on or off, from its first update:
+    // a later refit reads an instanced item's matrix from the tree's table, whenever the Instance was last named.  So does any tree
+    // while the switch is on (its own fp64 bound feeds the tree above).  k_nest_inst_named takes a live child's bound from the bounds
+    // table once that exists, and the commit's before: until the switch has been on no object under a bih can have moved.  Every other
+    // update is what it was.
+    const bool nested = m.n_live || (s->d_live && s->nested_on);
+    if (nested) {
+      nestupd::DNamedArgs A;
+      A.xfms = xfms_dev; A.rows = s->d_inst_rows + at; A.child_bounds = m.d_bounds; A.item_live = m.d_item_live; A.bounds = s->d_live; A.xf = m.d_xf; A.rec_off = m.d_rec_off;
+      A.ws_plane = ws_plane; A.ws_box = ws_box; A.box64 = m.d_box64; A.n = n_named; A.error = err;
+      hipLaunchKernelGGL(nestupd::k_nest_inst_named, grid(n_named), dim3(64), 0, st, A);
+    } else {
       instupd::DItemArgs A;
       A.xfms = xfms_dev; A.rows = s->d_inst_rows + at; A.bounds = m.d_bounds; A.rec_off = m.d_rec_off; A.ws_plane = ws_plane; A.ws_box = ws_box; A.n = n_named; A.error = err;
       hipLaunchKernelGGL(instupd::k_inst_item_box, grid(n_named), dim3(64), 0, st, A);
@@ -1338,7 +1408,11 @@ int glome_scene_instance_update_dev(glome_scene* s, const int32_t* ids, const do
     const uint32_t blocks = std::max<uint32_t>(1u, std::min<uint32_t>((n_items + 63u) >> 6, (uint32_t)meshupd::kBoundMaxBlocks));
     hipLaunchKernelGGL(instupd::k_inst_box_fold, dim3(blocks), dim3(64), 0, st, (const float4*)ws_box, n_items, part);
     hipLaunchKernelGGL(bihupd::k_bih_bound_store, dim3(1), dim3(64), 0, st, (const float4*)part, blocks, (float4*)s->dev.bihhdr + 3 * (size_t)B.hdr);
+    if (nested && s->d_live)  // the tree's own fp64 bound: the join of its items' boxes from box_empty
+      hipLaunchKernelGGL(nestupd::k_nest_fold_store, dim3(1), dim3(nestupd::kFoldBlock), 0, st, (const double*)m.d_box64, n_items, kInfinity, s->d_live + 6 * (size_t)s->live_slot.at(pb.first), err);
   }
+  if (s->nested_on)  // the update has refitted the tree that holds the Instance: the trees above that one are stale
+    for (const InstanceUpdateInfo* u : U) for (int a : u->nested.above) if (a != u->bih) s->stale.insert(a);
   HIPCHK(ctx, hipGetLastError());
   if (e1) HIPCHK(ctx, hipEventRecord(e1, st));
   ctx->slot().launched = true; ctx->slot().launched_on = ctx->stream;  // (a matrix entry that is not finite is reported at the next synchronize)
@@ -1380,6 +1454,126 @@ int glome_scene_instance_update(glome_scene* s, const int32_t* ids, const double
   if (!dx) { ctx->err = "staging allocation failed"; return GLOME_E_HIP; }
   if (gpu_ms) HIPCHK(ctx, hipEventRecord(ctx->ev0, ctx->stream));
   if (int rc = glome_scene_instance_update_dev(s, ids, dx, n)) return rc;
+  if (gpu_ms) HIPCHK(ctx, hipEventRecord(ctx->ev1, ctx->stream));
+  HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+  if (gpu_ms) HIPCHK(ctx, hipEventElapsedTime(gpu_ms, ctx->ev0, ctx->ev1));
+  return check_device_error(ctx);
+}
+
+// ---- the bihs above an updated object, refitted one tree per call (nested_update_kernels.hpp) ----
+static const NestedAnswer* nested_answer_of(const glome_scene* s, int32_t node) {
+  { auto it = s->meshes.find(node); if (it != s->meshes.end()) return &it->second.info.nested; }
+  { auto it = s->bihs.find(node); if (it != s->bihs.end()) return &it->second.info.nested; }
+  { auto it = s->insts.find(node); if (it != s->insts.end()) return &it->second.nested; }
+  { auto it = s->ibihs.find(node); if (it != s->ibihs.end()) return &it->second.info.nested; }
+  return nullptr;
+}
+int32_t glome_scene_bihs_above(const glome_scene* s, int32_t node_id, int32_t* out, int32_t cap) {
+  if (!s) return GLOME_E_INVALID;
+  const NestedAnswer* A = nested_answer_of(s, node_id);
+  if (!A) { s->ctx->err = "bihs_above: node " + std::to_string(node_id) + " is not a Mesh, a triangle bih, an Instance or a refittable bih of this scene"; return GLOME_E_INVALID; }
+  if (!A->ok) { s->ctx->err = "bihs_above: " + A->why_not; return GLOME_E_INVALID; }
+  for (size_t k = 0; k < A->above.size() && (int32_t)k < cap && out; k++) out[k] = A->above[k];
+  return (int32_t)A->above.size();
+}
+int32_t glome_scene_stale_bihs(const glome_scene* s, int32_t* out, int32_t cap) {
+  if (!s) return GLOME_E_INVALID;
+  // a tree below another has every tree above that one above itself, and that one: more trees above, so it comes first
+  std::vector<int> order(s->stale.begin(), s->stale.end());
+  std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return s->ibihs.at(a).info.nested.above.size() > s->ibihs.at(b).info.nested.above.size(); });
+  for (size_t k = 0; k < order.size() && (int32_t)k < cap && out; k++) out[k] = order[k];
+  return (int32_t)order.size();
+}
+int glome_scene_nested_updates(glome_scene* s, int on) {
+  if (!s) return GLOME_E_INVALID;
+  glome_ctx* ctx = s->ctx;
+  if (!on) {
+    if (!s->stale.empty()) { ctx->err = "nested updates: bih " + std::to_string(*s->stale.begin()) + " is stale: refit the stale bihs before turning the switch off"; return GLOME_E_INVALID; }
+    s->nested_on = false;
+    return 0;
+  }
+  if (!s->d_live) {  // the bounds table with the commit's values, and the partial boxes of a bound's first stage: kept until glome_scene_release
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    void *d = nullptr, *p = nullptr;
+    HIPCHK(ctx, hipMalloc(&d, std::max<size_t>(6, s->live_bound0.size()) * sizeof(double)));
+    s->allocs.push_back(d);
+    HIPCHK(ctx, hipMalloc(&p, 6 * (size_t)nestupd::kPartMaxBlocks * sizeof(double)));
+    s->allocs.push_back(p);
+    if (!s->live_bound0.empty()) HIPCHK(ctx, hipMemcpy(d, s->live_bound0.data(), s->live_bound0.size() * sizeof(double), hipMemcpyHostToDevice));
+    s->d_live = (double*)d; s->d_live_part = (double*)p;
+  }
+  s->nested_on = true;
+  return 0;
+}
+// what both forms refuse before anything is launched
+static int bih_refit_check(glome_scene* s, int32_t bih_id, glome_scene::InstBih** out) {
+  glome_ctx* ctx = s->ctx;
+  auto it = s->ibihs.find(bih_id);
+  if (it == s->ibihs.end()) { ctx->err = "bih refit: node " + std::to_string(bih_id) + " is not a bih of this scene that holds a Mesh, a Bih or an Instance as an item"; return GLOME_E_INVALID; }
+  if (!s->nested_on) { ctx->err = "bih refit refused: nested updates are off (glome_scene_nested_updates)"; return GLOME_E_INVALID; }
+  for (int below : it->second.info.live)
+    if (below >= 0 && s->stale.count(below)) { ctx->err = "bih refit refused: bih " + std::to_string(below) + " below bih " + std::to_string(bih_id) + " is stale: refit bih " + std::to_string(below) + " first"; return GLOME_E_INVALID; }
+  *out = &it->second;
+  return 0;
+}
+int glome_scene_bih_refit_dev(glome_scene* s, int32_t bih_id) {
+  if (!s) return GLOME_E_INVALID;
+  glome_ctx* ctx = s->ctx;
+  glome_scene::InstBih* mp = nullptr;
+  if (int rc = bih_refit_check(s, bih_id, &mp)) return rc;
+  glome_scene::InstBih& m = *mp;
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  if (int rc = ensure_tree_ws(s, m)) return rc;
+  hipStream_t st = ctx->stream;
+  const InstBihInfo& B = m.info;
+  const uint32_t max_items = (uint32_t)ctx->prop.multiProcessorCount * 32u * 4u, n_items = (uint32_t)B.kind.size();
+  auto grid = [&](uint32_t lanes) { return dim3(std::max<uint32_t>(1u, std::min<uint32_t>((lanes + 63u) >> 6, max_items))); };
+  hipEvent_t e0 = nullptr, e1 = nullptr;
+  if (ctx->timing && launch_events(ctx, e0, e1)) HIPCHK(ctx, hipEventRecord(e0, st)); else e1 = nullptr;
+  unsigned int* err = &ctx->slot().d_counters->error;
+  float4* ws_plane = m.d_ws;
+  float4* ws_node = ws_plane + 2 * (size_t)B.rec_span;
+  float4* ws_box = ws_node + 2 * (size_t)B.n_slots;
+  float4* part = ws_box + 2 * (size_t)n_items;
+  if (m.n_live) {  // every live item, changed or not: its rows from its object's bound as it stands
+    nestupd::DItemsArgs A;
+    A.live = m.d_live_items; A.bounds = s->d_live; A.xf = m.d_xf; A.rec_off = m.d_rec_off; A.ws_plane = ws_plane; A.ws_box = ws_box; A.box64 = m.d_box64; A.n = m.n_live; A.error = err;
+    hipLaunchKernelGGL(nestupd::k_nest_item_rows, grid(m.n_live), dim3(64), 0, st, A);
+  }
+  {  // the planes, a launch per tree level, deepest first, then the header's box: the Instance update's own launches
+    bihupd::DLevelArgs A;
+    A.nodes = m.d_levels; A.bihnodes = (float4*)s->dev.bihnodes; A.pknodes = nullptr;
+    A.ws_tri = ws_plane; A.ws_node = ws_node; A.first_rec = B.first_rec; A.first_slot = B.first_slot;
+    for (size_t l = 0; l + 1 < B.level_off.size(); l++) {
+      const uint32_t width = B.level_off[l + 1] - B.level_off[l];
+      hipLaunchKernelGGL(bihupd::k_bih_level, grid(width), dim3(64), 0, st, A, B.level_off[l], width);
+    }
+  }
+  const uint32_t blocks = std::max<uint32_t>(1u, std::min<uint32_t>((n_items + 63u) >> 6, (uint32_t)meshupd::kBoundMaxBlocks));
+  hipLaunchKernelGGL(instupd::k_inst_box_fold, dim3(blocks), dim3(64), 0, st, (const float4*)ws_box, n_items, part);
+  hipLaunchKernelGGL(bihupd::k_bih_bound_store, dim3(1), dim3(64), 0, st, (const float4*)part, blocks, (float4*)s->dev.bihhdr + 3 * (size_t)B.hdr);
+  hipLaunchKernelGGL(nestupd::k_nest_fold_store, dim3(1), dim3(nestupd::kFoldBlock), 0, st, (const double*)m.d_box64, n_items, kInfinity, s->d_live + 6 * (size_t)s->live_slot.at(bih_id), err);
+  HIPCHK(ctx, hipGetLastError());
+  if (e1) HIPCHK(ctx, hipEventRecord(e1, st));
+  s->stale.erase(bih_id);
+  ctx->slot().launched = true; ctx->slot().launched_on = ctx->stream;  // (a box that reaches infinity is reported at the next synchronize)
+  return 0;
+}
+int glome_scene_bih_refit(glome_scene* s, int32_t bih_id, float* gpu_ms) {
+  if (!s) return GLOME_E_INVALID;
+  glome_ctx* ctx = s->ctx;
+  if (gpu_ms) *gpu_ms = 0;
+  glome_scene::InstBih* m = nullptr;
+  if (int rc = bih_refit_check(s, bih_id, &m)) return rc;
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  // every slot of the context may have a launch in flight that reads the pools about to be written
+  HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+  for (auto& sl : ctx->slots)
+    if (sl.launched_on && sl.launched_on != ctx->stream) (void)hipStreamSynchronize(sl.launched_on);
+  (void)hipGetLastError();  // (a stream its owner has destroyed since must not be this call's error: other_slots_busy)
+  if (int rc = ensure_tree_ws(s, *m)) return rc;  // (outside the timed span)
+  if (gpu_ms) HIPCHK(ctx, hipEventRecord(ctx->ev0, ctx->stream));
+  if (int rc = glome_scene_bih_refit_dev(s, bih_id)) return rc;
   if (gpu_ms) HIPCHK(ctx, hipEventRecord(ctx->ev1, ctx->stream));
   HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
   if (gpu_ms) HIPCHK(ctx, hipEventElapsedTime(gpu_ms, ctx->ev0, ctx->ev1));

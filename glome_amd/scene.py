@@ -158,3 +158,42 @@ class SceneDesc:
                 nmap.append(getattr(backend, name)(*args))
         updates_before(len(self.ops))
         return nmap, mmap
+
+
+class DescScene:
+    """A description committed to the GPU, addressed by the DESCRIPTION's node ids: commit_desc(ctx, sd) replays sd into a product
+    builder and commits it; the update calls below map a SceneDesc id to the builder's id and back.  With nested=True (the default) the
+    switch of glome_scene_nested_updates is on, so an object under bihs can be updated and refit_above(node) then refits the trees above
+    it, inner trees first."""
+
+    def __init__(self, scene, builder, nmap):
+        self.scene, self.builder, self.nmap = scene, builder, list(nmap)
+        self.back = {b: k for k, b in enumerate(self.nmap)}
+
+    def mesh_update(self, node, verts, norms=None): return self.scene.mesh_update(self.nmap[node], verts, norms)
+    def bih_update(self, node, pts9): return self.scene.bih_update(self.nmap[node], pts9)
+    def instance_update(self, nodes, xfms): return self.scene.instance_update([self.nmap[n] for n in nodes], xfms)
+    def bih_refit(self, node): return self.scene.bih_refit(self.nmap[node])
+
+    def _ids(self, builder_ids):
+        """builder ids as description ids (None for a bih made inside the builder, by bih_tolist say: it has none)"""
+        return [self.back.get(b) for b in builder_ids]
+
+    def bihs_above(self, node): return self._ids(self.scene.bihs_above(self.nmap[node]))
+    def stale_bihs(self): return self._ids(self.scene.stale_bihs())
+
+    def refit_above(self, node):
+        """refit every bih above `node`, inner trees first; returns the summed device milliseconds"""
+        return self.scene.refit_above(self.nmap[node])
+
+    def release(self): self.scene.release()
+
+
+def commit_desc(ctx, sd, nested=True):
+    from . import api
+    b = api.Builder()
+    nmap, _ = sd.replay(b)
+    sc = ctx.commit(b, nmap[sd.root])
+    if nested:
+        sc.nested_updates(True)
+    return DescScene(sc, b, nmap)

@@ -145,6 +145,19 @@ int32_t glome_sb_bih_items(glome_sb*, int32_t bih_id, int32_t* out, int32_t cap)
  * box would be infinite, as glome_sb_bih refuses it) with a message naming the node, and nothing is touched.  Host only; the
  * specification of glome_scene_instance_update. */
 int glome_sb_instance_set_transforms(glome_sb*, const int32_t* ids, const double* xfms, int n);
+/* What `bih` derives from its items' bounds, made again for the tree as it stands: every branch's planes and the tree's box from
+ * glome_sb_bound of the items' current state -- the last step of glome_sb_bih_set_triangles and glome_sb_instance_set_transforms, on its
+ * own.  Topology stays.  With it the host spells the nested case: glome_sb_mesh_set_vertices / _bih_set_triangles /
+ * _instance_set_transforms, then glome_sb_bih_refit of every bih above the object, inner trees first (glome_sb_bihs_above gives that
+ * order).  That sequence is the specification of glome_scene_bih_refit.  GLOME_E_INVALID for an id that is not a Bih; GLOME_E_SCENE with
+ * the constructor's "bih: infinite bounding box" when the joined box reaches +-1e6, and nothing is touched then.  Host only. */
+int glome_sb_bih_refit(glome_sb*, int32_t bih_id);
+/* The bihs above node_id -- a Mesh, a bih of plain triangles, an Instance, or a bih that holds a Mesh, a Bih or an Instance as an item --
+ * in the scene under `root`: every Bih on any path from root (or from a Warp material's frame / scene) down to the node, in an order in
+ * which they can be refitted, a tree after every tree below it.  Returns their number (0: none) and fills out[0 .. min(number, cap)).
+ * Runs the flattener's marking, no GPU.  GLOME_E_INVALID, the reason in glome_sb_last_error, when an update of the node would be refused
+ * even with glome_scene_nested_updates on (the rule is stated there). */
+int32_t glome_sb_bihs_above(glome_sb*, int32_t root, int32_t node_id, int32_t* out, int32_t cap);
 int32_t glome_sb_tex(glome_sb*, int32_t id, int32_t material);                                   /* Tex.hs:33-34 */
 int32_t glome_sb_tag(glome_sb*, int32_t id);                                                     /* Tex.hs:38-39 (tags feed picking only) */
 int32_t glome_sb_noshadow(glome_sb*, int32_t id);                                                /* Tex.hs:43 */
@@ -325,6 +338,50 @@ int glome_scene_bih_update_dev(glome_scene*, int32_t bih_id, const double* pts9_
  * stream once, to grow its table. */
 int glome_scene_instance_update(glome_scene*, const int32_t* ids, const double* xfms, int n, float* gpu_ms);
 int glome_scene_instance_update_dev(glome_scene*, const int32_t* ids, const double* xfms_dev, int n);
+
+/* ---- update objects under a bih: the chain of bihs above refitted on the GPU, one call per tree ----
+ * The three updates above refuse an object as soon as a bih lies above it (a second one for an Instance): that tree's planes and box
+ * were built from the object's bound.  glome_scene_nested_updates(scene, 1) lifts that: the updates then accept an object X -- a Mesh, a
+ * bih of plain triangles, an Instance that is an item of a bih -- when on EVERY path from the committed root (or a Warp material's frame /
+ * scene) down to X every bih B on the path holds, on that path, an item that is LIVE over the next thing down (X, or the next bih): the
+ * item, Tex / Tag / NoShadow / OnlyShadow wrappers peeled off, is that thing itself (a direct item) or an Instance whose child, peeled
+ * again, is that thing (an instanced item).  For an Instance X its own bih holds X as the item.  Still refused, the message naming the
+ * node in the way: a list, a CSG node, a Bound / InnerBound or a second Instance between two trees, an Instance deeper inside an item, a
+ * triangle the scene also reaches outside its bih, an Instance that is an item more than once.  One object under several items or
+ * several bihs is fine (a mesh instanced five times, a bih shared by two outer trees).  With the switch off -- the default -- every call
+ * accepts and refuses exactly what it did, with the same messages.
+ *   An accepted update of an object with bihs above it also leaves the object's fp64 bound on the device (Mesh: min(p - delta) / max(p +
+ * delta) over all vertices; triangle bih: the same from +-1e6 over all item vertices; a refitted bih: the join of its items' fp64 boxes
+ * from +-1e6) and marks every bih above as STALE (glome_scene_stale_bihs; an Instance update refits the bih that holds the Instance itself,
+ * so it marks the trees above that one).  The folds are fp64 min / max of finite values, exact in any order; a component that folds to
+ * zero is stored as +0 whenever an operand was +0 (p - delta and p + delta never give -0), and a refit stores what it is given.
+ * glome_scene_instance_update also stores the named Instances' 24 doubles in a device table the refits read.
+ *   glome_scene_bih_refit(scene, B) makes again, for ALL live items of B (not only the changed ones: the simpler choice, an item is 200
+ * bytes), the item's plane-form and box-form rows and its fp64 box from the object's bound -- an instanced item's through its matrix,
+ * eight corners, glome_scene_instance_update's arithmetic --, then every branch's planes, the header's box and B's own fp64 bound, and
+ * clears B's stale mark.  Call it once per tree, inner trees first: the order of glome_scene_bihs_above.  After the last one the scene is,
+ * bit for bit, the scene glome_scene_commit would have made after the builder calls glome_sb_bih_refit documents.
+ *   Refused with GLOME_E_INVALID before anything is launched: B is not a bih of this scene that holds a Mesh, Bih or Instance item, the
+ * switch is off, or a tree below B is stale ("refit bih N first").  Turning the switch off while a tree is stale is refused too.  An item
+ * box or joined box that reaches +-1e6 is found on the device and reported by the next glome_ctx_synchronize, through the updates' error
+ * word (the message names this call too); the tree is then unspecified, never out of bounds, until a valid update and refit.
+ *   glome_scene_bih_refit waits for every launch of the context (all slots) and returns when the refit is complete, *gpu_ms (may be NULL)
+ * the HIP-event time of its kernels; glome_scene_bih_refit_dev is asynchronous on the current stream and slot, ordered after the updates
+ * enqueued before it, and takes part in glome_ctx_timing_begin / _end (one event pair per call).  Turning the switch on allocates and
+ * fills the bounds table, and the first refit or Instance update of a tree allocates and fills its workspace (32 bytes per record the
+ * tree spans, per node and per item, and 240 bytes of fp64 per item), both with blocking calls, kept until glome_scene_release.
+ *   The _dev forms of two updates of objects under bihs, or of two refits, must not run at the same time on different streams / slots of one
+ * scene: a bound's partial boxes pass through one buffer per scene, as an Instance update's rows do.  Order them on one stream, or with
+ * events; the host forms wait for every slot and need nothing.
+ *   Rendering while a bih is stale is allowed: the picture is unspecified but never out of bounds -- an update writes planes, boxes and
+ * records, never a reference.
+ * glome_scene_bihs_above: glome_sb_bihs_above for the committed root.  glome_scene_stale_bihs: the stale trees, in an order in which they
+ * can be refitted; both return the number and fill out[0 .. min(number, cap)). */
+int glome_scene_nested_updates(glome_scene*, int on);              /* default 0 */
+int glome_scene_bih_refit(glome_scene*, int32_t bih_id, float* gpu_ms);
+int glome_scene_bih_refit_dev(glome_scene*, int32_t bih_id);       /* asynchronous on the current stream / slot */
+int32_t glome_scene_bihs_above(const glome_scene*, int32_t node_id, int32_t* out, int32_t cap);
+int32_t glome_scene_stale_bihs(const glome_scene*, int32_t* out, int32_t cap);
 
 /* ---- per-ray seams (Solid.hs:146-166), host buffers ---- */
 /* closest hit: t < 0 marks a miss (RayMiss), and then prim is -1, tex8 all -1 and the normal UNSPECIFIED (whatever the traversal
