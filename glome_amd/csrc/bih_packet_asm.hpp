@@ -417,7 +417,10 @@ constexpr uint32_t PKREF_LEAF = 3u;  // low bits of a reference in the walk's ow
   "  s_cbranch_vccz L_nf" SET TAG "_%=\n"                                                               \
   "  s_cmp_ge_u32 m0, %[cap]\n"                                                                         \
   "  s_cbranch_scc1 L_slow_%=\n"                                                                        \
-  "  v_max_f32 " TF ", " TF ", %[near]\n"   /* the far child's interval starts here */                  \
+  /* the far child's interval starts at `fmax t2 near`; a NaN near (bbclip_ub's, Q1) must stay NaN, which v_max_f32 dropped.  gfx950's IEEE */ \
+  /* maximum returns NaN when ANY operand is one: for a NaN near that is bih_tri_packet's gmaxf(t2, near); for a NaN t2 it is NaN where gmaxf   */ \
+  /* gives near -- a lane with a NaN t2 failed `t2 < far` above, is not in the pushed entry's mask, and its value is never read             */ \
+  "  v_maximum3_f32 " TF ", " TF ", %[near], %[near]\n"                                                  \
   "  v_writelane_b32 %[ur], " FC ", m0\n"   /* the uniform part of the entry: lane `sp` of ur / ulo / uhi */ \
   "  v_writelane_b32 %[ulo], vcc_lo, m0\n"                                                              \
   "  v_writelane_b32 %[uhi], vcc_hi, m0\n"                                                              \

@@ -85,7 +85,6 @@ typedef unsigned long long LaneMask;  // one bit per lane of the wave
 // min / max of values that are known not to be NaN where it matters: one instruction, without the quieting moves the
 // compiler puts in front of fminf / fmaxf on values it cannot see the origin of
 GD float min_nn(float a, float b) { float r; asm("v_min_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b)); return r; }
-GD float max_nn(float a, float b) { float r; asm("v_max_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b)); return r; }
 GD LaneMask wave_ballot(bool p) { return __builtin_amdgcn_ballot_w64(p); }
 GD bool wave_any(bool p) { return __ballot(p) != 0ull; }
 GD bool lane_of(LaneMask m) { return __builtin_amdgcn_inverse_ballot_w64(m); }  // this lane's bit (m is wave-uniform)
@@ -821,7 +820,10 @@ GD PacketResult bih_tri_packet(const F4* nodes, const F4* tris, uint32_t ref, ui
       // (an empty leaf child has its plane at -+inf, flatten.hpp: both tests fail for it, it is never entered)
       const LaneMask m1 = wave_ballot(nearv < t1) & am;
       const LaneMask m2 = wave_ballot(t2 < farv) & am;
-      const float f1 = min_nn(t1, farv), n2 = max_nn(t2, nearv);
+      // n2: the reference's `fmax t2 near` as the per-lane walks take it (gmaxf, a compare-select): a NaN `near` -- bbclip_ub's for a direction
+      // component of -0 with the origin exactly on that face of the bounds, Q1 -- stays NaN, and such a lane enters no near child ever after
+      // (bih_tri, Bih.hs:332-368).  v_max_f32 returned t2 for it, and from the first far child on the packet went where the reference does not.
+      const float f1 = min_nn(t1, farv), n2 = gmaxf(t2, nearv);
       if ((m1 != 0) & (m2 != 0)) { stk.push_wave(sp, c2, m2, n2, farv); sp++; }  // depth <= capacity (validated at commit)
       const bool g1 = m1 != 0;
       ref = g1 ? c1 : c2;
@@ -920,7 +922,10 @@ GD PacketResult bih_tri_packet_hw(const F4* nodes, uint32_t nbytes, const float*
       const uint32_t c1 = fwd ? left : right, c2 = fwd ? right : left;
       const float t1 = fwd ? dl : dr, t2 = fwd ? dr : dl;
       const LaneMask m1 = wave_ballot(nearv < t1) & am, m2 = wave_ballot(t2 < farv) & am;
-      const float f1 = min_nn(t1, farv), n2 = max_nn(t2, nearv);
+      // n2: the reference's `fmax t2 near` as the per-lane walks take it (gmaxf, a compare-select): a NaN `near` -- bbclip_ub's for a direction
+      // component of -0 with the origin exactly on that face of the bounds, Q1 -- stays NaN, and such a lane enters no near child ever after
+      // (bih_tri, Bih.hs:332-368).  v_max_f32 returned t2 for it, and from the first far child on the packet went where the reference does not.
+      const float f1 = min_nn(t1, farv), n2 = gmaxf(t2, nearv);
       if ((m1 != 0) & (m2 != 0)) { stk.push_dump(sp, c2, m2, n2, farv); sp++; }  // depth <= capacity (validated at commit)
       const bool g1 = m1 != 0;
       ref = g1 ? c1 : c2;
@@ -979,8 +984,8 @@ GD bool bih_tri_wave(const DScene& S, uint32_t hdr, const Ray& r, float d, bool 
   // once per pattern with the other lanes switched off (a lane takes part in exactly one walk).
   const uint32_t oct = (rcp.x > 0 ? 1u : 0u) | (rcp.y > 0 ? 2u : 0u) | (rcp.z > 0 ? 4u : 0u);
   // `am`: the lanes whose ray has a non-empty interval in the current node.  Their (near, far) are live; the other
-  // lanes' are don't-cares, so no sentinel values are needed and plain min / max serve (a NaN plane distance only
-  // arises on a lane that fails the activity test of that child).
+  // lanes' are don't-cares, so no sentinel values are needed and a plain min serves for `far` (a NaN plane distance only
+  // arises on a lane that fails the activity test of that child); `near` may be NaN from the root on and keeps it (gmaxf).
   LaneMask todo = wave_ballot(bih_root_enters(valid, nearv, farv));
   bool occ = false;
   while (todo != 0) {

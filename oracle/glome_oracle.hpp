@@ -48,6 +48,26 @@ struct Counters {
 };
 inline Counters& tls_counters() { static thread_local Counters c; return c; }
 
+// The reference advances a ray through a CSG solid by recursion (rayint_advance, Solid.hs:85-91) and nothing bounds it: an advance that
+// is NaN (a slab's 0 * inf inside an Intersection, say) never moves the ray, and the recursion ends with the thread's stack.  This
+// restatement counts the nesting instead.  Past kAdvanceNesting it stops: the ray misses and is marked DIVERGED, and no other answer
+// changes.  The bound is a condition, not a tuning value:
+//   above what any scene of the suite needs -- deepest nesting measured (glo_advance_nesting_max; frames at maxdepth 3 on one thread and 12,000
+//     random rays, double and float alike): 56 over test_csg_items_of_the_flat_tier_advance_without_a_cap's scenes (the fuzz scene
+//     zoo.random_flat(12094) under its rig; the 31-operand Intersection takes 6), 46 over the fuzz scenes (zoo.random_composites and
+//     zoo.random_flat under zoo.random_rig, seeds 1-40, 3199, 5059, 5069, 12094), 6 over the scenes of zoo.ALL;
+//   below what a thread's stack holds -- the crash ray of tests/test_oracle_kat.py nests to the bound and returns on a thread with a 2 MiB
+//     stack, double and float (it does not with 1 MiB: between 0.5 and 1 KiB a nesting); a thread gets 8 MiB, the render threads too.
+constexpr int kAdvanceNesting = 2048;
+struct AdvanceState { int depth = 0, deepest = 0; bool diverged = false; };
+inline AdvanceState& tls_advance() { static thread_local AdvanceState a; return a; }
+struct AdvanceScope {  // one nesting of rayint_advance; ok() is false past the bound (and the ray is marked)
+  AdvanceState& a;
+  AdvanceScope() : a(tls_advance()) { a.depth++; if (a.depth > a.deepest) a.deepest = a.depth; }
+  ~AdvanceScope() { a.depth--; }
+  bool ok() const { if (a.depth > kAdvanceNesting) { a.diverged = true; return false; } return true; }
+};
+
 // ---------------------------------------------------------------------------------------
 // Vec.hs
 // ---------------------------------------------------------------------------------------
@@ -477,6 +497,8 @@ template <class R> SP<R> make_instance(SP<R> s, const Xfm<R>& x, int uid) {
 
 // rayint_advance, Solid.hs:85-91
 template <class R> Rayint<R> rayint_advance(const Solid<R>& s, const Ray<R>& r, R d, const TexList& t, R adv) {
+  AdvanceScope nest;
+  if (!nest.ok()) return {};
   R a = adv + Math<R>::delta();
   Rayint<R> h = s.rayint(ray_move(r, a), d - a, t);
   if (!h.hit) return h;
@@ -863,6 +885,8 @@ template <class R> struct Intersection : Solid<R> {
     return advance_from(from, r, d, t, hs.depth);
   }
   Rayint<R> advance_from(size_t from, const Ray<R>& r, R d, const TexList& t, R adv) const {  // Solid.hs:85-91 on (Intersection slds)
+    AdvanceScope nest;
+    if (!nest.ok()) return {};
     R a = adv + Math<R>::delta();
     Rayint<R> h = rayint_from(from, ray_move(r, a), d - a, t);
     if (!h.hit) return h;

@@ -14,6 +14,7 @@ to be right.  Every function cites the reference file:line.
 Backend protocol: the constructor names of glome_amd/scene.py SceneDesc.replay().
 """
 import math
+import sys
 
 INF = 1000000.0  # infinity, Vec.hs:12-14
 DELTA = 0.0001   # delta, Vec.hs:40
@@ -532,10 +533,38 @@ def noise(p):  # :93-108
 def perlin(v): return (noise(v) + 1) * 0.5  # :110-117
 
 
+ADVANCE_NESTING = 2048  # kAdvanceNesting of glome_oracle.hpp (the measurements are written there): past it the ray misses and is marked
+
+
+class _Advance:
+    depth = 0          # nestings of rayint_advance the interpreter is in
+    diverged = False   # set when a ray passed the bound; the caller clears it before a ray and reads it after
+
+
 def rayint_advance(s, o, d, dist, texs, adv):  # Solid.hs:85-91
-    a = adv + DELTA
-    h = s.rayint(vscaleadd(o, d, a), d, dist - a, texs)
-    return None if h is None else (h[0] + a,) + h[1:]
+    _Advance.depth += 1
+    outermost = _Advance.depth == 1
+    if outermost:  # a nesting takes a few interpreter frames: room for ADVANCE_NESTING of them while this ray is advanced, the old limit after it
+        limit = sys.getrecursionlimit()
+        sys.setrecursionlimit(max(limit, 8 * ADVANCE_NESTING + limit))
+    try:
+        if _Advance.depth > ADVANCE_NESTING:
+            _Advance.diverged = True
+            return None
+        a = adv + DELTA
+        h = s.rayint(vscaleadd(o, d, a), d, dist - a, texs)
+        return None if h is None else (h[0] + a,) + h[1:]
+    finally:
+        _Advance.depth -= 1
+        if outermost:
+            sys.setrecursionlimit(limit)
+
+
+def rayint_flagged(s, o, d, dist, texs=()):
+    """(rayint's answer, diverged): the second is True when rayint_advance passed ADVANCE_NESTING on this ray"""
+    _Advance.diverged = False
+    h = s.rayint(o, d, dist, texs)
+    return h, _Advance.diverged
 
 
 class Difference(Solid):  # Csg.hs

@@ -54,6 +54,7 @@ struct IOracle {
   virtual int bound(int id, double* out6) = 0;
   virtual long bih_dump(int id, long cap, double* lsplit, double* rsplit, int* axis, int* nleaf, int* leaf_prims, long cap_prims) = 0;
   virtual int kind_name(int id, char* buf, int cap) = 0;
+  std::vector<uint8_t> diverged;  // per ray of the last rayint_batch / shadow_batch: rayint_advance passed kAdvanceNesting (glome_oracle.hpp)
 };
 
 template <class R> struct Impl : IOracle {
@@ -251,9 +252,12 @@ template <class R> struct Impl : IOracle {
   }
   int rayint_batch(int root, size_t n, const double* const* od, const double* tmax, double* t, int* prim, double* pos, double* nrm, int* tex0, int* ntex) override {
     SP<R> s = get(root);
+    diverged.assign(n, 0);
     for (size_t i = 0; i < n; i++) {
       Ray<R> r{{R(od[0][i]), R(od[1][i]), R(od[2][i])}, {R(od[3][i]), R(od[4][i]), R(od[5][i])}};
+      tls_advance().diverged = false;
       Rayint<R> h = s->rayint(r, R(tmax[i]), TexList());
+      diverged[i] = tls_advance().diverged ? 1 : 0;
       t[i] = h.hit ? double(h.depth) : -1.0;
       if (prim) prim[i] = h.hit ? h.prim : -1;
       if (pos) { pos[3 * i] = h.pos.x; pos[3 * i + 1] = h.pos.y; pos[3 * i + 2] = h.pos.z; }
@@ -265,9 +269,12 @@ template <class R> struct Impl : IOracle {
   }
   int shadow_batch(int root, size_t n, const double* const* od, const double* tmax, uint8_t* occ) override {
     SP<R> s = get(root);
+    diverged.assign(n, 0);
     for (size_t i = 0; i < n; i++) {
       Ray<R> r{{R(od[0][i]), R(od[1][i]), R(od[2][i])}, {R(od[3][i]), R(od[4][i]), R(od[5][i])}};
+      tls_advance().diverged = false;
       occ[i] = s->shadow(r, R(tmax[i])) ? 1 : 0;
+      diverged[i] = tls_advance().diverged ? 1 : 0;
     }
     return 0;
   }
@@ -385,6 +392,16 @@ int glo_inside_batch(void* h, int root, size_t n, const double* px, const double
   const double* p[3] = {px, py, pz};
   return guard(h, [&](IOracle* o) { return o->inside_batch(root, n, p, in); });
 }
+// the rays of the last glo_rayint_batch / glo_shadow_batch on this handle whose advance recursion passed kAdvanceNesting: returns their number
+long glo_last_diverged(void* h, uint8_t* out, size_t n) {
+  IOracle* o = (IOracle*)h;
+  long k = 0;
+  for (size_t i = 0; i < n; i++) { out[i] = i < o->diverged.size() ? o->diverged[i] : 0; k += out[i]; }
+  return k;
+}
+int glo_advance_nesting_bound() { return kAdvanceNesting; }
+// the deepest nesting of rayint_advance on the CALLING thread since the last reset (a measurement for the comment beside kAdvanceNesting)
+int glo_advance_nesting_max(int reset) { int d = tls_advance().deepest; if (reset) tls_advance().deepest = 0; return d; }
 // params: width,height,mode,blocksize,maxdepth,fog,tile_first,tile_stride ; thresholds[4]
 int glo_render(void* h, const int* iparams, const double* thresholds, double* out5, uint32_t* packed, int nthreads, int max_tiles, uint64_t* counters) {
   RenderParams P;

@@ -32,6 +32,7 @@ def lib():
         _lib.glo_last_error.restype = C.c_char_p
         _lib.glo_bih_dump.restype = C.c_long
         _lib.glo_rgbf.restype = C.c_uint32
+        _lib.glo_last_diverged.restype = C.c_long
     return _lib
 
 
@@ -169,7 +170,14 @@ class Oracle:
         tex = np.zeros((n, 8), np.int32); ntex = np.zeros(n, np.int32)
         self._chk(self.L.glo_rayint_batch(self.h, C.c_int(int(root)), C.c_size_t(n), *[_dp(c) for c in cols], _dp(tm), _dp(t), prim.ctypes.data_as(c_ip),
                                           _dp(pos), _dp(nrm), tex.ctypes.data_as(c_ip), ntex.ctypes.data_as(c_ip)), "glo_rayint_batch")
-        return {"t": t, "prim": prim, "pos": pos, "n": nrm, "tex": tex, "ntex": ntex}
+        return {"t": t, "prim": prim, "pos": pos, "n": nrm, "tex": tex, "ntex": ntex, "diverged": self._diverged(n)}
+
+    def _diverged(self, n):
+        """per ray of the last batch: rayint_advance nested deeper than kAdvanceNesting (glome_oracle.hpp) and the ray was given up as a miss"""
+        out = np.zeros(n, np.uint8)
+        self.L.glo_last_diverged(self.h, out.ctypes.data_as(C.POINTER(C.c_uint8)), C.c_size_t(n))
+        self.last_diverged = out.astype(bool)
+        return self.last_diverged
 
     def shadow(self, root, o, d, tmax):
         o = np.asarray(o, dtype=np.float64).reshape(-1, 3)
@@ -179,6 +187,7 @@ class Oracle:
         cols = [np.ascontiguousarray(o[:, k]) for k in range(3)] + [np.ascontiguousarray(d[:, k]) for k in range(3)]
         occ = np.zeros(n, np.uint8)
         self._chk(self.L.glo_shadow_batch(self.h, C.c_int(int(root)), C.c_size_t(n), *[_dp(c) for c in cols], _dp(tm), occ.ctypes.data_as(C.POINTER(C.c_uint8))), "glo_shadow_batch")
+        self._diverged(n)  # (kept in self.last_diverged: the return value stays the occlusion array)
         return occ.astype(bool)
 
     def inside(self, root, p):

@@ -19,7 +19,6 @@ GD float as_f(uint32_t u) { float f; std::memcpy(&f, &u, 4); return f; }
 GD uint32_t as_u(float f) { uint32_t u; std::memcpy(&u, &f, 4); return u; }
 typedef unsigned long long LaneMask;
 GD float min_nn(float a, float b) { return fminf(a, b); }
-GD float max_nn(float a, float b) { return fmaxf(a, b); }
 GD LaneMask wave_ballot(bool p) { return p ? 1ull : 0ull; }
 GD bool wave_any(bool p) { return p; }
 GD bool lane_of(LaneMask m) { return (m & 1ull) != 0; }

@@ -111,9 +111,9 @@ int hostsim_rayint(void* sv, int tier, int analysis, size_t n, const float* ox, 
     Ray r; r.o = v3(ox[i], oy[i], oz[i]); r.d = v3(dx[i], dy[i], dz[i]);
     HitG h;
     if (tier == 0) {
-      if (analysis & 1) { HostFlatTier<true, true, false> T{s->D, nullptr, 0, hs.lane(kFlatStack), Cnt()}; h = (analysis & 2) ? T.closest_wave(r, tmax[i], true) : T.closest(r, tmax[i]); total.bih += T.cnt.bih; total.prim += T.cnt.prim; total.mesh += T.cnt.mesh; }
-      else if (!unit_length(r.d)) { HostFlatTier<true, false, false> T{s->D, nullptr, 0, hs.lane(kFlatStack), Cnt()}; h = T.closest(r, tmax[i]); }  // (k_rayint_batch_flat's rule for a caller's non-unit ray)
-      else { HostFlatTier<false, false, false> T{s->D, nullptr, 0, hs.lane(kFlatStack), Cnt()}; h = (analysis & 2) ? T.closest_wave(r, tmax[i], true) : T.closest(r, tmax[i]); }
+      if (analysis & 1) { HostFlatTier<true, true, false> T{s->D, nullptr, 0, hs.lane(kFlatStack), Cnt()}; h = (analysis & 2) ? T.closest_wave(r, tmax[i], true) : T.closest(r, tmax[i]); err |= T.err; total.bih += T.cnt.bih; total.prim += T.cnt.prim; total.mesh += T.cnt.mesh; }
+      else if (!unit_length(r.d)) { HostFlatTier<true, false, false> T{s->D, nullptr, 0, hs.lane(kFlatStack), Cnt()}; h = T.closest(r, tmax[i]); err |= T.err; }  // (k_rayint_batch_flat's rule for a caller's non-unit ray)
+      else { HostFlatTier<false, false, false> T{s->D, nullptr, 0, hs.lane(kFlatStack), Cnt()}; h = (analysis & 2) ? T.closest_wave(r, tmax[i], true) : T.closest(r, tmax[i]); err |= T.err; }  // (k_rayint_batch_flat: `if (T.err)`)
     } else {
       HostGenericTier T{s->D, nullptr, 0, Cnt()}; T.packets();
       h = T.closest(r, tmax[i]);
@@ -136,7 +136,7 @@ int hostsim_shadow(void* sv, int tier, size_t n, const float* ox, const float* o
   unsigned int err = 0;
   for (size_t i = 0; i < n; i++) {
     Ray r; r.o = v3(ox[i], oy[i], oz[i]); r.d = v3(dx[i], dy[i], dz[i]);
-    if (tier == 0) { HostFlatTier<false, false, false> T{s->D, nullptr, 0, hs.lane(kFlatStack), Cnt()}; occ[i] = T.occluded(r, tmax[i]); }
+    if (tier == 0) { HostFlatTier<false, false, false> T{s->D, nullptr, 0, hs.lane(kFlatStack), Cnt()}; occ[i] = T.occluded(r, tmax[i]); err |= T.err; }
     else { HostGenericTier T{s->D, nullptr, 0, Cnt()}; T.packets(); occ[i] = T.occluded(r, tmax[i]); err |= T.err; }
   }
   return err ? -2 : 0;

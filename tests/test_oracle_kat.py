@@ -273,3 +273,37 @@ def test_stripe_waves():
     assert np.allclose(_weight(3, [1, 0, 0], pts), [0, 0.5, 1, 0.5, 0.5, 0.5])      # triangle_wave
     assert np.allclose(_weight(4, [1, 0, 0], pts), np.sin(x * 2 * np.pi) * 0.5 + 0.5)
     assert np.allclose(_weight(3, [4, 8, 5], [[0.1, 0.2, 0.3]]), [1.0])             # vdot = 3.5 -> offset 0.5 -> 2 - 1
+
+
+@pytest.mark.parametrize("use_float", [False, True], ids=["double", "float"])
+def test_an_advance_that_never_moves_ends_flagged_not_in_the_stack(built, use_float):
+    """The ray that used to end the process: its origin lies on the box's face x = -1 and the direction's x is -0, so the slab gives
+    0 * -inf = NaN, the advance is NaN and rayint_advance (Solid.hs:85-91) recurses without moving -- the reference does not terminate
+    either.  The oracle counts the nesting (kAdvanceNesting, glome_oracle.hpp): the ray comes back a miss, flagged as diverged, in rayint
+    and in shadow; its neighbours in the batch are not flagged and answer as before; np_scene.py stops at the same bound."""
+    o = O.Oracle(use_float)
+    x = o.intersection([o.sphere([0, 0, 0], 2), o.box([-1, -1, -3], [1, 1, 3]), o.plane_offset([0, 1, 0], 0.5)])
+    orig = [[0, 0, -10], [-1, 2.5, 1], [0.25, 0.25, -10]]
+    d = [[0, 0, 1], [-0.0, -2, -2], [-0.0, -0.0, 1]]
+    r = o.rayint(x, orig, d, [20, 7.5, 20])
+    assert r["diverged"].tolist() == [False, True, False]
+    assert r["t"][1] == -1 and r["prim"][1] == -1
+    assert r["t"][0] == 8                                      # (the sphere's hit, inside the other two: the box's rayint is never asked, Q14)
+    assert r["t"][2] == pytest.approx(10 - math.sqrt(4 - 0.125), rel=1e-6)
+    assert o.shadow(x, orig, d, [20, 7.5, 20]).tolist() == [True, False, True] and o.last_diverged.tolist() == [False, True, False]
+    L = O.lib()
+    assert L.glo_advance_nesting_bound() == 2048
+    L.glo_advance_nesting_max(1)
+    o.rayint(x, orig[1:2], d[1:2], 7.5)
+    assert L.glo_advance_nesting_max(1) == 2049               # it stopped at the bound, one nesting past it
+    o.rayint(x, orig[2:], d[2:], 20)
+    assert L.glo_advance_nesting_max(1) <= 1
+    if not use_float:
+        from oracle import np_scene as NS
+        assert NS.ADVANCE_NESTING == 2048
+        s = NS.Intersection([NS.Sphere((0.0, 0.0, 0.0), 2.0), NS.Box((-1.0, -1.0, -3.0), (1.0, 1.0, 3.0)), NS.Plane((0.0, 1.0, 0.0), 0.5)])
+        import sys
+        limit = sys.getrecursionlimit()
+        assert NS.rayint_flagged(s, (-1.0, 2.5, 1.0), (-0.0, -2.0, -2.0), 7.5) == (None, True)
+        h, flagged = NS.rayint_flagged(s, (0.25, 0.25, -10.0), (-0.0, -0.0, 1.0), 20.0)
+        assert not flagged and h[0] == r["t"][2] and sys.getrecursionlimit() == limit
