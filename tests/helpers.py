@@ -88,6 +88,24 @@ class HostSim:
         return out, cnt
 
 
+def _hs_trace(self, o, d, lights, maxdepth, full=1, faithful=0, tier=-1, tmax=np.inf):
+    """Trace.trace over rays (hostsim_trace): (n x 5 float32 (r, g, b, a, depth), n x 2 uint32 (shadow rays, secondary rays the ray spawned)).
+    lights: [(pos, color, rad, shadow)]; full = 0: the lean tier (FULL == false), refused (rc -3) where the product launches no lean kernel."""
+    n, cols = self._cols(o, d, tmax)
+    lv = np.array([list(p) + list(c) + [r, float(s)] for (p, c, r, s) in lights], np.float32).reshape(-1, 8)
+    if not len(lv):
+        lv = np.zeros((1, 8), np.float32)
+    out, cnt = np.zeros((n, 5), np.float32), np.zeros((n, 2), np.uint32)
+    rc = self.lib.hostsim_trace(self.h, tier, full, faithful, C.c_size_t(n), *[c.ctypes.data_as(c_fp) for c in cols], lv.ctypes.data_as(c_fp), len(lights), maxdepth,
+                                out.ctypes.data_as(c_fp), cnt.ctypes.data_as(C.POINTER(C.c_uint)))
+    if rc != 0:
+        raise RuntimeError(f"hostsim_trace rc={rc}")
+    return out, cnt
+
+
+HostSim.trace = _hs_trace
+
+
 def _hs_render_subsample(self, cam, lights, width, height, maxdepth, blocksize=65, thresholds=(0.14, 0.15, 0.16, 0.18), tier=-1):
     camv = np.array(list(cam.pos) + list(cam.fwd) + list(cam.up) + list(cam.right), np.float32)
     lv = np.array([list(l.pos) + list(l.color) + [l.rad, float(l.shadow)] for l in lights], np.float32).reshape(-1, 8)

@@ -17,6 +17,7 @@ using namespace glome;
 struct SimScene {
   FlatScene F;
   DScene D;
+  CommitRules rules;  // what the product's commit derives for the choice of a kernel instance (capi_shared.hpp)
   std::string err;
 };
 
@@ -89,6 +90,7 @@ void* hostsim_commit(glome_sb* sb, int root, char* errbuf, int cap) {
   D.n_entries = F.tier == 0 ? (uint32_t)F.entries.size() : 0; D.root_rec = F.root_rec; D.tier = F.tier; D.n_mats = (uint32_t)sb_graph(sb).mats.size(); D.tex_bits = F.tex_bits;
   D.pk_generic_cap = scene_caps(F).pk_generic_cap;  // (the product's commit-time rule, instances.hpp)
   if (getenv("GLOME_DEBUG_NO_GENERIC_PACKETS")) D.pk_generic_cap = 0;  // (the product's switch, runtime.hip glome_scene_commit)
+  s->rules = commit_rules(sb_graph(sb), F);
   return s;
 }
 void hostsim_free(void* s) { delete (SimScene*)s; }
@@ -173,6 +175,44 @@ int hostsim_render(void* sv, int tier, const float* cam, const float* lights, in
       o[0] = c.r; o[1] = c.g; o[2] = c.b; o[3] = c.a; o[4] = h.hit ? h.t : kInf;
     }
   if (counters) { counters[0] = (unsigned long long)width * height; counters[1] = total.shadow; counters[2] = total.secondary; }
+  return err ? -2 : 0;
+}
+
+// Trace.trace over a caller's rays (what k_trace_batch_* runs per lane): out5 = (r, g, b, a, depth) per ray, counts = the shadow and the
+// secondary rays each ray spawned (words 3 and 4 of a work record).  full = 0 instantiates the tier with FULL == false, so trace_primary
+// takes shade_hit_lean; it is refused (-3) where the product's own rule (instances.hpp choose_trace: full_shading) launches no lean kernel
+// -- the generic tier has none at all.  faithful: asked for; the rule adds exact_traversal as choose_trace does.
+}  // extern "C"
+template <class TIER> static void trace_one(TIER& T, const Ray& r, float tmax, int maxdepth, float* o, unsigned int* cnt2, unsigned int& err) {
+  HitG h;
+  CA c = trace_primary(T, r, tmax, maxdepth, true, &h);
+  o[0] = c.r; o[1] = c.g; o[2] = c.b; o[3] = c.a; o[4] = h.hit ? h.t : kInf;
+  cnt2[0] = (unsigned int)T.cnt.shadow; cnt2[1] = (unsigned int)T.cnt.secondary;
+  err |= T.err;
+}
+extern "C" {
+int hostsim_trace(void* sv, int tier, int full, int faithful, size_t n, const float* ox, const float* oy, const float* oz, const float* dx, const float* dy,
+                  const float* dz, const float* tmax, const float* lights, int nl, int maxdepth, float* out5, unsigned int* counts2) {
+  SimScene* s = (SimScene*)sv;
+  if (tier < 0) tier = (int)s->D.tier;
+  if (tier == 0 && s->D.tier != 0) return -1;
+  if (nl < 0 || nl > kMaxLights || maxdepth < 1 || maxdepth > kMaxTraceDepth) return -5;
+  if (!full && (tier != 0 || full_shading(s->rules.traits, maxdepth))) return -3;
+  DLight L[kMaxLights];
+  for (int i = 0; i < nl; i++) { memcpy(L[i].pos, lights + 8 * i, 12); memcpy(L[i].color, lights + 8 * i + 3, 12); L[i].rad = lights[8 * i + 6]; L[i].shadow = lights[8 * i + 7] != 0; }
+  HostStack hs;
+  unsigned int err = 0;
+  const bool exact = faithful || exact_traversal(s->rules.traits.has_refract, maxdepth);
+  for (size_t i = 0; i < n; i++) {
+    Ray r; r.o = v3(ox[i], oy[i], oz[i]); r.d = v3(dx[i], dy[i], dz[i]);
+    if (tier == 0 && !exact && !unit_length(r.d)) return -4;  // (trace_batch_loop's CHECK: kErrNonUnit)
+    float* o = out5 + 5 * i; unsigned int* c = counts2 + 2 * i;
+    if (tier != 0) { HostGenericTier T{s->D, L, nl, Cnt()}; T.packets(); trace_one(T, r, tmax[i], maxdepth, o, c, err); }
+    else if (exact && full) { HostFlatTier<true, false, true> T{s->D, L, nl, hs.lane(kFlatStack), Cnt()}; trace_one(T, r, tmax[i], maxdepth, o, c, err); }
+    else if (exact) { HostFlatTier<true, false, false> T{s->D, L, nl, hs.lane(kFlatStack), Cnt()}; trace_one(T, r, tmax[i], maxdepth, o, c, err); }
+    else if (full) { HostFlatTier<false, false, true> T{s->D, L, nl, hs.lane(kFlatStack), Cnt()}; trace_one(T, r, tmax[i], maxdepth, o, c, err); }
+    else { HostFlatTier<false, false, false> T{s->D, L, nl, hs.lane(kFlatStack), Cnt()}; trace_one(T, r, tmax[i], maxdepth, o, c, err); }
+  }
   return err ? -2 : 0;
 }
 
