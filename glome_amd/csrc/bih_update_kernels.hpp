@@ -1,7 +1,7 @@
 // bih_update_kernels.hpp -- new triangles for a committed triangle bih (glome_scene_bih_update): what flatten.hpp's emit_bih / emit_tri /
 // emit_pairs derive from the items' vertices, made again in the scene's own pools, bit for bit what a commit of the same tree with the
-// new triangles (glome_sb_bih_set_triangles) would upload.  Included by runtime.hip only, like mesh_update_kernels.hpp, whose record
-// arithmetic (tri_record) and bound reduction (k_mesh_bound) it shares.
+// new triangles (glome_sb_bih_set_triangles) would upload.  Included by runtime.hip only, like mesh_update_kernels.hpp, with which it
+// shares the record arithmetic (tri_record) and the bound reduction (k_points_bound) of update_common.hpp.
 //
 // A branch's planes are round_up(lmax + kDelta) and round_down(rmin - kDelta), lmax / rmin the max / min over a subtree of the items'
 // box hi[axis] / lo[axis] from -+kInfinity, and an item's box is max(p) + kDelta / min(p) - kDelta (host_graph.hpp: bound, BihBuild::rec).
@@ -9,12 +9,13 @@
 // value is rounded to fp32 per vertex and folded in fp32 above it, in any order, from round_up(-kInfinity + kDelta) and
 // round_down(kInfinity - kDelta) -- what an empty subtree gives on the host.  A node holds two planes, not two boxes, so the pass keeps a
 // box per record and per branch slot in a workspace: an ancestor may split on any axis.  The tree's own box is ONE pad deep, a different
-// fp32 value: it is reduced on its own over all vertices (k_mesh_bound), from the host's box_empty.
+// fp32 value: it is reduced on its own over all vertices (k_points_bound), from the host's box_empty.
 //   k_bih_tris           one lane per record: the tris record, its words of its pair record, its plane-form box into the workspace
 //   k_bih_level          one launch per tree level from the deepest up, one lane per branch node: its planes, its box
 //   k_bih_levels_merged  a run of narrow levels (each at most kMergeBlock nodes) in ONE block, a block barrier between levels: off by
 //                        default (GLOME_DEBUG_BIH_UPDATE_MERGED) until measured to win; wide levels then keep k_bih_level
-//   k_bih_bound_store    folds k_mesh_bound's partial boxes into the tree's header
+// and, of update_common.hpp, k_bound_store with (float)kInfinity as the start: k_points_bound's partial boxes into the tree's header.
+// The levels and the header's store are also what an item bih's refit launches (item_bih_update_kernels.hpp).
 // The library flushes fp32 subnormals: as in the mesh update, a component whose fp32 rounding is subnormal is stored as zero.
 // No wave waits for a wave of another block: the order between the launches is the stream's, inside the merged launch the barrier's.
 #pragma once
@@ -23,7 +24,7 @@
 #include <cstdint>
 
 #include "flatten.hpp"
-#include "mesh_update_kernels.hpp"
+#include "update_common.hpp"
 
 namespace glome {
 namespace bihupd {
@@ -50,27 +51,13 @@ struct DLevelArgs {
   uint32_t first_rec, first_slot;
 };
 
-__device__ __forceinline__ float plane_lo0() { return round_down(__dsub_rn(kInfinity, kDelta)); }
-__device__ __forceinline__ float plane_hi0() { return round_up(__dadd_rn(-kInfinity, kDelta)); }
-
-// a vertex folded into a plane-form box: the item's pad and the plane's, two fp64 additions (not p -+ 2 kDelta), rounded outward once
-__device__ __forceinline__ void plane_add(const double p[3], float lo[3], float hi[3]) {
-  for (int k = 0; k < 3; k++) {
-    lo[k] = fminf(lo[k], round_down(__dsub_rn(__dsub_rn(p[k], kDelta), kDelta)));
-    hi[k] = fmaxf(hi[k], round_up(__dadd_rn(__dadd_rn(p[k], kDelta), kDelta)));
-  }
-}
-
 __global__ void __launch_bounds__(64) k_bih_tris(DTrisArgs A) {
-  const uint32_t items = (A.n + 63u) >> 6;
-  for (uint32_t item = blockIdx.x; item < items; item += gridDim.x) {
-    const uint32_t j = item * 64u + threadIdx.x;
-    if (j >= A.n) continue;
+  upd::for_lanes(A.n, [&](uint32_t j) {
     const uint2 row = A.rows[j];
     double a[3], b[3], c[3];
-    meshupd::d3_load(A.pts9, 3 * (int)row.x, a); meshupd::d3_load(A.pts9, 3 * (int)row.x + 1, b); meshupd::d3_load(A.pts9, 3 * (int)row.x + 2, c);
+    upd::d3_load(A.pts9, 3 * (int)row.x, a); upd::d3_load(A.pts9, 3 * (int)row.x + 1, b); upd::d3_load(A.pts9, 3 * (int)row.x + 2, c);
     float4 rec[3];
-    meshupd::tri_record(a, b, c, rec);
+    upd::tri_record(a, b, c, rec);
     float4* o = A.tris + 3 * (size_t)j;
     o[0] = rec[0]; o[1] = rec[1]; o[2] = rec[2];
     if (row.y != BihUpdateInfo::kNoPair) {  // emit_pairs: word w of the record is r[6 w ..] = A.x B.x A.y B.y A.z B.z
@@ -85,11 +72,10 @@ __global__ void __launch_bounds__(64) k_bih_tris(DTrisArgs A) {
         }
       }
     }
-    float lo[3] = {plane_lo0(), plane_lo0(), plane_lo0()}, hi[3] = {plane_hi0(), plane_hi0(), plane_hi0()};
-    plane_add(a, lo, hi); plane_add(b, lo, hi); plane_add(c, lo, hi);
-    A.ws[2 * (size_t)j] = make_float4(lo[0], lo[1], lo[2], 0.0f);
-    A.ws[2 * (size_t)j + 1] = make_float4(hi[0], hi[1], hi[2], 0.0f);
-  }
+    float lo[3] = {upd::plane_lo0(), upd::plane_lo0(), upd::plane_lo0()}, hi[3] = {upd::plane_hi0(), upd::plane_hi0(), upd::plane_hi0()};
+    upd::plane_add(a, lo, hi); upd::plane_add(b, lo, hi); upd::plane_add(c, lo, hi);
+    upd::store_rows(A.ws + 2 * (size_t)j, lo, hi);
+  });
 }
 
 // A child's plane-form box.  A leaf: the fold of its records' boxes, its count in the reference or, for 7 and more, in its slot with its
@@ -98,13 +84,8 @@ __device__ __forceinline__ void child_box(const DLevelArgs& A, uint32_t ref, flo
   if (ref & BREF_LEAF_BIT) {
     uint32_t count = (ref >> 26) & 7u, first = ref & (BREF_FIRST_LIMIT - 1u);
     if (count == 7u) { const float4 ln = A.bihnodes[first]; count = __float_as_uint(ln.z); first = __float_as_uint(ln.w); }
-    for (int a = 0; a < 3; a++) { lo[a] = plane_lo0(); hi[a] = plane_hi0(); }
-    const float4* w = A.ws_tri + 2 * (size_t)(first - A.first_rec);
-    for (uint32_t q = 0; q < count; q++) {
-      const float4 l = w[2 * (size_t)q], h = w[2 * (size_t)q + 1];
-      lo[0] = fminf(lo[0], l.x); lo[1] = fminf(lo[1], l.y); lo[2] = fminf(lo[2], l.z);
-      hi[0] = fmaxf(hi[0], h.x); hi[1] = fmaxf(hi[1], h.y); hi[2] = fmaxf(hi[2], h.z);
-    }
+    for (int a = 0; a < 3; a++) { lo[a] = upd::plane_lo0(); hi[a] = upd::plane_hi0(); }
+    upd::fold_rows(A.ws_tri + 2 * (size_t)(first - A.first_rec), 0u, count, 1u, lo, hi);
   } else {
     const float4 l = A.ws_node[2 * (size_t)(ref - A.first_slot)], h = A.ws_node[2 * (size_t)(ref - A.first_slot) + 1];
     lo[0] = l.x; lo[1] = l.y; lo[2] = l.z; hi[0] = h.x; hi[1] = h.y; hi[2] = h.z;
@@ -130,11 +111,7 @@ __device__ __forceinline__ void refit_node(const DLevelArgs& A, uint32_t slot) {
 
 // one level: nodes [first, first + n) of A.nodes
 __global__ void __launch_bounds__(64) k_bih_level(DLevelArgs A, uint32_t first, uint32_t n) {
-  const uint32_t items = (n + 63u) >> 6;
-  for (uint32_t item = blockIdx.x; item < items; item += gridDim.x) {
-    const uint32_t j = item * 64u + threadIdx.x;
-    if (j < n) refit_node(A, A.nodes[first + j]);
-  }
+  upd::for_lanes(n, [&](uint32_t j) { refit_node(A, A.nodes[first + j]); });
 }
 // Levels l0 .. l1 - 1, each of at most kMergeBlock nodes, in one block: level l is A.nodes[off[l] .. off[l + 1]).  Between two levels
 // every wave's stores are made visible to the block (a block-scope fence: the block's waves share one CU and its L1, so nothing has to
@@ -145,24 +122,6 @@ __global__ void __launch_bounds__(kMergeBlock) k_bih_levels_merged(DLevelArgs A,
     if (threadIdx.x < n) refit_node(A, A.nodes[first + threadIdx.x]);
     __threadfence_block();
     __syncthreads();
-  }
-}
-
-// one wave: the partial boxes into the tree's two header words; .w (the root reference, the class) keeps its bits.  meshupd::k_mesh_bound_store
-// but for where the fold starts: a mesh's box is box_of_points, which starts from a vertex, so that kernel starts from real infinities;
-// a bih's box is a join of item boxes from box_empty (host_graph.hpp `bih`), +-kInfinity = 1e6, and that start shows in a tree of no
-// items or of coordinates beyond 1e6.  The mesh's kernel is an existing one and stays as it is rather than grow a start value.
-__global__ void __launch_bounds__(64) k_bih_bound_store(const float4* part, uint32_t nparts, float4* hdr) {
-  float lo[3] = {(float)kInfinity, (float)kInfinity, (float)kInfinity}, hi[3] = {-(float)kInfinity, -(float)kInfinity, -(float)kInfinity};
-  for (uint32_t i = threadIdx.x; i < nparts; i += 64u) {
-    const float4 l = part[2 * (size_t)i], h = part[2 * (size_t)i + 1];
-    lo[0] = fminf(lo[0], l.x); lo[1] = fminf(lo[1], l.y); lo[2] = fminf(lo[2], l.z);
-    hi[0] = fmaxf(hi[0], h.x); hi[1] = fmaxf(hi[1], h.y); hi[2] = fmaxf(hi[2], h.z);
-  }
-  meshupd::wave_fold(lo, hi);
-  if (threadIdx.x == 0) {
-    hdr[0] = make_float4(lo[0], lo[1], lo[2], hdr[0].w);
-    hdr[1] = make_float4(hi[0], hi[1], hi[2], hdr[1].w);
   }
 }
 

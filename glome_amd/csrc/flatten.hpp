@@ -19,10 +19,13 @@ namespace glome {
 // a b c na nb nc, the triangle's first trinorms word or -1, a spare word.  The placeholder record of an empty leaf has a = -1.
 // The second answer of mark_updatable, per Mesh, triangle bih and Instance: whether an update is accepted when the bihs above the object
 // are refitted after it (glome_scene_nested_updates, glome_scene_bih_refit), and those bihs in an order in which they can be refitted --
-// a tree after every tree below it.  `updatable` / `why_not` stay what they were: the answer with the switch off.
-struct NestedAnswer {
+// a tree after every tree below it.  `plain` stays what it was: the answer with the switch off.  Both answers have one shape: whether,
+// and if not the reason.
+struct UpdateAnswer {
   bool ok = true;
   std::string why_not;
+};
+struct NestedAnswer : UpdateAnswer {
   std::vector<int> above;
 };
 
@@ -35,8 +38,8 @@ struct MeshUpdateInfo {
   std::vector<int32_t> rows;
   std::vector<uint32_t> level_nodes;  // its branch nodes, deepest tree level first ...
   std::vector<uint32_t> level_off;    // ... level l is level_nodes[level_off[l] .. level_off[l + 1])
-  bool updatable = true;          // false: a path from the committed root to the mesh passes through a Bih, whose planes and root box were
-  std::string why_not;            // built from the mesh's bound (Bih.hs:309-324) -- the reason, naming that bih
+  UpdateAnswer plain;             // not ok: a path from the committed root to the mesh passes through a Bih, whose planes and root box were
+                                  // built from the mesh's bound (Bih.hs:309-324) -- the reason, naming that bih
   NestedAnswer nested;            // the answer with glome_scene_nested_updates on (Flattener::mark_nested)
   double bound6[6] = {0, 0, 0, 0, 0, 0};  // bound(mesh) at commit: lo, hi
 };
@@ -58,8 +61,7 @@ struct BihUpdateInfo {
   std::vector<uint32_t> rows;
   std::vector<uint32_t> level_nodes;  // its branch slots (bihnodes indices), deepest tree level first ...
   std::vector<uint32_t> level_off;    // ... level l is level_nodes[level_off[l] .. level_off[l + 1])
-  bool updatable = true;          // false: another Bih lies above it, or the scene holds another copy of one of its triangles -- the reason
-  std::string why_not;
+  UpdateAnswer plain;             // not ok: another Bih lies above it, or the scene holds another copy of one of its triangles -- the reason
   NestedAnswer nested;
   double bound6[6] = {0, 0, 0, 0, 0, 0};  // bound(bih) at commit
 };
@@ -73,8 +75,7 @@ struct InstanceUpdateInfo {
   std::vector<uint32_t> slots;    // xfm indices (six float4 each)
   int bih = -1;                   // the bih it is an item of (builder id), -1: of none
   uint32_t item = 0;              // ... and its item there (an index into InstBihInfo's per-item arrays)
-  bool updatable = true;          // false: see Flattener::mark_updatable -- the reason
-  std::string why_not;
+  UpdateAnswer plain;             // not ok: see Flattener::mark_updatable -- the reason
   NestedAnswer nested;
 };
 // Per emitted bih, of class BC_CSG or BC_GENERIC (no other class can hold one), with at least one Instance item or one LIVE item: an
@@ -374,14 +375,14 @@ class Flattener {
     return d;
   }
 
-  // Which emitted meshes may have their vertices replaced in the committed scene (MeshUpdateInfo::updatable): every one that no Bih
+  // Which emitted meshes may have their vertices replaced in the committed scene (MeshUpdateInfo::plain): every one that no Bih
   // lies above, on any path from the root or from a Warp material's frame / scene.  Of the composites, only a Bih keeps something derived
   // from a child's bound -- its planes and its root box.  A list, an Instance, a Difference, an Intersection and the Tex / Tag / shadow
   // wrappers emit no box at all (emit, below), and the bounding solid of a Bound / InnerBound is the caller's own object.
-  // And which triangle bihs may have their triangles replaced (BihUpdateInfo::updatable): every one that no OTHER Bih lies above -- for
+  // And which triangle bihs may have their triangles replaced (BihUpdateInfo::plain): every one that no OTHER Bih lies above -- for
   // the same reason -- and whose item triangles the scene reaches through this bih alone: a triangle node that is also in a group beside
   // the bih, or in another bih, has a record of its own there, which an update of this bih could not move.
-  // And which Instances may have their matrices replaced (InstanceUpdateInfo::updatable).  An Instance's matrix is read from its xfm
+  // And which Instances may have their matrices replaced (InstanceUpdateInfo::plain).  An Instance's matrix is read from its xfm
   // slots alone, so one with no Bih above it on any path is a write of those slots.  One that IS an item of a bih (wrappers only in
   // between), that bih having no other above it, also moves the item's box: that tree's planes and box are refitted from the tables of
   // emit_bih.  Refused: an Instance that lies deeper inside an item (the item's box depends on it through a list, a CSG node, a Bound or
@@ -395,9 +396,9 @@ class Flattener {
     for (size_t k = 0; k < F.inst_updates.size(); k++) islot_of[F.inst_updates[k].node] = k;
     for (const InstItem& I : inst_items) {
       InstanceUpdateInfo& U = F.inst_updates[islot_of.at(I.inst)];
-      if (U.bih >= 0 && U.updatable) {
-        U.updatable = false;
-        U.why_not = "instance " + std::to_string(I.inst) + " is an item of a bih more than once (bih " + std::to_string(U.bih) + " and bih " + std::to_string(I.bih) + ")";
+      if (U.bih >= 0 && U.plain.ok) {
+        U.plain.ok = false;
+        U.plain.why_not = "instance " + std::to_string(I.inst) + " is an item of a bih more than once (bih " + std::to_string(U.bih) + " and bih " + std::to_string(I.bih) + ")";
       }
       U.bih = I.bih; U.item = I.item;
     }
@@ -425,14 +426,14 @@ class Flattener {
         case K_DIFF: case K_BOUND: case K_INNERBOUND: stack.push_back({n.a, it.bih, it.inner, 0}); stack.push_back({n.b, it.bih, it.inner, 0}); break;
         case K_INSTANCE: {
           auto sl = islot_of.find(it.id);
-          if (sl != islot_of.end() && F.inst_updates[sl->second].updatable && it.bih >= 0) {
+          if (sl != islot_of.end() && F.inst_updates[sl->second].plain.ok && it.bih >= 0) {
             InstanceUpdateInfo& U = F.inst_updates[sl->second];
             if (it.bih != it.inner) {
-              U.updatable = false;
-              U.why_not = "instance " + std::to_string(it.id) + " lies under bih " + std::to_string(it.inner) + " inside bih " + std::to_string(it.bih) + ", whose planes and root box were built from the inner tree's bound";
+              U.plain.ok = false;
+              U.plain.why_not = "instance " + std::to_string(it.id) + " lies under bih " + std::to_string(it.inner) + " inside bih " + std::to_string(it.bih) + ", whose planes and root box were built from the inner tree's bound";
             } else if (!it.direct) {
-              U.updatable = false;
-              U.why_not = "instance " + std::to_string(it.id) + " lies inside an item of bih " + std::to_string(it.inner) + " rather than being the item: that item's box depends on it through a list, CSG, Bound or Instance, which an update does not recompute";
+              U.plain.ok = false;
+              U.plain.why_not = "instance " + std::to_string(it.id) + " lies inside an item of bih " + std::to_string(it.inner) + " rather than being the item: that item's box depends on it through a list, CSG, Bound or Instance, which an update does not recompute";
             }
           }
           stack.push_back({n.a, it.bih, it.inner, 0});
@@ -441,20 +442,20 @@ class Flattener {
         case K_TEX: case K_TAG: case K_NOSHADOW: case K_ONLYSHADOW: stack.push_back({n.a, it.bih, it.inner, it.direct}); break;
         case K_BIH: {
           auto sl = bslot_of.find(it.id);
-          if (it.bih >= 0 && sl != bslot_of.end() && F.bih_updates[sl->second].updatable) {
+          if (it.bih >= 0 && sl != bslot_of.end() && F.bih_updates[sl->second].plain.ok) {
             BihUpdateInfo& U = F.bih_updates[sl->second];
-            U.updatable = false;
-            U.why_not = "bih " + std::to_string(it.id) + " lies inside bih " + std::to_string(it.bih) + ", whose planes and root box were built from its bound";
+            U.plain.ok = false;
+            U.plain.why_not = "bih " + std::to_string(it.id) + " lies inside bih " + std::to_string(it.bih) + ", whose planes and root box were built from its bound";
           }
           for (auto& bn : n.bih->nodes) for (int k : bn.items) stack.push_back({k, it.bih < 0 ? it.id : it.bih, it.id, 1});
           break;
         }
         case K_MESH: {
           auto sl = slot_of.find(it.id);
-          if (it.bih >= 0 && sl != slot_of.end() && F.mesh_updates[sl->second].updatable) {
+          if (it.bih >= 0 && sl != slot_of.end() && F.mesh_updates[sl->second].plain.ok) {
             MeshUpdateInfo& U = F.mesh_updates[sl->second];
-            U.updatable = false;
-            U.why_not = "mesh " + std::to_string(it.id) + " lies inside bih " + std::to_string(it.bih) + ", whose planes and root box were built from the mesh's bound";
+            U.plain.ok = false;
+            U.plain.why_not = "mesh " + std::to_string(it.id) + " lies inside bih " + std::to_string(it.bih) + ", whose planes and root box were built from the mesh's bound";
           }
           break;
         }
@@ -462,17 +463,17 @@ class Flattener {
       }
     }
     for (BihUpdateInfo& U : F.bih_updates) {
-      if (!U.updatable) continue;
+      if (!U.plain.ok) continue;
       for (const BihTree::Node& bn : G.at(U.node).bih->nodes) {
         for (int item : bn.items) {
           const int t = G.peel_wrappers(item);
           const int u = tri_under[(size_t)t];
           if (u == U.node || u == kUnseen) continue;  // (kUnseen: the bih itself is not reachable from the root -- nothing renders it)
-          U.updatable = false;
-          U.why_not = "triangle " + std::to_string(t) + " of bih " + std::to_string(U.node) + " is also part of the scene outside that bih, as a copy an update could not move";
+          U.plain.ok = false;
+          U.plain.why_not = "triangle " + std::to_string(t) + " of bih " + std::to_string(U.node) + " is also part of the scene outside that bih, as a copy an update could not move";
           break;
         }
-        if (!U.updatable) break;
+        if (!U.plain.ok) break;
       }
     }
   }
@@ -570,7 +571,7 @@ class Flattener {
     };
     for (MeshUpdateInfo& U : F.mesh_updates) U.nested = answer(U.node);
     for (BihUpdateInfo& U : F.bih_updates) {
-      if (U.why_not.rfind("bih " + std::to_string(U.node) + " holds triangle", 0) == 0) { U.nested.ok = false; U.nested.why_not = U.why_not; continue; }  // (emit_bih's refusal)
+      if (U.plain.why_not.rfind("bih " + std::to_string(U.node) + " holds triangle", 0) == 0) { U.nested.ok = false; U.nested.why_not = U.plain.why_not; continue; }  // (emit_bih's refusal)
       U.nested = answer(U.node);
       if (!U.nested.ok) continue;
       for (const BihTree::Node& bn : G.at(U.node).bih->nodes) {
@@ -759,25 +760,27 @@ class Flattener {
     return (k >= R_SPHERE && k <= R_CONE) || (k == R_LIST && (c.x & RF_PRIMLIST) != 0);
   }
 
-  // A tree's branch slots by tree level, deepest first (a level's children were refitted before it): what the triangle bih's update and
-  // the Instance update launch k_bih_level over.  Nothing for a tree whose root is a leaf.
-  static void bih_levels(const BihTree& T, uint32_t base, const std::vector<uint32_t>& slot, std::vector<uint32_t>& level_nodes, std::vector<uint32_t>& level_off) {
-    if (T.nodes.empty() || T.nodes[0].leaf) return;
-    std::vector<int> depth(T.nodes.size(), 0), order{0};  // (a parent before its children, whatever the numbering)
+  // A tree's branch nodes by tree level, deepest first (a level's children were refitted by the launch before it): what the Mesh's update
+  // launches k_mesh_refit_level over, and the triangle bih's update and an item bih's refit k_bih_level.  `nodes`: a BihTree's or a
+  // MeshData's, each with leaf / left / right; stored(k): where node k lies in its pool.  Nothing for a tree whose root is a leaf.
+  template <class Nodes, class Stored>
+  static void tree_levels(const Nodes& nodes, Stored stored, std::vector<uint32_t>& level_nodes, std::vector<uint32_t>& level_off) {
+    if (nodes.empty() || nodes[0].leaf) return;
+    std::vector<int> depth(nodes.size(), 0), order{0};  // (a parent before its children, whatever the numbering)
     for (size_t q = 0; q < order.size(); q++) {
-      const BihTree::Node& bn = T.nodes[(size_t)order[q]];
+      const auto& bn = nodes[(size_t)order[q]];
       if (bn.leaf) continue;
       for (int c : {bn.left, bn.right}) { depth[(size_t)c] = depth[(size_t)order[q]] + 1; order.push_back(c); }
     }
     int deepest = 0;
-    for (int k : order) if (!T.nodes[(size_t)k].leaf) deepest = std::max(deepest, depth[(size_t)k]);
+    for (int k : order) if (!nodes[(size_t)k].leaf) deepest = std::max(deepest, depth[(size_t)k]);
     std::vector<uint32_t> per_level((size_t)deepest + 2, 0);
-    for (int k : order) if (!T.nodes[(size_t)k].leaf) per_level[(size_t)(deepest - depth[(size_t)k]) + 1]++;
+    for (int k : order) if (!nodes[(size_t)k].leaf) per_level[(size_t)(deepest - depth[(size_t)k]) + 1]++;
     for (size_t l = 1; l < per_level.size(); l++) per_level[l] += per_level[l - 1];
     level_off = per_level;
     level_nodes.resize(per_level.back());
     std::vector<uint32_t> fill(per_level.begin(), per_level.end() - 1);
-    for (int k : order) if (!T.nodes[(size_t)k].leaf) level_nodes[fill[(size_t)(deepest - depth[(size_t)k])]++] = base + slot[(size_t)k];
+    for (int k : order) if (!nodes[(size_t)k].leaf) level_nodes[fill[(size_t)(deepest - depth[(size_t)k])]++] = stored((size_t)k);
   }
 
   // BIH: nodes in preorder; leaf items become consecutive records, and (for homogeneous leaves) consecutive pool
@@ -858,9 +861,9 @@ class Flattener {
       std::vector<char> tri_seen(G.nodes.size(), 0);  // an item, or a triangle under two items, that the tree holds twice has two records: one row cannot name both
       for (size_t k = 0; k < order.size(); k++) {
         const int t = G.peel_wrappers(order[k]);
-        if ((item_of[(size_t)order[k]] != 0xffffffffu || tri_seen[(size_t)t]) && U.updatable) {
-          U.updatable = false;
-          U.why_not = "bih " + std::to_string(id) + " holds triangle " + std::to_string(t) + " more than once";
+        if ((item_of[(size_t)order[k]] != 0xffffffffu || tri_seen[(size_t)t]) && U.plain.ok) {
+          U.plain.ok = false;
+          U.plain.why_not = "bih " + std::to_string(id) + " holds triangle " + std::to_string(t) + " more than once";
         }
         item_of[(size_t)order[k]] = (uint32_t)k; tri_seen[(size_t)t] = 1;
       }
@@ -949,7 +952,7 @@ class Flattener {
       U.n_tris = (uint32_t)(U.rows.size() / 2); U.pk = pk;
       box6(T.bb, U.bound6);
       if (!pk) for (size_t j = 0; j < U.n_tris; j++) U.rows[2 * j + 1] = BihUpdateInfo::kNoPair;  // (the packet form was given up part way)
-      bih_levels(T, base, slot, U.level_nodes, U.level_off);
+      tree_levels(T.nodes, [&](size_t k) { return base + slot[k]; }, U.level_nodes, U.level_off);
       F.bih_updates.push_back(std::move(U));
       movable_bihs.insert(id);
     }
@@ -986,7 +989,7 @@ class Flattener {
           B.live_xf.insert(B.live_xf.end(), x.i.m, x.i.m + 12);
         }
       }
-      bih_levels(T, base, slot, B.level_nodes, B.level_off);
+      tree_levels(T.nodes, [&](size_t k) { return base + slot[k]; }, B.level_nodes, B.level_off);
       F.inst_bihs.push_back(std::move(B));
     }
     return U4{R_BIH, hdr, 0, (uint32_t)n.uid};
@@ -1067,24 +1070,7 @@ class Flattener {
     F.meshhdr.push_back(mk4(round_up(M.bb.hi.x), round_up(M.bb.hi.y), round_up(M.bb.hi.z), 0));
     U.n_nodes = nb; U.n_tris = (uint32_t)(F.mtris.size() / 3) - U.first_tri;
     box6(M.bb, U.bound6);
-    if (nb) {  // the branch nodes by tree level, deepest first: a level's children were refitted by the launch before it
-      std::vector<int> depth(M.nodes.size(), 0);
-      std::vector<int> order{0};  // (a parent before its children, whatever the numbering)
-      for (size_t q = 0; q < order.size(); q++) {
-        const MeshData::Node& mn = M.nodes[(size_t)order[q]];
-        if (mn.leaf) continue;
-        for (int c : {mn.left, mn.right}) { depth[(size_t)c] = depth[(size_t)order[q]] + 1; order.push_back(c); }
-      }
-      int deepest = 0;
-      for (int k : order) if (!M.nodes[(size_t)k].leaf) deepest = std::max(deepest, depth[(size_t)k]);
-      std::vector<uint32_t> per_level((size_t)deepest + 2, 0);
-      for (int k : order) if (!M.nodes[(size_t)k].leaf) per_level[(size_t)(deepest - depth[(size_t)k]) + 1]++;
-      for (size_t l = 1; l < per_level.size(); l++) per_level[l] += per_level[l - 1];
-      U.level_off = per_level;
-      U.level_nodes.resize(nb);
-      std::vector<uint32_t> fill(per_level.begin(), per_level.end() - 1);
-      for (int k : order) if (!M.nodes[(size_t)k].leaf) U.level_nodes[fill[(size_t)(deepest - depth[(size_t)k])]++] = bidx[(size_t)k];
-    }
+    tree_levels(M.nodes, [&](size_t k) { return bidx[k]; }, U.level_nodes, U.level_off);
     F.mesh_updates.push_back(std::move(U));
     return U4{R_MESH, hdr, 0, (uint32_t)n.uid};
   }

@@ -3,8 +3,8 @@
 // sampler and batch kernels through kernel_launch.hpp (the instances live in kernel_parts.hip, chosen by instances.hpp) and holds
 // only the light kernels: the kernel-argument self-test, the coordinate tables, tile transport, the tree builders
 // (bih_build_device.hpp), the flagship launch's cull pass (cull_kernels.hpp) and the updates of a committed Mesh (mesh_update_kernels.hpp)
-// and of a committed triangle bih (bih_update_kernels.hpp), and of committed Instances' matrices (instance_update_kernels.hpp), and the
-// refit of the bihs above an updated object (nested_update_kernels.hpp).
+// and of a committed triangle bih (bih_update_kernels.hpp), and of committed Instances' matrices and the refit of the bihs above an
+// updated object (item_bih_update_kernels.hpp); what those kernels share is in update_common.hpp.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -28,8 +28,7 @@
 #include "cull_kernels.hpp"
 #include "mesh_update_kernels.hpp"
 #include "bih_update_kernels.hpp"
-#include "instance_update_kernels.hpp"
-#include "nested_update_kernels.hpp"
+#include "item_bih_update_kernels.hpp"
 
 using namespace glome;
 
@@ -183,7 +182,7 @@ struct glome_scene {
     // two words per record of the tree's span (plane-form rows), two per node slot, two per item (box-form rows), then the bound's partial
     // boxes: allocated, and filled with the commit-time rows, at the first update that touches the tree
     float4* d_ws = nullptr;
-    // the refit's tables (nested_update_kernels.hpp), allocated and filled with the workspace: six doubles of bound(item) per item, then 24
+    // the refit's tables (item_bih_update_kernels.hpp), allocated and filled with the workspace: six doubles of bound(item) per item, then 24
     // doubles of matrix per item (the commit's for an instanced live item, zeros until an update names the item otherwise); the live items
     // as (item, the object's row of the bounds table | kInstancedBit); per item the row of its live child, kNoLive for none
     double* d_box64 = nullptr;
@@ -1063,25 +1062,115 @@ int glome_inside_batch(glome_scene* s, size_t n, const float* px, const float* p
   return 0;
 }
 
-// ---- objects under a bih (nested_update_kernels.hpp): the pieces the three updates share with glome_scene_bih_refit ----
+// ---- updates of a committed scene: what the four updates share ----
+// every slot of the context may have a launch in flight that reads the pools about to be written
+static int quiesce(glome_ctx* ctx) {
+  HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+  for (auto& sl : ctx->slots)
+    if (sl.launched_on && sl.launched_on != ctx->stream) (void)hipStreamSynchronize(sl.launched_on);
+  (void)hipGetLastError();  // (a stream its owner has destroyed since must not be this call's error: other_slots_busy)
+  return 0;
+}
+// What a blocking form does once it has quiesced and staged: its device form between the context's event pair, the wait, the error word.
+template <class Dev> static int run_blocking(glome_ctx* ctx, float* gpu_ms, Dev dev) {
+  if (gpu_ms) HIPCHK(ctx, hipEventRecord(ctx->ev0, ctx->stream));
+  if (int rc = dev()) return rc;
+  if (gpu_ms) HIPCHK(ctx, hipEventRecord(ctx->ev1, ctx->stream));
+  HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+  if (gpu_ms) HIPCHK(ctx, hipEventElapsedTime(gpu_ms, ctx->ev0, ctx->ev1));
+  return check_device_error(ctx);
+}
+// One event pair per update while timing is on; with the update's split switch (GLOME_DEBUG_MESH_UPDATE_SPLIT,
+// GLOME_DEBUG_BIH_UPDATE_SPLIT: tools/probe/*_update_rate.py) one per stage -- records, levels, bound.
+struct UpdateSpan {
+  glome_ctx* ctx;
+  bool split;
+  hipEvent_t e0 = nullptr, e1 = nullptr;
+  UpdateSpan(glome_ctx* c, const char* split_env) : ctx(c), split(split_env && getenv(split_env) != nullptr) {}
+  hipError_t begin() { return ctx->timing && launch_events(ctx, e0, e1) ? hipEventRecord(e0, ctx->stream) : (e1 = nullptr, hipSuccess); }
+  hipError_t end() { return e1 ? hipEventRecord(e1, ctx->stream) : hipSuccess; }
+  hipError_t stage() {
+    if (!split) return hipSuccess;
+    const hipError_t e = end();
+    return e != hipSuccess ? e : begin();
+  }
+};
+// n lanes, 64 to a block, at most CUs * 128 blocks -- the kernels stride (upd::for_lanes); no launch for no lane
+template <class K, class... Args> static void launch_lanes(glome_ctx* ctx, K kernel, uint32_t n, Args... args) {
+  if (!n) return;
+  const uint32_t max_items = (uint32_t)ctx->prop.multiProcessorCount * 32u * 4u;
+  hipLaunchKernelGGL(kernel, dim3(std::min<uint32_t>((n + 63u) >> 6, max_items)), dim3(64), 0, ctx->stream, args...);
+}
+static void mark_launched(glome_ctx* ctx) { ctx->slot().launched = true; ctx->slot().launched_on = ctx->stream; }
+// an update's workspace, `words` float4, allocated at the object's first update and kept until glome_scene_release
+static int ensure_ws(glome_scene* s, float4*& d_ws, size_t words) {
+  if (d_ws) return 0;
+  void* d = nullptr;
+  HIPCHK(s->ctx, hipMalloc(&d, words * sizeof(float4)));
+  s->allocs.push_back(d);
+  d_ws = (float4*)d;
+  return 0;
+}
+// the answer with the switch off or on (Flattener::mark_updatable, mark_nested), and the refusal's text
+static int accepted(glome_scene* s, const char* what, const UpdateAnswer& plain, const NestedAnswer& nested) {
+  const UpdateAnswer& A = s->nested_on ? nested : plain;
+  if (!A.ok) { s->ctx->err = std::string(what) + " refused: " + A.why_not; return GLOME_E_INVALID; }
+  return 0;
+}
+// The fp32 box over all points of an array into a header's two box words: partial boxes, then their fold from +-start (update_common.hpp).
+static void launch_bound32(glome_ctx* ctx, const double* pts_dev, uint32_t n_pts, float4* part, float start, float4* hdr) {
+  const uint32_t blocks = std::max<uint32_t>(1u, std::min<uint32_t>((n_pts + upd::kBoundBlock - 1) / upd::kBoundBlock, (uint32_t)upd::kBoundMaxBlocks));
+  upd::DBoundArgs A;
+  A.verts = pts_dev; A.nv = n_pts; A.part = part; A.error = &ctx->slot().d_counters->error;
+  hipLaunchKernelGGL(upd::k_points_bound, dim3(blocks), dim3(upd::kBoundBlock), 0, ctx->stream, A);
+  hipLaunchKernelGGL(upd::k_bound_store, dim3(1), dim3(64), 0, ctx->stream, (const float4*)part, blocks, start, hdr);
+}
+// A bih's planes: a launch of k_bih_level per tree level, deepest first.  merged_off (the triangle bih alone, behind its switch): the
+// device copy of level_off, and every run of two or more narrow levels goes to ONE block of k_bih_levels_merged instead.
+static void launch_levels(glome_ctx* ctx, const bihupd::DLevelArgs& A, const std::vector<uint32_t>& level_off, const uint32_t* merged_off) {
+  const size_t levels = level_off.empty() ? 0 : level_off.size() - 1;
+  auto width = [&](size_t l) { return level_off[l + 1] - level_off[l]; };
+  for (size_t l = 0; l < levels;) {
+    size_t e = l;
+    while (merged_off && e < levels && width(e) <= (uint32_t)bihupd::kMergeBlock) e++;
+    if (e > l + 1) {  // a run of narrow levels: one block
+      hipLaunchKernelGGL(bihupd::k_bih_levels_merged, dim3(1), dim3(bihupd::kMergeBlock), 0, ctx->stream, A, merged_off, (uint32_t)l, (uint32_t)e);
+      l = e;
+    } else {
+      launch_lanes(ctx, bihupd::k_bih_level, width(l), A, level_off[l], width(l));
+      l++;
+    }
+  }
+}
+
+// ---- objects under a bih, and the item bihs above them (item_bih_update_kernels.hpp) ----
 // An updated object's fp64 bound into its row of the bounds table -- two launches on the current stream -- and the trees above it stale.
 static void nested_points_bound(glome_scene* s, int node, const double* pts_dev, uint32_t n_pts, double start, const std::vector<int>& above) {
   glome_ctx* ctx = s->ctx;
-  const uint32_t blocks = std::min<uint32_t>((n_pts + nestupd::kFoldBlock - 1) / nestupd::kFoldBlock, (uint32_t)nestupd::kPartMaxBlocks);
-  if (blocks) hipLaunchKernelGGL(nestupd::k_nest_points_part, dim3(blocks), dim3(nestupd::kFoldBlock), 0, ctx->stream, pts_dev, n_pts, s->d_live_part);
-  hipLaunchKernelGGL(nestupd::k_nest_fold_store, dim3(1), dim3(nestupd::kFoldBlock), 0, ctx->stream, (const double*)s->d_live_part, blocks, start,
+  const uint32_t blocks = std::min<uint32_t>((n_pts + itemupd::kFoldBlock - 1) / itemupd::kFoldBlock, (uint32_t)itemupd::kPartMaxBlocks);
+  if (blocks) hipLaunchKernelGGL(itemupd::k_nest_points_part, dim3(blocks), dim3(itemupd::kFoldBlock), 0, ctx->stream, pts_dev, n_pts, s->d_live_part);
+  hipLaunchKernelGGL(itemupd::k_nest_fold_store, dim3(1), dim3(itemupd::kFoldBlock), 0, ctx->stream, (const double*)s->d_live_part, blocks, start,
                      s->d_live + 6 * (size_t)s->live_slot.at(node), &ctx->slot().d_counters->error);
   s->stale.insert(above.begin(), above.end());
 }
+// An item bih's workspace, in float4 from its start: two words per record of the tree's span (plane-form rows), two per node slot, two
+// per item (box-form rows), then the bound's partial boxes.
+struct TreeWs {
+  uint32_t n_items;
+  size_t node, box, part, words;
+  explicit TreeWs(const InstBihInfo& B)
+      : n_items((uint32_t)B.kind.size()), node(2 * (size_t)B.rec_span), box(node + 2 * (size_t)B.n_slots), part(box + 2 * (size_t)n_items), words(part + 2 * (size_t)upd::kBoundMaxBlocks) {}
+};
 // A tree's workspace and tables, allocated and given the commit-time rows of all its items at the first update or refit that touches it
 // (blocking calls: nothing has read them yet, and the launches that follow are ordered after the copies).
 static int ensure_tree_ws(glome_scene* s, glome_scene::InstBih& m) {
   glome_ctx* ctx = s->ctx;
   if (m.d_ws) return 0;
   const InstBihInfo& B = m.info;
-  const size_t n_items = B.rows.size() / 4, words = 2 * ((size_t)B.rec_span + B.n_slots + n_items + meshupd::kBoundMaxBlocks);
-  std::vector<float4> init(words, make_float4(0.0f, 0.0f, 0.0f, 0.0f));
-  float4* box = init.data() + 2 * ((size_t)B.rec_span + B.n_slots);
+  const TreeWs W(B);
+  const size_t n_items = W.n_items;
+  std::vector<float4> init(W.words, make_float4(0.0f, 0.0f, 0.0f, 0.0f));
+  float4* box = init.data() + W.box;
   for (size_t j = 0; j < n_items; j++) {
     const F4* r = &B.rows[4 * j];
     float4* plane = init.data() + 2 * (size_t)m.info.rec_off[j];
@@ -1091,18 +1180,18 @@ static int ensure_tree_ws(glome_scene* s, glome_scene::InstBih& m) {
   std::vector<double> d64(30 * n_items, 0.0);  // box64, then the matrices
   std::copy(B.box64.begin(), B.box64.end(), d64.begin());
   std::vector<uint2> live;
-  std::vector<uint32_t> item_live(n_items, nestupd::kNoLive);
+  std::vector<uint32_t> item_live(n_items, itemupd::kNoLive);
   for (size_t j = 0; j < n_items; j++) {
     if (B.xf_at[j] >= 0) std::copy(B.live_xf.begin() + 24 * (ptrdiff_t)B.xf_at[j], B.live_xf.begin() + 24 * (ptrdiff_t)B.xf_at[j] + 24, d64.begin() + 6 * (ptrdiff_t)n_items + 24 * (ptrdiff_t)j);
     if (B.kind[j] != InstBihInfo::kDirectLive && B.kind[j] != InstBihInfo::kInstancedLive) continue;
     const uint32_t row = s->live_slot.at(B.live[j]);
-    live.push_back(make_uint2((uint32_t)j, row | (B.kind[j] == InstBihInfo::kInstancedLive ? nestupd::kInstancedBit : 0u)));
+    live.push_back(make_uint2((uint32_t)j, row | (B.kind[j] == InstBihInfo::kInstancedLive ? itemupd::kInstancedBit : 0u)));
     if (B.kind[j] == InstBihInfo::kInstancedLive) item_live[j] = row;
   }
   void *d = nullptr, *d2 = nullptr;
-  HIPCHK(ctx, hipMalloc(&d, words * sizeof(float4)));
+  HIPCHK(ctx, hipMalloc(&d, W.words * sizeof(float4)));
   s->allocs.push_back(d);
-  HIPCHK(ctx, hipMemcpy(d, init.data(), words * sizeof(float4), hipMemcpyHostToDevice));
+  HIPCHK(ctx, hipMemcpy(d, init.data(), W.words * sizeof(float4), hipMemcpyHostToDevice));
   HIPCHK(ctx, hipMalloc(&d2, std::max<size_t>(1, d64.size()) * sizeof(double)));
   s->allocs.push_back(d2);
   if (!d64.empty()) HIPCHK(ctx, hipMemcpy(d2, d64.data(), d64.size() * sizeof(double), hipMemcpyHostToDevice));
@@ -1111,6 +1200,25 @@ static int ensure_tree_ws(glome_scene* s, glome_scene::InstBih& m) {
   m.d_ws = (float4*)d;
   m.info.rows = {}; m.info.box64 = {}; m.info.live_xf = {};
   return 0;
+}
+// An item bih made again from its workspace rows, which the caller has brought up to date: the planes, a launch per tree level over the
+// plane-form rows (the triangle bih's own kernel); the header's box, the fold of the box-form rows from box_empty; and -- fold64 -- the
+// tree's own fp64 bound, the join of its items' boxes from box_empty, into its row of the bounds table.
+static void refit_item_tree(glome_scene* s, int bih_id, glome_scene::InstBih& m, bool fold64) {
+  glome_ctx* ctx = s->ctx;
+  const InstBihInfo& B = m.info;
+  const TreeWs W(B);
+  bihupd::DLevelArgs A;
+  A.nodes = m.d_levels; A.bihnodes = (float4*)s->dev.bihnodes; A.pknodes = nullptr;
+  A.ws_tri = m.d_ws; A.ws_node = m.d_ws + W.node; A.first_rec = B.first_rec; A.first_slot = B.first_slot;
+  launch_levels(ctx, A, B.level_off, nullptr);
+  float4* part = m.d_ws + W.part;
+  const uint32_t blocks = std::max<uint32_t>(1u, std::min<uint32_t>((W.n_items + 63u) >> 6, (uint32_t)upd::kBoundMaxBlocks));
+  hipLaunchKernelGGL(itemupd::k_inst_box_fold, dim3(blocks), dim3(64), 0, ctx->stream, (const float4*)(m.d_ws + W.box), W.n_items, part);
+  hipLaunchKernelGGL(upd::k_bound_store, dim3(1), dim3(64), 0, ctx->stream, (const float4*)part, blocks, (float)kInfinity, (float4*)s->dev.bihhdr + 3 * (size_t)B.hdr);
+  if (fold64)
+    hipLaunchKernelGGL(itemupd::k_nest_fold_store, dim3(1), dim3(itemupd::kFoldBlock), 0, ctx->stream, (const double*)m.d_box64, W.n_items, kInfinity,
+                       s->d_live + 6 * (size_t)s->live_slot.at(bih_id), &ctx->slot().d_counters->error);
 }
 
 // ---- new vertices for a committed Mesh (mesh_update_kernels.hpp) ----
@@ -1123,7 +1231,7 @@ static int mesh_update_check(glome_scene* s, int32_t mesh_id, const void* verts,
   if (nv != U.nv) { ctx->err = "mesh update: the mesh has " + std::to_string(U.nv) + " vertices, not " + std::to_string(nv); return GLOME_E_INVALID; }
   if (nn != U.nn) { ctx->err = "mesh update: the mesh has " + std::to_string(U.nn) + " normals, not " + std::to_string(nn); return GLOME_E_INVALID; }
   if ((nv && !verts) || (nn && !norms)) { ctx->err = "mesh update: null vertex / normal array"; return GLOME_E_INVALID; }
-  if (!(s->nested_on ? U.nested.ok : U.updatable)) { ctx->err = "mesh update refused: " + (s->nested_on ? U.nested.why_not : U.why_not); return GLOME_E_INVALID; }
+  if (int rc = accepted(s, "mesh update", U.plain, U.nested)) return rc;
   *out = &it->second;
   return 0;
 }
@@ -1134,47 +1242,29 @@ int glome_scene_mesh_update_dev(glome_scene* s, int32_t mesh_id, const double* v
   if (int rc = mesh_update_check(s, mesh_id, verts_dev, nv, norms_dev, nn, &m)) return rc;
   HIPCHK(ctx, hipSetDevice(ctx->device));
   const MeshUpdateInfo& U = m->info;
-  if (!m->d_ws) {  // 32 bytes per record and the bound's partial boxes: kept until glome_scene_release
-    void* d = nullptr;
-    HIPCHK(ctx, hipMalloc(&d, ((size_t)U.n_tris + meshupd::kBoundMaxBlocks) * 2 * sizeof(float4)));
-    s->allocs.push_back(d);
-    m->d_ws = (float4*)d;
-  }
-  hipStream_t st = ctx->stream;
-  const uint32_t max_items = (uint32_t)ctx->prop.multiProcessorCount * 32u * 4u;
-  // one event pair per update while timing is on; with GLOME_DEBUG_MESH_UPDATE_SPLIT one per stage -- records, levels, bound -- (tools/probe/mesh_update_rate.py)
-  const bool split = getenv("GLOME_DEBUG_MESH_UPDATE_SPLIT") != nullptr;
-  hipEvent_t e0 = nullptr, e1 = nullptr;
-  auto begin = [&]() -> hipError_t { return ctx->timing && launch_events(ctx, e0, e1) ? hipEventRecord(e0, st) : (e1 = nullptr, hipSuccess); };
-  auto end = [&]() -> hipError_t { return e1 ? hipEventRecord(e1, st) : hipSuccess; };
-  HIPCHK(ctx, begin());
+  if (int rc = ensure_ws(s, m->d_ws, 2 * ((size_t)U.n_tris + upd::kBoundMaxBlocks))) return rc;  // a box per record, and the bound's partial boxes
+  UpdateSpan span(ctx, "GLOME_DEBUG_MESH_UPDATE_SPLIT");
+  HIPCHK(ctx, span.begin());
   {
     meshupd::DTrisArgs A;
     A.verts = verts_dev; A.norms = norms_dev; A.rows = (const int4*)m->d_rows;
     A.mtris = (float4*)s->dev.mtris + 3 * (size_t)U.first_tri; A.trinorms = (float4*)s->dev.trinorms; A.ws = m->d_ws; A.n = U.n_tris;
-    hipLaunchKernelGGL(meshupd::k_mesh_tris, dim3(std::min<uint32_t>((U.n_tris + 63u) >> 6, max_items)), dim3(64), 0, st, A);
+    launch_lanes(ctx, meshupd::k_mesh_tris, U.n_tris, A);
   }
-  if (split) { HIPCHK(ctx, end()); HIPCHK(ctx, begin()); }
+  HIPCHK(ctx, span.stage());
   for (size_t l = 0; l + 1 < U.level_off.size(); l++) {
     meshupd::DLevelArgs A;
     A.nodes = m->d_levels + U.level_off[l]; A.n = U.level_off[l + 1] - U.level_off[l];
     A.meshnodes = (float4*)s->dev.meshnodes; A.mtrimeta = (const uint4*)s->dev.mtrimeta; A.ws = m->d_ws; A.first_tri = U.first_tri;
-    hipLaunchKernelGGL(meshupd::k_mesh_refit_level, dim3(std::min<uint32_t>((A.n + 63u) >> 6, max_items)), dim3(64), 0, st, A);
+    launch_lanes(ctx, meshupd::k_mesh_refit_level, A.n, A);
   }
-  if (split) { HIPCHK(ctx, end()); HIPCHK(ctx, begin()); }
-  if (nv > 0) {
-    const uint32_t blocks = std::min<uint32_t>(((uint32_t)nv + meshupd::kBoundBlock - 1) / meshupd::kBoundBlock, (uint32_t)meshupd::kBoundMaxBlocks);
-    float4* part = m->d_ws + 2 * (size_t)U.n_tris;
-    meshupd::DBoundArgs A;
-    A.verts = verts_dev; A.nv = (uint32_t)nv; A.part = part; A.error = &ctx->slot().d_counters->error;
-    hipLaunchKernelGGL(meshupd::k_mesh_bound, dim3(blocks), dim3(meshupd::kBoundBlock), 0, st, A);
-    hipLaunchKernelGGL(meshupd::k_mesh_bound_store, dim3(1), dim3(64), 0, st, (const float4*)part, blocks, (float4*)s->dev.meshhdr + 2 * (size_t)U.hdr);
-  }
+  HIPCHK(ctx, span.stage());
   // box_of_points starts from a vertex (real infinities); a mesh of no vertices keeps box_empty
+  if (nv > 0) launch_bound32(ctx, verts_dev, (uint32_t)nv, m->d_ws + 2 * (size_t)U.n_tris, __builtin_huge_valf(), (float4*)s->dev.meshhdr + 2 * (size_t)U.hdr);
   if (s->nested_on && !U.nested.above.empty()) nested_points_bound(s, mesh_id, verts_dev, (uint32_t)nv, nv > 0 ? __builtin_huge_val() : kInfinity, U.nested.above);
   HIPCHK(ctx, hipGetLastError());
-  HIPCHK(ctx, end());
-  ctx->slot().launched = true; ctx->slot().launched_on = ctx->stream;  // (a vertex that is not finite is reported at the next synchronize)
+  HIPCHK(ctx, span.end());
+  mark_launched(ctx);  // (a vertex that is not finite is reported at the next synchronize)
   return 0;
 }
 int glome_scene_mesh_update(glome_scene* s, int32_t mesh_id, const double* verts, int nv, const double* norms, int nn, float* gpu_ms) {
@@ -1186,21 +1276,12 @@ int glome_scene_mesh_update(glome_scene* s, int32_t mesh_id, const double* verts
   for (size_t k = 0; k < 3 * (size_t)nv; k++) if (!std::isfinite(verts[k])) { ctx->err = "mesh update: a vertex coordinate is not finite"; return GLOME_E_INVALID; }
   for (size_t k = 0; k < 3 * (size_t)nn; k++) if (!std::isfinite(norms[k])) { ctx->err = "mesh update: a normal coordinate is not finite"; return GLOME_E_INVALID; }
   HIPCHK(ctx, hipSetDevice(ctx->device));
-  // every slot of the context may have a launch in flight that reads the pools about to be written
-  HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-  for (auto& sl : ctx->slots)
-    if (sl.launched_on && sl.launched_on != ctx->stream) (void)hipStreamSynchronize(sl.launched_on);
-  (void)hipGetLastError();  // (a stream its owner has destroyed since must not be this call's error: other_slots_busy)
+  if (int rc = quiesce(ctx)) return rc;
   Staging stg{ctx, {}};
   double* dv = stg.in<double>(verts, 3 * (size_t)nv);
   double* dn = nn ? stg.in<double>(norms, 3 * (size_t)nn) : nullptr;
   if (!dv || (nn && !dn)) { ctx->err = "staging allocation failed"; return GLOME_E_HIP; }
-  if (gpu_ms) HIPCHK(ctx, hipEventRecord(ctx->ev0, ctx->stream));
-  if (int rc = glome_scene_mesh_update_dev(s, mesh_id, dv, nv, dn, nn)) return rc;
-  if (gpu_ms) HIPCHK(ctx, hipEventRecord(ctx->ev1, ctx->stream));
-  HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-  if (gpu_ms) HIPCHK(ctx, hipEventElapsedTime(gpu_ms, ctx->ev0, ctx->ev1));
-  return check_device_error(ctx);
+  return run_blocking(ctx, gpu_ms, [&] { return glome_scene_mesh_update_dev(s, mesh_id, dv, nv, dn, nn); });
 }
 
 // ---- new triangles for a committed triangle bih (bih_update_kernels.hpp) ----
@@ -1212,7 +1293,7 @@ static int bih_update_check(glome_scene* s, int32_t bih_id, const void* pts9, in
   const BihUpdateInfo& U = it->second.info;
   if (n != U.n_items) { ctx->err = "bih update: the bih has " + std::to_string(U.n_items) + " items, not " + std::to_string(n); return GLOME_E_INVALID; }
   if (n && !pts9) { ctx->err = "bih update: null triangle array"; return GLOME_E_INVALID; }
-  if (!(s->nested_on ? U.nested.ok : U.updatable)) { ctx->err = "bih update refused: " + (s->nested_on ? U.nested.why_not : U.why_not); return GLOME_E_INVALID; }
+  if (int rc = accepted(s, "bih update", U.plain, U.nested)) return rc;
   *out = &it->second;
   return 0;
 }
@@ -1223,61 +1304,33 @@ int glome_scene_bih_update_dev(glome_scene* s, int32_t bih_id, const double* pts
   if (int rc = bih_update_check(s, bih_id, pts9_dev, n, &m)) return rc;
   HIPCHK(ctx, hipSetDevice(ctx->device));
   const BihUpdateInfo& U = m->info;
-  if (!m->d_ws) {  // 32 bytes per record and per node slot, and the bound's partial boxes: kept until glome_scene_release
-    void* d = nullptr;
-    HIPCHK(ctx, hipMalloc(&d, ((size_t)U.n_tris + U.n_slots + meshupd::kBoundMaxBlocks) * 2 * sizeof(float4)));
-    s->allocs.push_back(d);
-    m->d_ws = (float4*)d;
-  }
-  hipStream_t st = ctx->stream;
-  const uint32_t max_items = (uint32_t)ctx->prop.multiProcessorCount * 32u * 4u;
-  // one event pair per update while timing is on; with GLOME_DEBUG_BIH_UPDATE_SPLIT one per stage -- records, levels, bound.  The levels run
-  // a launch each: the merged launch of the narrow levels (k_bih_levels_merged) stays behind GLOME_DEBUG_BIH_UPDATE_MERGED until
-  // tools/probe/bih_update_rate.py has shown on the hardware that it wins beyond the run-to-run spread
-  const bool split = getenv("GLOME_DEBUG_BIH_UPDATE_SPLIT") != nullptr, per_level = getenv("GLOME_DEBUG_BIH_UPDATE_MERGED") == nullptr;
-  hipEvent_t e0 = nullptr, e1 = nullptr;
-  auto begin = [&]() -> hipError_t { return ctx->timing && launch_events(ctx, e0, e1) ? hipEventRecord(e0, st) : (e1 = nullptr, hipSuccess); };
-  auto end = [&]() -> hipError_t { return e1 ? hipEventRecord(e1, st) : hipSuccess; };
-  HIPCHK(ctx, begin());
-  if (U.n_tris) {
+  // a box per record and per node slot, and the bound's partial boxes
+  if (int rc = ensure_ws(s, m->d_ws, 2 * ((size_t)U.n_tris + U.n_slots + upd::kBoundMaxBlocks))) return rc;
+  // The levels run a launch each: the merged launch of the narrow levels (k_bih_levels_merged) stays behind GLOME_DEBUG_BIH_UPDATE_MERGED
+  // until tools/probe/bih_update_rate.py has shown on the hardware that it wins beyond the run-to-run spread
+  const bool merged = getenv("GLOME_DEBUG_BIH_UPDATE_MERGED") != nullptr;
+  UpdateSpan span(ctx, "GLOME_DEBUG_BIH_UPDATE_SPLIT");
+  HIPCHK(ctx, span.begin());
+  {
     bihupd::DTrisArgs A;
     A.pts9 = pts9_dev; A.rows = (const uint2*)m->d_rows; A.tris = (float4*)s->dev.tris + 3 * (size_t)U.first_tri; A.tripairs = (float*)s->dev.tripairs;
     A.ws = m->d_ws; A.n = U.n_tris;
-    hipLaunchKernelGGL(bihupd::k_bih_tris, dim3(std::min<uint32_t>((U.n_tris + 63u) >> 6, max_items)), dim3(64), 0, st, A);
+    launch_lanes(ctx, bihupd::k_bih_tris, U.n_tris, A);
   }
-  if (split) { HIPCHK(ctx, end()); HIPCHK(ctx, begin()); }
+  HIPCHK(ctx, span.stage());
   {
     bihupd::DLevelArgs A;
     A.nodes = m->d_levels; A.bihnodes = (float4*)s->dev.bihnodes; A.pknodes = U.pk ? (float4*)s->dev.pknodes : nullptr;
     A.ws_tri = m->d_ws; A.ws_node = m->d_ws + 2 * (size_t)U.n_tris; A.first_rec = U.first_rec; A.first_slot = U.first_slot;
-    const size_t levels = U.level_off.empty() ? 0 : U.level_off.size() - 1;
-    auto width = [&](size_t l) { return U.level_off[l + 1] - U.level_off[l]; };
-    for (size_t l = 0; l < levels;) {
-      size_t e = l;
-      while (!per_level && e < levels && width(e) <= (uint32_t)bihupd::kMergeBlock) e++;
-      if (e > l + 1) {  // a run of narrow levels: one block
-        hipLaunchKernelGGL(bihupd::k_bih_levels_merged, dim3(1), dim3(bihupd::kMergeBlock), 0, st, A, m->d_level_off, (uint32_t)l, (uint32_t)e);
-        l = e;
-      } else {
-        hipLaunchKernelGGL(bihupd::k_bih_level, dim3(std::min<uint32_t>((width(l) + 63u) >> 6, max_items)), dim3(64), 0, st, A, U.level_off[l], width(l));
-        l++;
-      }
-    }
+    launch_levels(ctx, A, U.level_off, merged ? m->d_level_off : nullptr);
   }
-  if (split) { HIPCHK(ctx, end()); HIPCHK(ctx, begin()); }
-  {
-    const uint32_t nv = 3u * (uint32_t)n;
-    const uint32_t blocks = std::max<uint32_t>(1u, std::min<uint32_t>((nv + meshupd::kBoundBlock - 1) / meshupd::kBoundBlock, (uint32_t)meshupd::kBoundMaxBlocks));
-    float4* part = m->d_ws + 2 * ((size_t)U.n_tris + U.n_slots);
-    meshupd::DBoundArgs A;
-    A.verts = pts9_dev; A.nv = nv; A.part = part; A.error = &ctx->slot().d_counters->error;
-    hipLaunchKernelGGL(meshupd::k_mesh_bound, dim3(blocks), dim3(meshupd::kBoundBlock), 0, st, A);
-    hipLaunchKernelGGL(bihupd::k_bih_bound_store, dim3(1), dim3(64), 0, st, (const float4*)part, blocks, (float4*)s->dev.bihhdr + 3 * (size_t)U.hdr);
-  }
-  if (s->nested_on && !U.nested.above.empty()) nested_points_bound(s, bih_id, pts9_dev, 3u * (uint32_t)n, kInfinity, U.nested.above);  // (the join of the triangles' boxes, from box_empty)
+  HIPCHK(ctx, span.stage());
+  // the join of the triangles' boxes, from box_empty: in fp32 into the header, in fp64 into the bounds table
+  launch_bound32(ctx, pts9_dev, 3u * (uint32_t)n, m->d_ws + 2 * ((size_t)U.n_tris + U.n_slots), (float)kInfinity, (float4*)s->dev.bihhdr + 3 * (size_t)U.hdr);
+  if (s->nested_on && !U.nested.above.empty()) nested_points_bound(s, bih_id, pts9_dev, 3u * (uint32_t)n, kInfinity, U.nested.above);
   HIPCHK(ctx, hipGetLastError());
-  HIPCHK(ctx, end());
-  ctx->slot().launched = true; ctx->slot().launched_on = ctx->stream;  // (a coordinate that is not finite is reported at the next synchronize)
+  HIPCHK(ctx, span.end());
+  mark_launched(ctx);  // (a coordinate that is not finite is reported at the next synchronize)
   return 0;
 }
 int glome_scene_bih_update(glome_scene* s, int32_t bih_id, const double* pts9, int n, float* gpu_ms) {
@@ -1288,23 +1341,14 @@ int glome_scene_bih_update(glome_scene* s, int32_t bih_id, const double* pts9, i
   if (int rc = bih_update_check(s, bih_id, pts9, n, &m)) return rc;
   for (size_t k = 0; k < 9 * (size_t)n; k++) if (!std::isfinite(pts9[k])) { ctx->err = "bih update: a vertex coordinate is not finite"; return GLOME_E_INVALID; }
   HIPCHK(ctx, hipSetDevice(ctx->device));
-  // every slot of the context may have a launch in flight that reads the pools about to be written
-  HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-  for (auto& sl : ctx->slots)
-    if (sl.launched_on && sl.launched_on != ctx->stream) (void)hipStreamSynchronize(sl.launched_on);
-  (void)hipGetLastError();  // (a stream its owner has destroyed since must not be this call's error: other_slots_busy)
+  if (int rc = quiesce(ctx)) return rc;
   Staging stg{ctx, {}};
   double* dp = stg.in<double>(pts9, 9 * (size_t)n);
   if (!dp) { ctx->err = "staging allocation failed"; return GLOME_E_HIP; }
-  if (gpu_ms) HIPCHK(ctx, hipEventRecord(ctx->ev0, ctx->stream));
-  if (int rc = glome_scene_bih_update_dev(s, bih_id, dp, n)) return rc;
-  if (gpu_ms) HIPCHK(ctx, hipEventRecord(ctx->ev1, ctx->stream));
-  HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-  if (gpu_ms) HIPCHK(ctx, hipEventElapsedTime(gpu_ms, ctx->ev0, ctx->ev1));
-  return check_device_error(ctx);
+  return run_blocking(ctx, gpu_ms, [&] { return glome_scene_bih_update_dev(s, bih_id, dp, n); });
 }
 
-// ---- new matrices for committed Instances (instance_update_kernels.hpp) ----
+// ---- new matrices for committed Instances (item_bih_update_kernels.hpp) ----
 // what both forms refuse before anything is launched; out[k] = the tables of ids[k]
 static int instance_update_check(glome_scene* s, const int32_t* ids, const void* xfms, int n, std::vector<const InstanceUpdateInfo*>& out) {
   glome_ctx* ctx = s->ctx;
@@ -1313,7 +1357,7 @@ static int instance_update_check(glome_scene* s, const int32_t* ids, const void*
   for (int k = 0; k < n; k++) {
     auto it = s->insts.find(ids[k]);
     if (it == s->insts.end()) { ctx->err = "instance update: node " + std::to_string(ids[k]) + " is not an Instance of this scene"; return GLOME_E_INVALID; }
-    if (!(s->nested_on ? it->second.nested.ok : it->second.updatable)) { ctx->err = "instance update refused: " + (s->nested_on ? it->second.nested.why_not : it->second.why_not); return GLOME_E_INVALID; }
+    if (int rc = accepted(s, "instance update", it->second.plain, it->second.nested)) return rc;
     out.push_back(&it->second);
   }
   std::vector<int32_t> sorted(ids, ids + n);
@@ -1356,66 +1400,40 @@ int glome_scene_instance_update_dev(glome_scene* s, const int32_t* ids, const do
   std::copy(rows.begin(), rows.end(), stage.h);
   // the workspaces of the bihs this call refits, allocated and given the commit-time rows of all their items at their first update
   for (auto& pb : per_bih) if (int rc = ensure_tree_ws(s, s->ibihs.at(pb.first))) return rc;
-  const uint32_t max_items = (uint32_t)ctx->prop.multiProcessorCount * 32u * 4u;
-  auto grid = [&](uint32_t lanes) { return dim3(std::max<uint32_t>(1u, std::min<uint32_t>((lanes + 63u) >> 6, max_items))); };
-  // one event pair per update while timing is on
-  hipEvent_t e0 = nullptr, e1 = nullptr;
-  if (ctx->timing && launch_events(ctx, e0, e1)) HIPCHK(ctx, hipEventRecord(e0, st)); else e1 = nullptr;
+  UpdateSpan span(ctx, nullptr);
+  HIPCHK(ctx, span.begin());
   HIPCHK(ctx, hipMemcpyAsync(s->d_inst_rows, stage.h, rows.size() * sizeof(uint2), hipMemcpyHostToDevice, st));
   HIPCHK(ctx, hipEventRecord(stage.ev, st));
   stage.pending = true;
   unsigned int* err = &ctx->slot().d_counters->error;
   {
-    instupd::DXfmArgs A;
+    itemupd::DXfmArgs A;
     A.xfms = xfms_dev; A.rows = s->d_inst_rows; A.pool = (float4*)s->dev.xfms; A.n = n_xfm; A.error = err;
-    hipLaunchKernelGGL(instupd::k_inst_xfm, grid(n_xfm), dim3(64), 0, st, A);
+    launch_lanes(ctx, itemupd::k_inst_xfm, n_xfm, A);
   }
   uint32_t at = n_xfm;
   for (auto& pb : per_bih) {
     glome_scene::InstBih& m = s->ibihs.at(pb.first);
-    const InstBihInfo& B = m.info;
-    const uint32_t n_named = (uint32_t)pb.second.size(), n_items = (uint32_t)(B.child_bound.size() / 6);
-    float4* ws_plane = m.d_ws;
-    float4* ws_node = ws_plane + 2 * (size_t)B.rec_span;
-    float4* ws_box = ws_node + 2 * (size_t)B.n_slots;
-    float4* part = ws_box + 2 * (size_t)n_items;
+    const TreeWs W(m.info);
+    const uint32_t n_named = (uint32_t)pb.second.size();
     // A tree whose items hang on objects that move keeps its matrices and fp64 boxes ALWAYS, switch on or off, from its first update:
     // a later refit reads an instanced item's matrix from the tree's table, whenever the Instance was last named.  So does any tree
-    // while the switch is on (its own fp64 bound feeds the tree above).  k_nest_inst_named takes a live child's bound from the bounds
-    // table once that exists, and the commit's before: until the switch has been on no object under a bih can have moved.  Every other
-    // update is what it was.
+    // while the switch is on (its own fp64 bound feeds the tree above).  k_nest_inst_named<true> takes a live child's bound from the
+    // bounds table once that exists, and the commit's before: until the switch has been on no object under a bih can have moved.
+    // Every other update runs the instance without the tables (item_bih_update_kernels.hpp: why both exist).
     const bool nested = m.n_live || (s->d_live && s->nested_on);
-    if (nested) {
-      nestupd::DNamedArgs A;
-      A.xfms = xfms_dev; A.rows = s->d_inst_rows + at; A.child_bounds = m.d_bounds; A.item_live = m.d_item_live; A.bounds = s->d_live; A.xf = m.d_xf; A.rec_off = m.d_rec_off;
-      A.ws_plane = ws_plane; A.ws_box = ws_box; A.box64 = m.d_box64; A.n = n_named; A.error = err;
-      hipLaunchKernelGGL(nestupd::k_nest_inst_named, grid(n_named), dim3(64), 0, st, A);
-    } else {
-      instupd::DItemArgs A;
-      A.xfms = xfms_dev; A.rows = s->d_inst_rows + at; A.bounds = m.d_bounds; A.rec_off = m.d_rec_off; A.ws_plane = ws_plane; A.ws_box = ws_box; A.n = n_named; A.error = err;
-      hipLaunchKernelGGL(instupd::k_inst_item_box, grid(n_named), dim3(64), 0, st, A);
-    }
+    itemupd::DNamedArgs A;
+    A.xfms = xfms_dev; A.rows = s->d_inst_rows + at; A.child_bounds = m.d_bounds; A.item_live = m.d_item_live; A.bounds = s->d_live; A.xf = m.d_xf; A.rec_off = m.d_rec_off;
+    A.ws_plane = m.d_ws; A.ws_box = m.d_ws + W.box; A.box64 = m.d_box64; A.n = n_named; A.error = err;
+    launch_lanes(ctx, nested ? itemupd::k_nest_inst_named<true> : itemupd::k_nest_inst_named<false>, n_named, A);
     at += n_named;
-    {  // the planes, a launch per tree level, deepest first: the triangle bih's own kernel over the plane-form rows
-      bihupd::DLevelArgs A;
-      A.nodes = m.d_levels; A.bihnodes = (float4*)s->dev.bihnodes; A.pknodes = nullptr;
-      A.ws_tri = ws_plane; A.ws_node = ws_node; A.first_rec = B.first_rec; A.first_slot = B.first_slot;
-      for (size_t l = 0; l + 1 < B.level_off.size(); l++) {
-        const uint32_t width = B.level_off[l + 1] - B.level_off[l];
-        hipLaunchKernelGGL(bihupd::k_bih_level, grid(width), dim3(64), 0, st, A, B.level_off[l], width);
-      }
-    }
-    const uint32_t blocks = std::max<uint32_t>(1u, std::min<uint32_t>((n_items + 63u) >> 6, (uint32_t)meshupd::kBoundMaxBlocks));
-    hipLaunchKernelGGL(instupd::k_inst_box_fold, dim3(blocks), dim3(64), 0, st, (const float4*)ws_box, n_items, part);
-    hipLaunchKernelGGL(bihupd::k_bih_bound_store, dim3(1), dim3(64), 0, st, (const float4*)part, blocks, (float4*)s->dev.bihhdr + 3 * (size_t)B.hdr);
-    if (nested && s->d_live)  // the tree's own fp64 bound: the join of its items' boxes from box_empty
-      hipLaunchKernelGGL(nestupd::k_nest_fold_store, dim3(1), dim3(nestupd::kFoldBlock), 0, st, (const double*)m.d_box64, n_items, kInfinity, s->d_live + 6 * (size_t)s->live_slot.at(pb.first), err);
+    refit_item_tree(s, pb.first, m, nested && s->d_live);  // (the tree's own fp64 bound: the join of its items' boxes from box_empty)
   }
   if (s->nested_on)  // the update has refitted the tree that holds the Instance: the trees above that one are stale
     for (const InstanceUpdateInfo* u : U) for (int a : u->nested.above) if (a != u->bih) s->stale.insert(a);
   HIPCHK(ctx, hipGetLastError());
-  if (e1) HIPCHK(ctx, hipEventRecord(e1, st));
-  ctx->slot().launched = true; ctx->slot().launched_on = ctx->stream;  // (a matrix entry that is not finite is reported at the next synchronize)
+  HIPCHK(ctx, span.end());
+  mark_launched(ctx);  // (a matrix entry that is not finite is reported at the next synchronize)
   return 0;
 }
 int glome_scene_instance_update(glome_scene* s, const int32_t* ids, const double* xfms, int n, float* gpu_ms) {
@@ -1444,23 +1462,14 @@ int glome_scene_instance_update(glome_scene* s, const int32_t* ids, const double
   }
   if (n == 0) return 0;
   HIPCHK(ctx, hipSetDevice(ctx->device));
-  // every slot of the context may have a launch in flight that reads the pools about to be written
-  HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-  for (auto& sl : ctx->slots)
-    if (sl.launched_on && sl.launched_on != ctx->stream) (void)hipStreamSynchronize(sl.launched_on);
-  (void)hipGetLastError();  // (a stream its owner has destroyed since must not be this call's error: other_slots_busy)
+  if (int rc = quiesce(ctx)) return rc;
   Staging stg{ctx, {}};
   double* dx = stg.in<double>(xfms, 24 * (size_t)n);
   if (!dx) { ctx->err = "staging allocation failed"; return GLOME_E_HIP; }
-  if (gpu_ms) HIPCHK(ctx, hipEventRecord(ctx->ev0, ctx->stream));
-  if (int rc = glome_scene_instance_update_dev(s, ids, dx, n)) return rc;
-  if (gpu_ms) HIPCHK(ctx, hipEventRecord(ctx->ev1, ctx->stream));
-  HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-  if (gpu_ms) HIPCHK(ctx, hipEventElapsedTime(gpu_ms, ctx->ev0, ctx->ev1));
-  return check_device_error(ctx);
+  return run_blocking(ctx, gpu_ms, [&] { return glome_scene_instance_update_dev(s, ids, dx, n); });
 }
 
-// ---- the bihs above an updated object, refitted one tree per call (nested_update_kernels.hpp) ----
+// ---- the bihs above an updated object, refitted one tree per call (item_bih_update_kernels.hpp) ----
 static const NestedAnswer* nested_answer_of(const glome_scene* s, int32_t node) {
   { auto it = s->meshes.find(node); if (it != s->meshes.end()) return &it->second.info.nested; }
   { auto it = s->bihs.find(node); if (it != s->bihs.end()) return &it->second.info.nested; }
@@ -1497,7 +1506,7 @@ int glome_scene_nested_updates(glome_scene* s, int on) {
     void *d = nullptr, *p = nullptr;
     HIPCHK(ctx, hipMalloc(&d, std::max<size_t>(6, s->live_bound0.size()) * sizeof(double)));
     s->allocs.push_back(d);
-    HIPCHK(ctx, hipMalloc(&p, 6 * (size_t)nestupd::kPartMaxBlocks * sizeof(double)));
+    HIPCHK(ctx, hipMalloc(&p, 6 * (size_t)itemupd::kPartMaxBlocks * sizeof(double)));
     s->allocs.push_back(p);
     if (!s->live_bound0.empty()) HIPCHK(ctx, hipMemcpy(d, s->live_bound0.data(), s->live_bound0.size() * sizeof(double), hipMemcpyHostToDevice));
     s->d_live = (double*)d; s->d_live_part = (double*)p;
@@ -1524,39 +1533,20 @@ int glome_scene_bih_refit_dev(glome_scene* s, int32_t bih_id) {
   glome_scene::InstBih& m = *mp;
   HIPCHK(ctx, hipSetDevice(ctx->device));
   if (int rc = ensure_tree_ws(s, m)) return rc;
-  hipStream_t st = ctx->stream;
-  const InstBihInfo& B = m.info;
-  const uint32_t max_items = (uint32_t)ctx->prop.multiProcessorCount * 32u * 4u, n_items = (uint32_t)B.kind.size();
-  auto grid = [&](uint32_t lanes) { return dim3(std::max<uint32_t>(1u, std::min<uint32_t>((lanes + 63u) >> 6, max_items))); };
-  hipEvent_t e0 = nullptr, e1 = nullptr;
-  if (ctx->timing && launch_events(ctx, e0, e1)) HIPCHK(ctx, hipEventRecord(e0, st)); else e1 = nullptr;
-  unsigned int* err = &ctx->slot().d_counters->error;
-  float4* ws_plane = m.d_ws;
-  float4* ws_node = ws_plane + 2 * (size_t)B.rec_span;
-  float4* ws_box = ws_node + 2 * (size_t)B.n_slots;
-  float4* part = ws_box + 2 * (size_t)n_items;
-  if (m.n_live) {  // every live item, changed or not: its rows from its object's bound as it stands
-    nestupd::DItemsArgs A;
-    A.live = m.d_live_items; A.bounds = s->d_live; A.xf = m.d_xf; A.rec_off = m.d_rec_off; A.ws_plane = ws_plane; A.ws_box = ws_box; A.box64 = m.d_box64; A.n = m.n_live; A.error = err;
-    hipLaunchKernelGGL(nestupd::k_nest_item_rows, grid(m.n_live), dim3(64), 0, st, A);
+  const TreeWs W(m.info);
+  UpdateSpan span(ctx, nullptr);
+  HIPCHK(ctx, span.begin());
+  {  // every live item, changed or not: its rows from its object's bound as it stands
+    itemupd::DItemsArgs A;
+    A.live = m.d_live_items; A.bounds = s->d_live; A.xf = m.d_xf; A.rec_off = m.d_rec_off; A.ws_plane = m.d_ws; A.ws_box = m.d_ws + W.box; A.box64 = m.d_box64; A.n = m.n_live;
+    A.error = &ctx->slot().d_counters->error;
+    launch_lanes(ctx, itemupd::k_nest_item_rows, m.n_live, A);
   }
-  {  // the planes, a launch per tree level, deepest first, then the header's box: the Instance update's own launches
-    bihupd::DLevelArgs A;
-    A.nodes = m.d_levels; A.bihnodes = (float4*)s->dev.bihnodes; A.pknodes = nullptr;
-    A.ws_tri = ws_plane; A.ws_node = ws_node; A.first_rec = B.first_rec; A.first_slot = B.first_slot;
-    for (size_t l = 0; l + 1 < B.level_off.size(); l++) {
-      const uint32_t width = B.level_off[l + 1] - B.level_off[l];
-      hipLaunchKernelGGL(bihupd::k_bih_level, grid(width), dim3(64), 0, st, A, B.level_off[l], width);
-    }
-  }
-  const uint32_t blocks = std::max<uint32_t>(1u, std::min<uint32_t>((n_items + 63u) >> 6, (uint32_t)meshupd::kBoundMaxBlocks));
-  hipLaunchKernelGGL(instupd::k_inst_box_fold, dim3(blocks), dim3(64), 0, st, (const float4*)ws_box, n_items, part);
-  hipLaunchKernelGGL(bihupd::k_bih_bound_store, dim3(1), dim3(64), 0, st, (const float4*)part, blocks, (float4*)s->dev.bihhdr + 3 * (size_t)B.hdr);
-  hipLaunchKernelGGL(nestupd::k_nest_fold_store, dim3(1), dim3(nestupd::kFoldBlock), 0, st, (const double*)m.d_box64, n_items, kInfinity, s->d_live + 6 * (size_t)s->live_slot.at(bih_id), err);
+  refit_item_tree(s, bih_id, m, true);  // the Instance update's own launches
   HIPCHK(ctx, hipGetLastError());
-  if (e1) HIPCHK(ctx, hipEventRecord(e1, st));
+  HIPCHK(ctx, span.end());
   s->stale.erase(bih_id);
-  ctx->slot().launched = true; ctx->slot().launched_on = ctx->stream;  // (a box that reaches infinity is reported at the next synchronize)
+  mark_launched(ctx);  // (a box that reaches infinity is reported at the next synchronize)
   return 0;
 }
 int glome_scene_bih_refit(glome_scene* s, int32_t bih_id, float* gpu_ms) {
@@ -1566,18 +1556,9 @@ int glome_scene_bih_refit(glome_scene* s, int32_t bih_id, float* gpu_ms) {
   glome_scene::InstBih* m = nullptr;
   if (int rc = bih_refit_check(s, bih_id, &m)) return rc;
   HIPCHK(ctx, hipSetDevice(ctx->device));
-  // every slot of the context may have a launch in flight that reads the pools about to be written
-  HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-  for (auto& sl : ctx->slots)
-    if (sl.launched_on && sl.launched_on != ctx->stream) (void)hipStreamSynchronize(sl.launched_on);
-  (void)hipGetLastError();  // (a stream its owner has destroyed since must not be this call's error: other_slots_busy)
+  if (int rc = quiesce(ctx)) return rc;
   if (int rc = ensure_tree_ws(s, *m)) return rc;  // (outside the timed span)
-  if (gpu_ms) HIPCHK(ctx, hipEventRecord(ctx->ev0, ctx->stream));
-  if (int rc = glome_scene_bih_refit_dev(s, bih_id)) return rc;
-  if (gpu_ms) HIPCHK(ctx, hipEventRecord(ctx->ev1, ctx->stream));
-  HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-  if (gpu_ms) HIPCHK(ctx, hipEventElapsedTime(gpu_ms, ctx->ev0, ctx->ev1));
-  return check_device_error(ctx);
+  return run_blocking(ctx, gpu_ms, [&] { return glome_scene_bih_refit_dev(s, bih_id); });
 }
 
 // ---- the trace seam: Trace.trace over a caller's ray streams (trace_kernels.hpp) ----

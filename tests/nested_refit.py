@@ -1,7 +1,7 @@
 """The scenes, poses and helpers of the nested refit tests (test_nested_refit_host.py, test_nested_update_gpu.py) -- test infrastructure.
 Objects that lie UNDER a bih move -- a triangle bih, a mesh, Instances -- and the bihs above them are refitted, inner trees first.
 Constants are float64 throughout (SceneDesc(round32=False)): the arithmetic is fp64 and is held to the bit.  No coordinate is chosen so
-that a padded value p -+ 1e-4 is zero: the sign of a zero is the one thing a fold's order could show (nested_update_kernels.hpp).
+that a padded value p -+ 1e-4 is zero: the sign of a zero is the one thing a fold's order could show (item_bih_update_kernels.hpp).
 
 A fixture is built at a POSE in the manner of instances_refit.py: pose None is the scene as committed, "grow" / "shrink" the scene with
 every movable moved.  A movable is ("bih", node, n x 9 triangles), ("mesh", node, vertices) or ("inst", node, base): `moves(B, pose)`
