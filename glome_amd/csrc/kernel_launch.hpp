@@ -1,8 +1,8 @@
 // kernel_launch.hpp -- the seam between the host runtime (runtime.hip) and the kernel parts (kernel_parts.hip): the launchers the parts
-// define and what a launch is described by.  No kernel lives here.  Two device-side conventions are here as well because both
-// sides must agree on them and runtime.hip does not include the kernels: kernel_args (the runtime's self-test checks what the
-// kernels assume) and the adaptive sampler's plan of a launch (the runtime sizes the grid and the control words by the same
-// ss_plan the kernel walks).
+// define and what a launch is described by.  No kernel lives here.  One device-side convention is here as well because both
+// sides must agree on it and runtime.hip does not include the kernels: kernel_args (the runtime's self-test checks what the
+// kernels assume).  (The other, the adaptive sampler's plan of a launch -- the runtime sizes the grid and the control words by the
+// same ss_plan the kernel walks -- is in rt_device.hpp.)
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -29,24 +29,8 @@ struct FlatLaunch { int grid; size_t lds; hipStream_t st; int stack_cap; uint32_
 struct RayStream { const float *ox, *oy, *oz, *dx, *dy, *dz, *tmax; };
 struct HitStream { float* t; int32_t* prim; float *nx, *ny, *nz; int32_t* tex8; };
 
-// ---- the adaptive sampler's plan of a launch: queue heads and, per pass, the items of a head's sequence (render_kernels.hpp ss_frame_loop)
-constexpr uint32_t kSSHeads = 8, kSSHeadStride = 32;
-struct SSPlan {  // per pass: regions per tile, regions per tile row, first item of the pass in a head's sequence
-  uint32_t per_tile[6], nrx[6], first[7];
-  uint32_t tiles_per_head;
-};
-__host__ __device__ inline SSPlan ss_plan(const DRenderArgs& A) {
-  SSPlan P;
-  P.tiles_per_head = ((uint32_t)A.ntiles * (uint32_t)A.nframes + kSSHeads - 1) / kSSHeads;  // (a tile of every frame of the launch)
-  P.first[1] = 0; P.per_tile[0] = 0; P.nrx[0] = 1; P.first[0] = 0;
-  for (int p = 1; p <= 5; p++) {
-    int nrx;
-    P.per_tile[p] = (uint32_t)ss_regions_per_tile(p, A.blocksize, A.ss_rw[p], A.ss_rh[p], nrx);  // laid out for full tiles; edge tiles leave regions empty
-    P.nrx[p] = (uint32_t)nrx;
-    P.first[p + 1] = P.first[p] + P.per_tile[p] * P.tiles_per_head;
-  }
-  return P;
-}
+// ---- the adaptive sampler's plan of a launch (kSSHeads, SSPlan, ss_plan) stands beside the sampler's other item arithmetic in
+// rt_device.hpp, where the CPU suite runs it too
 
 // ---- the launchers (kernel_parts.hip; a flat launcher answers false when its part does not hold instance `key`)
 bool launch_flat_p1(int key, const FlatLaunch& L, const DRenderArgs& A);

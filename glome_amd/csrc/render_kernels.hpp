@@ -426,13 +426,9 @@ __device__ __forceinline__ void ss_frame_loop(const DRenderArgs& A, TIER& T) {
     const float thr = pass >= 2 ? A.thresholds[pass - 2] : 0.0f;
     int ox[4], oy[4];
     ss_neighbours(pass, ox, oy);
-    int bw, bh;
-    ss_block_shape(pass, bw, bh);
-    // the region's blocks inside the (possibly clipped) tile: [bx0, bx1) x [by0, by1)
-    const int rw = A.ss_rw[pass], rh = A.ss_rh[pass];
-    const int bx0 = rx * rw, by0 = ry * rh;
-    const int bx1 = min(bx0 + rw, (t.w + bw - 1) / bw), by1 = min(by0 + rh, (t.h + bh - 1) / bh);
-    const int nbx = bx1 - bx0, nb = nbx > 0 && by1 > by0 ? nbx * (by1 - by0) : 0;
+    // the region's blocks inside the (possibly clipped) tile (ss_region_blocks, rt_device.hpp)
+    int bx0, by0, nbx, nb;
+    ss_region_blocks(pass, t.w, t.h, rx, ry, A.ss_rw[pass], A.ss_rh[pass], bx0, by0, nbx, nb);
     // ---- decide block after block; whenever 64 candidates wait for a sample (and at the region's end) they are traced as
     // one packet -- neighbours in the image.  Every pixel of the tile is written by exactly one of the passes 1-4 before a
     // later pass reads it (Glome.hs:241-297), so the blank initial value (:231) is only ever seen outside the tile (getc).

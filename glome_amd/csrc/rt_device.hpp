@@ -2093,6 +2093,34 @@ GHD int ss_regions_per_tile(int p, int tile_size, int rw, int rh, int& nrx) {
   nrx = (tile_size + bw * rw - 1) / (bw * rw);
   return nrx * ((tile_size + bh * rh - 1) / (bh * rh));
 }
+// the blocks of region (rx, ry) of pass p inside a (possibly clipped) tile of w x h pixels: [bx0, bx0 + nbx) x [by0, by0 + nb / nbx);
+// nb = 0: the region lies outside the tile
+GHD void ss_region_blocks(int p, int w, int h, int rx, int ry, int rw, int rh, int& bx0, int& by0, int& nbx, int& nb) {
+  int bw, bh; ss_block_shape(p, bw, bh);
+  bx0 = rx * rw; by0 = ry * rh;
+  const int xe = (w + bw - 1) / bw, ye = (h + bh - 1) / bh;
+  const int bx1 = bx0 + rw < xe ? bx0 + rw : xe, by1 = by0 + rh < ye ? by0 + rh : ye;
+  nbx = bx1 - bx0; nb = nbx > 0 && by1 > by0 ? nbx * (by1 - by0) : 0;
+}
+// ---- the adaptive sampler's plan of a launch: queue heads and, per pass, the items of a head's sequence (render_kernels.hpp
+// ss_frame_loop; the runtime sizes the grid and the control words by the same plan the kernel walks)
+constexpr uint32_t kSSHeads = 8, kSSHeadStride = 32;
+struct SSPlan {  // per pass: regions per tile, regions per tile row, first item of the pass in a head's sequence
+  uint32_t per_tile[6], nrx[6], first[7];
+  uint32_t tiles_per_head;
+};
+GHD SSPlan ss_plan(const DRenderArgs& A) {
+  SSPlan P;
+  P.tiles_per_head = ((uint32_t)A.ntiles * (uint32_t)A.nframes + kSSHeads - 1) / kSSHeads;  // (a tile of every frame of the launch)
+  P.first[1] = 0; P.per_tile[0] = 0; P.nrx[0] = 1; P.first[0] = 0;
+  for (int p = 1; p <= 5; p++) {
+    int nrx;
+    P.per_tile[p] = (uint32_t)ss_regions_per_tile(p, A.blocksize, A.ss_rw[p], A.ss_rh[p], nrx);  // laid out for full tiles; edge tiles leave regions empty
+    P.nrx[p] = (uint32_t)nrx;
+    P.first[p + 1] = P.first[p] + P.per_tile[p] * P.tiles_per_head;
+  }
+  return P;
+}
 // candidate pixel (tile-local) of `lane` in block (bx, by) of pass p; every lane of a block maps to a distinct candidate
 GD void ss_block_pixel(int p, int bx, int by, int lane, int& dx, int& dy) {
   const int k = lane & 7, ly = lane >> 3;

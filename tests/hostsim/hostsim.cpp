@@ -308,4 +308,58 @@ int hostsim_render_subsample(void* sv, int tier, const float* cam, const float* 
   if (counters) { counters[0] = nprim; counters[1] = nshadow; counters[2] = nsec; }
   return err ? -2 : 0;
 }
+
+// The adaptive sampler's item arithmetic, walked the way ss_frame_loop (render_kernels.hpp) walks it: ss_plan of a launch with
+// this blocksize and these region shapes, then for every region r of a tile (rx = r % nrx, ry = r / nrx) its blocks inside a
+// tw x th tile (ss_region_blocks), block b at (bx0 + b % nbx, by0 + b / nbx), and the candidate of each of its 64 lanes
+// (ss_block_pixel).  pass: 1..5.  rw, rh: indexed by pass like DRenderArgs::ss_rw / ss_rh.
+//   items (may be null): 5 ints per lane -- region, block, lane, dx, dy -- while they fit in cap_items entries
+//   cover (may be null): 65 x 65 counts of how often a pixel with dx < tw and dy < th came up
+//   plan  (may be null): per_tile[6], nrx[6], first[7], tiles_per_head, kSSHeads  (21 words)
+// Returns the number of (region, block, lane) triples walked.  pass 0: all five passes, cover = 5 x 65 x 65 (no item list).
+long long hostsim_ss_items(int pass, int blocksize, int tw, int th, const int* rw, const int* rh, int ntiles, int nframes,
+                           int* items, long long cap_items, unsigned short* cover, unsigned int* plan) {
+  if (pass == 0) {
+    long long total = 0;
+    for (int p = 1; p <= 5; p++) {
+      const long long n = hostsim_ss_items(p, blocksize, tw, th, rw, rh, ntiles, nframes, nullptr, 0, cover ? cover + (p - 1) * 65 * 65 : nullptr, plan);
+      if (n < 0) return n;
+      total += n;
+    }
+    return total;
+  }
+  if (pass < 1 || pass > 5 || blocksize < 1 || blocksize > 65 || tw < 1 || th < 1 || tw > blocksize || th > blocksize) return -1;
+  DRenderArgs A;
+  memset(&A, 0, sizeof(A));
+  A.blocksize = blocksize; A.ntiles = ntiles; A.nframes = nframes;
+  for (int p = 1; p <= 5; p++) { A.ss_rw[p] = (int8_t)rw[p]; A.ss_rh[p] = (int8_t)rh[p]; }
+  const SSPlan PL = ss_plan(A);
+  if (plan) {
+    for (int p = 0; p < 6; p++) { plan[p] = PL.per_tile[p]; plan[6 + p] = PL.nrx[p]; }
+    for (int p = 0; p < 7; p++) plan[12 + p] = PL.first[p];
+    plan[19] = PL.tiles_per_head; plan[20] = kSSHeads;
+  }
+  if (cover) memset(cover, 0, 65 * 65 * sizeof(unsigned short));
+  long long n = 0;
+  for (int r = 0; r < (int)PL.per_tile[pass]; r++) {
+    const int rx = r % (int)PL.nrx[pass], ry = r / (int)PL.nrx[pass];
+    int bx0, by0, nbx, nb;
+    ss_region_blocks(pass, tw, th, rx, ry, A.ss_rw[pass], A.ss_rh[pass], bx0, by0, nbx, nb);
+    for (int b = 0; b < nb; b++) {
+      const int bx = bx0 + b % nbx, by = by0 + b / nbx;
+      for (int lane = 0; lane < 64; lane++, n++) {
+        int dx, dy;
+        ss_block_pixel(pass, bx, by, lane, dx, dy);
+        if (items && n < cap_items) { int* o = items + 5 * n; o[0] = r; o[1] = b; o[2] = lane; o[3] = dx; o[4] = dy; }
+        if (cover && dx < tw && dy < th) {
+          if (dx < 0 || dy < 0) return -2;
+          cover[dy * 65 + dx]++;
+        }
+      }
+    }
+  }
+  return n;
+}
+// ss_region_shape (rt_device.hpp): the flat tier's region of pass p at size 0, 1, 2
+void hostsim_ss_region_shape(int pass, int size, int* rw, int* rh) { int a, b; ss_region_shape(pass, size, a, b); *rw = a; *rh = b; }
 }
