@@ -250,6 +250,12 @@ class Builder:
         p = np.ascontiguousarray(np.asarray(pts9, dtype=np.float64).reshape(-1, 9))
         self._chk(self.lib.glome_sb_bih_set_triangles(self.h, int(node), p.ctypes.data_as(L.c_dp) if p.shape[0] else None, p.shape[0]), "glome_sb_bih_set_triangles")
 
+    def bih_set_spheres(self, node, c3r):
+        """Same tree, new spheres (glome_sb_bih_set_spheres): four values per item in update order (bih_items), cx cy cz r with r > 0; the
+        bih's planes and box are made again, its topology stays."""
+        p = np.ascontiguousarray(np.asarray(c3r, dtype=np.float64).reshape(-1, 4))
+        self._chk(self.lib.glome_sb_bih_set_spheres(self.h, int(node), p.ctypes.data_as(L.c_dp) if p.shape[0] else None, p.shape[0]), "glome_sb_bih_set_spheres")
+
     def instance_set_transforms(self, ids, xfms):
         """New matrices for Instances (glome_sb_instance_set_transforms): xfms holds 24 values per id (api.translate / rotate / compose ...);
         every bih that holds one of them as an item has its planes and box made again, its topology stays."""
@@ -517,6 +523,22 @@ class Scene:
         p = np.ascontiguousarray(np.asarray(pts9, dtype=np.float64).reshape(-1, 9))
         ms = C.c_float(0)
         self._chk(self.lib.glome_scene_bih_update(self.h, int(bih_id), p.ctypes.data_as(L.c_dp) if p.shape[0] else None, p.shape[0], C.byref(ms)), "glome_scene_bih_update")
+        return ms.value
+
+    def sphere_bih_update(self, bih_id, c3r):
+        """New centres and radii for a committed sphere bih, its planes refitted on the GPU (glome_scene_sphere_bih_update): the scene a
+        commit after Builder.bih_set_spheres would have made.  NumPy arrays (or anything array-like) take the host form, which returns the
+        device milliseconds of the finished update; a CUDA torch.float64 tensor takes the device form, asynchronous on the context's
+        stream (returns None; the tensor must stay alive until it has run)."""
+        if hasattr(c3r, "data_ptr"):  # a torch tensor: the device form
+            t = c3r
+            if not t.is_cuda or str(t.dtype) != "torch.float64" or not t.is_contiguous() or t.numel() % 4:
+                raise GlomeError("sphere_bih_update: c3r must be a contiguous CUDA torch.float64 tensor of 4 values per row")
+            self._chk(self.lib.glome_scene_sphere_bih_update_dev(self.h, int(bih_id), C.c_void_p(t.data_ptr()) if t.numel() else None, t.numel() // 4), "glome_scene_sphere_bih_update_dev")
+            return None
+        p = np.ascontiguousarray(np.asarray(c3r, dtype=np.float64).reshape(-1, 4))
+        ms = C.c_float(0)
+        self._chk(self.lib.glome_scene_sphere_bih_update(self.h, int(bih_id), p.ctypes.data_as(L.c_dp) if p.shape[0] else None, p.shape[0], C.byref(ms)), "glome_scene_sphere_bih_update")
         return ms.value
 
     def instance_update(self, ids, xfms):

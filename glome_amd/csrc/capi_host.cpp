@@ -134,6 +134,13 @@ int glome_sb_bih_set_triangles(glome_sb* sb, int32_t bih_id, const double* pts9,
     return 0;
   });
 }
+int glome_sb_bih_set_spheres(glome_sb* sb, int32_t bih_id, const double* c3r, int n) {
+  return guard(sb, [&] {
+    if (n < 0 || (n && !c3r)) throw std::invalid_argument("bih_set_spheres: null sphere array");
+    sb->graph.bih_set_spheres(bih_id, std::vector<double>(c3r, c3r + 4 * (size_t)n));
+    return 0;
+  });
+}
 int glome_sb_instance_set_transforms(glome_sb* sb, const int32_t* ids, const double* xfms, int n) {
   return guard(sb, [&] {
     if (n < 0 || (n && (!ids || !xfms))) throw std::invalid_argument("instance_set_transforms: bad count or null array");
@@ -163,9 +170,10 @@ int32_t glome_sb_bihs_above(glome_sb* sb, int32_t root, int32_t node_id, int32_t
     const NestedAnswer* A = nullptr;
     for (const MeshUpdateInfo& U : F.mesh_updates) if (U.node == node_id) A = &U.nested;
     for (const BihUpdateInfo& U : F.bih_updates) if (U.node == node_id) A = &U.nested;
+    for (const SphereBihUpdateInfo& U : F.sphere_bih_updates) if (U.node == node_id) A = &U.nested;
     for (const InstanceUpdateInfo& U : F.inst_updates) if (U.node == node_id) A = &U.nested;
     for (const InstBihInfo& B : F.inst_bihs) if (B.node == node_id) A = &B.nested;
-    if (!A) throw std::invalid_argument("bihs_above: node " + std::to_string(node_id) + " is not a Mesh, a triangle bih, an Instance or a refittable bih of the scene under node " + std::to_string(root));
+    if (!A) throw std::invalid_argument("bihs_above: node " + std::to_string(node_id) + " is not a Mesh, a triangle bih, an Instance or a refittable bih of the scene under node " + std::to_string(root) + " (nor a sphere bih)");
     if (!A->ok) throw std::invalid_argument("bihs_above: " + A->why_not);
     for (size_t k = 0; k < A->above.size() && (int32_t)k < cap && out; k++) out[k] = A->above[k];
     return (int)A->above.size();

@@ -66,6 +66,24 @@ struct BihUpdateInfo {
   double bound6[6] = {0, 0, 0, 0, 0, 0};  // bound(bih) at commit
 };
 
+// What an update of a committed sphere bih's spheres needs (glome_scene_sphere_bih_update; sphere_bih_update_kernels.hpp), recorded per
+// emitted bih of class BC_SPHERE and kept beside the scene, outside DScene.  As in a triangle bih the leaves are emitted in preorder with
+// nothing in between: record j of the tree is `recs` record first_rec + j and `spheres` record first_sphere + j, and rows[j] is the
+// record's item (its index in BihTree::update_order).  A sphere tree has no packet node copy: its walk reads bihnodes.
+struct SphereBihUpdateInfo {
+  int node = -1;                  // the bih's builder id
+  int n_items = 0;
+  uint32_t hdr = 0;               // bihhdr index
+  uint32_t first_slot = 0, n_slots = 0;  // its node slots (bihnodes index, count; unused slots included)
+  uint32_t first_sphere = 0, first_rec = 0, n_recs = 0;
+  std::vector<uint32_t> rows;
+  std::vector<uint32_t> level_nodes;  // its branch slots (bihnodes indices), deepest tree level first ...
+  std::vector<uint32_t> level_off;    // ... level l is level_nodes[level_off[l] .. level_off[l + 1])
+  UpdateAnswer plain;             // not ok: another Bih lies above it, or the scene holds another copy of one of its spheres -- the reason
+  NestedAnswer nested;
+  double bound6[6] = {0, 0, 0, 0, 0, 0};  // bound(bih) at commit
+};
+
 // What an update of committed Instances' matrices needs (glome_scene_instance_update; instance_update_kernels.hpp), kept beside the
 // scene, outside DScene.  Per emitted Instance node: its slots in the `xfms` pool (emit memoises a node's record, so today a node has
 // exactly one however many parents hold it; the list is what the update walks), and -- when it is an item of a bih -- which bih and which
@@ -88,7 +106,7 @@ struct InstanceUpdateInfo {
 // four F4 per item, (plane lo, plane hi, box lo, box hi).  child_bound: per item the six doubles of bound(child) when the item is an
 // Instance (lo, hi), zeros otherwise.  kind / live / box64 / live_xf: the tables of a refit -- per item its kind and the builder id of
 // the object it hangs on (-1: none), the six doubles of bound(item) at commit, and for the instanced items, in item order, the 24 doubles
-// of the Instance's matrix at commit (xf_at: which row).  An item over a Bih the scene cannot update (spheres, say) counts as static.
+// of the Instance's matrix at commit (xf_at: which row).  An item over a Bih the scene cannot update (boxes, say) counts as static.
 struct InstBihInfo {
   enum ItemKind : uint8_t { kStatic = 0, kInstance = 1, kDirectLive = 2, kInstancedLive = 3 };
   std::vector<uint8_t> kind;
@@ -125,6 +143,7 @@ struct FlatScene {
   bool pk_all = true;       // every triangle BIH has the packet walk's node form (emit_bih)
   std::vector<MeshUpdateInfo> mesh_updates;  // one per emitted mesh (emit_mesh), in emission order
   std::vector<BihUpdateInfo> bih_updates;    // one per emitted triangle bih (emit_bih), in emission order
+  std::vector<SphereBihUpdateInfo> sphere_bih_updates;  // one per emitted sphere bih (emit_bih), in emission order
   std::vector<InstanceUpdateInfo> inst_updates;  // one per emitted Instance node (emit), in emission order
   std::vector<InstBihInfo> inst_bihs;        // one per emitted bih that holds an Instance as an item (emit_bih), in emission order
 };
@@ -388,11 +407,13 @@ class Flattener {
   // emit_bih.  Refused: an Instance that lies deeper inside an item (the item's box depends on it through a list, a CSG node, a Bound or
   // another Instance, which the update does not recompute), one with two or more bihs above it on some path (the outer tree's item box is
   // the inner tree's box), and one that is an item more than once (a single table entry could not name both).
+  // And which sphere bihs may have their spheres replaced (SphereBihUpdateInfo::plain): exactly as a triangle bih, Sphere for Triangle.
   void mark_updatable(int root) {
-    if (F.mesh_updates.empty() && F.bih_updates.empty() && F.inst_updates.empty()) return;
-    std::unordered_map<int, size_t> slot_of, bslot_of, islot_of;
+    if (F.mesh_updates.empty() && F.bih_updates.empty() && F.sphere_bih_updates.empty() && F.inst_updates.empty()) return;
+    std::unordered_map<int, size_t> slot_of, bslot_of, sslot_of, islot_of;
     for (size_t k = 0; k < F.mesh_updates.size(); k++) slot_of[F.mesh_updates[k].node] = k;
     for (size_t k = 0; k < F.bih_updates.size(); k++) bslot_of[F.bih_updates[k].node] = k;
+    for (size_t k = 0; k < F.sphere_bih_updates.size(); k++) sslot_of[F.sphere_bih_updates[k].node] = k;
     for (size_t k = 0; k < F.inst_updates.size(); k++) islot_of[F.inst_updates[k].node] = k;
     for (const InstItem& I : inst_items) {
       InstanceUpdateInfo& U = F.inst_updates[islot_of.at(I.inst)];
@@ -402,9 +423,9 @@ class Flattener {
       }
       U.bih = I.bih; U.item = I.item;
     }
-    // per Triangle node, the innermost Bih it was reached under: kUnseen, a bih's id, -1 for none, kMixed once two of those differ
+    // per Triangle and Sphere node, the innermost Bih it was reached under: kUnseen, a bih's id, -1 for none, kMixed once two of those differ
     constexpr int kUnseen = -3, kMixed = -2;
-    std::vector<int> tri_under(F.bih_updates.empty() ? 0 : G.nodes.size(), kUnseen);
+    std::vector<int> tri_under(F.bih_updates.empty() && F.sphere_bih_updates.empty() ? 0 : G.nodes.size(), kUnseen);
     struct Item { int id, bih, inner, direct; };  // bih: the outermost Bih above, inner: the innermost (-1: none), direct: only wrappers since that bih's item list
     struct Seen { int bih, inner, direct; bool operator==(const Seen& o) const { return bih == o.bih && inner == o.inner && direct == o.direct; } };
     std::unordered_map<int, std::vector<Seen>> seen;  // composites and wrappers only (a primitive has nothing below it): the states a node was visited with
@@ -415,7 +436,7 @@ class Flattener {
       stack.pop_back();
       const Node& n = G.at(it.id);
       if (is_prim(n.kind) || n.kind == K_VOID) {
-        if (n.kind == K_TRI && !tri_under.empty()) { int& u = tri_under[(size_t)it.id]; u = (u == kUnseen || u == it.inner) ? it.inner : kMixed; }
+        if ((n.kind == K_TRI || n.kind == K_SPHERE) && !tri_under.empty()) { int& u = tri_under[(size_t)it.id]; u = (u == kUnseen || u == it.inner) ? it.inner : kMixed; }
         continue;
       }
       std::vector<Seen>& sn = seen[it.id];
@@ -444,6 +465,12 @@ class Flattener {
           auto sl = bslot_of.find(it.id);
           if (it.bih >= 0 && sl != bslot_of.end() && F.bih_updates[sl->second].plain.ok) {
             BihUpdateInfo& U = F.bih_updates[sl->second];
+            U.plain.ok = false;
+            U.plain.why_not = "bih " + std::to_string(it.id) + " lies inside bih " + std::to_string(it.bih) + ", whose planes and root box were built from its bound";
+          }
+          auto ss = sslot_of.find(it.id);
+          if (it.bih >= 0 && ss != sslot_of.end() && F.sphere_bih_updates[ss->second].plain.ok) {
+            SphereBihUpdateInfo& U = F.sphere_bih_updates[ss->second];
             U.plain.ok = false;
             U.plain.why_not = "bih " + std::to_string(it.id) + " lies inside bih " + std::to_string(it.bih) + ", whose planes and root box were built from its bound";
           }
@@ -476,6 +503,24 @@ class Flattener {
         if (!U.plain.ok) break;
       }
     }
+    for (SphereBihUpdateInfo& U : F.sphere_bih_updates) {
+      if (!U.plain.ok) continue;
+      const std::string why = sphere_outside(U.node, tri_under);
+      if (!why.empty()) { U.plain.ok = false; U.plain.why_not = why; }
+    }
+  }
+  // A sphere bih's item that the scene also reaches outside that bih (tri_under: mark_updatable), named; empty: none.  BC_SPHERE items are
+  // emitted fresh, so such a copy has a second record, which an update of this bih could not move.
+  std::string sphere_outside(int bih, const std::vector<int>& under) const {
+    constexpr int kUnseen = -3;
+    for (const BihTree::Node& bn : G.at(bih).bih->nodes)
+      for (int item : bn.items) {
+        const int t = G.peel_wrappers(item);
+        const int u = under[(size_t)t];
+        if (u == bih || u == kUnseen) continue;  // (kUnseen: the bih itself is not reachable from the root -- nothing renders it)
+        return "sphere " + std::to_string(t) + " of bih " + std::to_string(bih) + " is also part of the scene outside that bih, as a copy an update could not move";
+      }
+    return std::string();
   }
 
   // The second answer (NestedAnswer), for glome_scene_nested_updates: an update of X -- a Mesh, a triangle bih, an Instance that is an
@@ -488,12 +533,12 @@ class Flattener {
   // of those rows is derived from the same bound.  The walk records, per Mesh, Bih and Instance, the states it was reached in
   // (innermost bih, what lies between that bih's item list and the node); the answers are then resolved bih by bih, memoised.
   void mark_nested(int root) {
-    if (F.mesh_updates.empty() && F.bih_updates.empty() && F.inst_updates.empty() && F.inst_bihs.empty()) return;
+    if (F.mesh_updates.empty() && F.bih_updates.empty() && F.sphere_bih_updates.empty() && F.inst_updates.empty() && F.inst_bihs.empty()) return;
     enum { kDirect = 0, kInst = 1, kBroken = 2 };
     struct Edge { int bih, link, blocker, via; };   // blocker: the first list / CSG / Bound / second Instance since the item list; via: the Instance passed first (-1: none)
     struct Item { int id, inner, link, blocker, via; };
     constexpr int kUnseen = -3, kMixed = -2;
-    std::vector<int> tri_under(F.bih_updates.empty() ? 0 : G.nodes.size(), kUnseen);
+    std::vector<int> tri_under(F.bih_updates.empty() && F.sphere_bih_updates.empty() ? 0 : G.nodes.size(), kUnseen);
     std::unordered_map<int, std::vector<Edge>> edges;
     std::unordered_map<int, std::vector<std::pair<int, int>>> seen;
     std::vector<Item> stack{{root, -1, kDirect, -1, -1}};
@@ -503,7 +548,7 @@ class Flattener {
       stack.pop_back();
       const Node& n = G.at(it.id);
       if (is_prim(n.kind) || n.kind == K_VOID) {
-        if (n.kind == K_TRI && !tri_under.empty()) { int& u = tri_under[(size_t)it.id]; u = (u == kUnseen || u == it.inner) ? it.inner : kMixed; }
+        if ((n.kind == K_TRI || n.kind == K_SPHERE) && !tri_under.empty()) { int& u = tri_under[(size_t)it.id]; u = (u == kUnseen || u == it.inner) ? it.inner : kMixed; }
         continue;
       }
       std::vector<std::pair<int, int>>& sn = seen[it.id];
@@ -585,6 +630,13 @@ class Flattener {
         }
         if (!U.nested.ok) break;
       }
+    }
+    for (SphereBihUpdateInfo& U : F.sphere_bih_updates) {
+      if (U.plain.why_not.rfind("bih " + std::to_string(U.node) + " holds sphere", 0) == 0) { U.nested.ok = false; U.nested.why_not = U.plain.why_not; continue; }  // (emit_bih's refusal)
+      U.nested = answer(U.node);
+      if (!U.nested.ok) continue;
+      const std::string why = sphere_outside(U.node, tri_under);
+      if (!why.empty()) { U.nested.ok = false; U.nested.why_not = why; }
     }
     std::unordered_map<int, std::pair<int, int>> item_of_bih;  // Instance -> (its first bih, how often it is an item)
     for (const InstItem& I : inst_items) { auto r = item_of_bih.insert({I.inst, {I.bih, 0}}); r.first->second.second++; }
@@ -868,6 +920,22 @@ class Flattener {
         item_of[(size_t)order[k]] = (uint32_t)k; tri_seen[(size_t)t] = 1;
       }
     }
+    SphereBihUpdateInfo SU;  // a sphere bih: the same tables, Sphere for Triangle
+    if (cls == BC_SPHERE) {
+      SU.node = id; SU.hdr = hdr; SU.first_slot = base; SU.n_slots = nslots;
+      const std::vector<int> order = T.update_order();
+      SU.n_items = (int)order.size();
+      item_of.assign(G.nodes.size(), 0xffffffffu);
+      std::vector<char> sph_seen(G.nodes.size(), 0);
+      for (size_t k = 0; k < order.size(); k++) {
+        const int t = G.peel_wrappers(order[k]);
+        if ((item_of[(size_t)order[k]] != 0xffffffffu || sph_seen[(size_t)t]) && SU.plain.ok) {
+          SU.plain.ok = false;
+          SU.plain.why_not = "bih " + std::to_string(id) + " holds sphere " + std::to_string(t) + " more than once";
+        }
+        item_of[(size_t)order[k]] = (uint32_t)k; sph_seen[(size_t)t] = 1;
+      }
+    }
     for (size_t k = 0; k < T.nodes.size(); k++) {
       const BihTree::Node& bn = T.nodes[k];
       if (!bn.leaf) { ref[k] = base + slot[k]; continue; }
@@ -913,6 +981,10 @@ class Flattener {
           U.rows.push_back(!paired ? BihUpdateInfo::kNoPair : (pair | (q & 1u ? BihUpdateInfo::kPairHalfB : 0u) | (q + 1 == count && !(q & 1u) ? BihUpdateInfo::kPairBoth : 0u)));
         }
       }
+      if (cls == BC_SPHERE && count) {
+        if (SU.rows.empty()) { SU.first_sphere = first_prim; SU.first_rec = first_rec; }
+        for (uint32_t q = 0; q < count; q++) SU.rows.push_back(item_of[(size_t)bn.items[q]]);
+      }
       if (count == 0) ref[k] = BREF_LEAF_BIT;
       else if (count <= 6) ref[k] = BREF_LEAF_BIT | (count << 26) | first_rec;
       else {
@@ -954,6 +1026,13 @@ class Flattener {
       if (!pk) for (size_t j = 0; j < U.n_tris; j++) U.rows[2 * j + 1] = BihUpdateInfo::kNoPair;  // (the packet form was given up part way)
       tree_levels(T.nodes, [&](size_t k) { return base + slot[k]; }, U.level_nodes, U.level_off);
       F.bih_updates.push_back(std::move(U));
+      movable_bihs.insert(id);
+    }
+    if (cls == BC_SPHERE) {
+      SU.n_recs = (uint32_t)SU.rows.size();
+      box6(T.bb, SU.bound6);
+      tree_levels(T.nodes, [&](size_t k) { return base + slot[k]; }, SU.level_nodes, SU.level_off);
+      F.sphere_bih_updates.push_back(std::move(SU));
       movable_bihs.insert(id);
     }
     if (has_inst) {
@@ -1006,8 +1085,8 @@ class Flattener {
     if (can_move(c)) { live = c; return InstBihInfo::kInstancedLive; }
     return InstBihInfo::kInstance;
   }
-  // a Mesh, or a Bih that has update tables of its own -- a triangle bih, a bih with Instance or live items -- which emit_bih has made
-  // by the time a parent asks (an item is emitted before its kind is looked at).  A bih of spheres, say, never changes: static.
+  // a Mesh, or a Bih that has update tables of its own -- a triangle bih, a sphere bih, a bih with Instance or live items -- which emit_bih
+  // has made by the time a parent asks (an item is emitted before its kind is looked at).  A bih of boxes, say, never changes: static.
   bool can_move(int id) const { return G.at(id).kind == K_MESH || (G.at(id).kind == K_BIH && movable_bihs.count(id) != 0); }
   std::set<int> movable_bihs;
   struct InstItem { int inst, bih; uint32_t item; };

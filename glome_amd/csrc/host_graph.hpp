@@ -535,6 +535,33 @@ struct Graph {
     }
     bih_refit(id);
   }
+  // Same tree, new spheres (glome_sb_bih_set_spheres): item k of the tree, a Sphere under any number of Tex / Tag / shadow wrappers, gets
+  // the centre c3r[4 k ..] and the radius c3r[4 k + 3]; then bih_refit, as above.  A Sphere's box is c -+ r with no pad (`bound`).  Every
+  // radius is > 0: c - r and c + r are then never -0 in round-to-nearest, so a min / max over them has no tie between zeros of two signs
+  // and is the same in any order (the device folds them in another one: sphere_bih_update_kernels.hpp); a sphere of radius 0 is nothing
+  // anyway.  Nothing is touched unless everything is valid.
+  void bih_set_spheres(int id, const std::vector<double>& c3r) {
+    if (at(id).kind != K_BIH) throw std::invalid_argument(std::string("bih_set_spheres: node ") + std::to_string(id) + " is a " + kind_name(at(id).kind) + ", not a Bih");
+    BihTree& T = *nodes[(size_t)id].bih;
+    const std::vector<int> order = T.update_order();
+    if (c3r.size() != 4 * order.size()) throw std::invalid_argument("bih_set_spheres: the bih has " + std::to_string(order.size()) + " items, not " + std::to_string(c3r.size() / 4));
+    std::vector<int> sph(order.size());
+    {
+      std::vector<int> sorted;
+      for (size_t k = 0; k < order.size(); k++) {
+        sph[k] = peel_wrappers(order[k]);
+        if (at(sph[k]).kind != K_SPHERE) throw std::invalid_argument("bih_set_spheres: item " + std::to_string(k) + " (node " + std::to_string(order[k]) + ") is a " + kind_name(at(sph[k]).kind) + ", not a plain Sphere");
+        sorted.push_back(sph[k]);
+      }
+      std::sort(sorted.begin(), sorted.end());
+      auto dup = std::adjacent_find(sorted.begin(), sorted.end());
+      if (dup != sorted.end()) throw std::invalid_argument("bih_set_spheres: sphere " + std::to_string(*dup) + " is an item of the bih more than once");
+    }
+    for (double v : c3r) if (!std::isfinite(v)) throw std::invalid_argument("bih_set_spheres: a value is not finite");
+    for (size_t k = 0; k < order.size(); k++) if (!(c3r[4 * k + 3] > 0)) throw std::invalid_argument("bih_set_spheres: radius of item " + std::to_string(k) + " is not positive");
+    for (size_t k = 0; k < order.size(); k++) std::copy(c3r.begin() + 4 * (ptrdiff_t)k, c3r.begin() + 4 * (ptrdiff_t)k + 4, nodes[(size_t)sph[k]].p);
+    bih_refit(id);
+  }
   // What `bih` derives from its items' bounds, made again for the tree as it stands (the pass both bih_set_triangles and
   // instance_set_transforms end with): the tree's box and every branch's two planes, by the definitions quoted above.
   void bih_refit(int id) {

@@ -3,8 +3,9 @@
 // sampler and batch kernels through kernel_launch.hpp (the instances live in kernel_parts.hip, chosen by instances.hpp) and holds
 // only the light kernels: the kernel-argument self-test, the coordinate tables, tile transport, the tree builders
 // (bih_build_device.hpp), the flagship launch's cull pass (cull_kernels.hpp) and the updates of a committed Mesh (mesh_update_kernels.hpp)
-// and of a committed triangle bih (bih_update_kernels.hpp), and of committed Instances' matrices and the refit of the bihs above an
-// updated object (item_bih_update_kernels.hpp); what those kernels share is in update_common.hpp.
+// and of a committed triangle bih (bih_update_kernels.hpp) and sphere bih (sphere_bih_update_kernels.hpp), and of committed Instances'
+// matrices and the refit of the bihs above an updated object (item_bih_update_kernels.hpp); what those kernels share is in
+// update_common.hpp.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -29,6 +30,7 @@
 #include "mesh_update_kernels.hpp"
 #include "bih_update_kernels.hpp"
 #include "item_bih_update_kernels.hpp"
+#include "sphere_bih_update_kernels.hpp"
 
 using namespace glome;
 
@@ -171,6 +173,15 @@ struct glome_scene {
     float4* d_ws = nullptr;            // two words per record, two per node slot, then the bound's partial boxes: allocated at the first update
   };
   std::map<int, BihUpd> bihs;
+  // and for glome_scene_sphere_bih_update, of every sphere bih of the scene (flatten.hpp SphereBihUpdateInfo)
+  struct SphBihUpd {
+    SphereBihUpdateInfo info;          // (rows and level_nodes emptied once uploaded)
+    const uint32_t* d_rows = nullptr;
+    const uint32_t* d_levels = nullptr;
+    const uint32_t* d_level_off = nullptr;
+    float4* d_ws = nullptr;            // two words per record, two per node slot, then the bound's partial boxes: allocated at the first update
+  };
+  std::map<int, SphBihUpd> sph_bihs;
   // and for glome_scene_instance_update: every Instance of the scene by its builder id, and every bih that holds one as an item
   // (flatten.hpp InstanceUpdateInfo, InstBihInfo)
   std::map<int, InstanceUpdateInfo> insts;
@@ -192,7 +203,7 @@ struct glome_scene {
     uint32_t n_live = 0;
   };
   std::map<int, InstBih> ibihs;
-  // glome_scene_nested_updates: the switch; every Mesh, triangle bih and table-holding bih has a row of six doubles in d_live, its fp64
+  // glome_scene_nested_updates: the switch; every Mesh, triangle bih, sphere bih and table-holding bih has a row of six doubles in d_live, its fp64
   // bound (live_bound0: the commit's, what the table is filled with when the switch is first turned on); d_live_part: the partial boxes
   // of a bound's first stage; stale: the bihs whose planes and box no longer match an object below them
   bool nested_on = false;
@@ -586,6 +597,12 @@ glome_scene* glome_scene_commit(glome_ctx* ctx, glome_sb* sb, int32_t root) {
     U.rows = {}; U.level_nodes = {};
     m.info = std::move(U);
   }
+  for (SphereBihUpdateInfo& U : F.sphere_bih_updates) {
+    glome_scene::SphBihUpd& m = s->sph_bihs[U.node];
+    if ((!U.rows.empty() && upload(s, U.rows, &m.d_rows)) || (!U.level_nodes.empty() && (upload(s, U.level_nodes, &m.d_levels) || upload(s, U.level_off, &m.d_level_off)))) { glome_scene_release(s); return nullptr; }
+    U.rows = {}; U.level_nodes = {};
+    m.info = std::move(U);
+  }
   for (InstBihInfo& B : F.inst_bihs) {
     glome_scene::InstBih& m = s->ibihs[B.node];
     if ((!B.level_nodes.empty() && upload(s, B.level_nodes, &m.d_levels)) || upload(s, B.rec_off, &m.d_rec_off) || upload(s, B.child_bound, &m.d_bounds)) { glome_scene_release(s); return nullptr; }
@@ -596,6 +613,7 @@ glome_scene* glome_scene_commit(glome_ctx* ctx, glome_sb* sb, int32_t root) {
   auto live_row = [&](int node, const double* b6) { s->live_slot[node] = (uint32_t)(s->live_bound0.size() / 6); s->live_bound0.insert(s->live_bound0.end(), b6, b6 + 6); };
   for (auto& m : s->meshes) live_row(m.first, m.second.info.bound6);
   for (auto& m : s->bihs) live_row(m.first, m.second.info.bound6);
+  for (auto& m : s->sph_bihs) live_row(m.first, m.second.info.bound6);
   for (auto& m : s->ibihs) live_row(m.first, m.second.info.bound6);
   return s;
 }
@@ -693,11 +711,13 @@ static int device_error_status(glome_ctx* ctx, unsigned int e) {
     ctx->err = "a ray direction is not unit length: set glome_trace_params.faithful to trace such rays (the reference's own traversal)";
     return GLOME_E_INVALID;
   }
-  if (e & kErrBadVertex) {  // (only the three updates set it; the word does not say which)
+  if (e & kErrBadVertex) {  // (only the updates set it; the word does not say which)
     ctx->err = "a mesh update met a vertex coordinate that is not finite: the scene's mesh is unspecified until a valid update"
                " (or a bih update, glome_scene_bih_update: then the bih is; or an Instance update, glome_scene_instance_update, met a matrix"
                " entry that is not finite or a bih item box that reaches infinity: then those Instances and the bih that holds them are; or a"
-               " refit, glome_scene_bih_refit, met an item box or joined box that reaches infinity: then that bih and the bihs above it are)";
+               " refit, glome_scene_bih_refit, met an item box or joined box that reaches infinity: then that bih and the bihs above it are;"
+               " or a sphere bih update, glome_scene_sphere_bih_update, met a value that is not finite or a radius that is not positive: then"
+               " that bih is)";
     return GLOME_E_INVALID;
   }
   ctx->err = "device-side limit hit (traversal stack or CSG advance cap)";
@@ -1348,6 +1368,79 @@ int glome_scene_bih_update(glome_scene* s, int32_t bih_id, const double* pts9, i
   return run_blocking(ctx, gpu_ms, [&] { return glome_scene_bih_update_dev(s, bih_id, dp, n); });
 }
 
+// ---- new spheres for a committed sphere bih (sphere_bih_update_kernels.hpp) ----
+// what both forms refuse before anything is launched; *out = the bih's tables
+static int sphere_bih_update_check(glome_scene* s, int32_t bih_id, const void* c3r, int n, glome_scene::SphBihUpd** out) {
+  glome_ctx* ctx = s->ctx;
+  auto it = s->sph_bihs.find(bih_id);
+  if (it == s->sph_bihs.end()) { ctx->err = "sphere bih update: node " + std::to_string(bih_id) + " is not a bih of plain spheres of this scene"; return GLOME_E_INVALID; }
+  const SphereBihUpdateInfo& U = it->second.info;
+  if (n != U.n_items) { ctx->err = "sphere bih update: the bih has " + std::to_string(U.n_items) + " items, not " + std::to_string(n); return GLOME_E_INVALID; }
+  if (n && !c3r) { ctx->err = "sphere bih update: null sphere array"; return GLOME_E_INVALID; }
+  if (int rc = accepted(s, "sphere bih update", U.plain, U.nested)) return rc;
+  *out = &it->second;
+  return 0;
+}
+int glome_scene_sphere_bih_update_dev(glome_scene* s, int32_t bih_id, const double* c3r_dev, int n) {
+  if (!s) return GLOME_E_INVALID;
+  glome_ctx* ctx = s->ctx;
+  glome_scene::SphBihUpd* m = nullptr;
+  if (int rc = sphere_bih_update_check(s, bih_id, c3r_dev, n, &m)) return rc;
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  const SphereBihUpdateInfo& U = m->info;
+  // a box per record and per node slot, and the bound's partial boxes
+  if (int rc = ensure_ws(s, m->d_ws, 2 * ((size_t)U.n_recs + U.n_slots + upd::kBoundMaxBlocks))) return rc;
+  const bool merged = getenv("GLOME_DEBUG_BIH_UPDATE_MERGED") != nullptr;  // (as in the triangle bih's update)
+  UpdateSpan span(ctx, "GLOME_DEBUG_BIH_UPDATE_SPLIT");
+  HIPCHK(ctx, span.begin());
+  {
+    sphupd::DItemsArgs A;
+    A.c3r = c3r_dev; A.rows = m->d_rows; A.spheres = (float4*)s->dev.spheres + (size_t)U.first_sphere; A.ws = m->d_ws; A.n = U.n_recs;
+    A.error = &ctx->slot().d_counters->error;
+    launch_lanes(ctx, sphupd::k_sph_items, U.n_recs, A);
+  }
+  HIPCHK(ctx, span.stage());
+  {
+    bihupd::DLevelArgs A;
+    A.nodes = m->d_levels; A.bihnodes = (float4*)s->dev.bihnodes; A.pknodes = nullptr;  // (a sphere tree's walk reads bihnodes alone)
+    A.ws_tri = m->d_ws; A.ws_node = m->d_ws + 2 * (size_t)U.n_recs; A.first_rec = U.first_rec; A.first_slot = U.first_slot;
+    launch_levels(ctx, A, U.level_off, merged ? m->d_level_off : nullptr);
+  }
+  HIPCHK(ctx, span.stage());
+  {  // the join of the spheres' boxes, from box_empty: in fp32 into the header, in fp64 into the bounds table
+    float4* part = m->d_ws + 2 * ((size_t)U.n_recs + U.n_slots);
+    const uint32_t blocks = std::max<uint32_t>(1u, std::min<uint32_t>(((uint32_t)n + upd::kBoundBlock - 1) / upd::kBoundBlock, (uint32_t)upd::kBoundMaxBlocks));
+    hipLaunchKernelGGL(sphupd::k_sph_bound, dim3(blocks), dim3(upd::kBoundBlock), 0, ctx->stream, c3r_dev, (uint32_t)n, part);
+    hipLaunchKernelGGL(upd::k_bound_store, dim3(1), dim3(64), 0, ctx->stream, (const float4*)part, blocks, (float)kInfinity, (float4*)s->dev.bihhdr + 3 * (size_t)U.hdr);
+  }
+  if (s->nested_on && !U.nested.above.empty()) {
+    const uint32_t blocks = std::min<uint32_t>(((uint32_t)n + itemupd::kFoldBlock - 1) / itemupd::kFoldBlock, (uint32_t)itemupd::kPartMaxBlocks);
+    if (blocks) hipLaunchKernelGGL(sphupd::k_nest_spheres_part, dim3(blocks), dim3(itemupd::kFoldBlock), 0, ctx->stream, c3r_dev, (uint32_t)n, s->d_live_part);
+    hipLaunchKernelGGL(itemupd::k_nest_fold_store, dim3(1), dim3(itemupd::kFoldBlock), 0, ctx->stream, (const double*)s->d_live_part, blocks, kInfinity,
+                       s->d_live + 6 * (size_t)s->live_slot.at(bih_id), &ctx->slot().d_counters->error);
+    s->stale.insert(U.nested.above.begin(), U.nested.above.end());
+  }
+  HIPCHK(ctx, hipGetLastError());
+  HIPCHK(ctx, span.end());
+  mark_launched(ctx);  // (a value that is not finite or a radius that is not positive is reported at the next synchronize)
+  return 0;
+}
+int glome_scene_sphere_bih_update(glome_scene* s, int32_t bih_id, const double* c3r, int n, float* gpu_ms) {
+  if (!s) return GLOME_E_INVALID;
+  glome_ctx* ctx = s->ctx;
+  if (gpu_ms) *gpu_ms = 0;
+  glome_scene::SphBihUpd* m = nullptr;
+  if (int rc = sphere_bih_update_check(s, bih_id, c3r, n, &m)) return rc;
+  for (size_t k = 0; k < 4 * (size_t)n; k++) if (!std::isfinite(c3r[k])) { ctx->err = "sphere bih update: a value is not finite"; return GLOME_E_INVALID; }
+  for (size_t k = 0; k < (size_t)n; k++) if (!(c3r[4 * k + 3] > 0)) { ctx->err = "sphere bih update: radius of item " + std::to_string(k) + " is not positive"; return GLOME_E_INVALID; }
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  if (int rc = quiesce(ctx)) return rc;
+  Staging stg{ctx, {}};
+  double* dp = stg.in<double>(c3r, 4 * (size_t)n);
+  if (!dp) { ctx->err = "staging allocation failed"; return GLOME_E_HIP; }
+  return run_blocking(ctx, gpu_ms, [&] { return glome_scene_sphere_bih_update_dev(s, bih_id, dp, n); });
+}
+
 // ---- new matrices for committed Instances (item_bih_update_kernels.hpp) ----
 // what both forms refuse before anything is launched; out[k] = the tables of ids[k]
 static int instance_update_check(glome_scene* s, const int32_t* ids, const void* xfms, int n, std::vector<const InstanceUpdateInfo*>& out) {
@@ -1473,6 +1566,7 @@ int glome_scene_instance_update(glome_scene* s, const int32_t* ids, const double
 static const NestedAnswer* nested_answer_of(const glome_scene* s, int32_t node) {
   { auto it = s->meshes.find(node); if (it != s->meshes.end()) return &it->second.info.nested; }
   { auto it = s->bihs.find(node); if (it != s->bihs.end()) return &it->second.info.nested; }
+  { auto it = s->sph_bihs.find(node); if (it != s->sph_bihs.end()) return &it->second.info.nested; }
   { auto it = s->insts.find(node); if (it != s->insts.end()) return &it->second.nested; }
   { auto it = s->ibihs.find(node); if (it != s->ibihs.end()) return &it->second.info.nested; }
   return nullptr;
@@ -1480,7 +1574,7 @@ static const NestedAnswer* nested_answer_of(const glome_scene* s, int32_t node) 
 int32_t glome_scene_bihs_above(const glome_scene* s, int32_t node_id, int32_t* out, int32_t cap) {
   if (!s) return GLOME_E_INVALID;
   const NestedAnswer* A = nested_answer_of(s, node_id);
-  if (!A) { s->ctx->err = "bihs_above: node " + std::to_string(node_id) + " is not a Mesh, a triangle bih, an Instance or a refittable bih of this scene"; return GLOME_E_INVALID; }
+  if (!A) { s->ctx->err = "bihs_above: node " + std::to_string(node_id) + " is not a Mesh, a triangle bih, an Instance or a refittable bih of this scene (nor a sphere bih)"; return GLOME_E_INVALID; }
   if (!A->ok) { s->ctx->err = "bihs_above: " + A->why_not; return GLOME_E_INVALID; }
   for (size_t k = 0; k < A->above.size() && (int32_t)k < cap && out; k++) out[k] = A->above[k];
   return (int32_t)A->above.size();

@@ -172,6 +172,7 @@ class DescScene:
 
     def mesh_update(self, node, verts, norms=None): return self.scene.mesh_update(self.nmap[node], verts, norms)
     def bih_update(self, node, pts9): return self.scene.bih_update(self.nmap[node], pts9)
+    def sphere_bih_update(self, node, c3r): return self.scene.sphere_bih_update(self.nmap[node], c3r)
     def instance_update(self, nodes, xfms): return self.scene.instance_update([self.nmap[n] for n in nodes], xfms)
     def bih_refit(self, node): return self.scene.bih_refit(self.nmap[node])
 

@@ -128,6 +128,19 @@ int glome_sb_mesh_set_vertices(glome_sb*, int32_t mesh_id, const double* verts, 
  * GLOME_E_INVALID with a message (an item that is not a plain triangle is named), and nothing is touched.  Host only; the specification
  * of glome_scene_bih_update. */
 int glome_sb_bih_set_triangles(glome_sb*, int32_t bih_id, const double* pts9, int n);
+/* Same tree, new spheres: glome_sb_bih_set_triangles for a bih of spheres.  bih_id names a Bih node, whoever made it; n is its item
+ * count and c3r holds four doubles per item in update order (glome_sb_bih_items): cx cy cz r, every one finite, every r > 0.  Every item
+ * must be a Sphere under any number of Tex / Tag / NoShadow / OnlyShadow wrappers, and no Sphere node may be an item twice.  Sets the
+ * item spheres' centres and radii (a Sphere node that is also used elsewhere in the builder moves there too) and makes again what `bih`
+ * derives from its items' bounds, as glome_sb_bih_refit does: a Sphere's box is c - r / c + r with no pad (Sphere.hs:78-81), so lsplit =
+ * (max over the left subtree of (c + r)[axis]) + delta, rsplit = (min over the right subtree of (c - r)[axis]) - delta, and the tree's
+ * box is [min(c - r), max(c + r)].  What the builder decided -- nodes, axes, leaf lists, depth -- stays, and the tree stays correct for
+ * the reason given above.  Why r > 0: c - r and c + r are then never -0 in round-to-nearest, so the min / max folds give the same bits
+ * in any order (the device folds in another one); a sphere of radius 0 is nothing anyway.  All or nothing: anything else is
+ * GLOME_E_INVALID with a message (an item that is not a plain Sphere is named, and so are a Sphere held twice and the item whose radius
+ * is not positive), and nothing is touched.  The reference has no such call; the result is the Bih the reference would print for the
+ * same tree with the new spheres.  Host only; the specification of glome_scene_sphere_bih_update. */
+int glome_sb_bih_set_spheres(glome_sb*, int32_t bih_id, const double* c3r, int n);
 /* the item ids of a Bih in update order: returns their number and fills out[0 .. min(number, cap)) (out may be NULL: count first) */
 int32_t glome_sb_bih_items(glome_sb*, int32_t bih_id, int32_t* out, int32_t cap);
 /* New matrices for Instances.  Every id names an Instance node, whoever made it -- glome_sb_transform (of anything but a triangle, an
@@ -152,7 +165,7 @@ int glome_sb_instance_set_transforms(glome_sb*, const int32_t* ids, const double
  * order).  That sequence is the specification of glome_scene_bih_refit.  GLOME_E_INVALID for an id that is not a Bih; GLOME_E_SCENE with
  * the constructor's "bih: infinite bounding box" when the joined box reaches +-1e6, and nothing is touched then.  Host only. */
 int glome_sb_bih_refit(glome_sb*, int32_t bih_id);
-/* The bihs above node_id -- a Mesh, a bih of plain triangles, an Instance, or a bih that holds a Mesh, a Bih or an Instance as an item --
+/* The bihs above node_id -- a Mesh, a bih of plain triangles or of plain spheres, an Instance, or a bih that holds a Mesh, a Bih or an Instance as an item --
  * in the scene under `root`: every Bih on any path from root (or from a Warp material's frame / scene) down to the node, in an order in
  * which they can be refitted, a tree after every tree below it.  Returns their number (0: none) and fills out[0 .. min(number, cap)).
  * Runs the flattener's marking, no GPU.  GLOME_E_INVALID, the reason in glome_sb_last_error, when an update of the node would be refused
@@ -300,6 +313,37 @@ int glome_scene_mesh_update_dev(glome_scene*, int32_t mesh_id, const double* ver
 int glome_scene_bih_update(glome_scene*, int32_t bih_id, const double* pts9, int n, float* gpu_ms);
 int glome_scene_bih_update_dev(glome_scene*, int32_t bih_id, const double* pts9_dev, int n);
 
+/* ---- animate a committed sphere bih: new centres and radii, its planes refitted on the GPU ----
+ * A sphere bih is a Bih whose items are all plain Spheres (under Tex / Tag wrappers, at most two Tex levels): the benchmark scenes'
+ * `bih [tex (sphere ..) mat ...]`, a lattice, particles, a point cloud.  After an update the committed scene is, bit for bit, the scene
+ * glome_scene_commit would have made had glome_sb_bih_set_spheres been called with the same array first: the sphere records, every
+ * branch's two planes, the tree's box.  The tree's topology stays (see glome_sb_bih_set_triangles); nothing else of the scene is read or
+ * written, and one update moves every Instance of the bih.  (The other updates' deviation holds: a component whose fp32 value would be
+ * subnormal is stored as zero.)  The builder is not touched: a host that also wants the new tree there calls both.
+ *   bih_id  the builder id of a sphere bih that is part of this scene; n its item count; c3r four doubles per item in update order
+ *           (glome_sb_bih_items): cx cy cz r.
+ *   Refused with GLOME_E_INVALID before anything is launched, the scene untouched: an id that is not a sphere bih of this scene, a count
+ *   mismatch, a missing array, a bih with another `bih` above it on any path from the committed root (or from a Warp material's frame /
+ *   scene) -- the message names it; glome_scene_nested_updates lifts this one --, a bih one of whose spheres the scene also reaches
+ *   outside it (in a group beside it, say: that copy has a record of its own, which could not be moved; the message names the sphere),
+ *   and a bih that holds a sphere twice.  The bounding solid of a Bound / InnerBound above is the caller's own object: it must still
+ *   contain the moved spheres.  glome_scene_bih_update keeps refusing a sphere bih, and this call a triangle bih.
+ * glome_scene_sphere_bih_update takes a host array, checks that every value is finite and every radius > 0, waits for every launch of
+ * the context (all slots), stages the array, updates and returns when the update is complete; *gpu_ms (may be NULL) = HIP-event time of
+ * its kernels.
+ * glome_scene_sphere_bih_update_dev takes a DEVICE pointer (fp64) and is asynchronous on the context's current stream and slot, like
+ * glome_scene_bih_update_dev: launches enqueued after it on that stream see the new spheres, and the array must stay valid until it has
+ * run.  Launches still in flight on OTHER slots / streams read the same pools: ordering an update against them is the caller's
+ * responsibility.  It takes part in glome_ctx_timing_begin / _end (one event pair per update).  A value that is not finite or a radius
+ * that is not positive is found on the device: the next glome_ctx_synchronize returns GLOME_E_INVALID (the error word is the other
+ * updates': the message names this call too), and the tree is unspecified -- though never out of bounds -- until a valid update.
+ *   With glome_scene_nested_updates on (below), an accepted update of a sphere bih under bihs also leaves its fp64 bound, min(c - r) /
+ * max(c + r) from +-1e6, in the scene's bounds table and marks the trees above stale; glome_scene_bih_refit of those, inner trees first,
+ * then gives the scene a commit after glome_sb_bih_set_spheres + glome_sb_bih_refit would give, bit for bit.
+ * The first update of a bih allocates its workspace (32 bytes per sphere and per node), kept until glome_scene_release. */
+int glome_scene_sphere_bih_update(glome_scene*, int32_t bih_id, const double* c3r, int n, float* gpu_ms);
+int glome_scene_sphere_bih_update_dev(glome_scene*, int32_t bih_id, const double* c3r_dev, int n);
+
 /* ---- animate committed Instances: new matrices, the bih that holds them refitted on the GPU ----
  * Every `transform` that is not pushed down into a primitive is an Instance: a rigid object, and every `cylinder` and `cone`.  After an
  * update the committed scene is, bit for bit, the scene glome_scene_commit would have made had glome_sb_instance_set_transforms been
@@ -342,7 +386,7 @@ int glome_scene_instance_update_dev(glome_scene*, const int32_t* ids, const doub
 /* ---- update objects under a bih: the chain of bihs above refitted on the GPU, one call per tree ----
  * The three updates above refuse an object as soon as a bih lies above it (a second one for an Instance): that tree's planes and box
  * were built from the object's bound.  glome_scene_nested_updates(scene, 1) lifts that: the updates then accept an object X -- a Mesh, a
- * bih of plain triangles, an Instance that is an item of a bih -- when on EVERY path from the committed root (or a Warp material's frame /
+ * bih of plain triangles or plain spheres, an Instance that is an item of a bih -- when on EVERY path from the committed root (or a Warp material's frame /
  * scene) down to X every bih B on the path holds, on that path, an item that is LIVE over the next thing down (X, or the next bih): the
  * item, Tex / Tag / NoShadow / OnlyShadow wrappers peeled off, is that thing itself (a direct item) or an Instance whose child, peeled
  * again, is that thing (an instanced item).  For an Instance X its own bih holds X as the item.  Still refused, the message naming the
