@@ -107,6 +107,7 @@ SYMBOLS = [
     ("glome_sb_bih", C.c_int32, [vp, c_ip, C.c_int]),
     ("glome_sb_mesh", C.c_int32, [vp, c_dp, C.c_int, c_dp, C.c_int, c_ip, C.c_int, c_ip, C.c_int]),
     ("glome_sb_bih_set_triangles", C.c_int, [vp, C.c_int32, c_dp, C.c_int]),
+    ("glome_sb_bih_set_triangles_indexed", C.c_int, [vp, C.c_int32, c_dp, C.c_int, c_ip, C.c_int]),
     ("glome_sb_bih_set_spheres", C.c_int, [vp, C.c_int32, c_dp, C.c_int]),
     ("glome_sb_instance_set_transforms", C.c_int, [vp, c_ip, c_dp, C.c_int]),
     ("glome_sb_bih_items", C.c_int32, [vp, C.c_int32, c_ip, C.c_int32]),
@@ -147,6 +148,14 @@ SYMBOLS = [
     ("glome_scene_bih_update_dev", C.c_int, [vp, C.c_int32, vp, C.c_int]),
     ("glome_scene_sphere_bih_update", C.c_int, [vp, C.c_int32, c_dp, C.c_int, C.POINTER(C.c_float)]),
     ("glome_scene_sphere_bih_update_dev", C.c_int, [vp, C.c_int32, vp, C.c_int]),
+    ("glome_scene_bih_update_indexed", C.c_int, [vp, C.c_int32, vp, C.c_int32, C.c_int, c_ip, C.c_int, C.POINTER(C.c_float)]),
+    ("glome_scene_bih_update_indexed_dev", C.c_int, [vp, C.c_int32, vp, C.c_int32, C.c_int, vp, C.c_int]),
+    ("glome_scene_bih_update_f32", C.c_int, [vp, C.c_int32, c_fp, C.c_int, C.POINTER(C.c_float)]),
+    ("glome_scene_bih_update_f32_dev", C.c_int, [vp, C.c_int32, vp, C.c_int]),
+    ("glome_scene_mesh_update_f32", C.c_int, [vp, C.c_int32, c_fp, C.c_int, c_fp, C.c_int, C.POINTER(C.c_float)]),
+    ("glome_scene_mesh_update_f32_dev", C.c_int, [vp, C.c_int32, vp, C.c_int, vp, C.c_int]),
+    ("glome_scene_sphere_bih_update_f32", C.c_int, [vp, C.c_int32, c_fp, c_fp, C.c_int, C.POINTER(C.c_float)]),
+    ("glome_scene_sphere_bih_update_f32_dev", C.c_int, [vp, C.c_int32, vp, vp, C.c_int]),
     ("glome_scene_instance_update", C.c_int, [vp, c_ip, c_dp, C.c_int, C.POINTER(C.c_float)]),
     ("glome_scene_instance_update_dev", C.c_int, [vp, c_ip, vp, C.c_int]),
     ("glome_scene_nested_updates", C.c_int, [vp, C.c_int]),

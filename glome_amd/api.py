@@ -250,6 +250,14 @@ class Builder:
         p = np.ascontiguousarray(np.asarray(pts9, dtype=np.float64).reshape(-1, 9))
         self._chk(self.lib.glome_sb_bih_set_triangles(self.h, int(node), p.ctypes.data_as(L.c_dp) if p.shape[0] else None, p.shape[0]), "glome_sb_bih_set_triangles")
 
+    def bih_set_triangles_indexed(self, node, verts, idx):
+        """bih_set_triangles from a vertex array [nv, 3] and an index table [n, 3] of vertex indices per item in update order
+        (glome_sb_bih_set_triangles_indexed): only referenced vertices count."""
+        v = np.ascontiguousarray(np.asarray(verts, dtype=np.float64).reshape(-1, 3))
+        i = np.ascontiguousarray(np.asarray(idx, dtype=np.int32).reshape(-1, 3))
+        self._chk(self.lib.glome_sb_bih_set_triangles_indexed(self.h, int(node), v.ctypes.data_as(L.c_dp) if v.shape[0] else None, v.shape[0],
+                                                              i.ctypes.data_as(L.c_ip) if i.shape[0] else None, i.shape[0]), "glome_sb_bih_set_triangles_indexed")
+
     def bih_set_spheres(self, node, c3r):
         """Same tree, new spheres (glome_sb_bih_set_spheres): four values per item in update order (bih_items), cx cy cz r with r > 0; the
         bih's planes and box are made again, its topology stays."""
@@ -539,6 +547,81 @@ class Scene:
         p = np.ascontiguousarray(np.asarray(c3r, dtype=np.float64).reshape(-1, 4))
         ms = C.c_float(0)
         self._chk(self.lib.glome_scene_sphere_bih_update(self.h, int(bih_id), p.ctypes.data_as(L.c_dp) if p.shape[0] else None, p.shape[0], C.byref(ms)), "glome_scene_sphere_bih_update")
+        return ms.value
+
+    @staticmethod
+    def _dev_arg(t, call, what, dtypes, per_row):
+        """(pointer, rows) of a torch tensor handed to a device form, refused in the wording of the fp64 methods"""
+        if not hasattr(t, "data_ptr") or not t.is_cuda or str(t.dtype) not in dtypes or not t.is_contiguous() or t.numel() % per_row:
+            raise GlomeError(f"{call}: {what} must be a contiguous CUDA {' or '.join(dtypes)} tensor of {per_row} value{'s' if per_row > 1 else ''} per row")
+        return (C.c_void_p(t.data_ptr()) if t.numel() else None), t.numel() // per_row
+
+    def bih_update_indexed(self, bih_id, verts, idx):
+        """bih_update from the arrays a simulation holds (glome_scene_bih_update_indexed): vertices [nv, 3], float32 or float64, and an int32
+        table [n, 3] of three vertex indices per item in update order.  The scene bih_update gives for the gathered, widened array, bit for
+        bit; only referenced vertices count.  NumPy arrays take the host form (a float32 array is staged as float32, anything else as
+        float64) and return the device milliseconds; CUDA torch tensors -- float32 or float64 vertices, int32 indices -- take the device
+        form, asynchronous on the context's stream (returns None; the tensors must stay alive until it has run)."""
+        if hasattr(verts, "data_ptr") or hasattr(idx, "data_ptr"):  # torch tensors: the device form
+            pv, nv = self._dev_arg(verts, "bih_update_indexed", "verts", ("torch.float32", "torch.float64"), 3)
+            pi, n = self._dev_arg(idx, "bih_update_indexed", "idx", ("torch.int32",), 3)
+            dtype = 1 if str(verts.dtype) == "torch.float32" else 0  # GLOME_F32 / GLOME_F64
+            self._chk(self.lib.glome_scene_bih_update_indexed_dev(self.h, int(bih_id), pv, dtype, nv, pi, n), "glome_scene_bih_update_indexed_dev")
+            return None
+        v = np.asarray(verts)
+        dtype = 1 if v.dtype == np.float32 else 0
+        v = np.ascontiguousarray(np.asarray(v, dtype=np.float32 if dtype else np.float64).reshape(-1, 3))
+        i = np.ascontiguousarray(np.asarray(idx, dtype=np.int32).reshape(-1, 3))
+        ms = C.c_float(0)
+        self._chk(self.lib.glome_scene_bih_update_indexed(self.h, int(bih_id), C.c_void_p(v.ctypes.data) if v.shape[0] else None, dtype, v.shape[0],
+                                                          i.ctypes.data_as(L.c_ip) if i.shape[0] else None, i.shape[0], C.byref(ms)), "glome_scene_bih_update_indexed")
+        return ms.value
+
+    def bih_update_f32(self, bih_id, pts9):
+        """bih_update from float32 (glome_scene_bih_update_f32): nine values per item; the scene bih_update gives for the widened array, bit
+        for bit.  NumPy arrays take the host form; a CUDA torch.float32 tensor takes the device form (returns None)."""
+        if hasattr(pts9, "data_ptr"):
+            p, n = self._dev_arg(pts9, "bih_update_f32", "pts9", ("torch.float32",), 9)
+            self._chk(self.lib.glome_scene_bih_update_f32_dev(self.h, int(bih_id), p, n), "glome_scene_bih_update_f32_dev")
+            return None
+        p = np.ascontiguousarray(np.asarray(pts9, dtype=np.float32).reshape(-1, 9))
+        ms = C.c_float(0)
+        self._chk(self.lib.glome_scene_bih_update_f32(self.h, int(bih_id), p.ctypes.data_as(L.c_fp) if p.shape[0] else None, p.shape[0], C.byref(ms)), "glome_scene_bih_update_f32")
+        return ms.value
+
+    def mesh_update_f32(self, mesh_id, verts, norms=None):
+        """mesh_update from float32 (glome_scene_mesh_update_f32): the scene mesh_update gives for the widened arrays, bit for bit.  NumPy
+        arrays take the host form; CUDA torch.float32 tensors take the device form (returns None)."""
+        if hasattr(verts, "data_ptr"):
+            pv, nv = self._dev_arg(verts, "mesh_update_f32", "verts", ("torch.float32",), 3)
+            pn, nn = (None, 0) if norms is None else self._dev_arg(norms, "mesh_update_f32", "norms", ("torch.float32",), 3)
+            self._chk(self.lib.glome_scene_mesh_update_f32_dev(self.h, int(mesh_id), pv, nv, pn, nn), "glome_scene_mesh_update_f32_dev")
+            return None
+        v = np.ascontiguousarray(np.asarray(verts, dtype=np.float32).reshape(-1, 3))
+        n = None if norms is None else np.ascontiguousarray(np.asarray(norms, dtype=np.float32).reshape(-1, 3))
+        ms = C.c_float(0)
+        self._chk(self.lib.glome_scene_mesh_update_f32(self.h, int(mesh_id), v.ctypes.data_as(L.c_fp), v.shape[0], n.ctypes.data_as(L.c_fp) if n is not None and n.shape[0] else None,
+                                                       0 if n is None else n.shape[0], C.byref(ms)), "glome_scene_mesh_update_f32")
+        return ms.value
+
+    def sphere_bih_update_f32(self, bih_id, centres, radii):
+        """sphere_bih_update from two float32 streams, centres [n, 3] and radii [n], as a particle system holds them
+        (glome_scene_sphere_bih_update_f32): the scene sphere_bih_update gives for the widened, interleaved array, bit for bit.  NumPy
+        arrays take the host form; CUDA torch.float32 tensors take the device form (returns None)."""
+        if hasattr(centres, "data_ptr") or hasattr(radii, "data_ptr"):
+            pc, n = self._dev_arg(centres, "sphere_bih_update_f32", "centres", ("torch.float32",), 3)
+            pr, nr = self._dev_arg(radii, "sphere_bih_update_f32", "radii", ("torch.float32",), 1)
+            if nr != n:
+                raise GlomeError(f"sphere_bih_update_f32: {n} centres but {nr} radii")
+            self._chk(self.lib.glome_scene_sphere_bih_update_f32_dev(self.h, int(bih_id), pc, pr, n), "glome_scene_sphere_bih_update_f32_dev")
+            return None
+        c = np.ascontiguousarray(np.asarray(centres, dtype=np.float32).reshape(-1, 3))
+        r = np.ascontiguousarray(np.asarray(radii, dtype=np.float32).ravel())
+        if r.shape[0] != c.shape[0]:
+            raise GlomeError(f"sphere_bih_update_f32: {c.shape[0]} centres but {r.shape[0]} radii")
+        ms = C.c_float(0)
+        self._chk(self.lib.glome_scene_sphere_bih_update_f32(self.h, int(bih_id), c.ctypes.data_as(L.c_fp) if c.shape[0] else None, r.ctypes.data_as(L.c_fp) if c.shape[0] else None,
+                                                             c.shape[0], C.byref(ms)), "glome_scene_sphere_bih_update_f32")
         return ms.value
 
     def instance_update(self, ids, xfms):

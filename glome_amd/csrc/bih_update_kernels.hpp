@@ -10,7 +10,8 @@
 // round_down(kInfinity - kDelta) -- what an empty subtree gives on the host.  A node holds two planes, not two boxes, so the pass keeps a
 // box per record and per branch slot in a workspace: an ancestor may split on any axis.  The tree's own box is ONE pad deep, a different
 // fp32 value: it is reduced on its own over all vertices (k_points_bound), from the host's box_empty.
-//   k_bih_tris           one lane per record: the tris record, its words of its pair record, its plane-form box into the workspace
+//   k_bih_tris           one lane per record: the tris record, its words of its pair record, its plane-form box into the workspace; an
+//                        instance per point source (update_common.hpp: dense or indexed, fp64 or fp32), one body after the load
 //   k_bih_level          one launch per tree level from the deepest up, one lane per branch node: its planes, its box
 //   k_bih_levels_merged  a run of narrow levels (each at most kMergeBlock nodes) in ONE block, a block barrier between levels: off by
 //                        default (GLOME_DEBUG_BIH_UPDATE_MERGED) until measured to win; wide levels then keep k_bih_level
@@ -34,8 +35,8 @@ namespace bihupd {
 // grid-stride launches of 64-lane blocks like the mesh update's.
 constexpr int kMergeBlock = 1024;
 
-struct DTrisArgs {
-  const double* pts9;    // nine per item: p1 p2 p3
+template <class Src> struct DTrisArgs {
+  Src src;               // the items' vertices, three points per item: p1 p2 p3 (update_common.hpp: a point source)
   const uint2* rows;     // per record: (item, pair words -- BihUpdateInfo)
   float4* tris;          // the tree's first record
   float* tripairs;       // the scene's pool
@@ -51,11 +52,11 @@ struct DLevelArgs {
   uint32_t first_rec, first_slot;
 };
 
-__global__ void __launch_bounds__(64) k_bih_tris(DTrisArgs A) {
+template <class Src> __global__ void __launch_bounds__(64) k_bih_tris(DTrisArgs<Src> A) {
   upd::for_lanes(A.n, [&](uint32_t j) {
     const uint2 row = A.rows[j];
     double a[3], b[3], c[3];
-    upd::d3_load(A.pts9, 3 * (int)row.x, a); upd::d3_load(A.pts9, 3 * (int)row.x + 1, b); upd::d3_load(A.pts9, 3 * (int)row.x + 2, c);
+    A.src.load(3 * (int)row.x, a); A.src.load(3 * (int)row.x + 1, b); A.src.load(3 * (int)row.x + 2, c);
     float4 rec[3];
     upd::tri_record(a, b, c, rec);
     float4* o = A.tris + 3 * (size_t)j;

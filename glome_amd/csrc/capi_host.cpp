@@ -134,6 +134,19 @@ int glome_sb_bih_set_triangles(glome_sb* sb, int32_t bih_id, const double* pts9,
     return 0;
   });
 }
+int glome_sb_bih_set_triangles_indexed(glome_sb* sb, int32_t bih_id, const double* verts, int nv, const int32_t* idx3, int n) {
+  return guard(sb, [&] {
+    if (n < 0 || nv < 0 || (n && !idx3) || (nv && !verts)) throw std::invalid_argument("bih_set_triangles_indexed: null vertex or index array");
+    std::vector<D3> P;  // the gathered array: only referenced vertices are looked at
+    for (size_t k = 0; k < 3 * (size_t)n; k++) {
+      const int32_t i = idx3[k];
+      if (i < 0 || i >= nv) throw std::invalid_argument("bih_set_triangles_indexed: item " + std::to_string(k / 3) + " has vertex index " + std::to_string(i) + ", outside [0, " + std::to_string(nv) + ")");
+      P.push_back(d3(verts + 3 * (size_t)i));
+    }
+    sb->graph.bih_set_triangles(bih_id, P);
+    return 0;
+  });
+}
 int glome_sb_bih_set_spheres(glome_sb* sb, int32_t bih_id, const double* c3r, int n) {
   return guard(sb, [&] {
     if (n < 0 || (n && !c3r)) throw std::invalid_argument("bih_set_spheres: null sphere array");

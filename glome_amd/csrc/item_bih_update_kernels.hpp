@@ -120,14 +120,15 @@ __device__ __forceinline__ void block_fold(double lo[3], double hi[3], double (*
     for (int w = 1; w < kFoldBlock / 64; w++) for (int a = 0; a < 3; a++) { lo[a] = fmin(lo[a], sh[w][a]); hi[a] = fmax(hi[a], sh[w][3 + a]); }
 }
 
-// part[6 b ..]: block b's box over points b * 256 + lane, (b + gridDim.x) * 256 + lane, ...; real infinities where it saw none
-__global__ void __launch_bounds__(kFoldBlock) k_nest_points_part(const double* pts, uint32_t n, double* part) {
+// part[6 b ..]: block b's box over points b * 256 + lane, (b + gridDim.x) * 256 + lane, ... of a point source (update_common.hpp); real
+// infinities where it saw none
+template <class Src> __global__ void __launch_bounds__(kFoldBlock) k_nest_points_part(Src pts, uint32_t n, double* part) {
   __shared__ double sh[kFoldBlock / 64][6];
   const double inf = __builtin_huge_val();
   double lo[3] = {inf, inf, inf}, hi[3] = {-inf, -inf, -inf};
   for (uint32_t i = blockIdx.x * kFoldBlock + threadIdx.x; i < n; i += gridDim.x * kFoldBlock) {
     double p[3];
-    upd::d3_load(pts, (int)i, p);
+    pts.load((int)i, p);
     for (int a = 0; a < 3; a++) { lo[a] = fmin(lo[a], __dsub_rn(p[a], kDelta)); hi[a] = fmax(hi[a], __dadd_rn(p[a], kDelta)); }
   }
   block_fold(lo, hi, sh);

@@ -7,7 +7,8 @@
 // round_up(x + kDelta) are monotone, so they commute with min and max: a triangle's fp32 box is folded per vertex, and every box above
 // it is an fp32 min / max of boxes below.  No fp64 above the leaves, and the order of a reduction does not matter (min and max are exact;
 // p -+ kDelta is never -0, so there is no tie between zeros of two signs either).
-//   k_mesh_tris          one lane per mtris record: the record, its trinorms words, its fp32 box into the workspace
+//   k_mesh_tris          one lane per mtris record: the record, its trinorms words, its fp32 box into the workspace; an instance per
+//                        point source (fp64 or fp32 arrays), one body after the load
 //   k_mesh_refit_level   one launch per tree level from the deepest up, one lane per branch node: its two boxes
 // and, of update_common.hpp, with real infinity as the start:
 //   k_points_bound       the box over ALL vertices (Mesh.hs:55), per block, and the check that every coordinate is finite
@@ -27,9 +28,9 @@
 namespace glome {
 namespace meshupd {
 
-struct DTrisArgs {
-  const double* verts;
-  const double* norms;   // null when the mesh has none
+template <class Src> struct DTrisArgs {
+  Src verts;             // a dense point source (update_common.hpp), fp64 or fp32: the rows below are the mesh's own index table
+  Src norms;             // null when the mesh has none
   const int4* rows;      // two per record: (a, b, c, na) (nb, nc, trinorms base or -1, -)
   float4* mtris;         // the mesh's first record
   float4* trinorms;      // the scene's pool
@@ -45,19 +46,19 @@ struct DLevelArgs {
   uint32_t first_tri;    // the record ws[0] belongs to
 };
 
-__global__ void __launch_bounds__(64) k_mesh_tris(DTrisArgs A) {
+template <class Src> __global__ void __launch_bounds__(64) k_mesh_tris(DTrisArgs<Src> A) {
   upd::for_lanes(A.n, [&](uint32_t j) {
     const int4 r0 = A.rows[2 * (size_t)j], r1 = A.rows[2 * (size_t)j + 1];
     if (r0.x < 0) return;  // the placeholder of an empty leaf: no triangle, and no leaf folds its box
     double a[3], b[3], c[3];
-    upd::d3_load(A.verts, r0.x, a); upd::d3_load(A.verts, r0.y, b); upd::d3_load(A.verts, r0.z, c);
+    A.verts.load(r0.x, a); A.verts.load(r0.y, b); A.verts.load(r0.z, c);
     float4 rec[3];
     upd::tri_record(a, b, c, rec);
     float4* o = A.mtris + 3 * (size_t)j;
     o[0] = rec[0]; o[1] = rec[1]; o[2] = rec[2];
     if (r1.z >= 0) {
       const int ni[3] = {r0.w, r1.x, r1.y};
-      for (int k = 0; k < 3; k++) { double v[3]; upd::d3_load(A.norms, ni[k], v); A.trinorms[(size_t)r1.z + k] = make_float4((float)v[0], (float)v[1], (float)v[2], 0.0f); }
+      for (int k = 0; k < 3; k++) { double v[3]; A.norms.load(ni[k], v); A.trinorms[(size_t)r1.z + k] = make_float4((float)v[0], (float)v[1], (float)v[2], 0.0f); }
     }
     const float inf = __builtin_huge_valf();
     float lo[3] = {inf, inf, inf}, hi[3] = {-inf, -inf, -inf};

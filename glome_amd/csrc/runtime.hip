@@ -717,7 +717,8 @@ static int device_error_status(glome_ctx* ctx, unsigned int e) {
                " entry that is not finite or a bih item box that reaches infinity: then those Instances and the bih that holds them are; or a"
                " refit, glome_scene_bih_refit, met an item box or joined box that reaches infinity: then that bih and the bihs above it are;"
                " or a sphere bih update, glome_scene_sphere_bih_update, met a value that is not finite or a radius that is not positive: then"
-               " that bih is)";
+               " that bih is); or an indexed bih update, glome_scene_bih_update_indexed_dev, met a vertex index outside [0, nv), read vertex 0 in"
+               " its place, and left that bih unspecified";
     return GLOME_E_INVALID;
   }
   ctx->err = "device-side limit hit (traversal stack or CSG advance cap)";
@@ -1137,12 +1138,16 @@ static int accepted(glome_scene* s, const char* what, const UpdateAnswer& plain,
   if (!A.ok) { s->ctx->err = std::string(what) + " refused: " + A.why_not; return GLOME_E_INVALID; }
   return 0;
 }
-// The fp32 box over all points of an array into a header's two box words: partial boxes, then their fold from +-start (update_common.hpp).
-static void launch_bound32(glome_ctx* ctx, const double* pts_dev, uint32_t n_pts, float4* part, float start, float4* hdr) {
+// The point sources of the updates (update_common.hpp): dense or indexed, fp64 or fp32.
+template <class T> static upd::IndexedPts<T> indexed_pts(glome_ctx* ctx, const void* verts_dev, int nv, const int32_t* idx_dev) {
+  return upd::IndexedPts<T>{(const T*)verts_dev, idx_dev, (uint32_t)nv, &ctx->slot().d_counters->error};
+}
+// The fp32 box over all points of a source into a header's two box words: partial boxes, then their fold from +-start (update_common.hpp).
+template <class Src> static void launch_bound32(glome_ctx* ctx, Src pts, uint32_t n_pts, float4* part, float start, float4* hdr) {
   const uint32_t blocks = std::max<uint32_t>(1u, std::min<uint32_t>((n_pts + upd::kBoundBlock - 1) / upd::kBoundBlock, (uint32_t)upd::kBoundMaxBlocks));
-  upd::DBoundArgs A;
-  A.verts = pts_dev; A.nv = n_pts; A.part = part; A.error = &ctx->slot().d_counters->error;
-  hipLaunchKernelGGL(upd::k_points_bound, dim3(blocks), dim3(upd::kBoundBlock), 0, ctx->stream, A);
+  upd::DBoundArgs<Src> A;
+  A.src = pts; A.nv = n_pts; A.part = part; A.error = &ctx->slot().d_counters->error;
+  hipLaunchKernelGGL(upd::k_points_bound<Src>, dim3(blocks), dim3(upd::kBoundBlock), 0, ctx->stream, A);
   hipLaunchKernelGGL(upd::k_bound_store, dim3(1), dim3(64), 0, ctx->stream, (const float4*)part, blocks, start, hdr);
 }
 // A bih's planes: a launch of k_bih_level per tree level, deepest first.  merged_off (the triangle bih alone, behind its switch): the
@@ -1165,10 +1170,10 @@ static void launch_levels(glome_ctx* ctx, const bihupd::DLevelArgs& A, const std
 
 // ---- objects under a bih, and the item bihs above them (item_bih_update_kernels.hpp) ----
 // An updated object's fp64 bound into its row of the bounds table -- two launches on the current stream -- and the trees above it stale.
-static void nested_points_bound(glome_scene* s, int node, const double* pts_dev, uint32_t n_pts, double start, const std::vector<int>& above) {
+template <class Src> static void nested_points_bound(glome_scene* s, int node, Src pts, uint32_t n_pts, double start, const std::vector<int>& above) {
   glome_ctx* ctx = s->ctx;
   const uint32_t blocks = std::min<uint32_t>((n_pts + itemupd::kFoldBlock - 1) / itemupd::kFoldBlock, (uint32_t)itemupd::kPartMaxBlocks);
-  if (blocks) hipLaunchKernelGGL(itemupd::k_nest_points_part, dim3(blocks), dim3(itemupd::kFoldBlock), 0, ctx->stream, pts_dev, n_pts, s->d_live_part);
+  if (blocks) hipLaunchKernelGGL(itemupd::k_nest_points_part<Src>, dim3(blocks), dim3(itemupd::kFoldBlock), 0, ctx->stream, pts, n_pts, s->d_live_part);
   hipLaunchKernelGGL(itemupd::k_nest_fold_store, dim3(1), dim3(itemupd::kFoldBlock), 0, ctx->stream, (const double*)s->d_live_part, blocks, start,
                      s->d_live + 6 * (size_t)s->live_slot.at(node), &ctx->slot().d_counters->error);
   s->stale.insert(above.begin(), above.end());
@@ -1255,21 +1260,24 @@ static int mesh_update_check(glome_scene* s, int32_t mesh_id, const void* verts,
   *out = &it->second;
   return 0;
 }
-int glome_scene_mesh_update_dev(glome_scene* s, int32_t mesh_id, const double* verts_dev, int nv, const double* norms_dev, int nn) {
+// the device form, for arrays of T: the launches, on the current stream
+template <class T> static int mesh_update_dev(glome_scene* s, int32_t mesh_id, const T* verts_p, int nv, const T* norms_p, int nn) {
   if (!s) return GLOME_E_INVALID;
   glome_ctx* ctx = s->ctx;
   glome_scene::MeshUpd* m = nullptr;
-  if (int rc = mesh_update_check(s, mesh_id, verts_dev, nv, norms_dev, nn, &m)) return rc;
+  if (int rc = mesh_update_check(s, mesh_id, verts_p, nv, norms_p, nn, &m)) return rc;
   HIPCHK(ctx, hipSetDevice(ctx->device));
+  using Src = upd::DensePts<T>;
+  const Src verts_dev{verts_p}, norms_dev{norms_p};
   const MeshUpdateInfo& U = m->info;
   if (int rc = ensure_ws(s, m->d_ws, 2 * ((size_t)U.n_tris + upd::kBoundMaxBlocks))) return rc;  // a box per record, and the bound's partial boxes
   UpdateSpan span(ctx, "GLOME_DEBUG_MESH_UPDATE_SPLIT");
   HIPCHK(ctx, span.begin());
   {
-    meshupd::DTrisArgs A;
+    meshupd::DTrisArgs<Src> A;
     A.verts = verts_dev; A.norms = norms_dev; A.rows = (const int4*)m->d_rows;
     A.mtris = (float4*)s->dev.mtris + 3 * (size_t)U.first_tri; A.trinorms = (float4*)s->dev.trinorms; A.ws = m->d_ws; A.n = U.n_tris;
-    launch_lanes(ctx, meshupd::k_mesh_tris, U.n_tris, A);
+    launch_lanes(ctx, meshupd::k_mesh_tris<Src>, U.n_tris, A);
   }
   HIPCHK(ctx, span.stage());
   for (size_t l = 0; l + 1 < U.level_off.size(); l++) {
@@ -1287,7 +1295,8 @@ int glome_scene_mesh_update_dev(glome_scene* s, int32_t mesh_id, const double* v
   mark_launched(ctx);  // (a vertex that is not finite is reported at the next synchronize)
   return 0;
 }
-int glome_scene_mesh_update(glome_scene* s, int32_t mesh_id, const double* verts, int nv, const double* norms, int nn, float* gpu_ms) {
+// the host form, for arrays of T: staged as they are
+template <class T> static int mesh_update_host(glome_scene* s, int32_t mesh_id, const T* verts, int nv, const T* norms, int nn, float* gpu_ms) {
   if (!s) return GLOME_E_INVALID;
   glome_ctx* ctx = s->ctx;
   if (gpu_ms) *gpu_ms = 0;
@@ -1298,10 +1307,22 @@ int glome_scene_mesh_update(glome_scene* s, int32_t mesh_id, const double* verts
   HIPCHK(ctx, hipSetDevice(ctx->device));
   if (int rc = quiesce(ctx)) return rc;
   Staging stg{ctx, {}};
-  double* dv = stg.in<double>(verts, 3 * (size_t)nv);
-  double* dn = nn ? stg.in<double>(norms, 3 * (size_t)nn) : nullptr;
+  T* dv = stg.in<T>(verts, 3 * (size_t)nv);
+  T* dn = nn ? stg.in<T>(norms, 3 * (size_t)nn) : nullptr;
   if (!dv || (nn && !dn)) { ctx->err = "staging allocation failed"; return GLOME_E_HIP; }
-  return run_blocking(ctx, gpu_ms, [&] { return glome_scene_mesh_update_dev(s, mesh_id, dv, nv, dn, nn); });
+  return run_blocking(ctx, gpu_ms, [&] { return mesh_update_dev<T>(s, mesh_id, dv, nv, dn, nn); });
+}
+int glome_scene_mesh_update_dev(glome_scene* s, int32_t mesh_id, const double* verts_dev, int nv, const double* norms_dev, int nn) {
+  return mesh_update_dev<double>(s, mesh_id, verts_dev, nv, norms_dev, nn);
+}
+int glome_scene_mesh_update(glome_scene* s, int32_t mesh_id, const double* verts, int nv, const double* norms, int nn, float* gpu_ms) {
+  return mesh_update_host<double>(s, mesh_id, verts, nv, norms, nn, gpu_ms);
+}
+int glome_scene_mesh_update_f32_dev(glome_scene* s, int32_t mesh_id, const float* verts_dev, int nv, const float* norms_dev, int nn) {
+  return mesh_update_dev<float>(s, mesh_id, verts_dev, nv, norms_dev, nn);
+}
+int glome_scene_mesh_update_f32(glome_scene* s, int32_t mesh_id, const float* verts, int nv, const float* norms, int nn, float* gpu_ms) {
+  return mesh_update_host<float>(s, mesh_id, verts, nv, norms, nn, gpu_ms);
 }
 
 // ---- new triangles for a committed triangle bih (bih_update_kernels.hpp) ----
@@ -1317,11 +1338,10 @@ static int bih_update_check(glome_scene* s, int32_t bih_id, const void* pts9, in
   *out = &it->second;
   return 0;
 }
-int glome_scene_bih_update_dev(glome_scene* s, int32_t bih_id, const double* pts9_dev, int n) {
-  if (!s) return GLOME_E_INVALID;
+// The launches of an update the checks have accepted, on the current stream: `pts` yields the items' 3 n vertices (update_common.hpp: a
+// point source), and every kernel that reads them is its instance for that source.
+template <class Src> static int bih_update_launch(glome_scene* s, int32_t bih_id, glome_scene::BihUpd* m, Src pts9_dev, int n) {
   glome_ctx* ctx = s->ctx;
-  glome_scene::BihUpd* m = nullptr;
-  if (int rc = bih_update_check(s, bih_id, pts9_dev, n, &m)) return rc;
   HIPCHK(ctx, hipSetDevice(ctx->device));
   const BihUpdateInfo& U = m->info;
   // a box per record and per node slot, and the bound's partial boxes
@@ -1332,10 +1352,10 @@ int glome_scene_bih_update_dev(glome_scene* s, int32_t bih_id, const double* pts
   UpdateSpan span(ctx, "GLOME_DEBUG_BIH_UPDATE_SPLIT");
   HIPCHK(ctx, span.begin());
   {
-    bihupd::DTrisArgs A;
-    A.pts9 = pts9_dev; A.rows = (const uint2*)m->d_rows; A.tris = (float4*)s->dev.tris + 3 * (size_t)U.first_tri; A.tripairs = (float*)s->dev.tripairs;
+    bihupd::DTrisArgs<Src> A;
+    A.src = pts9_dev; A.rows = (const uint2*)m->d_rows; A.tris = (float4*)s->dev.tris + 3 * (size_t)U.first_tri; A.tripairs = (float*)s->dev.tripairs;
     A.ws = m->d_ws; A.n = U.n_tris;
-    launch_lanes(ctx, bihupd::k_bih_tris, U.n_tris, A);
+    launch_lanes(ctx, bihupd::k_bih_tris<Src>, U.n_tris, A);
   }
   HIPCHK(ctx, span.stage());
   {
@@ -1350,10 +1370,17 @@ int glome_scene_bih_update_dev(glome_scene* s, int32_t bih_id, const double* pts
   if (s->nested_on && !U.nested.above.empty()) nested_points_bound(s, bih_id, pts9_dev, 3u * (uint32_t)n, kInfinity, U.nested.above);
   HIPCHK(ctx, hipGetLastError());
   HIPCHK(ctx, span.end());
-  mark_launched(ctx);  // (a coordinate that is not finite is reported at the next synchronize)
+  mark_launched(ctx);  // (a coordinate that is not finite, or an index outside the vertex array, is reported at the next synchronize)
   return 0;
 }
-int glome_scene_bih_update(glome_scene* s, int32_t bih_id, const double* pts9, int n, float* gpu_ms) {
+template <class T> static int bih_update_dev(glome_scene* s, int32_t bih_id, const T* pts9_dev, int n) {
+  if (!s) return GLOME_E_INVALID;
+  glome_scene::BihUpd* m = nullptr;
+  if (int rc = bih_update_check(s, bih_id, pts9_dev, n, &m)) return rc;
+  return bih_update_launch(s, bih_id, m, upd::DensePts<T>{pts9_dev}, n);
+}
+// the host form, for an array of T: staged as it is
+template <class T> static int bih_update_host(glome_scene* s, int32_t bih_id, const T* pts9, int n, float* gpu_ms) {
   if (!s) return GLOME_E_INVALID;
   glome_ctx* ctx = s->ctx;
   if (gpu_ms) *gpu_ms = 0;
@@ -1363,9 +1390,53 @@ int glome_scene_bih_update(glome_scene* s, int32_t bih_id, const double* pts9, i
   HIPCHK(ctx, hipSetDevice(ctx->device));
   if (int rc = quiesce(ctx)) return rc;
   Staging stg{ctx, {}};
-  double* dp = stg.in<double>(pts9, 9 * (size_t)n);
+  T* dp = stg.in<T>(pts9, 9 * (size_t)n);
   if (!dp) { ctx->err = "staging allocation failed"; return GLOME_E_HIP; }
-  return run_blocking(ctx, gpu_ms, [&] { return glome_scene_bih_update_dev(s, bih_id, dp, n); });
+  return run_blocking(ctx, gpu_ms, [&] { return bih_update_dev<T>(s, bih_id, dp, n); });
+}
+int glome_scene_bih_update_dev(glome_scene* s, int32_t bih_id, const double* pts9_dev, int n) { return bih_update_dev<double>(s, bih_id, pts9_dev, n); }
+int glome_scene_bih_update(glome_scene* s, int32_t bih_id, const double* pts9, int n, float* gpu_ms) { return bih_update_host<double>(s, bih_id, pts9, n, gpu_ms); }
+int glome_scene_bih_update_f32_dev(glome_scene* s, int32_t bih_id, const float* pts9_dev, int n) { return bih_update_dev<float>(s, bih_id, pts9_dev, n); }
+int glome_scene_bih_update_f32(glome_scene* s, int32_t bih_id, const float* pts9, int n, float* gpu_ms) { return bih_update_host<float>(s, bih_id, pts9, n, gpu_ms); }
+
+// The indexed forms: the items' vertices are verts[3 * idx3[3 k + c] ..], a vertex array of `dtype` and an index table.  What both forms
+// refuse beyond bih_update_check, before anything is launched.
+static int bih_update_indexed_check(glome_scene* s, int32_t bih_id, const void* verts, int32_t dtype, int nv, const int32_t* idx3, int n, glome_scene::BihUpd** out) {
+  glome_ctx* ctx = s->ctx;
+  if (int rc = bih_update_check(s, bih_id, idx3, n, out)) return rc;  // (the array it asks for is the one there is one entry per item of)
+  if (dtype != GLOME_F64 && dtype != GLOME_F32) { ctx->err = "bih update: dtype " + std::to_string(dtype) + " is neither GLOME_F64 nor GLOME_F32"; return GLOME_E_INVALID; }
+  if (nv < 0 || (nv && !verts)) { ctx->err = "bih update: null vertex array"; return GLOME_E_INVALID; }
+  if (n > 0 && nv == 0) { ctx->err = "bih update: " + std::to_string(n) + " items index an array of no vertices"; return GLOME_E_INVALID; }
+  return 0;
+}
+int glome_scene_bih_update_indexed_dev(glome_scene* s, int32_t bih_id, const void* verts_dev, int32_t dtype, int nv, const int32_t* idx3_dev, int n) {
+  if (!s) return GLOME_E_INVALID;
+  glome_scene::BihUpd* m = nullptr;
+  if (int rc = bih_update_indexed_check(s, bih_id, verts_dev, dtype, nv, idx3_dev, n, &m)) return rc;
+  if (dtype == GLOME_F32) return bih_update_launch(s, bih_id, m, indexed_pts<float>(s->ctx, verts_dev, nv, idx3_dev), n);
+  return bih_update_launch(s, bih_id, m, indexed_pts<double>(s->ctx, verts_dev, nv, idx3_dev), n);
+}
+int glome_scene_bih_update_indexed(glome_scene* s, int32_t bih_id, const void* verts, int32_t dtype, int nv, const int32_t* idx3, int n, float* gpu_ms) {
+  if (!s) return GLOME_E_INVALID;
+  glome_ctx* ctx = s->ctx;
+  if (gpu_ms) *gpu_ms = 0;
+  glome_scene::BihUpd* m = nullptr;
+  if (int rc = bih_update_indexed_check(s, bih_id, verts, dtype, nv, idx3, n, &m)) return rc;
+  for (size_t k = 0; k < 3 * (size_t)n; k++) {  // only referenced vertices count: an unreferenced one may be anything
+    const int32_t i = idx3[k];
+    if (i < 0 || i >= nv) { ctx->err = "bih update: item " + std::to_string(k / 3) + " has vertex index " + std::to_string(i) + ", outside [0, " + std::to_string(nv) + ")"; return GLOME_E_INVALID; }
+    bool finite = true;
+    for (int a = 0; a < 3; a++) finite = finite && (dtype == GLOME_F32 ? std::isfinite(((const float*)verts)[3 * (size_t)i + a]) : std::isfinite(((const double*)verts)[3 * (size_t)i + a]));
+    if (!finite) { ctx->err = "bih update: a vertex coordinate is not finite (vertex " + std::to_string(i) + ", of item " + std::to_string(k / 3) + ")"; return GLOME_E_INVALID; }
+  }
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  if (int rc = quiesce(ctx)) return rc;
+  Staging stg{ctx, {}};
+  const size_t vbytes = 3 * (size_t)nv * (dtype == GLOME_F32 ? sizeof(float) : sizeof(double));
+  char* dv = stg.in<char>((const char*)verts, vbytes);  // the caller's arrays as they are: no widened, gathered copy
+  int32_t* di = stg.in<int32_t>(idx3, 3 * (size_t)n);
+  if (!dv || !di) { ctx->err = "staging allocation failed"; return GLOME_E_HIP; }
+  return run_blocking(ctx, gpu_ms, [&] { return glome_scene_bih_update_indexed_dev(s, bih_id, dv, dtype, nv, di, n); });
 }
 
 // ---- new spheres for a committed sphere bih (sphere_bih_update_kernels.hpp) ----
@@ -1381,11 +1452,10 @@ static int sphere_bih_update_check(glome_scene* s, int32_t bih_id, const void* c
   *out = &it->second;
   return 0;
 }
-int glome_scene_sphere_bih_update_dev(glome_scene* s, int32_t bih_id, const double* c3r_dev, int n) {
-  if (!s) return GLOME_E_INVALID;
+// The launches of an update the checks have accepted, on the current stream: `c3r_dev` yields the items' spheres
+// (sphere_bih_update_kernels.hpp: a sphere source), and every kernel that reads them is its instance for that source.
+template <class Src> static int sphere_bih_update_launch(glome_scene* s, int32_t bih_id, glome_scene::SphBihUpd* m, Src c3r_dev, int n) {
   glome_ctx* ctx = s->ctx;
-  glome_scene::SphBihUpd* m = nullptr;
-  if (int rc = sphere_bih_update_check(s, bih_id, c3r_dev, n, &m)) return rc;
   HIPCHK(ctx, hipSetDevice(ctx->device));
   const SphereBihUpdateInfo& U = m->info;
   // a box per record and per node slot, and the bound's partial boxes
@@ -1394,10 +1464,10 @@ int glome_scene_sphere_bih_update_dev(glome_scene* s, int32_t bih_id, const doub
   UpdateSpan span(ctx, "GLOME_DEBUG_BIH_UPDATE_SPLIT");
   HIPCHK(ctx, span.begin());
   {
-    sphupd::DItemsArgs A;
-    A.c3r = c3r_dev; A.rows = m->d_rows; A.spheres = (float4*)s->dev.spheres + (size_t)U.first_sphere; A.ws = m->d_ws; A.n = U.n_recs;
+    sphupd::DItemsArgs<Src> A;
+    A.src = c3r_dev; A.rows = m->d_rows; A.spheres = (float4*)s->dev.spheres + (size_t)U.first_sphere; A.ws = m->d_ws; A.n = U.n_recs;
     A.error = &ctx->slot().d_counters->error;
-    launch_lanes(ctx, sphupd::k_sph_items, U.n_recs, A);
+    launch_lanes(ctx, sphupd::k_sph_items<Src>, U.n_recs, A);
   }
   HIPCHK(ctx, span.stage());
   {
@@ -1410,12 +1480,12 @@ int glome_scene_sphere_bih_update_dev(glome_scene* s, int32_t bih_id, const doub
   {  // the join of the spheres' boxes, from box_empty: in fp32 into the header, in fp64 into the bounds table
     float4* part = m->d_ws + 2 * ((size_t)U.n_recs + U.n_slots);
     const uint32_t blocks = std::max<uint32_t>(1u, std::min<uint32_t>(((uint32_t)n + upd::kBoundBlock - 1) / upd::kBoundBlock, (uint32_t)upd::kBoundMaxBlocks));
-    hipLaunchKernelGGL(sphupd::k_sph_bound, dim3(blocks), dim3(upd::kBoundBlock), 0, ctx->stream, c3r_dev, (uint32_t)n, part);
+    hipLaunchKernelGGL(sphupd::k_sph_bound<Src>, dim3(blocks), dim3(upd::kBoundBlock), 0, ctx->stream, c3r_dev, (uint32_t)n, part);
     hipLaunchKernelGGL(upd::k_bound_store, dim3(1), dim3(64), 0, ctx->stream, (const float4*)part, blocks, (float)kInfinity, (float4*)s->dev.bihhdr + 3 * (size_t)U.hdr);
   }
   if (s->nested_on && !U.nested.above.empty()) {
     const uint32_t blocks = std::min<uint32_t>(((uint32_t)n + itemupd::kFoldBlock - 1) / itemupd::kFoldBlock, (uint32_t)itemupd::kPartMaxBlocks);
-    if (blocks) hipLaunchKernelGGL(sphupd::k_nest_spheres_part, dim3(blocks), dim3(itemupd::kFoldBlock), 0, ctx->stream, c3r_dev, (uint32_t)n, s->d_live_part);
+    if (blocks) hipLaunchKernelGGL(sphupd::k_nest_spheres_part<Src>, dim3(blocks), dim3(itemupd::kFoldBlock), 0, ctx->stream, c3r_dev, (uint32_t)n, s->d_live_part);
     hipLaunchKernelGGL(itemupd::k_nest_fold_store, dim3(1), dim3(itemupd::kFoldBlock), 0, ctx->stream, (const double*)s->d_live_part, blocks, kInfinity,
                        s->d_live + 6 * (size_t)s->live_slot.at(bih_id), &ctx->slot().d_counters->error);
     s->stale.insert(U.nested.above.begin(), U.nested.above.end());
@@ -1424,6 +1494,12 @@ int glome_scene_sphere_bih_update_dev(glome_scene* s, int32_t bih_id, const doub
   HIPCHK(ctx, span.end());
   mark_launched(ctx);  // (a value that is not finite or a radius that is not positive is reported at the next synchronize)
   return 0;
+}
+int glome_scene_sphere_bih_update_dev(glome_scene* s, int32_t bih_id, const double* c3r_dev, int n) {
+  if (!s) return GLOME_E_INVALID;
+  glome_scene::SphBihUpd* m = nullptr;
+  if (int rc = sphere_bih_update_check(s, bih_id, c3r_dev, n, &m)) return rc;
+  return sphere_bih_update_launch(s, bih_id, m, sphupd::SphPacked64{c3r_dev}, n);
 }
 int glome_scene_sphere_bih_update(glome_scene* s, int32_t bih_id, const double* c3r, int n, float* gpu_ms) {
   if (!s) return GLOME_E_INVALID;
@@ -1439,6 +1515,35 @@ int glome_scene_sphere_bih_update(glome_scene* s, int32_t bih_id, const double* 
   double* dp = stg.in<double>(c3r, 4 * (size_t)n);
   if (!dp) { ctx->err = "staging allocation failed"; return GLOME_E_HIP; }
   return run_blocking(ctx, gpu_ms, [&] { return glome_scene_sphere_bih_update_dev(s, bih_id, dp, n); });
+}
+// The fp32 forms: two streams, centres [n, 3] and radii [n].
+static int sphere_bih_update_f32_check(glome_scene* s, int32_t bih_id, const float* centres3, const float* radii, int n, glome_scene::SphBihUpd** out) {
+  if (int rc = sphere_bih_update_check(s, bih_id, centres3, n, out)) return rc;
+  if (n && !radii) { s->ctx->err = "sphere bih update: null radius array"; return GLOME_E_INVALID; }
+  return 0;
+}
+int glome_scene_sphere_bih_update_f32_dev(glome_scene* s, int32_t bih_id, const float* centres3_dev, const float* radii_dev, int n) {
+  if (!s) return GLOME_E_INVALID;
+  glome_scene::SphBihUpd* m = nullptr;
+  if (int rc = sphere_bih_update_f32_check(s, bih_id, centres3_dev, radii_dev, n, &m)) return rc;
+  return sphere_bih_update_launch(s, bih_id, m, sphupd::SphSplit32{centres3_dev, radii_dev}, n);
+}
+int glome_scene_sphere_bih_update_f32(glome_scene* s, int32_t bih_id, const float* centres3, const float* radii, int n, float* gpu_ms) {
+  if (!s) return GLOME_E_INVALID;
+  glome_ctx* ctx = s->ctx;
+  if (gpu_ms) *gpu_ms = 0;
+  glome_scene::SphBihUpd* m = nullptr;
+  if (int rc = sphere_bih_update_f32_check(s, bih_id, centres3, radii, n, &m)) return rc;
+  for (size_t k = 0; k < 3 * (size_t)n; k++) if (!std::isfinite(centres3[k])) { ctx->err = "sphere bih update: a value is not finite"; return GLOME_E_INVALID; }
+  for (size_t k = 0; k < (size_t)n; k++) if (!std::isfinite(radii[k])) { ctx->err = "sphere bih update: a value is not finite"; return GLOME_E_INVALID; }
+  for (size_t k = 0; k < (size_t)n; k++) if (!(radii[k] > 0)) { ctx->err = "sphere bih update: radius of item " + std::to_string(k) + " is not positive"; return GLOME_E_INVALID; }
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  if (int rc = quiesce(ctx)) return rc;
+  Staging stg{ctx, {}};
+  float* dc = stg.in<float>(centres3, 3 * (size_t)n);
+  float* dr = stg.in<float>(radii, (size_t)n);
+  if (!dc || !dr) { ctx->err = "staging allocation failed"; return GLOME_E_HIP; }
+  return run_blocking(ctx, gpu_ms, [&] { return glome_scene_sphere_bih_update_f32_dev(s, bih_id, dc, dr, n); });
 }
 
 // ---- new matrices for committed Instances (item_bih_update_kernels.hpp) ----

@@ -8,6 +8,7 @@
 // Each header argues this for the values it makes.  fp64 arithmetic is spelled with explicit round-to-nearest operations in the host's
 // expression order (host_graph.hpp: operator-, cross, normalize): nothing contracts.
 //   for_lanes        the grid-stride loop over 64-element items, one lane per element
+//   DensePts / IndexedPts   where an update reads its points: a point source yields point k as three doubles, whatever the caller holds
 //   fold_rows        stored boxes -- float4 row pairs (lo, -) (hi, -) -- folded into lo / hi
 //   k_points_bound   the box over ALL points of an array (Mesh.hs:55), per block, and the check that every coordinate is finite
 //   k_bound_store    folds the blocks' boxes, from a start value, into a header's two box words
@@ -31,7 +32,30 @@ template <class F> __device__ __forceinline__ void for_lanes(uint32_t n, F f) {
   }
 }
 
-__device__ __forceinline__ void d3_load(const double* p, int i, double v[3]) { v[0] = p[3 * (size_t)i]; v[1] = p[3 * (size_t)i + 1]; v[2] = p[3 * (size_t)i + 2]; }
+// A point source: load(k, v) gives point k of an update's input as three doubles.  The kernels that read the input take the source as a
+// template argument -- an instance per kind rather than a copy per kind -- and everything after the load is the one body on the same
+// doubles: fp32 -> fp64 is exact, so an fp32 source gives what the fp64 source gives for the widened array, bit for bit (a subnormal
+// fp32 input may be read as zero: the library flushes them).
+//   DensePts<T>     point k is p[3 k ..], T = double (what every update took before there were sources: that instance's loads are
+//                   the ones it had) or float
+//   IndexedPts<T>   point k is p[3 idx[k] ..]: a vertex array and an index table, as a simulation holds a mesh.  An index outside
+//                   [0, nv) ORs kErrBadVertex into the slot's error word and reads vertex 0 instead: the index is clamped BEFORE the
+//                   load, so nothing is read out of bounds whatever the table holds (the host refuses nv == 0 with points to read).
+template <class T> struct DensePts {
+  const T* p;
+  __device__ __forceinline__ void load(int k, double v[3]) const { v[0] = (double)p[3 * (size_t)k]; v[1] = (double)p[3 * (size_t)k + 1]; v[2] = (double)p[3 * (size_t)k + 2]; }
+};
+template <class T> struct IndexedPts {
+  const T* p;
+  const int32_t* idx;
+  uint32_t nv;
+  unsigned int* error;   // the slot's sticky error word
+  __device__ __forceinline__ void load(int k, double v[3]) const {
+    uint32_t i = (uint32_t)idx[(size_t)k];
+    if (i >= nv) { atomicOr(error, kErrBadVertex); i = 0u; }  // (a negative index is a large unsigned one)
+    v[0] = (double)p[3 * (size_t)i]; v[1] = (double)p[3 * (size_t)i + 1]; v[2] = (double)p[3 * (size_t)i + 2];
+  }
+};
 // a vertex folded into an fp32 box: lo = round_down(p - kDelta), hi = round_up(p + kDelta) (box_of_points' pad, flatten.hpp's roundings)
 __device__ __forceinline__ void box_add(const double p[3], float lo[3], float hi[3]) {
   for (int a = 0; a < 3; a++) { lo[a] = fminf(lo[a], round_down(__dsub_rn(p[a], kDelta))); hi[a] = fmaxf(hi[a], round_up(__dadd_rn(p[a], kDelta))); }
@@ -81,26 +105,27 @@ __device__ __forceinline__ void store_rows(float4* rows, const float lo[3], cons
   rows[1] = make_float4(hi[0], hi[1], hi[2], w1);
 }
 
-struct DBoundArgs {
-  const double* verts;
-  uint32_t nv;
+template <class Src> struct DBoundArgs {
+  Src src;               // the points
+  uint32_t nv;           // how many
   float4* part;          // two per block: (lo, -) (hi, -)
   unsigned int* error;   // the slot's sticky error word
 };
 
-// The box over all points of an array -- a Mesh's vertices, unreferenced ones included; a triangle bih's 3 n vertices.  A block of 256
+// The box over all points of a source -- a Mesh's vertices, unreferenced ones included; a triangle bih's 3 n item vertices (gathered
+// through the index table when the source is indexed: a vertex no item references is never read).  A block of 256
 // lanes strides over the points, folds across each wave in registers and across its four waves through LDS, and stores one partial box;
 // k_bound_store folds the partial boxes.  A lane that meets a coordinate that is not finite ORs kErrBadVertex into the slot's error word
 // (glome_ctx_synchronize reports it).
 constexpr int kBoundBlock = 256, kBoundMaxBlocks = 1024;
-__global__ void __launch_bounds__(kBoundBlock) k_points_bound(DBoundArgs A) {
+template <class Src> __global__ void __launch_bounds__(kBoundBlock) k_points_bound(DBoundArgs<Src> A) {
   __shared__ float sh[kBoundBlock / 64][6];
   const float inf = __builtin_huge_valf();
   float lo[3] = {inf, inf, inf}, hi[3] = {-inf, -inf, -inf};
   bool bad = false;
   for (uint32_t i = blockIdx.x * kBoundBlock + threadIdx.x; i < A.nv; i += gridDim.x * kBoundBlock) {
     double p[3];
-    d3_load(A.verts, (int)i, p);
+    A.src.load((int)i, p);
     bad = bad || !(isfinite(p[0]) && isfinite(p[1]) && isfinite(p[2]));
     box_add(p, lo, hi);
   }

@@ -128,6 +128,12 @@ int glome_sb_mesh_set_vertices(glome_sb*, int32_t mesh_id, const double* verts, 
  * GLOME_E_INVALID with a message (an item that is not a plain triangle is named), and nothing is touched.  Host only; the specification
  * of glome_scene_bih_update. */
 int glome_sb_bih_set_triangles(glome_sb*, int32_t bih_id, const double* pts9, int n);
+/* The same from a vertex array and an index table, as a simulation holds a mesh: verts holds nv vertices of three doubles, idx3 three
+ * vertex indices per item, items in update order.  It is glome_sb_bih_set_triangles of the gathered array, pts9[9 k + 3 c ..] =
+ * verts[3 * idx3[3 k + c] ..], and refuses what that call refuses.  Only REFERENCED vertices count: a vertex no item names may be
+ * anything, not finite included, and takes no part in the tree's box.  An index outside [0, nv) is GLOME_E_INVALID, the message naming
+ * the item, and nothing is touched.  Host only; the specification of glome_scene_bih_update_indexed. */
+int glome_sb_bih_set_triangles_indexed(glome_sb*, int32_t bih_id, const double* verts, int nv, const int32_t* idx3, int n);
 /* Same tree, new spheres: glome_sb_bih_set_triangles for a bih of spheres.  bih_id names a Bih node, whoever made it; n is its item
  * count and c3r holds four doubles per item in update order (glome_sb_bih_items): cx cy cz r, every one finite, every r > 0.  Every item
  * must be a Sphere under any number of Tex / Tag / NoShadow / OnlyShadow wrappers, and no Sphere node may be an item twice.  Sets the
@@ -343,6 +349,38 @@ int glome_scene_bih_update_dev(glome_scene*, int32_t bih_id, const double* pts9_
  * The first update of a bih allocates its workspace (32 bytes per sphere and per node), kept until glome_scene_release. */
 int glome_scene_sphere_bih_update(glome_scene*, int32_t bih_id, const double* c3r, int n, float* gpu_ms);
 int glome_scene_sphere_bih_update_dev(glome_scene*, int32_t bih_id, const double* c3r_dev, int n);
+
+/* ---- the three updates above from the arrays a simulation holds: fp32, and a vertex array with an index table ----
+ * The calls above take one layout, contiguous fp64 expanded per item.  A producer on the GPU -- a cloth, terrain or skinning step, a
+ * particle step -- holds fp32 vertices [nv, 3] with an int32 face table [n, 3], or fp32 positions [n, 3] and radii [n]; these calls read
+ * those arrays as they are, so nothing is gathered or widened per frame.  Each leaves the committed scene bit for bit as its fp64 call
+ * leaves it when given the WIDENED AND GATHERED array: pts9[9 k + 3 c ..] = (double)verts[3 * idx3[3 k + c] ..], c3r[4 k ..] =
+ * ((double)centre, (double)radius).  fp32 -> fp64 is exact, and the kernels are the fp64 calls' own, instantiated for another way to
+ * load a point: there is no tolerance.  Everything else of the fp64 call's contract holds word for word -- the refusals before anything
+ * is launched, the host form's wait for all slots and its gpu_ms, the _dev form asynchronous on the current stream and slot with one
+ * event pair under glome_ctx_timing_begin, the workspace of the first update (the same one: the forms of one object share it), the
+ * subnormal-stored-as-zero deviation, and with glome_scene_nested_updates on the same fp64 bound in the bounds table and the same trees
+ * marked stale.  An fp32 INPUT that is subnormal may be read as zero.  The host forms stage the caller's arrays as they are.
+ *   glome_scene_bih_update_f32 / glome_scene_mesh_update_f32 / glome_scene_sphere_bih_update_f32: the fp64 call with fp32 arrays; the
+ *     sphere form takes two streams, centres3 [n, 3] and radii [n].
+ *   glome_scene_bih_update_indexed: verts holds nv vertices of three values of `dtype` (GLOME_F64: double, GLOME_F32: float), idx3 three
+ *     vertex indices per item, items in update order (glome_sb_bih_items); the specification is glome_sb_bih_set_triangles_indexed.
+ *     Only REFERENCED vertices count: the tree's box and its nested fp64 bound are folded over the gathered item vertices, never over
+ *     the vertex array, and a vertex no item names may be anything, NaN included (a Mesh keeps its own rule: its box is over ALL
+ *     vertices, Mesh.hs:55).  Refused up front as well: a dtype that is neither, a missing array, nv == 0 with n > 0.  The host form
+ *     checks every index -- one outside [0, nv) is GLOME_E_INVALID, the message naming the item, the scene untouched -- and finiteness
+ *     over the referenced vertices only.  The _dev form (both arrays DEVICE pointers) finds a bad index on the device: the lane raises
+ *     the updates' error word and reads vertex 0 instead -- the index is clamped before the load, so nothing is read out of bounds --,
+ *     the next glome_ctx_synchronize returns GLOME_E_INVALID, and the tree is unspecified, never out of bounds, until a valid update. */
+enum { GLOME_F64 = 0, GLOME_F32 = 1 };
+int glome_scene_bih_update_indexed(glome_scene*, int32_t bih_id, const void* verts, int32_t dtype, int nv, const int32_t* idx3, int n, float* gpu_ms);
+int glome_scene_bih_update_indexed_dev(glome_scene*, int32_t bih_id, const void* verts_dev, int32_t dtype, int nv, const int32_t* idx3_dev, int n);
+int glome_scene_bih_update_f32(glome_scene*, int32_t bih_id, const float* pts9, int n, float* gpu_ms);
+int glome_scene_bih_update_f32_dev(glome_scene*, int32_t bih_id, const float* pts9_dev, int n);
+int glome_scene_mesh_update_f32(glome_scene*, int32_t mesh_id, const float* verts, int nv, const float* norms, int nn, float* gpu_ms);
+int glome_scene_mesh_update_f32_dev(glome_scene*, int32_t mesh_id, const float* verts_dev, int nv, const float* norms_dev, int nn);
+int glome_scene_sphere_bih_update_f32(glome_scene*, int32_t bih_id, const float* centres3, const float* radii, int n, float* gpu_ms);
+int glome_scene_sphere_bih_update_f32_dev(glome_scene*, int32_t bih_id, const float* centres3_dev, const float* radii_dev, int n);
 
 /* ---- animate committed Instances: new matrices, the bih that holds them refitted on the GPU ----
  * Every `transform` that is not pushed down into a primitive is an Instance: a rigid object, and every `cylinder` and `cone`.  After an
