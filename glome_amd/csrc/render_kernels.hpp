@@ -28,9 +28,14 @@
 // FAITHFUL = the reference's exact node-visit order (no ordered early-out, Bih.hs:332-368); COUNT = node / primitive
 // work counters.  They back the `faithful` / `count_work` render params (byte-model measurement, parity tests).
 // The production variant traverses with early-out and counts rays only.
-template <bool FAITHFUL, bool COUNT_, bool FULL_, int CLS = CLS_ALL>
+template <bool FAITHFUL, bool COUNT_, bool FULL_, int CLS = CLS_ALL, bool SURFACE_ONLY_ = false>
 struct FlatTier {
   static constexpr bool FULL = FULL_;  // false: lean kernel (no secondary rays, no Blend / Layers)
+  // every material of the scene is a Surface: the two-row kernels, whose admission rule (instances.hpp use_two_rows over capi_shared.hpp
+  // commit_rules) refuses a scene with any other kind -- shading then reads no material kind and has no per-lane light list (rt_device.hpp
+  // trace_primary, postshade_lean)
+  static constexpr bool SURFACE_ONLY = SURFACE_ONLY_;
+  static_assert(!SURFACE_ONLY_ || !FULL_, "a full kernel shades every material kind");
   static constexpr bool COUNT = COUNT_;  // (rt_device.hpp tier_counts: a counting tier counts every ray per lane and keeps the primary ray's snapshot)
   static constexpr bool WARP = false;  // scenes with a Warp material (traces over other roots, Shader.hs:157-175) render on the generic tier
   const DScene& S;
@@ -317,7 +322,7 @@ __device__ __forceinline__ void render_loop(const DRenderArgs& A_, TIER& Tk) {
 template <bool FAITHFUL, bool COUNT, bool FULL, int CLS, int LB = 1, bool TWO_ROWS = false>
 __global__ void __launch_bounds__(64, LB) k_render_flat(DRenderArgs A, int stack_cap, uint32_t* ovf, int ovf_cap) {
   extern __shared__ uint32_t lds[];
-  FlatTier<FAITHFUL, COUNT, FULL, CLS> T{A.S, A.lights, A.nlights, lane_stack<TWO_ROWS>(lds, stack_cap, ovf, ovf_cap), Cnt()};
+  FlatTier<FAITHFUL, COUNT, FULL, CLS, TWO_ROWS> T{A.S, A.lights, A.nlights, lane_stack<TWO_ROWS>(lds, stack_cap, ovf, ovf_cap), Cnt()};
   render_loop<TWO_ROWS, TWO_ROWS>(A, T);
   if (A.want_counters) flush_counters(A.counters, T.cnt, T.err);
   else if ((CLS & (CLS_CSG | CLS_MESH)) && __builtin_amdgcn_ballot_w64(T.err != 0) && (threadIdx.x & 63) == 0) atomicOr(&A.counters->error, 1u);
@@ -488,7 +493,7 @@ __device__ __forceinline__ void ss_frame_loop(const DRenderArgs& A, TIER& T) {
 template <bool FULL, int CLS, int LB = 1, bool TWO_ROWS = false, bool FAITHFUL = false>
 __global__ void __launch_bounds__(64, LB) k_ss_frame_flat(DRenderArgs A, int stack_cap, uint32_t* ovf, int ovf_cap) {
   extern __shared__ uint32_t lds[];
-  FlatTier<FAITHFUL, false, FULL, CLS> T{A.S, A.lights, A.nlights, lane_stack<TWO_ROWS>(lds, stack_cap, ovf, ovf_cap), Cnt()};
+  FlatTier<FAITHFUL, false, FULL, CLS, TWO_ROWS> T{A.S, A.lights, A.nlights, lane_stack<TWO_ROWS>(lds, stack_cap, ovf, ovf_cap), Cnt()};
   ss_frame_loop(A, T);
   if (A.want_counters) flush_counters(A.counters, T.cnt, T.err);
   else if ((CLS & (CLS_CSG | CLS_MESH)) && __builtin_amdgcn_ballot_w64(T.err != 0) && (threadIdx.x & 63) == 0) atomicOr(&A.counters->error, 1u);

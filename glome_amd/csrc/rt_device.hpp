@@ -153,6 +153,10 @@ template <> struct PrimarySnap<true> { uint32_t p_bih = 0, p_mesh = 0, p_prim = 
 // does the tier count work?  (a tier without a COUNT member -- the host build's -- does not ask for what only counting instances do)
 template <class TIER, class = void> struct tier_counts { static constexpr bool value = false; };
 template <class TIER> struct tier_counts<TIER, decltype((void)TIER::COUNT)> { static constexpr bool value = TIER::COUNT; };
+// is every material the tier's kernel can meet a Surface?  (TIER::SURFACE_ONLY, set by the two-row kernels: use_two_rows admits no scene
+// with another kind, rt_types.h DMatKind; a tier without the member shades every kind)
+template <class TIER, class = void> struct tier_surface_only { static constexpr bool value = false; };
+template <class TIER> struct tier_surface_only<TIER, decltype((void)TIER::SURFACE_ONLY)> { static constexpr bool value = TIER::SURFACE_ONLY; };
 // `p` rays of a wave-wide step: one scalar add on the device (the host build's "wave" is one lane: its per-lane counter)
 #if defined(__HIP_DEVICE_COMPILE__) && !defined(GLOME_RB_OLD_COUNT)
 GD void count_wave(uint32_t&, uint32_t& per_wave, bool p) { per_wave += (uint32_t)__builtin_popcountll(__builtin_amdgcn_ballot_w64(p)); }
@@ -1767,22 +1771,28 @@ GD float refract_cs2(float ior, const Ray& ray, const HitCore& h, float& eta, fl
 template <class TIER>
 GD CA postshade_lean(TIER& T, LightCache& lc, uint32_t mat, const Ray& ray, const HitCore& h, int recurs) {
   const DScene& S = T.S;
-  F4 m0 = ld4(S.mats, 3 * mat), m1 = ld4(S.mats, 3 * mat + 1);
-  uint32_t kind = as_u(m0.x);
-  if (kind == DM_SURFACE) {
-    if (!lc.done) { lc.mask = preshade(T, h); lc.done = true; }
-    return surface_shade(T, m1, ld4(S.mats, 3 * mat + 2), lc.mask, ray, h);
-  }
-  if (kind == DM_REFLECT) {  // Shader.hs:107-118
-    float refl = m1.x;
-    return ((refl > 0) && (recurs > 0)) ? ca(0, 0, 0, 0 * refl) : ca(0, 0, 0, 1);
-  }
-  if (kind == DM_REFRACT) {  // Shader.hs:120-155: both children are traceMiss, except total internal reflection -> ca_black
-    float refl = m1.x, refr = m1.y, eta, c1;
-    if ((refl > 0 || refr > 0) && (recurs > 0)) return ca(0, 0, 0, (refract_cs2(m1.z, ray, h, eta, c1) < 0) ? (0 * refl + 1 * refr) : 0.0f);
+  if constexpr (tier_surface_only<TIER>::value) {
+    // no kind to dispatch on, and trace_primary has made the light list of every lane that comes here (its `eager` is this loop's
+    // `id != 0`): the per-lane preshade and its C++ traversal are not instantiated in these kernels
+    return surface_shade(T, ld4(S.mats, 3 * mat + 1), ld4(S.mats, 3 * mat + 2), lc.mask, ray, h);
+  } else {
+    F4 m0 = ld4(S.mats, 3 * mat), m1 = ld4(S.mats, 3 * mat + 1);
+    uint32_t kind = as_u(m0.x);
+    if (kind == DM_SURFACE) {
+      if (!lc.done) { lc.mask = preshade(T, h); lc.done = true; }
+      return surface_shade(T, m1, ld4(S.mats, 3 * mat + 2), lc.mask, ray, h);
+    }
+    if (kind == DM_REFLECT) {  // Shader.hs:107-118
+      float refl = m1.x;
+      return ((refl > 0) && (recurs > 0)) ? ca(0, 0, 0, 0 * refl) : ca(0, 0, 0, 1);
+    }
+    if (kind == DM_REFRACT) {  // Shader.hs:120-155: both children are traceMiss, except total internal reflection -> ca_black
+      float refl = m1.x, refr = m1.y, eta, c1;
+      if ((refl > 0 || refr > 0) && (recurs > 0)) return ca(0, 0, 0, (refract_cs2(m1.z, ray, h, eta, c1) < 0) ? (0 * refl + 1 * refr) : 0.0f);
+      return ca(0, 0, 0, 0);
+    }
     return ca(0, 0, 0, 0);
   }
-  return ca(0, 0, 0, 0);
 }
 // trace's fold over the hit's texture stack until opaque (Trace.hs:67-80, Q16), lean kernels
 template <class TIER>
@@ -1962,7 +1972,7 @@ GD CA shade_vm(TIER& T, const Ray& ray0, float tmax, int maxdepth, bool valid, H
 // the pixel loop's entry: `Trace.trace lights shader sld ray infinity maxdepth` (Glome.hs:33), maxdepth <= kMaxTraceDepth.
 // Called by all lanes of a wave together (`valid` = the lane has a pixel).  Lean kernels: the primary rays and, where the
 // first material of the hit is a Surface -- which always forces the light list (Trace.hs:63, Shader.hs:96) -- the shadow
-// rays are traced wave-wide.  Full kernels: shade_vm.
+// rays are traced wave-wide (a SURFACE_ONLY tier: wherever the hit has a material at all).  Full kernels: shade_vm.
 template <class TIER> GD CA trace_primary(TIER& T, const Ray& ray, float tmax, int maxdepth, bool valid, HitG* hout) {
   if constexpr (TIER::FULL) return shade_vm(T, ray, tmax, maxdepth, valid, hout);
   else {
@@ -1974,7 +1984,8 @@ template <class TIER> GD CA trace_primary(TIER& T, const Ray& ray, float tmax, i
     bool eager = false;
     if (valid && h.hit) {
       uint32_t id = tex_head(h.tex, (int)T.S.tex_bits);
-      if (id != 0) eager = as_u(ld4(T.S.mats, 3 * (id - 1)).x) == DM_SURFACE;
+      if constexpr (tier_surface_only<TIER>::value) eager = id != 0;  // (no material to ask: two dependent loads less in front of the shadow walk)
+      else if (id != 0) eager = as_u(ld4(T.S.mats, 3 * (id - 1)).x) == DM_SURFACE;
     }
     if (wave_any(eager)) {
       uint32_t m = preshade_wave(T, h, eager);

@@ -54,7 +54,11 @@ constexpr uint32_t kBihItemsInPlace = 1u << 31;  // bihhdr[3h + 2].w: the tree's
 enum BihLeafClass : uint32_t { BC_GENERIC = 0, BC_TRI = 1, BC_SPHERE = 2, BC_SIMPLE = 3, BC_CSG = 4 /* primitives and CSG over primitives */ };
 constexpr uint32_t MESH_BRANCH = 0xffffffffu;  // count value marking "ref is a branch node"
 
-enum DMatKind : uint32_t { DM_SURFACE = 0, DM_REFLECT = 1, DM_REFRACT = 2, DM_LAYERS = 3, DM_BLEND = 4, DM_WARP = 5 };
+enum DMatKind : uint32_t { DM_SURFACE = 0, DM_REFLECT = 1, DM_REFRACT = 2, DM_LAYERS = 3, DM_BLEND = 4, DM_WARP = 5, DM_KINDS_ };
+// The two-row kernels are compiled for scenes whose every material is a Surface (TIER::SURFACE_ONLY, rt_device.hpp trace_primary): they
+// never read a material's kind.  What admits a scene to them is commit_rules (capi_shared.hpp), which names each of the five other kinds
+// as secondary or nested, and use_two_rows (instances.hpp), which refuses both.  A further kind must be classified there first.
+static_assert(DM_KINDS_ == 6, "a new material kind: classify it in commit_rules before the two-row kernels may meet it");
 
 // A texture stack (a ray's accumulated `texs`, Tex.hs:53-74): material ids, innermost first, stored as id+1 (0 = end), in one
 // 64-bit word -- 8 of them at 8 bits each in a scene of at most 254 materials (DScene::tex_bits = 8), 4 at 16 bits otherwise.

@@ -7,6 +7,8 @@ item -> pixel, pixel -> ray, the root box test, the stores).
   KIND=sky|scene python tools/probe/item_overhead.py        one kind only: the workload for a counter pass, e.g.
       PMC_SCRIPT=tools/probe/item_overhead.py KIND=sky tools/pmc_pass.sh OUT "SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_SMEM SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR SQ_INSTS_LDS SQ_INSTS_BRANCH"
   python tools/probe/item_overhead.py --pmc OUT/pass1       instructions per item by kind from that pass's counter_collection.csv
+  python tools/probe/item_overhead.py --pmc OUT/pass1 --live N     the same per LIVE item: N = live_items_per_launch of a KIND=scene run (what the
+      cull pass queued, glome_ctx_last_cull) -- the render kernel's instructions over the items it walks, and k_cull_items' over all items
 
 Through the C ABI as glome_amd binds it (include/glome_hip.h); reads nothing but the scene."""
 import collections
@@ -42,17 +44,19 @@ def items_per_frame(P, width, height, blocksize=64):
     return sum(waves(w, h) for w in chunk(width) for h in chunk(height))
 
 
-def summarise_pmc(passdir, items):
-    """mean per launch of every counter over the render kernel's dispatches (run the pass with one KIND), per item"""
+def summarise_pmc(passdir, items, kernel="k_render", per_launch=None):
+    """mean per launch of every counter over the dispatches of `kernel` (run the pass with one KIND), per item: of `items` per frame, or of
+    `per_launch` items in the whole launch"""
     per = collections.defaultdict(list)
     for f in sorted(glob.glob(passdir + "/**/*counter_collection.csv", recursive=True)):
         for r in csv.DictReader(open(f)):
-            if "k_render" in r["Kernel_Name"]:
+            if kernel in r["Kernel_Name"]:
                 per[r["Counter_Name"]].append(float(r["Counter_Value"]))
     out = {}
     for c, v in sorted(per.items()):
-        out[c] = round(sum(v) / len(v) / (items * GROUP), 1)
+        out[c] = round(sum(v) / len(v) / (per_launch or items * GROUP), 1)
     out["all"] = round(sum(out.values()), 1)
+    out["per_launch"] = round(sum(sum(v) / len(v) for v in per.values()))
     return out
 
 
@@ -66,8 +70,14 @@ def main():
     P = api.render_params(width=W, height=H, maxdepth=cfg["maxdepth"])
     n_items = items_per_frame(P, W, H)
     if "--pmc" in sys.argv:
-        print(json.dumps({"pass": sys.argv[sys.argv.index("--pmc") + 1], "items_per_frame": n_items, "frames_per_launch": GROUP,
-                          "instructions_per_item": summarise_pmc(sys.argv[sys.argv.index("--pmc") + 1], n_items)}))
+        passdir = sys.argv[sys.argv.index("--pmc") + 1]
+        out = {"pass": passdir, "items_per_frame": n_items, "frames_per_launch": GROUP, "instructions_per_item": summarise_pmc(passdir, n_items)}
+        if "--live" in sys.argv:  # a flagship launch: the render kernel walks the live items only, the cull pass looks at every item
+            live = int(sys.argv[sys.argv.index("--live") + 1])
+            out["live_items_per_launch"] = live
+            out["instructions_per_live_item"] = summarise_pmc(passdir, n_items, per_launch=live)
+            out["cull_pass_instructions_per_item"] = summarise_pmc(passdir, n_items, kernel="k_cull_items")
+        print(json.dumps(out))
         return
     sd = cfg["make"]()
     b = api.Builder()
@@ -97,9 +107,14 @@ def main():
         if kind == "sky":
             assert hit == 0.0, "the all-sky camera sees the scene"
         med, lo, hi = float(np.median(ms[:n])), float(ms[:n].min()), float(ms[:n].max())
+        live = None  # what the cull pass of the last launch queued (a flagship launch of a library that has the pass)
+        if hasattr(ctx.lib, "glome_ctx_last_cull"):
+            lv, tot = C.c_int64(-1), C.c_int64(-1)
+            if ctx.lib.glome_ctx_last_cull(ctx.h, C.byref(lv), C.byref(tot)) == 0 and tot.value == GROUP * n_items:
+                live = lv.value
         print(json.dumps({"scene": name, "kind": kind, "frames_per_launch": GROUP, "items_per_frame": n_items, "launches": n,
                           "ms_per_frame_median": round(med / GROUP, 4), "ms_per_frame_min": round(lo / GROUP, 4), "ms_per_frame_max": round(hi / GROUP, 4),
-                          "ns_per_item_of_the_launch": round(med * 1e6 / (GROUP * n_items), 2), "pixels_hit": round(hit, 4), "lib": os.environ.get("GLOME_DEBUG_LIB", "in-tree")}), flush=True)
+                          "ns_per_item_of_the_launch": round(med * 1e6 / (GROUP * n_items), 2), "live_items_per_launch": live, "pixels_hit": round(hit, 4), "lib": os.environ.get("GLOME_DEBUG_LIB", "in-tree")}), flush=True)
     sc.release()
     ctx.close()
 
