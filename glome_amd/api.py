@@ -19,6 +19,11 @@ class GlomeError(RuntimeError):
     pass
 
 
+# what the scene updates take, by numpy dtype: the pointer type of a host form's array, the torch dtype of a device form's tensor
+_HOST_PTR = {np.float64: L.c_dp, np.float32: L.c_fp, np.int32: L.c_ip}
+_TORCH_NAME = {np.float64: ("torch.float64",), np.float32: ("torch.float32",)}
+
+
 # ---------------------------------------------------------------- transforms (24 doubles: forward 3x4 + inverse 3x4)
 def _xf(fn, *args):
     lib = L.load()
@@ -494,67 +499,61 @@ class Scene:
         if rc != 0:
             raise GlomeError(f"{what}: {self.ctx.err()} (status {rc})")
 
-    def mesh_update(self, mesh_id, verts, norms=None):
-        """New vertices for a committed Mesh, its BVH refitted on the GPU (glome_scene_mesh_update): the scene a commit after
-        Builder.mesh_set_vertices would have made.  NumPy arrays (or anything array-like) take the host form, which returns the device
-        milliseconds of the finished update; CUDA torch.float64 tensors take the device form, asynchronous on the context's stream
-        (returns None; the tensors must stay alive until it has run)."""
-        if hasattr(verts, "data_ptr"):  # torch tensors: the device form
-            def dev(t, what):
-                if t is None:
-                    return None, 0
-                if not t.is_cuda or str(t.dtype) != "torch.float64" or not t.is_contiguous() or t.numel() % 3:
-                    raise GlomeError(f"mesh_update: {what} must be a contiguous CUDA torch.float64 tensor of 3 values per row")
-                return (C.c_void_p(t.data_ptr()) if t.numel() else None), t.numel() // 3
-            pv, nv = dev(verts, "verts")
-            pn, nn = dev(norms, "norms")
-            self._chk(self.lib.glome_scene_mesh_update_dev(self.h, int(mesh_id), pv, nv, pn, nn), "glome_scene_mesh_update_dev")
-            return None
-        v = np.ascontiguousarray(np.asarray(verts, dtype=np.float64).reshape(-1, 3))
-        n = None if norms is None else np.ascontiguousarray(np.asarray(norms, dtype=np.float64).reshape(-1, 3))
-        ms = C.c_float(0)
-        self._chk(self.lib.glome_scene_mesh_update(self.h, int(mesh_id), v.ctypes.data_as(L.c_dp), v.shape[0], n.ctypes.data_as(L.c_dp) if n is not None and n.shape[0] else None,
-                                                   0 if n is None else n.shape[0], C.byref(ms)), "glome_scene_mesh_update")
-        return ms.value
-
-    def bih_update(self, bih_id, pts9):
-        """New triangles for a committed triangle bih, its planes refitted on the GPU (glome_scene_bih_update): the scene a commit after
-        Builder.bih_set_triangles would have made.  NumPy arrays (or anything array-like) take the host form, which returns the device
-        milliseconds of the finished update; a CUDA torch.float64 tensor takes the device form, asynchronous on the context's stream
-        (returns None; the tensor must stay alive until it has run)."""
-        if hasattr(pts9, "data_ptr"):  # a torch tensor: the device form
-            t = pts9
-            if not t.is_cuda or str(t.dtype) != "torch.float64" or not t.is_contiguous() or t.numel() % 9:
-                raise GlomeError("bih_update: pts9 must be a contiguous CUDA torch.float64 tensor of 9 values per row")
-            self._chk(self.lib.glome_scene_bih_update_dev(self.h, int(bih_id), C.c_void_p(t.data_ptr()) if t.numel() else None, t.numel() // 9), "glome_scene_bih_update_dev")
-            return None
-        p = np.ascontiguousarray(np.asarray(pts9, dtype=np.float64).reshape(-1, 9))
-        ms = C.c_float(0)
-        self._chk(self.lib.glome_scene_bih_update(self.h, int(bih_id), p.ctypes.data_as(L.c_dp) if p.shape[0] else None, p.shape[0], C.byref(ms)), "glome_scene_bih_update")
-        return ms.value
-
-    def sphere_bih_update(self, bih_id, c3r):
-        """New centres and radii for a committed sphere bih, its planes refitted on the GPU (glome_scene_sphere_bih_update): the scene a
-        commit after Builder.bih_set_spheres would have made.  NumPy arrays (or anything array-like) take the host form, which returns the
-        device milliseconds of the finished update; a CUDA torch.float64 tensor takes the device form, asynchronous on the context's
-        stream (returns None; the tensor must stay alive until it has run)."""
-        if hasattr(c3r, "data_ptr"):  # a torch tensor: the device form
-            t = c3r
-            if not t.is_cuda or str(t.dtype) != "torch.float64" or not t.is_contiguous() or t.numel() % 4:
-                raise GlomeError("sphere_bih_update: c3r must be a contiguous CUDA torch.float64 tensor of 4 values per row")
-            self._chk(self.lib.glome_scene_sphere_bih_update_dev(self.h, int(bih_id), C.c_void_p(t.data_ptr()) if t.numel() else None, t.numel() // 4), "glome_scene_sphere_bih_update_dev")
-            return None
-        p = np.ascontiguousarray(np.asarray(c3r, dtype=np.float64).reshape(-1, 4))
-        ms = C.c_float(0)
-        self._chk(self.lib.glome_scene_sphere_bih_update(self.h, int(bih_id), p.ctypes.data_as(L.c_dp) if p.shape[0] else None, p.shape[0], C.byref(ms)), "glome_scene_sphere_bih_update")
-        return ms.value
-
     @staticmethod
     def _dev_arg(t, call, what, dtypes, per_row):
         """(pointer, rows) of a torch tensor handed to a device form, refused in the wording of the fp64 methods"""
         if not hasattr(t, "data_ptr") or not t.is_cuda or str(t.dtype) not in dtypes or not t.is_contiguous() or t.numel() % per_row:
             raise GlomeError(f"{call}: {what} must be a contiguous CUDA {' or '.join(dtypes)} tensor of {per_row} value{'s' if per_row > 1 else ''} per row")
         return (C.c_void_p(t.data_ptr()) if t.numel() else None), t.numel() // per_row
+
+    def _host_update(self, fn, obj_id, arrays, args, ptr=_HOST_PTR):
+        """The blocking host form `fn` (the library's function) of an update of object obj_id; returns its device milliseconds.  arrays:
+        (values, numpy dtype, values per row) each, made contiguous; None stands for an array that is not given.  args(ptrs, rows) gives
+        the C arguments between the object's id and the milliseconds, from the arrays' pointers (None for one of no rows: the count says
+        that nothing is read) and row counts.  ptr: the pointer type by dtype."""
+        held = [None if a is None else np.ascontiguousarray(np.asarray(a, dtype=dt).reshape(-1, w)) for a, dt, w in arrays]
+        ptrs = [h.ctypes.data_as(ptr[dt]) if h is not None and h.shape[0] else None for h, (_, dt, _) in zip(held, arrays)]
+        ms = C.c_float(0)
+        self._chk(fn(self.h, int(obj_id), *args(ptrs, [0 if h is None else h.shape[0] for h in held]), C.byref(ms)), fn.__name__)
+        return ms.value
+
+    def mesh_update(self, mesh_id, verts, norms=None):
+        """New vertices for a committed Mesh, its BVH refitted on the GPU (glome_scene_mesh_update): the scene a commit after
+        Builder.mesh_set_vertices would have made.  NumPy arrays (or anything array-like) take the host form, which returns the device
+        milliseconds of the finished update; CUDA torch.float64 tensors take the device form, asynchronous on the context's stream
+        (returns None; the tensors must stay alive until it has run)."""
+        return self._mesh_update("mesh_update", self.lib.glome_scene_mesh_update, self.lib.glome_scene_mesh_update_dev, np.float64, mesh_id, verts, norms)
+
+    def _mesh_update(self, call, host, dev, dtype, mesh_id, verts, norms):
+        """mesh_update / mesh_update_f32: the library's host and device form, arrays and tensors of `dtype`"""
+        if hasattr(verts, "data_ptr"):  # torch tensors: the device form
+            pv, nv = self._dev_arg(verts, call, "verts", _TORCH_NAME[dtype], 3)
+            pn, nn = (None, 0) if norms is None else self._dev_arg(norms, call, "norms", _TORCH_NAME[dtype], 3)
+            self._chk(dev(self.h, int(mesh_id), pv, nv, pn, nn), dev.__name__)
+            return None
+        return self._host_update(host, mesh_id, [(verts, dtype, 3), (norms, dtype, 3)], lambda p, n: (p[0], n[0], p[1], n[1]))
+
+    def bih_update(self, bih_id, pts9):
+        """New triangles for a committed triangle bih, its planes refitted on the GPU (glome_scene_bih_update): the scene a commit after
+        Builder.bih_set_triangles would have made.  NumPy arrays (or anything array-like) take the host form, which returns the device
+        milliseconds of the finished update; a CUDA torch.float64 tensor takes the device form, asynchronous on the context's stream
+        (returns None; the tensor must stay alive until it has run)."""
+        return self._one_array_update("bih_update", self.lib.glome_scene_bih_update, self.lib.glome_scene_bih_update_dev, np.float64, bih_id, pts9, "pts9", 9)
+
+    def _one_array_update(self, call, host, dev, dtype, bih_id, values, what, per_row):
+        """the leaf bih updates that take one array of per_row values per item: the library's host and device form"""
+        if hasattr(values, "data_ptr"):  # a torch tensor: the device form
+            p, n = self._dev_arg(values, call, what, _TORCH_NAME[dtype], per_row)
+            self._chk(dev(self.h, int(bih_id), p, n), dev.__name__)
+            return None
+        return self._host_update(host, bih_id, [(values, dtype, per_row)], lambda p, n: (p[0], n[0]))
+
+    def sphere_bih_update(self, bih_id, c3r):
+        """New centres and radii for a committed sphere bih, its planes refitted on the GPU (glome_scene_sphere_bih_update): the scene a
+        commit after Builder.bih_set_spheres would have made.  NumPy arrays (or anything array-like) take the host form, which returns the
+        device milliseconds of the finished update; a CUDA torch.float64 tensor takes the device form, asynchronous on the context's
+        stream (returns None; the tensor must stay alive until it has run)."""
+        return self._one_array_update("sphere_bih_update", self.lib.glome_scene_sphere_bih_update, self.lib.glome_scene_sphere_bih_update_dev, np.float64, bih_id, c3r, "c3r", 4)
 
     def bih_update_indexed(self, bih_id, verts, idx):
         """bih_update from the arrays a simulation holds (glome_scene_bih_update_indexed): vertices [nv, 3], float32 or float64, and an int32
@@ -568,61 +567,35 @@ class Scene:
             dtype = 1 if str(verts.dtype) == "torch.float32" else 0  # GLOME_F32 / GLOME_F64
             self._chk(self.lib.glome_scene_bih_update_indexed_dev(self.h, int(bih_id), pv, dtype, nv, pi, n), "glome_scene_bih_update_indexed_dev")
             return None
-        v = np.asarray(verts)
-        dtype = 1 if v.dtype == np.float32 else 0
-        v = np.ascontiguousarray(np.asarray(v, dtype=np.float32 if dtype else np.float64).reshape(-1, 3))
-        i = np.ascontiguousarray(np.asarray(idx, dtype=np.int32).reshape(-1, 3))
-        ms = C.c_float(0)
-        self._chk(self.lib.glome_scene_bih_update_indexed(self.h, int(bih_id), C.c_void_p(v.ctypes.data) if v.shape[0] else None, dtype, v.shape[0],
-                                                          i.ctypes.data_as(L.c_ip) if i.shape[0] else None, i.shape[0], C.byref(ms)), "glome_scene_bih_update_indexed")
-        return ms.value
+        dtype = 1 if np.asarray(verts).dtype == np.float32 else 0
+        return self._host_update(self.lib.glome_scene_bih_update_indexed, bih_id, [(verts, np.float32 if dtype else np.float64, 3), (idx, np.int32, 3)],
+                                 lambda p, n: (p[0], dtype, n[0], p[1], n[1]), ptr={np.float32: C.c_void_p, np.float64: C.c_void_p, np.int32: L.c_ip})
 
     def bih_update_f32(self, bih_id, pts9):
         """bih_update from float32 (glome_scene_bih_update_f32): nine values per item; the scene bih_update gives for the widened array, bit
         for bit.  NumPy arrays take the host form; a CUDA torch.float32 tensor takes the device form (returns None)."""
-        if hasattr(pts9, "data_ptr"):
-            p, n = self._dev_arg(pts9, "bih_update_f32", "pts9", ("torch.float32",), 9)
-            self._chk(self.lib.glome_scene_bih_update_f32_dev(self.h, int(bih_id), p, n), "glome_scene_bih_update_f32_dev")
-            return None
-        p = np.ascontiguousarray(np.asarray(pts9, dtype=np.float32).reshape(-1, 9))
-        ms = C.c_float(0)
-        self._chk(self.lib.glome_scene_bih_update_f32(self.h, int(bih_id), p.ctypes.data_as(L.c_fp) if p.shape[0] else None, p.shape[0], C.byref(ms)), "glome_scene_bih_update_f32")
-        return ms.value
+        return self._one_array_update("bih_update_f32", self.lib.glome_scene_bih_update_f32, self.lib.glome_scene_bih_update_f32_dev, np.float32, bih_id, pts9, "pts9", 9)
 
     def mesh_update_f32(self, mesh_id, verts, norms=None):
         """mesh_update from float32 (glome_scene_mesh_update_f32): the scene mesh_update gives for the widened arrays, bit for bit.  NumPy
         arrays take the host form; CUDA torch.float32 tensors take the device form (returns None)."""
-        if hasattr(verts, "data_ptr"):
-            pv, nv = self._dev_arg(verts, "mesh_update_f32", "verts", ("torch.float32",), 3)
-            pn, nn = (None, 0) if norms is None else self._dev_arg(norms, "mesh_update_f32", "norms", ("torch.float32",), 3)
-            self._chk(self.lib.glome_scene_mesh_update_f32_dev(self.h, int(mesh_id), pv, nv, pn, nn), "glome_scene_mesh_update_f32_dev")
-            return None
-        v = np.ascontiguousarray(np.asarray(verts, dtype=np.float32).reshape(-1, 3))
-        n = None if norms is None else np.ascontiguousarray(np.asarray(norms, dtype=np.float32).reshape(-1, 3))
-        ms = C.c_float(0)
-        self._chk(self.lib.glome_scene_mesh_update_f32(self.h, int(mesh_id), v.ctypes.data_as(L.c_fp), v.shape[0], n.ctypes.data_as(L.c_fp) if n is not None and n.shape[0] else None,
-                                                       0 if n is None else n.shape[0], C.byref(ms)), "glome_scene_mesh_update_f32")
-        return ms.value
+        return self._mesh_update("mesh_update_f32", self.lib.glome_scene_mesh_update_f32, self.lib.glome_scene_mesh_update_f32_dev, np.float32, mesh_id, verts, norms)
 
     def sphere_bih_update_f32(self, bih_id, centres, radii):
         """sphere_bih_update from two float32 streams, centres [n, 3] and radii [n], as a particle system holds them
         (glome_scene_sphere_bih_update_f32): the scene sphere_bih_update gives for the widened, interleaved array, bit for bit.  NumPy
         arrays take the host form; CUDA torch.float32 tensors take the device form (returns None)."""
+        def same(n, nr):
+            if nr != n:
+                raise GlomeError(f"sphere_bih_update_f32: {n} centres but {nr} radii")
+            return n
         if hasattr(centres, "data_ptr") or hasattr(radii, "data_ptr"):
             pc, n = self._dev_arg(centres, "sphere_bih_update_f32", "centres", ("torch.float32",), 3)
             pr, nr = self._dev_arg(radii, "sphere_bih_update_f32", "radii", ("torch.float32",), 1)
-            if nr != n:
-                raise GlomeError(f"sphere_bih_update_f32: {n} centres but {nr} radii")
-            self._chk(self.lib.glome_scene_sphere_bih_update_f32_dev(self.h, int(bih_id), pc, pr, n), "glome_scene_sphere_bih_update_f32_dev")
+            self._chk(self.lib.glome_scene_sphere_bih_update_f32_dev(self.h, int(bih_id), pc, pr, same(n, nr)), "glome_scene_sphere_bih_update_f32_dev")
             return None
-        c = np.ascontiguousarray(np.asarray(centres, dtype=np.float32).reshape(-1, 3))
-        r = np.ascontiguousarray(np.asarray(radii, dtype=np.float32).ravel())
-        if r.shape[0] != c.shape[0]:
-            raise GlomeError(f"sphere_bih_update_f32: {c.shape[0]} centres but {r.shape[0]} radii")
-        ms = C.c_float(0)
-        self._chk(self.lib.glome_scene_sphere_bih_update_f32(self.h, int(bih_id), c.ctypes.data_as(L.c_fp) if c.shape[0] else None, r.ctypes.data_as(L.c_fp) if c.shape[0] else None,
-                                                             c.shape[0], C.byref(ms)), "glome_scene_sphere_bih_update_f32")
-        return ms.value
+        return self._host_update(self.lib.glome_scene_sphere_bih_update_f32, bih_id, [(centres, np.float32, 3), (radii, np.float32, 1)],
+                                 lambda p, n: (p[0], p[1], same(n[0], n[1])))
 
     def instance_update(self, ids, xfms):
         """New matrices for committed Instances, the bih that holds them refitted on the GPU (glome_scene_instance_update): the scene a

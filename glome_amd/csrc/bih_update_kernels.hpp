@@ -37,7 +37,7 @@ constexpr int kMergeBlock = 1024;
 
 template <class Src> struct DTrisArgs {
   Src src;               // the items' vertices, three points per item: p1 p2 p3 (update_common.hpp: a point source)
-  const uint2* rows;     // per record: (item, pair words -- BihUpdateInfo)
+  const uint2* rows;     // per record: (item, pair words -- LeafBihUpdateInfo)
   float4* tris;          // the tree's first record
   float* tripairs;       // the scene's pool
   float4* ws;            // two per record: the triangle's plane-form box (lo, -) (hi, -)
@@ -61,10 +61,10 @@ template <class Src> __global__ void __launch_bounds__(64) k_bih_tris(DTrisArgs<
     upd::tri_record(a, b, c, rec);
     float4* o = A.tris + 3 * (size_t)j;
     o[0] = rec[0]; o[1] = rec[1]; o[2] = rec[2];
-    if (row.y != BihUpdateInfo::kNoPair) {  // emit_pairs: word w of the record is r[6 w ..] = A.x B.x A.y B.y A.z B.z
-      float* r = A.tripairs + (size_t)(row.y & (BihUpdateInfo::kPairHalfB - 1u));
-      const uint32_t half = (row.y & BihUpdateInfo::kPairHalfB) ? 1u : 0u;
-      const bool both = (row.y & BihUpdateInfo::kPairBoth) != 0;
+    if (row.y != LeafBihUpdateInfo::kNoPair) {  // emit_pairs: word w of the record is r[6 w ..] = A.x B.x A.y B.y A.z B.z
+      float* r = A.tripairs + (size_t)(row.y & (LeafBihUpdateInfo::kPairHalfB - 1u));
+      const uint32_t half = (row.y & LeafBihUpdateInfo::kPairHalfB) ? 1u : 0u;
+      const bool both = (row.y & LeafBihUpdateInfo::kPairBoth) != 0;
       for (int w = 0; w < 3; w++) {
         const float v[3] = {rec[w].x, rec[w].y, rec[w].z};
         for (int k = 0; k < 3; k++) {

@@ -182,8 +182,7 @@ int32_t glome_sb_bihs_above(glome_sb* sb, int32_t root, int32_t node_id, int32_t
     fl.run(root);
     const NestedAnswer* A = nullptr;
     for (const MeshUpdateInfo& U : F.mesh_updates) if (U.node == node_id) A = &U.nested;
-    for (const BihUpdateInfo& U : F.bih_updates) if (U.node == node_id) A = &U.nested;
-    for (const SphereBihUpdateInfo& U : F.sphere_bih_updates) if (U.node == node_id) A = &U.nested;
+    for (const LeafBihUpdateInfo& U : F.leaf_bih_updates) if (U.node == node_id) A = &U.nested;
     for (const InstanceUpdateInfo& U : F.inst_updates) if (U.node == node_id) A = &U.nested;
     for (const InstBihInfo& B : F.inst_bihs) if (B.node == node_id) A = &B.nested;
     if (!A) throw std::invalid_argument("bihs_above: node " + std::to_string(node_id) + " is not a Mesh, a triangle bih, an Instance or a refittable bih of the scene under node " + std::to_string(root) + " (nor a sphere bih)");

@@ -44,44 +44,31 @@ struct MeshUpdateInfo {
   double bound6[6] = {0, 0, 0, 0, 0, 0};  // bound(mesh) at commit: lo, hi
 };
 
-// What an update of a committed triangle bih's triangles needs (glome_scene_bih_update; bih_update_kernels.hpp), recorded per emitted bih
-// of class BC_TRI and kept beside the scene, outside DScene.  The tree's leaves are emitted in preorder with nothing in between, so
-// record j of the tree is `recs` record first_rec + j and `tris` record first_tri + j.  rows[2 j] is the record's item (its index in
-// BihTree::update_order), rows[2 j + 1] where its words go in `tripairs`: the pair record's first word (a float index), kPairHalfB when
-// it is the record's second triangle, kPairBoth when it is an odd last one that is paired with itself; kNoPair when the tree has no
-// packet form.  A branch's two child references are read from its node, whose .zw words an update never writes.
-struct BihUpdateInfo {
+// What an update of a committed leaf bih's items needs -- a triangle bih's triangles (glome_scene_bih_update; bih_update_kernels.hpp) or a
+// sphere bih's spheres (glome_scene_sphere_bih_update; sphere_bih_update_kernels.hpp) -- recorded per emitted bih of class BC_TRI or
+// BC_SPHERE and kept beside the scene, outside DScene.  The tree's leaves are emitted in preorder with nothing in between, so record j of
+// the tree is `recs` record first_rec + j and `tris` / `spheres` record first_prim + j.  A row is row_words words.  A sphere's is its
+// item (its index in BihTree::update_order).  A triangle's is its item, then where its words go in `tripairs`: the pair record's first
+// word (a float index), kPairHalfB when it is the record's second triangle, kPairBoth when it is an odd last one that is paired with
+// itself; kNoPair when the tree has no packet form.  A branch's two child references are read from its node, whose .zw words an update
+// never writes.  A sphere tree has no packet node copy: its walk reads bihnodes.
+struct LeafBihUpdateInfo {
   static constexpr uint32_t kPairHalfB = 1u << 29, kPairBoth = 1u << 30, kNoPair = 0xffffffffu;
   int node = -1;                  // the bih's builder id
+  uint32_t cls = BC_TRI;          // BC_TRI or BC_SPHERE
   int n_items = 0;
   uint32_t hdr = 0;               // bihhdr index
   uint32_t first_slot = 0, n_slots = 0;  // its node slots (bihnodes index, count; unused slots included)
-  uint32_t first_tri = 0, first_rec = 0, n_tris = 0;
-  bool pk = false;                // the tree has the packet form: pknodes and tripairs follow
+  uint32_t first_prim = 0, first_rec = 0, n_recs = 0;
+  uint32_t row_words = 2;         // 2 for triangles, 1 for spheres
+  bool pk = false;                // the tree has the packet form: pknodes and tripairs follow (never a sphere tree)
   std::vector<uint32_t> rows;
   std::vector<uint32_t> level_nodes;  // its branch slots (bihnodes indices), deepest tree level first ...
   std::vector<uint32_t> level_off;    // ... level l is level_nodes[level_off[l] .. level_off[l + 1])
-  UpdateAnswer plain;             // not ok: another Bih lies above it, or the scene holds another copy of one of its triangles -- the reason
+  UpdateAnswer plain;             // not ok: another Bih lies above it, or the scene holds another copy of one of its items -- the reason
   NestedAnswer nested;
   double bound6[6] = {0, 0, 0, 0, 0, 0};  // bound(bih) at commit
-};
-
-// What an update of a committed sphere bih's spheres needs (glome_scene_sphere_bih_update; sphere_bih_update_kernels.hpp), recorded per
-// emitted bih of class BC_SPHERE and kept beside the scene, outside DScene.  As in a triangle bih the leaves are emitted in preorder with
-// nothing in between: record j of the tree is `recs` record first_rec + j and `spheres` record first_sphere + j, and rows[j] is the
-// record's item (its index in BihTree::update_order).  A sphere tree has no packet node copy: its walk reads bihnodes.
-struct SphereBihUpdateInfo {
-  int node = -1;                  // the bih's builder id
-  int n_items = 0;
-  uint32_t hdr = 0;               // bihhdr index
-  uint32_t first_slot = 0, n_slots = 0;  // its node slots (bihnodes index, count; unused slots included)
-  uint32_t first_sphere = 0, first_rec = 0, n_recs = 0;
-  std::vector<uint32_t> rows;
-  std::vector<uint32_t> level_nodes;  // its branch slots (bihnodes indices), deepest tree level first ...
-  std::vector<uint32_t> level_off;    // ... level l is level_nodes[level_off[l] .. level_off[l + 1])
-  UpdateAnswer plain;             // not ok: another Bih lies above it, or the scene holds another copy of one of its spheres -- the reason
-  NestedAnswer nested;
-  double bound6[6] = {0, 0, 0, 0, 0, 0};  // bound(bih) at commit
+  const char* item_word() const { return cls == BC_SPHERE ? "sphere" : "triangle"; }
 };
 
 // What an update of committed Instances' matrices needs (glome_scene_instance_update; instance_update_kernels.hpp), kept beside the
@@ -142,8 +129,7 @@ struct FlatScene {
   std::string why_generic;  // why the flat tier was not chosen
   bool pk_all = true;       // every triangle BIH has the packet walk's node form (emit_bih)
   std::vector<MeshUpdateInfo> mesh_updates;  // one per emitted mesh (emit_mesh), in emission order
-  std::vector<BihUpdateInfo> bih_updates;    // one per emitted triangle bih (emit_bih), in emission order
-  std::vector<SphereBihUpdateInfo> sphere_bih_updates;  // one per emitted sphere bih (emit_bih), in emission order
+  std::vector<LeafBihUpdateInfo> leaf_bih_updates;  // one per emitted triangle or sphere bih (emit_bih), in emission order
   std::vector<InstanceUpdateInfo> inst_updates;  // one per emitted Instance node (emit), in emission order
   std::vector<InstBihInfo> inst_bihs;        // one per emitted bih that holds an Instance as an item (emit_bih), in emission order
 };
@@ -398,7 +384,7 @@ class Flattener {
   // lies above, on any path from the root or from a Warp material's frame / scene.  Of the composites, only a Bih keeps something derived
   // from a child's bound -- its planes and its root box.  A list, an Instance, a Difference, an Intersection and the Tex / Tag / shadow
   // wrappers emit no box at all (emit, below), and the bounding solid of a Bound / InnerBound is the caller's own object.
-  // And which triangle bihs may have their triangles replaced (BihUpdateInfo::plain): every one that no OTHER Bih lies above -- for
+  // And which triangle bihs may have their triangles replaced (LeafBihUpdateInfo::plain): every one that no OTHER Bih lies above -- for
   // the same reason -- and whose item triangles the scene reaches through this bih alone: a triangle node that is also in a group beside
   // the bih, or in another bih, has a record of its own there, which an update of this bih could not move.
   // And which Instances may have their matrices replaced (InstanceUpdateInfo::plain).  An Instance's matrix is read from its xfm
@@ -407,13 +393,12 @@ class Flattener {
   // emit_bih.  Refused: an Instance that lies deeper inside an item (the item's box depends on it through a list, a CSG node, a Bound or
   // another Instance, which the update does not recompute), one with two or more bihs above it on some path (the outer tree's item box is
   // the inner tree's box), and one that is an item more than once (a single table entry could not name both).
-  // And which sphere bihs may have their spheres replaced (SphereBihUpdateInfo::plain): exactly as a triangle bih, Sphere for Triangle.
+  // And which sphere bihs may have their spheres replaced: exactly as a triangle bih, Sphere for Triangle -- one record, one rule.
   void mark_updatable(int root) {
-    if (F.mesh_updates.empty() && F.bih_updates.empty() && F.sphere_bih_updates.empty() && F.inst_updates.empty()) return;
-    std::unordered_map<int, size_t> slot_of, bslot_of, sslot_of, islot_of;
+    if (F.mesh_updates.empty() && F.leaf_bih_updates.empty() && F.inst_updates.empty()) return;
+    std::unordered_map<int, size_t> slot_of, bslot_of, islot_of;
     for (size_t k = 0; k < F.mesh_updates.size(); k++) slot_of[F.mesh_updates[k].node] = k;
-    for (size_t k = 0; k < F.bih_updates.size(); k++) bslot_of[F.bih_updates[k].node] = k;
-    for (size_t k = 0; k < F.sphere_bih_updates.size(); k++) sslot_of[F.sphere_bih_updates[k].node] = k;
+    for (size_t k = 0; k < F.leaf_bih_updates.size(); k++) bslot_of[F.leaf_bih_updates[k].node] = k;
     for (size_t k = 0; k < F.inst_updates.size(); k++) islot_of[F.inst_updates[k].node] = k;
     for (const InstItem& I : inst_items) {
       InstanceUpdateInfo& U = F.inst_updates[islot_of.at(I.inst)];
@@ -425,7 +410,7 @@ class Flattener {
     }
     // per Triangle and Sphere node, the innermost Bih it was reached under: kUnseen, a bih's id, -1 for none, kMixed once two of those differ
     constexpr int kUnseen = -3, kMixed = -2;
-    std::vector<int> tri_under(F.bih_updates.empty() && F.sphere_bih_updates.empty() ? 0 : G.nodes.size(), kUnseen);
+    std::vector<int> tri_under(F.leaf_bih_updates.empty() ? 0 : G.nodes.size(), kUnseen);
     struct Item { int id, bih, inner, direct; };  // bih: the outermost Bih above, inner: the innermost (-1: none), direct: only wrappers since that bih's item list
     struct Seen { int bih, inner, direct; bool operator==(const Seen& o) const { return bih == o.bih && inner == o.inner && direct == o.direct; } };
     std::unordered_map<int, std::vector<Seen>> seen;  // composites and wrappers only (a primitive has nothing below it): the states a node was visited with
@@ -463,14 +448,8 @@ class Flattener {
         case K_TEX: case K_TAG: case K_NOSHADOW: case K_ONLYSHADOW: stack.push_back({n.a, it.bih, it.inner, it.direct}); break;
         case K_BIH: {
           auto sl = bslot_of.find(it.id);
-          if (it.bih >= 0 && sl != bslot_of.end() && F.bih_updates[sl->second].plain.ok) {
-            BihUpdateInfo& U = F.bih_updates[sl->second];
-            U.plain.ok = false;
-            U.plain.why_not = "bih " + std::to_string(it.id) + " lies inside bih " + std::to_string(it.bih) + ", whose planes and root box were built from its bound";
-          }
-          auto ss = sslot_of.find(it.id);
-          if (it.bih >= 0 && ss != sslot_of.end() && F.sphere_bih_updates[ss->second].plain.ok) {
-            SphereBihUpdateInfo& U = F.sphere_bih_updates[ss->second];
+          if (it.bih >= 0 && sl != bslot_of.end() && F.leaf_bih_updates[sl->second].plain.ok) {
+            LeafBihUpdateInfo& U = F.leaf_bih_updates[sl->second];
             U.plain.ok = false;
             U.plain.why_not = "bih " + std::to_string(it.id) + " lies inside bih " + std::to_string(it.bih) + ", whose planes and root box were built from its bound";
           }
@@ -489,36 +468,22 @@ class Flattener {
         default: break;
       }
     }
-    for (BihUpdateInfo& U : F.bih_updates) {
+    for (LeafBihUpdateInfo& U : F.leaf_bih_updates) {
       if (!U.plain.ok) continue;
-      for (const BihTree::Node& bn : G.at(U.node).bih->nodes) {
-        for (int item : bn.items) {
-          const int t = G.peel_wrappers(item);
-          const int u = tri_under[(size_t)t];
-          if (u == U.node || u == kUnseen) continue;  // (kUnseen: the bih itself is not reachable from the root -- nothing renders it)
-          U.plain.ok = false;
-          U.plain.why_not = "triangle " + std::to_string(t) + " of bih " + std::to_string(U.node) + " is also part of the scene outside that bih, as a copy an update could not move";
-          break;
-        }
-        if (!U.plain.ok) break;
-      }
-    }
-    for (SphereBihUpdateInfo& U : F.sphere_bih_updates) {
-      if (!U.plain.ok) continue;
-      const std::string why = sphere_outside(U.node, tri_under);
+      const std::string why = item_outside(U, tri_under);
       if (!why.empty()) { U.plain.ok = false; U.plain.why_not = why; }
     }
   }
-  // A sphere bih's item that the scene also reaches outside that bih (tri_under: mark_updatable), named; empty: none.  BC_SPHERE items are
-  // emitted fresh, so such a copy has a second record, which an update of this bih could not move.
-  std::string sphere_outside(int bih, const std::vector<int>& under) const {
+  // A leaf bih's item that the scene also reaches outside that bih (tri_under: mark_updatable), named; empty: none.  BC_TRI and BC_SPHERE
+  // items are emitted fresh, so such a copy has a second record, which an update of this bih could not move.
+  std::string item_outside(const LeafBihUpdateInfo& U, const std::vector<int>& under) const {
     constexpr int kUnseen = -3;
-    for (const BihTree::Node& bn : G.at(bih).bih->nodes)
+    for (const BihTree::Node& bn : G.at(U.node).bih->nodes)
       for (int item : bn.items) {
         const int t = G.peel_wrappers(item);
         const int u = under[(size_t)t];
-        if (u == bih || u == kUnseen) continue;  // (kUnseen: the bih itself is not reachable from the root -- nothing renders it)
-        return "sphere " + std::to_string(t) + " of bih " + std::to_string(bih) + " is also part of the scene outside that bih, as a copy an update could not move";
+        if (u == U.node || u == kUnseen) continue;  // (kUnseen: the bih itself is not reachable from the root -- nothing renders it)
+        return std::string(U.item_word()) + " " + std::to_string(t) + " of bih " + std::to_string(U.node) + " is also part of the scene outside that bih, as a copy an update could not move";
       }
     return std::string();
   }
@@ -533,12 +498,12 @@ class Flattener {
   // of those rows is derived from the same bound.  The walk records, per Mesh, Bih and Instance, the states it was reached in
   // (innermost bih, what lies between that bih's item list and the node); the answers are then resolved bih by bih, memoised.
   void mark_nested(int root) {
-    if (F.mesh_updates.empty() && F.bih_updates.empty() && F.sphere_bih_updates.empty() && F.inst_updates.empty() && F.inst_bihs.empty()) return;
+    if (F.mesh_updates.empty() && F.leaf_bih_updates.empty() && F.inst_updates.empty() && F.inst_bihs.empty()) return;
     enum { kDirect = 0, kInst = 1, kBroken = 2 };
     struct Edge { int bih, link, blocker, via; };   // blocker: the first list / CSG / Bound / second Instance since the item list; via: the Instance passed first (-1: none)
     struct Item { int id, inner, link, blocker, via; };
     constexpr int kUnseen = -3, kMixed = -2;
-    std::vector<int> tri_under(F.bih_updates.empty() && F.sphere_bih_updates.empty() ? 0 : G.nodes.size(), kUnseen);
+    std::vector<int> tri_under(F.leaf_bih_updates.empty() ? 0 : G.nodes.size(), kUnseen);
     std::unordered_map<int, std::vector<Edge>> edges;
     std::unordered_map<int, std::vector<std::pair<int, int>>> seen;
     std::vector<Item> stack{{root, -1, kDirect, -1, -1}};
@@ -615,27 +580,11 @@ class Flattener {
       return A;
     };
     for (MeshUpdateInfo& U : F.mesh_updates) U.nested = answer(U.node);
-    for (BihUpdateInfo& U : F.bih_updates) {
-      if (U.plain.why_not.rfind("bih " + std::to_string(U.node) + " holds triangle", 0) == 0) { U.nested.ok = false; U.nested.why_not = U.plain.why_not; continue; }  // (emit_bih's refusal)
+    for (LeafBihUpdateInfo& U : F.leaf_bih_updates) {
+      if (U.plain.why_not.rfind("bih " + std::to_string(U.node) + " holds " + U.item_word(), 0) == 0) { U.nested.ok = false; U.nested.why_not = U.plain.why_not; continue; }  // (emit_bih's refusal)
       U.nested = answer(U.node);
       if (!U.nested.ok) continue;
-      for (const BihTree::Node& bn : G.at(U.node).bih->nodes) {
-        for (int item : bn.items) {
-          const int t = G.peel_wrappers(item);
-          const int u = tri_under[(size_t)t];
-          if (u == U.node || u == kUnseen) continue;
-          U.nested.ok = false;
-          U.nested.why_not = "triangle " + std::to_string(t) + " of bih " + std::to_string(U.node) + " is also part of the scene outside that bih, as a copy an update could not move";
-          break;
-        }
-        if (!U.nested.ok) break;
-      }
-    }
-    for (SphereBihUpdateInfo& U : F.sphere_bih_updates) {
-      if (U.plain.why_not.rfind("bih " + std::to_string(U.node) + " holds sphere", 0) == 0) { U.nested.ok = false; U.nested.why_not = U.plain.why_not; continue; }  // (emit_bih's refusal)
-      U.nested = answer(U.node);
-      if (!U.nested.ok) continue;
-      const std::string why = sphere_outside(U.node, tri_under);
+      const std::string why = item_outside(U, tri_under);
       if (!why.empty()) { U.nested.ok = false; U.nested.why_not = why; }
     }
     std::unordered_map<int, std::pair<int, int>> item_of_bih;  // Instance -> (its first bih, how often it is an item)
@@ -900,40 +849,25 @@ class Flattener {
     uint32_t delta = 0;
     bool have_delta = false;
     bool in_place = cls != BC_TRI && cls != BC_SPHERE;  // (those two have their own packet walk)
-    BihUpdateInfo U;
+    LeafBihUpdateInfo U;            // a triangle or sphere bih: its update tables
     std::vector<int> item_ids;        // a bih of class BC_CSG / BC_GENERIC: its items in emission order, and their records
     std::vector<uint32_t> item_recs;
     bool has_inst = false;            // ... one of them is an Instance (under wrappers): the tree gets an InstBihInfo
     std::vector<uint32_t> item_of;  // a triangle bih: item node id -> its index in the update order (BihTree::update_order, whichever way the tree was made)
-    if (cls == BC_TRI) {
-      U.node = id; U.hdr = hdr; U.first_slot = base; U.n_slots = nslots;
+    const bool leaf_bih = cls == BC_TRI || cls == BC_SPHERE;
+    if (leaf_bih) {
+      U.node = id; U.cls = cls; U.row_words = cls == BC_TRI ? 2u : 1u; U.hdr = hdr; U.first_slot = base; U.n_slots = nslots;
       const std::vector<int> order = T.update_order();
       U.n_items = (int)order.size();
       item_of.assign(G.nodes.size(), 0xffffffffu);
-      std::vector<char> tri_seen(G.nodes.size(), 0);  // an item, or a triangle under two items, that the tree holds twice has two records: one row cannot name both
+      std::vector<char> prim_seen(G.nodes.size(), 0);  // an item, or a primitive under two items, that the tree holds twice has two records: one row cannot name both
       for (size_t k = 0; k < order.size(); k++) {
         const int t = G.peel_wrappers(order[k]);
-        if ((item_of[(size_t)order[k]] != 0xffffffffu || tri_seen[(size_t)t]) && U.plain.ok) {
+        if ((item_of[(size_t)order[k]] != 0xffffffffu || prim_seen[(size_t)t]) && U.plain.ok) {
           U.plain.ok = false;
-          U.plain.why_not = "bih " + std::to_string(id) + " holds triangle " + std::to_string(t) + " more than once";
+          U.plain.why_not = "bih " + std::to_string(id) + " holds " + U.item_word() + " " + std::to_string(t) + " more than once";
         }
-        item_of[(size_t)order[k]] = (uint32_t)k; tri_seen[(size_t)t] = 1;
-      }
-    }
-    SphereBihUpdateInfo SU;  // a sphere bih: the same tables, Sphere for Triangle
-    if (cls == BC_SPHERE) {
-      SU.node = id; SU.hdr = hdr; SU.first_slot = base; SU.n_slots = nslots;
-      const std::vector<int> order = T.update_order();
-      SU.n_items = (int)order.size();
-      item_of.assign(G.nodes.size(), 0xffffffffu);
-      std::vector<char> sph_seen(G.nodes.size(), 0);
-      for (size_t k = 0; k < order.size(); k++) {
-        const int t = G.peel_wrappers(order[k]);
-        if ((item_of[(size_t)order[k]] != 0xffffffffu || sph_seen[(size_t)t]) && SU.plain.ok) {
-          SU.plain.ok = false;
-          SU.plain.why_not = "bih " + std::to_string(id) + " holds sphere " + std::to_string(t) + " more than once";
-        }
-        item_of[(size_t)order[k]] = (uint32_t)k; sph_seen[(size_t)t] = 1;
+        item_of[(size_t)order[k]] = (uint32_t)k; prim_seen[(size_t)t] = 1;
       }
     }
     for (size_t k = 0; k < T.nodes.size(); k++) {
@@ -963,7 +897,7 @@ class Flattener {
       }
       if (first_rec + items.size() >= BREF_FIRST_LIMIT) throw limit_error("too many records for the BIH leaf references");
       uint32_t count = (uint32_t)items.size();
-      if (count && (cls == BC_TRI || cls == BC_SPHERE)) {
+      if (count && leaf_bih) {
         uint32_t dl = first_prim - first_rec;  // both are emitted in leaf order, so this is one constant per BIH
         if (have_delta && dl != delta) throw scene_error("internal: BIH leaf pools are not contiguous");
         delta = dl; have_delta = true;
@@ -973,17 +907,14 @@ class Flattener {
         if (((uint64_t)F.tripairs.size() + (uint64_t)count * kPairWords) * 4 >= (1ull << 31)) pk = false;  // (a pair record's byte offset is a reference)
         else { pkleaf[k] = emit_pairs(first_prim, count, first_rec) | 3u; paired = true; }
       }
-      if (cls == BC_TRI && count) {
-        if (U.rows.empty()) { U.first_tri = first_prim; U.first_rec = first_rec; }
+      if (leaf_bih && count) {
+        if (U.rows.empty()) { U.first_prim = first_prim; U.first_rec = first_rec; }
         for (uint32_t q = 0; q < count; q++) {
-          const uint32_t pair = (pkleaf[k] & ~3u) / 4u + (q / 2u) * kPairWords;  // (a float index: below 2^29)
           U.rows.push_back(item_of[(size_t)bn.items[q]]);
-          U.rows.push_back(!paired ? BihUpdateInfo::kNoPair : (pair | (q & 1u ? BihUpdateInfo::kPairHalfB : 0u) | (q + 1 == count && !(q & 1u) ? BihUpdateInfo::kPairBoth : 0u)));
+          if (cls != BC_TRI) continue;
+          const uint32_t pair = (pkleaf[k] & ~3u) / 4u + (q / 2u) * kPairWords;  // (a float index: below 2^29)
+          U.rows.push_back(!paired ? U.kNoPair : (pair | (q & 1u ? U.kPairHalfB : 0u) | (q + 1 == count && !(q & 1u) ? U.kPairBoth : 0u)));
         }
-      }
-      if (cls == BC_SPHERE && count) {
-        if (SU.rows.empty()) { SU.first_sphere = first_prim; SU.first_rec = first_rec; }
-        for (uint32_t q = 0; q < count; q++) SU.rows.push_back(item_of[(size_t)bn.items[q]]);
       }
       if (count == 0) ref[k] = BREF_LEAF_BIT;
       else if (count <= 6) ref[k] = BREF_LEAF_BIT | (count << 26) | first_rec;
@@ -1020,19 +951,12 @@ class Flattener {
     in_place = in_place && !T.nodes.empty() && !T.nodes[0].leaf;
     F.bihhdr[3 * hdr + 2] = F4{as_float_bits(delta), as_float_bits(pkroot), as_float_bits(pk ? 1u : 0u), as_float_bits((uint32_t)T.depth | (in_place ? kBihItemsInPlace : 0u))};
     if (cls == BC_SPHERE || cls == BC_TRI || in_place) F.max_sphere_bih_depth = std::max(F.max_sphere_bih_depth, T.depth);
-    if (cls == BC_TRI) {
-      U.n_tris = (uint32_t)(U.rows.size() / 2); U.pk = pk;
+    if (leaf_bih) {
+      U.n_recs = (uint32_t)(U.rows.size() / U.row_words); U.pk = pk;
       box6(T.bb, U.bound6);
-      if (!pk) for (size_t j = 0; j < U.n_tris; j++) U.rows[2 * j + 1] = BihUpdateInfo::kNoPair;  // (the packet form was given up part way)
+      if (cls == BC_TRI && !pk) for (size_t j = 0; j < U.n_recs; j++) U.rows[2 * j + 1] = U.kNoPair;  // (the packet form was given up part way)
       tree_levels(T.nodes, [&](size_t k) { return base + slot[k]; }, U.level_nodes, U.level_off);
-      F.bih_updates.push_back(std::move(U));
-      movable_bihs.insert(id);
-    }
-    if (cls == BC_SPHERE) {
-      SU.n_recs = (uint32_t)SU.rows.size();
-      box6(T.bb, SU.bound6);
-      tree_levels(T.nodes, [&](size_t k) { return base + slot[k]; }, SU.level_nodes, SU.level_off);
-      F.sphere_bih_updates.push_back(std::move(SU));
+      F.leaf_bih_updates.push_back(std::move(U));
       movable_bihs.insert(id);
     }
     if (has_inst) {

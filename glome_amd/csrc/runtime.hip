@@ -164,24 +164,16 @@ struct glome_scene {
     float4* d_ws = nullptr;            // two words per record, then the bound's partial boxes: allocated at the first update
   };
   std::map<int, MeshUpd> meshes;
-  // the same for glome_scene_bih_update, of every triangle bih of the scene (flatten.hpp BihUpdateInfo)
-  struct BihUpd {
-    BihUpdateInfo info;                // (rows and level_nodes emptied once uploaded)
-    const uint32_t* d_rows = nullptr;
+  // the same for glome_scene_bih_update and glome_scene_sphere_bih_update, of every triangle bih and sphere bih of the scene (flatten.hpp
+  // LeafBihUpdateInfo: info.cls tells them apart)
+  struct LeafBihUpd {
+    LeafBihUpdateInfo info;            // (rows and level_nodes emptied once uploaded)
+    const uint32_t* d_rows = nullptr;  // info.row_words words per record
     const uint32_t* d_levels = nullptr;
     const uint32_t* d_level_off = nullptr;
     float4* d_ws = nullptr;            // two words per record, two per node slot, then the bound's partial boxes: allocated at the first update
   };
-  std::map<int, BihUpd> bihs;
-  // and for glome_scene_sphere_bih_update, of every sphere bih of the scene (flatten.hpp SphereBihUpdateInfo)
-  struct SphBihUpd {
-    SphereBihUpdateInfo info;          // (rows and level_nodes emptied once uploaded)
-    const uint32_t* d_rows = nullptr;
-    const uint32_t* d_levels = nullptr;
-    const uint32_t* d_level_off = nullptr;
-    float4* d_ws = nullptr;            // two words per record, two per node slot, then the bound's partial boxes: allocated at the first update
-  };
-  std::map<int, SphBihUpd> sph_bihs;
+  std::map<int, LeafBihUpd> leaf_bihs;
   // and for glome_scene_instance_update: every Instance of the scene by its builder id, and every bih that holds one as an item
   // (flatten.hpp InstanceUpdateInfo, InstBihInfo)
   std::map<int, InstanceUpdateInfo> insts;
@@ -591,14 +583,8 @@ glome_scene* glome_scene_commit(glome_ctx* ctx, glome_sb* sb, int32_t root) {
     U.rows = {}; U.level_nodes = {};
     m.info = std::move(U);
   }
-  for (BihUpdateInfo& U : F.bih_updates) {
-    glome_scene::BihUpd& m = s->bihs[U.node];
-    if ((!U.rows.empty() && upload(s, U.rows, &m.d_rows)) || (!U.level_nodes.empty() && (upload(s, U.level_nodes, &m.d_levels) || upload(s, U.level_off, &m.d_level_off)))) { glome_scene_release(s); return nullptr; }
-    U.rows = {}; U.level_nodes = {};
-    m.info = std::move(U);
-  }
-  for (SphereBihUpdateInfo& U : F.sphere_bih_updates) {
-    glome_scene::SphBihUpd& m = s->sph_bihs[U.node];
+  for (LeafBihUpdateInfo& U : F.leaf_bih_updates) {
+    glome_scene::LeafBihUpd& m = s->leaf_bihs[U.node];
     if ((!U.rows.empty() && upload(s, U.rows, &m.d_rows)) || (!U.level_nodes.empty() && (upload(s, U.level_nodes, &m.d_levels) || upload(s, U.level_off, &m.d_level_off)))) { glome_scene_release(s); return nullptr; }
     U.rows = {}; U.level_nodes = {};
     m.info = std::move(U);
@@ -612,8 +598,7 @@ glome_scene* glome_scene_commit(glome_ctx* ctx, glome_sb* sb, int32_t root) {
   for (InstanceUpdateInfo& U : F.inst_updates) { const int node = U.node; s->insts[node] = std::move(U); }
   auto live_row = [&](int node, const double* b6) { s->live_slot[node] = (uint32_t)(s->live_bound0.size() / 6); s->live_bound0.insert(s->live_bound0.end(), b6, b6 + 6); };
   for (auto& m : s->meshes) live_row(m.first, m.second.info.bound6);
-  for (auto& m : s->bihs) live_row(m.first, m.second.info.bound6);
-  for (auto& m : s->sph_bihs) live_row(m.first, m.second.info.bound6);
+  for (auto& m : s->leaf_bihs) live_row(m.first, m.second.info.bound6);
   for (auto& m : s->ibihs) live_row(m.first, m.second.info.bound6);
   return s;
 }
@@ -1101,6 +1086,29 @@ template <class Dev> static int run_blocking(glome_ctx* ctx, float* gpu_ms, Dev 
   if (gpu_ms) HIPCHK(ctx, hipEventElapsedTime(gpu_ms, ctx->ev0, ctx->ev1));
   return check_device_error(ctx);
 }
+// The frame of the updates' blocking host forms.  check(): what both forms of the call refuse.  validate(): what the host form alone can
+// see, the values in the caller's arrays.  stage(in) copies the arrays to the device through `in` and returns the device form as a
+// callable: the copies stay outside the timed span, the device form runs inside it.  Refusals keep this order: check, validation, device
+// work.  empty: the call names nothing to update -- once it has passed the check and the validation it is complete.
+struct StageIn {
+  Staging stg;
+  bool ok = true;
+  template <class T> T* operator()(const T* h, size_t n) { T* d = stg.in<T>(h, n); ok = ok && d; return d; }
+};
+template <class Check, class Validate, class Stage> static int blocking_update(glome_scene* s, float* gpu_ms, Check check, Validate validate, Stage stage, bool empty = false) {
+  if (!s) return GLOME_E_INVALID;
+  glome_ctx* ctx = s->ctx;
+  if (gpu_ms) *gpu_ms = 0;
+  if (int rc = check()) return rc;
+  if (int rc = validate()) return rc;
+  if (empty) return 0;
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  if (int rc = quiesce(ctx)) return rc;
+  StageIn in{{ctx, {}}};
+  auto dev = stage(in);
+  if (!in.ok) { ctx->err = "staging allocation failed"; return GLOME_E_HIP; }
+  return run_blocking(ctx, gpu_ms, dev);
+}
 // One event pair per update while timing is on; with the update's split switch (GLOME_DEBUG_MESH_UPDATE_SPLIT,
 // GLOME_DEBUG_BIH_UPDATE_SPLIT: tools/probe/*_update_rate.py) one per stage -- records, levels, bound.
 struct UpdateSpan {
@@ -1142,12 +1150,20 @@ static int accepted(glome_scene* s, const char* what, const UpdateAnswer& plain,
 template <class T> static upd::IndexedPts<T> indexed_pts(glome_ctx* ctx, const void* verts_dev, int nv, const int32_t* idx_dev) {
   return upd::IndexedPts<T>{(const T*)verts_dev, idx_dev, (uint32_t)nv, &ctx->slot().d_counters->error};
 }
-// The fp32 box over all points of a source into a header's two box words: partial boxes, then their fold from +-start (update_common.hpp).
-template <class Src> static void launch_bound32(glome_ctx* ctx, Src pts, uint32_t n_pts, float4* part, float start, float4* hdr) {
-  const uint32_t blocks = std::max<uint32_t>(1u, std::min<uint32_t>((n_pts + upd::kBoundBlock - 1) / upd::kBoundBlock, (uint32_t)upd::kBoundMaxBlocks));
-  upd::DBoundArgs<Src> A;
-  A.src = pts; A.nv = n_pts; A.part = part; A.error = &ctx->slot().d_counters->error;
-  hipLaunchKernelGGL(upd::k_points_bound<Src>, dim3(blocks), dim3(upd::kBoundBlock), 0, ctx->stream, A);
+// The spheres' sources (sphere_bih_update_kernels.hpp) yield items; every other source yields points (update_common.hpp).  What an update
+// launches for a source is picked by this alone.
+template <class Src> constexpr bool kSphereSrc = std::is_same<Src, sphupd::SphPacked64>::value || std::is_same<Src, sphupd::SphSplit32>::value;
+// The fp32 box over all points (all spheres) of a source into a header's two box words: partial boxes, then their fold from +-start
+// (update_common.hpp).
+template <class Src> static void launch_bound32(glome_ctx* ctx, Src src, uint32_t n, float4* part, float start, float4* hdr) {
+  const uint32_t blocks = std::max<uint32_t>(1u, std::min<uint32_t>((n + upd::kBoundBlock - 1) / upd::kBoundBlock, (uint32_t)upd::kBoundMaxBlocks));
+  if constexpr (kSphereSrc<Src>) {
+    hipLaunchKernelGGL(sphupd::k_sph_bound<Src>, dim3(blocks), dim3(upd::kBoundBlock), 0, ctx->stream, src, n, part);
+  } else {
+    upd::DBoundArgs<Src> A;
+    A.src = src; A.nv = n; A.part = part; A.error = &ctx->slot().d_counters->error;
+    hipLaunchKernelGGL(upd::k_points_bound<Src>, dim3(blocks), dim3(upd::kBoundBlock), 0, ctx->stream, A);
+  }
   hipLaunchKernelGGL(upd::k_bound_store, dim3(1), dim3(64), 0, ctx->stream, (const float4*)part, blocks, start, hdr);
 }
 // A bih's planes: a launch of k_bih_level per tree level, deepest first.  merged_off (the triangle bih alone, behind its switch): the
@@ -1170,10 +1186,11 @@ static void launch_levels(glome_ctx* ctx, const bihupd::DLevelArgs& A, const std
 
 // ---- objects under a bih, and the item bihs above them (item_bih_update_kernels.hpp) ----
 // An updated object's fp64 bound into its row of the bounds table -- two launches on the current stream -- and the trees above it stale.
-template <class Src> static void nested_points_bound(glome_scene* s, int node, Src pts, uint32_t n_pts, double start, const std::vector<int>& above) {
+// `part`: the kernel that makes the partial boxes of the source (k_nest_points_part, k_nest_spheres_part).
+template <class Src> static void nested_points_bound(glome_scene* s, int node, void (*part)(Src, uint32_t, double*), Src src, uint32_t n, double start, const std::vector<int>& above) {
   glome_ctx* ctx = s->ctx;
-  const uint32_t blocks = std::min<uint32_t>((n_pts + itemupd::kFoldBlock - 1) / itemupd::kFoldBlock, (uint32_t)itemupd::kPartMaxBlocks);
-  if (blocks) hipLaunchKernelGGL(itemupd::k_nest_points_part<Src>, dim3(blocks), dim3(itemupd::kFoldBlock), 0, ctx->stream, pts, n_pts, s->d_live_part);
+  const uint32_t blocks = std::min<uint32_t>((n + itemupd::kFoldBlock - 1) / itemupd::kFoldBlock, (uint32_t)itemupd::kPartMaxBlocks);
+  if (blocks) hipLaunchKernelGGL(part, dim3(blocks), dim3(itemupd::kFoldBlock), 0, ctx->stream, src, n, s->d_live_part);
   hipLaunchKernelGGL(itemupd::k_nest_fold_store, dim3(1), dim3(itemupd::kFoldBlock), 0, ctx->stream, (const double*)s->d_live_part, blocks, start,
                      s->d_live + 6 * (size_t)s->live_slot.at(node), &ctx->slot().d_counters->error);
   s->stale.insert(above.begin(), above.end());
@@ -1289,7 +1306,7 @@ template <class T> static int mesh_update_dev(glome_scene* s, int32_t mesh_id, c
   HIPCHK(ctx, span.stage());
   // box_of_points starts from a vertex (real infinities); a mesh of no vertices keeps box_empty
   if (nv > 0) launch_bound32(ctx, verts_dev, (uint32_t)nv, m->d_ws + 2 * (size_t)U.n_tris, __builtin_huge_valf(), (float4*)s->dev.meshhdr + 2 * (size_t)U.hdr);
-  if (s->nested_on && !U.nested.above.empty()) nested_points_bound(s, mesh_id, verts_dev, (uint32_t)nv, nv > 0 ? __builtin_huge_val() : kInfinity, U.nested.above);
+  if (s->nested_on && !U.nested.above.empty()) nested_points_bound(s, mesh_id, itemupd::k_nest_points_part<Src>, verts_dev, (uint32_t)nv, nv > 0 ? __builtin_huge_val() : kInfinity, U.nested.above);
   HIPCHK(ctx, hipGetLastError());
   HIPCHK(ctx, span.end());
   mark_launched(ctx);  // (a vertex that is not finite is reported at the next synchronize)
@@ -1297,20 +1314,19 @@ template <class T> static int mesh_update_dev(glome_scene* s, int32_t mesh_id, c
 }
 // the host form, for arrays of T: staged as they are
 template <class T> static int mesh_update_host(glome_scene* s, int32_t mesh_id, const T* verts, int nv, const T* norms, int nn, float* gpu_ms) {
-  if (!s) return GLOME_E_INVALID;
-  glome_ctx* ctx = s->ctx;
-  if (gpu_ms) *gpu_ms = 0;
   glome_scene::MeshUpd* m = nullptr;
-  if (int rc = mesh_update_check(s, mesh_id, verts, nv, norms, nn, &m)) return rc;
-  for (size_t k = 0; k < 3 * (size_t)nv; k++) if (!std::isfinite(verts[k])) { ctx->err = "mesh update: a vertex coordinate is not finite"; return GLOME_E_INVALID; }
-  for (size_t k = 0; k < 3 * (size_t)nn; k++) if (!std::isfinite(norms[k])) { ctx->err = "mesh update: a normal coordinate is not finite"; return GLOME_E_INVALID; }
-  HIPCHK(ctx, hipSetDevice(ctx->device));
-  if (int rc = quiesce(ctx)) return rc;
-  Staging stg{ctx, {}};
-  T* dv = stg.in<T>(verts, 3 * (size_t)nv);
-  T* dn = nn ? stg.in<T>(norms, 3 * (size_t)nn) : nullptr;
-  if (!dv || (nn && !dn)) { ctx->err = "staging allocation failed"; return GLOME_E_HIP; }
-  return run_blocking(ctx, gpu_ms, [&] { return mesh_update_dev<T>(s, mesh_id, dv, nv, dn, nn); });
+  return blocking_update(
+      s, gpu_ms, [&] { return mesh_update_check(s, mesh_id, verts, nv, norms, nn, &m); },
+      [&]() -> int {
+        for (size_t k = 0; k < 3 * (size_t)nv; k++) if (!std::isfinite(verts[k])) { s->ctx->err = "mesh update: a vertex coordinate is not finite"; return GLOME_E_INVALID; }
+        for (size_t k = 0; k < 3 * (size_t)nn; k++) if (!std::isfinite(norms[k])) { s->ctx->err = "mesh update: a normal coordinate is not finite"; return GLOME_E_INVALID; }
+        return 0;
+      },
+      [&](StageIn& in) {
+        T* dv = in(verts, 3 * (size_t)nv);
+        T* dn = nn ? in(norms, 3 * (size_t)nn) : nullptr;
+        return [=] { return mesh_update_dev<T>(s, mesh_id, dv, nv, dn, nn); };
+      });
 }
 int glome_scene_mesh_update_dev(glome_scene* s, int32_t mesh_id, const double* verts_dev, int nv, const double* norms_dev, int nn) {
   return mesh_update_dev<double>(s, mesh_id, verts_dev, nv, norms_dev, nn);
@@ -1325,74 +1341,89 @@ int glome_scene_mesh_update_f32(glome_scene* s, int32_t mesh_id, const float* ve
   return mesh_update_host<float>(s, mesh_id, verts, nv, norms, nn, gpu_ms);
 }
 
-// ---- new triangles for a committed triangle bih (bih_update_kernels.hpp) ----
-// what both forms refuse before anything is launched; *out = the bih's tables
-static int bih_update_check(glome_scene* s, int32_t bih_id, const void* pts9, int n, glome_scene::BihUpd** out) {
+// ---- new items for a committed leaf bih: triangles (bih_update_kernels.hpp) or spheres (sphere_bih_update_kernels.hpp) ----
+// One path serves both classes: the record (LeafBihUpdateInfo) says what differs in the tables, the source type what differs in the kernels.
+// What both forms refuse before anything is launched; *out = the bih's tables.  cls: the class the call is for; what: the call's name in
+// its texts ("bih update", "sphere bih update"); `items`: the array there is one entry per item of.
+static int leaf_bih_update_check(glome_scene* s, uint32_t cls, const char* what, int32_t bih_id, const void* items, int n, glome_scene::LeafBihUpd** out) {
   glome_ctx* ctx = s->ctx;
-  auto it = s->bihs.find(bih_id);
-  if (it == s->bihs.end()) { ctx->err = "bih update: node " + std::to_string(bih_id) + " is not a bih of plain triangles of this scene"; return GLOME_E_INVALID; }
-  const BihUpdateInfo& U = it->second.info;
-  if (n != U.n_items) { ctx->err = "bih update: the bih has " + std::to_string(U.n_items) + " items, not " + std::to_string(n); return GLOME_E_INVALID; }
-  if (n && !pts9) { ctx->err = "bih update: null triangle array"; return GLOME_E_INVALID; }
-  if (int rc = accepted(s, "bih update", U.plain, U.nested)) return rc;
+  auto refuse = [&](const std::string& why) { ctx->err = std::string(what) + ": " + why; return GLOME_E_INVALID; };  // (texts are made by a refusal alone)
+  const char* word = cls == BC_SPHERE ? "sphere" : "triangle";
+  auto it = s->leaf_bihs.find(bih_id);
+  if (it == s->leaf_bihs.end() || it->second.info.cls != cls) return refuse("node " + std::to_string(bih_id) + " is not a bih of plain " + word + "s of this scene");
+  const LeafBihUpdateInfo& U = it->second.info;
+  if (n != U.n_items) return refuse("the bih has " + std::to_string(U.n_items) + " items, not " + std::to_string(n));
+  if (n && !items) return refuse(std::string("null ") + word + " array");
+  if (int rc = accepted(s, what, U.plain, U.nested)) return rc;
   *out = &it->second;
   return 0;
 }
-// The launches of an update the checks have accepted, on the current stream: `pts` yields the items' 3 n vertices (update_common.hpp: a
-// point source), and every kernel that reads them is its instance for that source.
-template <class Src> static int bih_update_launch(glome_scene* s, int32_t bih_id, glome_scene::BihUpd* m, Src pts9_dev, int n) {
+static int bih_update_check(glome_scene* s, int32_t bih_id, const void* pts9, int n, glome_scene::LeafBihUpd** out) { return leaf_bih_update_check(s, BC_TRI, "bih update", bih_id, pts9, n, out); }
+static int sphere_bih_update_check(glome_scene* s, int32_t bih_id, const void* c3r, int n, glome_scene::LeafBihUpd** out) { return leaf_bih_update_check(s, BC_SPHERE, "sphere bih update", bih_id, c3r, n, out); }
+// The launches of an update the checks have accepted, on the current stream.  `src` yields the n items: a point source their 3 n vertices
+// (update_common.hpp), a sphere source their spheres (sphere_bih_update_kernels.hpp); every kernel that reads them is its instance for
+// that source.  The source's kind picks the records kernel and the two partial-box kernels; all else is one sequence.
+template <class Src> static int leaf_bih_update_launch(glome_scene* s, int32_t bih_id, glome_scene::LeafBihUpd* m, Src src, int n) {
   glome_ctx* ctx = s->ctx;
   HIPCHK(ctx, hipSetDevice(ctx->device));
-  const BihUpdateInfo& U = m->info;
+  const LeafBihUpdateInfo& U = m->info;
+  const uint32_t n_src = kSphereSrc<Src> ? (uint32_t)n : 3u * (uint32_t)n;  // what the bounds fold: spheres, or vertices
   // a box per record and per node slot, and the bound's partial boxes
-  if (int rc = ensure_ws(s, m->d_ws, 2 * ((size_t)U.n_tris + U.n_slots + upd::kBoundMaxBlocks))) return rc;
+  if (int rc = ensure_ws(s, m->d_ws, 2 * ((size_t)U.n_recs + U.n_slots + upd::kBoundMaxBlocks))) return rc;
   // The levels run a launch each: the merged launch of the narrow levels (k_bih_levels_merged) stays behind GLOME_DEBUG_BIH_UPDATE_MERGED
   // until tools/probe/bih_update_rate.py has shown on the hardware that it wins beyond the run-to-run spread
   const bool merged = getenv("GLOME_DEBUG_BIH_UPDATE_MERGED") != nullptr;
   UpdateSpan span(ctx, "GLOME_DEBUG_BIH_UPDATE_SPLIT");
   HIPCHK(ctx, span.begin());
-  {
+  if constexpr (kSphereSrc<Src>) {
+    sphupd::DItemsArgs<Src> A;
+    A.src = src; A.rows = m->d_rows; A.spheres = (float4*)s->dev.spheres + (size_t)U.first_prim; A.ws = m->d_ws; A.n = U.n_recs;
+    A.error = &ctx->slot().d_counters->error;
+    launch_lanes(ctx, sphupd::k_sph_items<Src>, U.n_recs, A);
+  } else {
     bihupd::DTrisArgs<Src> A;
-    A.src = pts9_dev; A.rows = (const uint2*)m->d_rows; A.tris = (float4*)s->dev.tris + 3 * (size_t)U.first_tri; A.tripairs = (float*)s->dev.tripairs;
-    A.ws = m->d_ws; A.n = U.n_tris;
-    launch_lanes(ctx, bihupd::k_bih_tris<Src>, U.n_tris, A);
+    A.src = src; A.rows = (const uint2*)m->d_rows; A.tris = (float4*)s->dev.tris + 3 * (size_t)U.first_prim; A.tripairs = (float*)s->dev.tripairs;
+    A.ws = m->d_ws; A.n = U.n_recs;
+    launch_lanes(ctx, bihupd::k_bih_tris<Src>, U.n_recs, A);
   }
   HIPCHK(ctx, span.stage());
   {
     bihupd::DLevelArgs A;
-    A.nodes = m->d_levels; A.bihnodes = (float4*)s->dev.bihnodes; A.pknodes = U.pk ? (float4*)s->dev.pknodes : nullptr;
-    A.ws_tri = m->d_ws; A.ws_node = m->d_ws + 2 * (size_t)U.n_tris; A.first_rec = U.first_rec; A.first_slot = U.first_slot;
+    A.nodes = m->d_levels; A.bihnodes = (float4*)s->dev.bihnodes; A.pknodes = U.pk ? (float4*)s->dev.pknodes : nullptr;  // (a sphere tree's walk reads bihnodes alone)
+    A.ws_tri = m->d_ws; A.ws_node = m->d_ws + 2 * (size_t)U.n_recs; A.first_rec = U.first_rec; A.first_slot = U.first_slot;
     launch_levels(ctx, A, U.level_off, merged ? m->d_level_off : nullptr);
   }
   HIPCHK(ctx, span.stage());
-  // the join of the triangles' boxes, from box_empty: in fp32 into the header, in fp64 into the bounds table
-  launch_bound32(ctx, pts9_dev, 3u * (uint32_t)n, m->d_ws + 2 * ((size_t)U.n_tris + U.n_slots), (float)kInfinity, (float4*)s->dev.bihhdr + 3 * (size_t)U.hdr);
-  if (s->nested_on && !U.nested.above.empty()) nested_points_bound(s, bih_id, pts9_dev, 3u * (uint32_t)n, kInfinity, U.nested.above);
+  // the join of the items' boxes, from box_empty: in fp32 into the header, in fp64 into the bounds table
+  launch_bound32(ctx, src, n_src, m->d_ws + 2 * ((size_t)U.n_recs + U.n_slots), (float)kInfinity, (float4*)s->dev.bihhdr + 3 * (size_t)U.hdr);
+  if (s->nested_on && !U.nested.above.empty()) {
+    if constexpr (kSphereSrc<Src>) nested_points_bound(s, bih_id, sphupd::k_nest_spheres_part<Src>, src, n_src, kInfinity, U.nested.above);
+    else nested_points_bound(s, bih_id, itemupd::k_nest_points_part<Src>, src, n_src, kInfinity, U.nested.above);
+  }
   HIPCHK(ctx, hipGetLastError());
   HIPCHK(ctx, span.end());
-  mark_launched(ctx);  // (a coordinate that is not finite, or an index outside the vertex array, is reported at the next synchronize)
+  mark_launched(ctx);  // (a value that is not finite, a radius that is not positive or an index outside the vertex array is reported at the next synchronize)
   return 0;
 }
 template <class T> static int bih_update_dev(glome_scene* s, int32_t bih_id, const T* pts9_dev, int n) {
   if (!s) return GLOME_E_INVALID;
-  glome_scene::BihUpd* m = nullptr;
+  glome_scene::LeafBihUpd* m = nullptr;
   if (int rc = bih_update_check(s, bih_id, pts9_dev, n, &m)) return rc;
-  return bih_update_launch(s, bih_id, m, upd::DensePts<T>{pts9_dev}, n);
+  return leaf_bih_update_launch(s, bih_id, m, upd::DensePts<T>{pts9_dev}, n);
 }
 // the host form, for an array of T: staged as it is
 template <class T> static int bih_update_host(glome_scene* s, int32_t bih_id, const T* pts9, int n, float* gpu_ms) {
-  if (!s) return GLOME_E_INVALID;
-  glome_ctx* ctx = s->ctx;
-  if (gpu_ms) *gpu_ms = 0;
-  glome_scene::BihUpd* m = nullptr;
-  if (int rc = bih_update_check(s, bih_id, pts9, n, &m)) return rc;
-  for (size_t k = 0; k < 9 * (size_t)n; k++) if (!std::isfinite(pts9[k])) { ctx->err = "bih update: a vertex coordinate is not finite"; return GLOME_E_INVALID; }
-  HIPCHK(ctx, hipSetDevice(ctx->device));
-  if (int rc = quiesce(ctx)) return rc;
-  Staging stg{ctx, {}};
-  T* dp = stg.in<T>(pts9, 9 * (size_t)n);
-  if (!dp) { ctx->err = "staging allocation failed"; return GLOME_E_HIP; }
-  return run_blocking(ctx, gpu_ms, [&] { return bih_update_dev<T>(s, bih_id, dp, n); });
+  glome_scene::LeafBihUpd* m = nullptr;
+  return blocking_update(
+      s, gpu_ms, [&] { return bih_update_check(s, bih_id, pts9, n, &m); },
+      [&]() -> int {
+        for (size_t k = 0; k < 9 * (size_t)n; k++) if (!std::isfinite(pts9[k])) { s->ctx->err = "bih update: a vertex coordinate is not finite"; return GLOME_E_INVALID; }
+        return 0;
+      },
+      [&](StageIn& in) {
+        T* dp = in(pts9, 9 * (size_t)n);
+        return [=] { return bih_update_dev<T>(s, bih_id, dp, n); };
+      });
 }
 int glome_scene_bih_update_dev(glome_scene* s, int32_t bih_id, const double* pts9_dev, int n) { return bih_update_dev<double>(s, bih_id, pts9_dev, n); }
 int glome_scene_bih_update(glome_scene* s, int32_t bih_id, const double* pts9, int n, float* gpu_ms) { return bih_update_host<double>(s, bih_id, pts9, n, gpu_ms); }
@@ -1401,7 +1432,7 @@ int glome_scene_bih_update_f32(glome_scene* s, int32_t bih_id, const float* pts9
 
 // The indexed forms: the items' vertices are verts[3 * idx3[3 k + c] ..], a vertex array of `dtype` and an index table.  What both forms
 // refuse beyond bih_update_check, before anything is launched.
-static int bih_update_indexed_check(glome_scene* s, int32_t bih_id, const void* verts, int32_t dtype, int nv, const int32_t* idx3, int n, glome_scene::BihUpd** out) {
+static int bih_update_indexed_check(glome_scene* s, int32_t bih_id, const void* verts, int32_t dtype, int nv, const int32_t* idx3, int n, glome_scene::LeafBihUpd** out) {
   glome_ctx* ctx = s->ctx;
   if (int rc = bih_update_check(s, bih_id, idx3, n, out)) return rc;  // (the array it asks for is the one there is one entry per item of)
   if (dtype != GLOME_F64 && dtype != GLOME_F32) { ctx->err = "bih update: dtype " + std::to_string(dtype) + " is neither GLOME_F64 nor GLOME_F32"; return GLOME_E_INVALID; }
@@ -1411,139 +1442,81 @@ static int bih_update_indexed_check(glome_scene* s, int32_t bih_id, const void* 
 }
 int glome_scene_bih_update_indexed_dev(glome_scene* s, int32_t bih_id, const void* verts_dev, int32_t dtype, int nv, const int32_t* idx3_dev, int n) {
   if (!s) return GLOME_E_INVALID;
-  glome_scene::BihUpd* m = nullptr;
+  glome_scene::LeafBihUpd* m = nullptr;
   if (int rc = bih_update_indexed_check(s, bih_id, verts_dev, dtype, nv, idx3_dev, n, &m)) return rc;
-  if (dtype == GLOME_F32) return bih_update_launch(s, bih_id, m, indexed_pts<float>(s->ctx, verts_dev, nv, idx3_dev), n);
-  return bih_update_launch(s, bih_id, m, indexed_pts<double>(s->ctx, verts_dev, nv, idx3_dev), n);
+  if (dtype == GLOME_F32) return leaf_bih_update_launch(s, bih_id, m, indexed_pts<float>(s->ctx, verts_dev, nv, idx3_dev), n);
+  return leaf_bih_update_launch(s, bih_id, m, indexed_pts<double>(s->ctx, verts_dev, nv, idx3_dev), n);
 }
 int glome_scene_bih_update_indexed(glome_scene* s, int32_t bih_id, const void* verts, int32_t dtype, int nv, const int32_t* idx3, int n, float* gpu_ms) {
-  if (!s) return GLOME_E_INVALID;
-  glome_ctx* ctx = s->ctx;
-  if (gpu_ms) *gpu_ms = 0;
-  glome_scene::BihUpd* m = nullptr;
-  if (int rc = bih_update_indexed_check(s, bih_id, verts, dtype, nv, idx3, n, &m)) return rc;
-  for (size_t k = 0; k < 3 * (size_t)n; k++) {  // only referenced vertices count: an unreferenced one may be anything
-    const int32_t i = idx3[k];
-    if (i < 0 || i >= nv) { ctx->err = "bih update: item " + std::to_string(k / 3) + " has vertex index " + std::to_string(i) + ", outside [0, " + std::to_string(nv) + ")"; return GLOME_E_INVALID; }
-    bool finite = true;
-    for (int a = 0; a < 3; a++) finite = finite && (dtype == GLOME_F32 ? std::isfinite(((const float*)verts)[3 * (size_t)i + a]) : std::isfinite(((const double*)verts)[3 * (size_t)i + a]));
-    if (!finite) { ctx->err = "bih update: a vertex coordinate is not finite (vertex " + std::to_string(i) + ", of item " + std::to_string(k / 3) + ")"; return GLOME_E_INVALID; }
-  }
-  HIPCHK(ctx, hipSetDevice(ctx->device));
-  if (int rc = quiesce(ctx)) return rc;
-  Staging stg{ctx, {}};
-  const size_t vbytes = 3 * (size_t)nv * (dtype == GLOME_F32 ? sizeof(float) : sizeof(double));
-  char* dv = stg.in<char>((const char*)verts, vbytes);  // the caller's arrays as they are: no widened, gathered copy
-  int32_t* di = stg.in<int32_t>(idx3, 3 * (size_t)n);
-  if (!dv || !di) { ctx->err = "staging allocation failed"; return GLOME_E_HIP; }
-  return run_blocking(ctx, gpu_ms, [&] { return glome_scene_bih_update_indexed_dev(s, bih_id, dv, dtype, nv, di, n); });
+  glome_scene::LeafBihUpd* m = nullptr;
+  return blocking_update(
+      s, gpu_ms, [&] { return bih_update_indexed_check(s, bih_id, verts, dtype, nv, idx3, n, &m); },
+      [&]() -> int {
+        glome_ctx* ctx = s->ctx;
+        for (size_t k = 0; k < 3 * (size_t)n; k++) {  // only referenced vertices count: an unreferenced one may be anything
+          const int32_t i = idx3[k];
+          if (i < 0 || i >= nv) { ctx->err = "bih update: item " + std::to_string(k / 3) + " has vertex index " + std::to_string(i) + ", outside [0, " + std::to_string(nv) + ")"; return GLOME_E_INVALID; }
+          bool finite = true;
+          for (int a = 0; a < 3; a++) finite = finite && (dtype == GLOME_F32 ? std::isfinite(((const float*)verts)[3 * (size_t)i + a]) : std::isfinite(((const double*)verts)[3 * (size_t)i + a]));
+          if (!finite) { ctx->err = "bih update: a vertex coordinate is not finite (vertex " + std::to_string(i) + ", of item " + std::to_string(k / 3) + ")"; return GLOME_E_INVALID; }
+        }
+        return 0;
+      },
+      [&](StageIn& in) {
+        const size_t vbytes = 3 * (size_t)nv * (dtype == GLOME_F32 ? sizeof(float) : sizeof(double));
+        char* dv = in((const char*)verts, vbytes);  // the caller's arrays as they are: no widened, gathered copy
+        int32_t* di = in(idx3, 3 * (size_t)n);
+        return [=] { return glome_scene_bih_update_indexed_dev(s, bih_id, dv, dtype, nv, di, n); };
+      });
 }
 
-// ---- new spheres for a committed sphere bih (sphere_bih_update_kernels.hpp) ----
-// what both forms refuse before anything is launched; *out = the bih's tables
-static int sphere_bih_update_check(glome_scene* s, int32_t bih_id, const void* c3r, int n, glome_scene::SphBihUpd** out) {
-  glome_ctx* ctx = s->ctx;
-  auto it = s->sph_bihs.find(bih_id);
-  if (it == s->sph_bihs.end()) { ctx->err = "sphere bih update: node " + std::to_string(bih_id) + " is not a bih of plain spheres of this scene"; return GLOME_E_INVALID; }
-  const SphereBihUpdateInfo& U = it->second.info;
-  if (n != U.n_items) { ctx->err = "sphere bih update: the bih has " + std::to_string(U.n_items) + " items, not " + std::to_string(n); return GLOME_E_INVALID; }
-  if (n && !c3r) { ctx->err = "sphere bih update: null sphere array"; return GLOME_E_INVALID; }
-  if (int rc = accepted(s, "sphere bih update", U.plain, U.nested)) return rc;
-  *out = &it->second;
-  return 0;
-}
-// The launches of an update the checks have accepted, on the current stream: `c3r_dev` yields the items' spheres
-// (sphere_bih_update_kernels.hpp: a sphere source), and every kernel that reads them is its instance for that source.
-template <class Src> static int sphere_bih_update_launch(glome_scene* s, int32_t bih_id, glome_scene::SphBihUpd* m, Src c3r_dev, int n) {
-  glome_ctx* ctx = s->ctx;
-  HIPCHK(ctx, hipSetDevice(ctx->device));
-  const SphereBihUpdateInfo& U = m->info;
-  // a box per record and per node slot, and the bound's partial boxes
-  if (int rc = ensure_ws(s, m->d_ws, 2 * ((size_t)U.n_recs + U.n_slots + upd::kBoundMaxBlocks))) return rc;
-  const bool merged = getenv("GLOME_DEBUG_BIH_UPDATE_MERGED") != nullptr;  // (as in the triangle bih's update)
-  UpdateSpan span(ctx, "GLOME_DEBUG_BIH_UPDATE_SPLIT");
-  HIPCHK(ctx, span.begin());
-  {
-    sphupd::DItemsArgs<Src> A;
-    A.src = c3r_dev; A.rows = m->d_rows; A.spheres = (float4*)s->dev.spheres + (size_t)U.first_sphere; A.ws = m->d_ws; A.n = U.n_recs;
-    A.error = &ctx->slot().d_counters->error;
-    launch_lanes(ctx, sphupd::k_sph_items<Src>, U.n_recs, A);
-  }
-  HIPCHK(ctx, span.stage());
-  {
-    bihupd::DLevelArgs A;
-    A.nodes = m->d_levels; A.bihnodes = (float4*)s->dev.bihnodes; A.pknodes = nullptr;  // (a sphere tree's walk reads bihnodes alone)
-    A.ws_tri = m->d_ws; A.ws_node = m->d_ws + 2 * (size_t)U.n_recs; A.first_rec = U.first_rec; A.first_slot = U.first_slot;
-    launch_levels(ctx, A, U.level_off, merged ? m->d_level_off : nullptr);
-  }
-  HIPCHK(ctx, span.stage());
-  {  // the join of the spheres' boxes, from box_empty: in fp32 into the header, in fp64 into the bounds table
-    float4* part = m->d_ws + 2 * ((size_t)U.n_recs + U.n_slots);
-    const uint32_t blocks = std::max<uint32_t>(1u, std::min<uint32_t>(((uint32_t)n + upd::kBoundBlock - 1) / upd::kBoundBlock, (uint32_t)upd::kBoundMaxBlocks));
-    hipLaunchKernelGGL(sphupd::k_sph_bound<Src>, dim3(blocks), dim3(upd::kBoundBlock), 0, ctx->stream, c3r_dev, (uint32_t)n, part);
-    hipLaunchKernelGGL(upd::k_bound_store, dim3(1), dim3(64), 0, ctx->stream, (const float4*)part, blocks, (float)kInfinity, (float4*)s->dev.bihhdr + 3 * (size_t)U.hdr);
-  }
-  if (s->nested_on && !U.nested.above.empty()) {
-    const uint32_t blocks = std::min<uint32_t>(((uint32_t)n + itemupd::kFoldBlock - 1) / itemupd::kFoldBlock, (uint32_t)itemupd::kPartMaxBlocks);
-    if (blocks) hipLaunchKernelGGL(sphupd::k_nest_spheres_part<Src>, dim3(blocks), dim3(itemupd::kFoldBlock), 0, ctx->stream, c3r_dev, (uint32_t)n, s->d_live_part);
-    hipLaunchKernelGGL(itemupd::k_nest_fold_store, dim3(1), dim3(itemupd::kFoldBlock), 0, ctx->stream, (const double*)s->d_live_part, blocks, kInfinity,
-                       s->d_live + 6 * (size_t)s->live_slot.at(bih_id), &ctx->slot().d_counters->error);
-    s->stale.insert(U.nested.above.begin(), U.nested.above.end());
-  }
-  HIPCHK(ctx, hipGetLastError());
-  HIPCHK(ctx, span.end());
-  mark_launched(ctx);  // (a value that is not finite or a radius that is not positive is reported at the next synchronize)
-  return 0;
-}
+// The sphere bih's forms: fp64 cx cy cz r interleaved; and fp32 in two streams, centres [n, 3] and radii [n].
 int glome_scene_sphere_bih_update_dev(glome_scene* s, int32_t bih_id, const double* c3r_dev, int n) {
   if (!s) return GLOME_E_INVALID;
-  glome_scene::SphBihUpd* m = nullptr;
+  glome_scene::LeafBihUpd* m = nullptr;
   if (int rc = sphere_bih_update_check(s, bih_id, c3r_dev, n, &m)) return rc;
-  return sphere_bih_update_launch(s, bih_id, m, sphupd::SphPacked64{c3r_dev}, n);
+  return leaf_bih_update_launch(s, bih_id, m, sphupd::SphPacked64{c3r_dev}, n);
 }
 int glome_scene_sphere_bih_update(glome_scene* s, int32_t bih_id, const double* c3r, int n, float* gpu_ms) {
-  if (!s) return GLOME_E_INVALID;
-  glome_ctx* ctx = s->ctx;
-  if (gpu_ms) *gpu_ms = 0;
-  glome_scene::SphBihUpd* m = nullptr;
-  if (int rc = sphere_bih_update_check(s, bih_id, c3r, n, &m)) return rc;
-  for (size_t k = 0; k < 4 * (size_t)n; k++) if (!std::isfinite(c3r[k])) { ctx->err = "sphere bih update: a value is not finite"; return GLOME_E_INVALID; }
-  for (size_t k = 0; k < (size_t)n; k++) if (!(c3r[4 * k + 3] > 0)) { ctx->err = "sphere bih update: radius of item " + std::to_string(k) + " is not positive"; return GLOME_E_INVALID; }
-  HIPCHK(ctx, hipSetDevice(ctx->device));
-  if (int rc = quiesce(ctx)) return rc;
-  Staging stg{ctx, {}};
-  double* dp = stg.in<double>(c3r, 4 * (size_t)n);
-  if (!dp) { ctx->err = "staging allocation failed"; return GLOME_E_HIP; }
-  return run_blocking(ctx, gpu_ms, [&] { return glome_scene_sphere_bih_update_dev(s, bih_id, dp, n); });
+  glome_scene::LeafBihUpd* m = nullptr;
+  return blocking_update(
+      s, gpu_ms, [&] { return sphere_bih_update_check(s, bih_id, c3r, n, &m); },
+      [&]() -> int {
+        for (size_t k = 0; k < 4 * (size_t)n; k++) if (!std::isfinite(c3r[k])) { s->ctx->err = "sphere bih update: a value is not finite"; return GLOME_E_INVALID; }
+        for (size_t k = 0; k < (size_t)n; k++) if (!(c3r[4 * k + 3] > 0)) { s->ctx->err = "sphere bih update: radius of item " + std::to_string(k) + " is not positive"; return GLOME_E_INVALID; }
+        return 0;
+      },
+      [&](StageIn& in) {
+        double* dp = in(c3r, 4 * (size_t)n);
+        return [=] { return glome_scene_sphere_bih_update_dev(s, bih_id, dp, n); };
+      });
 }
-// The fp32 forms: two streams, centres [n, 3] and radii [n].
-static int sphere_bih_update_f32_check(glome_scene* s, int32_t bih_id, const float* centres3, const float* radii, int n, glome_scene::SphBihUpd** out) {
+static int sphere_bih_update_f32_check(glome_scene* s, int32_t bih_id, const float* centres3, const float* radii, int n, glome_scene::LeafBihUpd** out) {
   if (int rc = sphere_bih_update_check(s, bih_id, centres3, n, out)) return rc;
   if (n && !radii) { s->ctx->err = "sphere bih update: null radius array"; return GLOME_E_INVALID; }
   return 0;
 }
 int glome_scene_sphere_bih_update_f32_dev(glome_scene* s, int32_t bih_id, const float* centres3_dev, const float* radii_dev, int n) {
   if (!s) return GLOME_E_INVALID;
-  glome_scene::SphBihUpd* m = nullptr;
+  glome_scene::LeafBihUpd* m = nullptr;
   if (int rc = sphere_bih_update_f32_check(s, bih_id, centres3_dev, radii_dev, n, &m)) return rc;
-  return sphere_bih_update_launch(s, bih_id, m, sphupd::SphSplit32{centres3_dev, radii_dev}, n);
+  return leaf_bih_update_launch(s, bih_id, m, sphupd::SphSplit32{centres3_dev, radii_dev}, n);
 }
 int glome_scene_sphere_bih_update_f32(glome_scene* s, int32_t bih_id, const float* centres3, const float* radii, int n, float* gpu_ms) {
-  if (!s) return GLOME_E_INVALID;
-  glome_ctx* ctx = s->ctx;
-  if (gpu_ms) *gpu_ms = 0;
-  glome_scene::SphBihUpd* m = nullptr;
-  if (int rc = sphere_bih_update_f32_check(s, bih_id, centres3, radii, n, &m)) return rc;
-  for (size_t k = 0; k < 3 * (size_t)n; k++) if (!std::isfinite(centres3[k])) { ctx->err = "sphere bih update: a value is not finite"; return GLOME_E_INVALID; }
-  for (size_t k = 0; k < (size_t)n; k++) if (!std::isfinite(radii[k])) { ctx->err = "sphere bih update: a value is not finite"; return GLOME_E_INVALID; }
-  for (size_t k = 0; k < (size_t)n; k++) if (!(radii[k] > 0)) { ctx->err = "sphere bih update: radius of item " + std::to_string(k) + " is not positive"; return GLOME_E_INVALID; }
-  HIPCHK(ctx, hipSetDevice(ctx->device));
-  if (int rc = quiesce(ctx)) return rc;
-  Staging stg{ctx, {}};
-  float* dc = stg.in<float>(centres3, 3 * (size_t)n);
-  float* dr = stg.in<float>(radii, (size_t)n);
-  if (!dc || !dr) { ctx->err = "staging allocation failed"; return GLOME_E_HIP; }
-  return run_blocking(ctx, gpu_ms, [&] { return glome_scene_sphere_bih_update_f32_dev(s, bih_id, dc, dr, n); });
+  glome_scene::LeafBihUpd* m = nullptr;
+  return blocking_update(
+      s, gpu_ms, [&] { return sphere_bih_update_f32_check(s, bih_id, centres3, radii, n, &m); },
+      [&]() -> int {
+        for (size_t k = 0; k < 3 * (size_t)n; k++) if (!std::isfinite(centres3[k])) { s->ctx->err = "sphere bih update: a value is not finite"; return GLOME_E_INVALID; }
+        for (size_t k = 0; k < (size_t)n; k++) if (!std::isfinite(radii[k])) { s->ctx->err = "sphere bih update: a value is not finite"; return GLOME_E_INVALID; }
+        for (size_t k = 0; k < (size_t)n; k++) if (!(radii[k] > 0)) { s->ctx->err = "sphere bih update: radius of item " + std::to_string(k) + " is not positive"; return GLOME_E_INVALID; }
+        return 0;
+      },
+      [&](StageIn& in) {
+        float* dc = in(centres3, 3 * (size_t)n);
+        float* dr = in(radii, (size_t)n);
+        return [=] { return glome_scene_sphere_bih_update_f32_dev(s, bih_id, dc, dr, n); };
+      });
 }
 
 // ---- new matrices for committed Instances (item_bih_update_kernels.hpp) ----
@@ -1635,43 +1608,39 @@ int glome_scene_instance_update_dev(glome_scene* s, const int32_t* ids, const do
   return 0;
 }
 int glome_scene_instance_update(glome_scene* s, const int32_t* ids, const double* xfms, int n, float* gpu_ms) {
-  if (!s) return GLOME_E_INVALID;
-  glome_ctx* ctx = s->ctx;
-  if (gpu_ms) *gpu_ms = 0;
   std::vector<const InstanceUpdateInfo*> U;
-  if (int rc = instance_update_check(s, ids, xfms, n, U)) return rc;
-  for (int k = 0; k < n; k++) {
-    const double* m = xfms + 24 * (size_t)k;
-    for (int q = 0; q < 24; q++) if (!std::isfinite(m[q])) { ctx->err = "instance update: a matrix entry of node " + std::to_string(ids[k]) + " is not finite"; return GLOME_E_INVALID; }
-    Xf x;
-    for (int q = 0; q < 12; q++) { x.f.m[q] = m[q]; x.i.m[q] = m[12 + q]; }
-    try { xf_check(x); } catch (const scene_error& e) { ctx->err = "instance update: node " + std::to_string(ids[k]) + ": " + e.what(); return GLOME_E_INVALID; }
-    if (U[(size_t)k]->bih < 0) continue;
-    // the item's new box, as `bound` makes it: `bih` refuses one that reaches the reference's infinity
-    const double* cb = &s->ibihs.at(U[(size_t)k]->bih).info.child_bound[6 * (size_t)U[(size_t)k]->item];
-    D3 pts[8];
-    int q = 0;
-    for (double px : {cb[0], cb[3]}) for (double py : {cb[1], cb[4]}) for (double pz : {cb[2], cb[5]}) pts[q++] = xf_point(x, D3{px, py, pz});
-    const Box3 b = box_of_points(pts, 8);
-    if (b.lo.x == -kInfinity || b.lo.y == -kInfinity || b.lo.z == -kInfinity || b.hi.x == kInfinity || b.hi.y == kInfinity || b.hi.z == kInfinity) {
-      ctx->err = "instance update: node " + std::to_string(ids[k]) + " in bih " + std::to_string(U[(size_t)k]->bih) + ": bih: infinite bounding box";
-      return GLOME_E_SCENE;
+  auto validate = [&]() -> int {
+    glome_ctx* ctx = s->ctx;
+    for (int k = 0; k < n; k++) {
+      const double* m = xfms + 24 * (size_t)k;
+      for (int q = 0; q < 24; q++) if (!std::isfinite(m[q])) { ctx->err = "instance update: a matrix entry of node " + std::to_string(ids[k]) + " is not finite"; return GLOME_E_INVALID; }
+      Xf x;
+      for (int q = 0; q < 12; q++) { x.f.m[q] = m[q]; x.i.m[q] = m[12 + q]; }
+      try { xf_check(x); } catch (const scene_error& e) { ctx->err = "instance update: node " + std::to_string(ids[k]) + ": " + e.what(); return GLOME_E_INVALID; }
+      if (U[(size_t)k]->bih < 0) continue;
+      // the item's new box, as `bound` makes it: `bih` refuses one that reaches the reference's infinity
+      const double* cb = &s->ibihs.at(U[(size_t)k]->bih).info.child_bound[6 * (size_t)U[(size_t)k]->item];
+      D3 pts[8];
+      int q = 0;
+      for (double px : {cb[0], cb[3]}) for (double py : {cb[1], cb[4]}) for (double pz : {cb[2], cb[5]}) pts[q++] = xf_point(x, D3{px, py, pz});
+      const Box3 b = box_of_points(pts, 8);
+      if (b.lo.x == -kInfinity || b.lo.y == -kInfinity || b.lo.z == -kInfinity || b.hi.x == kInfinity || b.hi.y == kInfinity || b.hi.z == kInfinity) {
+        ctx->err = "instance update: node " + std::to_string(ids[k]) + " in bih " + std::to_string(U[(size_t)k]->bih) + ": bih: infinite bounding box";
+        return GLOME_E_SCENE;
+      }
     }
-  }
-  if (n == 0) return 0;
-  HIPCHK(ctx, hipSetDevice(ctx->device));
-  if (int rc = quiesce(ctx)) return rc;
-  Staging stg{ctx, {}};
-  double* dx = stg.in<double>(xfms, 24 * (size_t)n);
-  if (!dx) { ctx->err = "staging allocation failed"; return GLOME_E_HIP; }
-  return run_blocking(ctx, gpu_ms, [&] { return glome_scene_instance_update_dev(s, ids, dx, n); });
+    return 0;
+  };
+  return blocking_update(s, gpu_ms, [&] { return instance_update_check(s, ids, xfms, n, U); }, validate, [&](StageIn& in) {
+    double* dx = in(xfms, 24 * (size_t)n);
+    return [=] { return glome_scene_instance_update_dev(s, ids, dx, n); };
+  }, n == 0);
 }
 
 // ---- the bihs above an updated object, refitted one tree per call (item_bih_update_kernels.hpp) ----
 static const NestedAnswer* nested_answer_of(const glome_scene* s, int32_t node) {
   { auto it = s->meshes.find(node); if (it != s->meshes.end()) return &it->second.info.nested; }
-  { auto it = s->bihs.find(node); if (it != s->bihs.end()) return &it->second.info.nested; }
-  { auto it = s->sph_bihs.find(node); if (it != s->sph_bihs.end()) return &it->second.info.nested; }
+  { auto it = s->leaf_bihs.find(node); if (it != s->leaf_bihs.end()) return &it->second.info.nested; }
   { auto it = s->insts.find(node); if (it != s->insts.end()) return &it->second.nested; }
   { auto it = s->ibihs.find(node); if (it != s->ibihs.end()) return &it->second.info.nested; }
   return nullptr;

@@ -53,7 +53,7 @@ struct SphSplit32 {
 
 template <class Src> struct DItemsArgs {
   Src src;               // per item: cx cy cz r
-  const uint32_t* rows;  // per record: its item (SphereBihUpdateInfo)
+  const uint32_t* rows;  // per record: its item (LeafBihUpdateInfo, one word a row)
   float4* spheres;       // the tree's first record
   float4* ws;            // two per record: the sphere's plane-form box (lo, -) (hi, -), where bihupd::child_box reads it
   uint32_t n;            // records
@@ -84,7 +84,7 @@ template <class Src> __global__ void __launch_bounds__(64) k_sph_items(DItemsArg
 }
 
 // part[2 b ..]: block b's box over items b * 256 + lane, (b + gridDim.x) * 256 + lane, ..., real infinities where it saw none.  The wave
-// folds in registers, the block's four waves through LDS, as k_points_bound does; at most upd::kBoundMaxBlocks blocks.
+// folds in registers, the block's four waves through LDS (upd::block_fold32, as k_points_bound does); at most upd::kBoundMaxBlocks blocks.
 template <class Src> __global__ void __launch_bounds__(upd::kBoundBlock) k_sph_bound(Src src, uint32_t n, float4* part) {
   __shared__ float sh[upd::kBoundBlock / 64][6];
   const float inf = __builtin_huge_valf();
@@ -95,13 +95,8 @@ template <class Src> __global__ void __launch_bounds__(upd::kBoundBlock) k_sph_b
     sphere_box(s, dlo, dhi);
     for (int a = 0; a < 3; a++) { lo[a] = fminf(lo[a], round_down(dlo[a])); hi[a] = fmaxf(hi[a], round_up(dhi[a])); }
   }
-  upd::wave_fold(lo, hi);
-  if ((threadIdx.x & 63) == 0) for (int a = 0; a < 3; a++) { sh[threadIdx.x >> 6][a] = lo[a]; sh[threadIdx.x >> 6][3 + a] = hi[a]; }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    for (int w = 1; w < upd::kBoundBlock / 64; w++) for (int a = 0; a < 3; a++) { lo[a] = fminf(lo[a], sh[w][a]); hi[a] = fmaxf(hi[a], sh[w][3 + a]); }
-    upd::store_rows(part + 2 * (size_t)blockIdx.x, lo, hi);
-  }
+  upd::block_fold32(lo, hi, sh);
+  if (threadIdx.x == 0) upd::store_rows(part + 2 * (size_t)blockIdx.x, lo, hi);
 }
 
 // part[6 b ..]: block b's fp64 box min(c - r) / max(c + r) over its share of the items; at most itemupd::kPartMaxBlocks blocks

@@ -10,6 +10,7 @@
 //   for_lanes        the grid-stride loop over 64-element items, one lane per element
 //   DensePts / IndexedPts   where an update reads its points: a point source yields point k as three doubles, whatever the caller holds
 //   fold_rows        stored boxes -- float4 row pairs (lo, -) (hi, -) -- folded into lo / hi
+//   block_fold32     a block's boxes folded into lane 0: the shared tail of k_points_bound and sphupd::k_sph_bound
 //   k_points_bound   the box over ALL points of an array (Mesh.hs:55), per block, and the check that every coordinate is finite
 //   k_bound_store    folds the blocks' boxes, from a start value, into a header's two box words
 // No kernel waits for another wave: the order between the launches is the stream's.
@@ -105,6 +106,17 @@ __device__ __forceinline__ void store_rows(float4* rows, const float lo[3], cons
   rows[1] = make_float4(hi[0], hi[1], hi[2], w1);
 }
 
+// The fold of a block of kBoundBlock lanes into lane 0 (valid there alone): across each wave in registers, across the waves through LDS
+// (item_bih_update_kernels.hpp block_fold is its fp64 twin).
+constexpr int kBoundBlock = 256, kBoundMaxBlocks = 1024;
+__device__ __forceinline__ void block_fold32(float lo[3], float hi[3], float (*sh)[6]) {
+  wave_fold(lo, hi);
+  if ((threadIdx.x & 63) == 0) for (int a = 0; a < 3; a++) { sh[threadIdx.x >> 6][a] = lo[a]; sh[threadIdx.x >> 6][3 + a] = hi[a]; }
+  __syncthreads();
+  if (threadIdx.x == 0)
+    for (int w = 1; w < kBoundBlock / 64; w++) for (int a = 0; a < 3; a++) { lo[a] = fminf(lo[a], sh[w][a]); hi[a] = fmaxf(hi[a], sh[w][3 + a]); }
+}
+
 template <class Src> struct DBoundArgs {
   Src src;               // the points
   uint32_t nv;           // how many
@@ -117,7 +129,6 @@ template <class Src> struct DBoundArgs {
 // lanes strides over the points, folds across each wave in registers and across its four waves through LDS, and stores one partial box;
 // k_bound_store folds the partial boxes.  A lane that meets a coordinate that is not finite ORs kErrBadVertex into the slot's error word
 // (glome_ctx_synchronize reports it).
-constexpr int kBoundBlock = 256, kBoundMaxBlocks = 1024;
 template <class Src> __global__ void __launch_bounds__(kBoundBlock) k_points_bound(DBoundArgs<Src> A) {
   __shared__ float sh[kBoundBlock / 64][6];
   const float inf = __builtin_huge_valf();
@@ -130,13 +141,8 @@ template <class Src> __global__ void __launch_bounds__(kBoundBlock) k_points_bou
     box_add(p, lo, hi);
   }
   if (bad) atomicOr(A.error, kErrBadVertex);
-  wave_fold(lo, hi);
-  if ((threadIdx.x & 63) == 0) for (int a = 0; a < 3; a++) { sh[threadIdx.x >> 6][a] = lo[a]; sh[threadIdx.x >> 6][3 + a] = hi[a]; }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    for (int w = 1; w < kBoundBlock / 64; w++) for (int a = 0; a < 3; a++) { lo[a] = fminf(lo[a], sh[w][a]); hi[a] = fmaxf(hi[a], sh[w][3 + a]); }
-    store_rows(A.part + 2 * (size_t)blockIdx.x, lo, hi);
-  }
+  block_fold32(lo, hi, sh);
+  if (threadIdx.x == 0) store_rows(A.part + 2 * (size_t)blockIdx.x, lo, hi);
 }
 // One wave: the partial boxes, folded from (start, -start), into a header's two box words; .w (the root reference; the unused word or the
 // class) keeps its bits.  Where the fold starts shows in a tree of no items or of coordinates beyond 1e6.  A mesh's box is

@@ -13,13 +13,15 @@ import pytest
 import bihs_refit as BR
 import meshes_refit as MR
 import parity
+import update_answers as UA
 from helpers import product_camera_lights, random_rays
 from glome_amd import _lib as L
 from glome_amd import api
+from update_answers import assert_same, frames
 
 pytestmark = pytest.mark.gpu
 
-W, H = 131, 66
+W, H = UA.SIZE
 
 
 def build(name, which="V0", wrap="tex"):
@@ -35,38 +37,12 @@ def make(ctx, name, which="V0", wrap="tex"):
     return b, ctx.commit(b, root), tree, cam, lights
 
 
-def frames(sc, cam, lights):
-    out = {}
-    for mode in (0, 1):
-        img, packed, _ = sc.render(cam, lights, api.render_params(width=W, height=H, mode=mode, maxdepth=2))
-        out[f"frame{mode}"], out[f"packed{mode}"] = img, packed
-    return out
-
-
 def answers(sc, cam, lights, which, hits_only_normals=False):
-    """everything a scene answers: the three per-ray seams, a frame in both render modes, the trace seam's rows
-    (hits_only_normals: the normal of a miss zeroed -- the Bound case, see the top of the file)"""
+    """update_answers.answers on the pose's rays (hits_only_normals: the Bound case, see the top of the file)"""
     k = MR.V2_SCALE if which == "V2" else 1.0
     shift = MR.V2_SHIFT if which == "V2" else np.zeros(3)
-    ro, rd = random_rays(4000, 23, center=tuple(np.array((0, 1.5, 0)) * k + shift), radius=13 * k, spread=7 * k)
-    out = frames(sc, cam, lights)
-    hit = sc.rayint(ro, rd)
-    out.update({"t": hit["t"], "prim": hit["prim"], "n": hit["n"], "tex8": hit["tex"]})
-    out["shadow"] = sc.shadow(ro, rd, np.random.default_rng(24).uniform(1, 30 * k, size=len(ro)).astype(np.float32))
-    out["inside"] = sc.inside((np.random.default_rng(25).uniform(-7, 7, size=(4000, 3)) * k + shift).astype(np.float32))
-    tr = sc.trace(ro, rd, lights, params=api.trace_params(maxdepth=2), want_hit=True)
-    out.update({"trace_" + key: tr[key] for key in ("rgba", "depth", "t", "prim", "n", "tex")})
-    if hits_only_normals:
-        out["n"] = np.where(hit["t"][:, None] >= 0, hit["n"], 0)
-        out["trace_n"] = np.where(np.asarray(tr["t"]).reshape(-1, 1) >= 0, np.asarray(tr["n"]).reshape(len(ro), -1), 0)
-    return out
-
-
-def assert_same(a, b, what):
-    assert a.keys() == b.keys()
-    for key in a:
-        x, y = np.asarray(a[key]), np.asarray(b[key])
-        assert x.shape == y.shape and np.array_equal(x, y, equal_nan=x.dtype.kind == "f"), f"{what}: {key} differs in {int(np.sum(x != y))} of {x.size} values"
+    rays = random_rays(4000, 23, center=tuple(np.array((0, 1.5, 0)) * k + shift), radius=13 * k, spread=7 * k)
+    return UA.answers(sc, cam, lights, rays, k, shift, hits_only_normals)
 
 
 CASES = [(n, "tex", w) for n in ("three", "mixed", "s3_20", "wide") for w in ("V1", "V2")] + [("mixed", wrap, "V1") for wrap in ("root", "instances", "bound")]

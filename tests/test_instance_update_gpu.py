@@ -12,9 +12,11 @@ import pytest
 import bihs_refit as BR
 import instances_refit as IR
 import parity
+import update_answers as UA
 from helpers import product_camera_lights, random_rays
 from glome_amd import _lib as L
 from glome_amd import api, scenes
+from update_answers import assert_same
 
 pytestmark = pytest.mark.gpu
 
@@ -23,11 +25,7 @@ N_RAYS = 3000
 
 
 def frames(sc, cam, lights):
-    out = {}
-    for mode in (0, 1):
-        img, packed, _ = sc.render(cam, lights, api.render_params(width=W, height=H, mode=mode, maxdepth=2))
-        out[f"frame{mode}"], out[f"packed{mode}"] = img, packed
-    return out
+    return UA.frames(sc, cam, lights, (W, H))
 
 
 def answers(sc, cam, lights, center=(0.0, 2.0, 0.0)):
@@ -40,13 +38,6 @@ def answers(sc, cam, lights, center=(0.0, 2.0, 0.0)):
     pts = np.random.default_rng(25).uniform(-5, 5, size=(N_RAYS, 3)) + np.asarray(center)
     out["inside"] = sc.inside(pts.astype(np.float32))
     return out
-
-
-def assert_same(a, b, what):
-    assert a.keys() == b.keys()
-    for key in a:
-        x, y = np.asarray(a[key]), np.asarray(b[key])
-        assert x.shape == y.shape and np.array_equal(x, y, equal_nan=x.dtype.kind == "f"), f"{what}: {key} differs in {int(np.sum(x != y))} of {x.size} values"
 
 
 def get(name):

@@ -10,16 +10,21 @@ import pytest
 import instances_refit as IR
 import nested_refit as NR
 import parity
+import update_answers as UA
 from helpers import product_camera_lights, random_rays
 from glome_amd import _lib as L
 from glome_amd import api, scenes
-from test_instance_update_gpu import assert_same, frames
+from update_answers import assert_same
 
 pytestmark = pytest.mark.gpu
 
 W, H = 64, 48
 N_RAYS = 3000
 CENTER = {"oak_in_scene": (0.3, 2.2, -0.5)}
+
+
+def frames(sc, cam, lights):
+    return UA.frames(sc, cam, lights, (W, H))
 
 
 def answers(sc, cam, lights, center):

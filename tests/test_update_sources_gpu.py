@@ -19,10 +19,10 @@ import update_sources as US
 from helpers import product_camera_lights
 from glome_amd import _lib as L
 from glome_amd import api
+from update_answers import assert_same
 
 pytestmark = pytest.mark.gpu
 
-assert_same = TB.assert_same
 _reference = {}
 
 

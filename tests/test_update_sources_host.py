@@ -86,3 +86,28 @@ def test_the_indexed_builder_call_refuses_and_leaves_the_tree_untouched(built):
     assert_described_alike(described(b, tree), before, "null arrays")
     b.bih_set_triangles_indexed(tree, verts, idx)  # and the valid call still works
     assert described(b, tree)[0] != before[0]
+
+
+class NotOnTheGpu:
+    """what the device forms' check reads of a torch tensor: here one of fp64 in host memory, nine values"""
+    is_cuda, dtype = False, "torch.float64"
+
+    def data_ptr(self):
+        return 0
+
+    def is_contiguous(self):
+        return True
+
+    def numel(self):
+        return 9
+
+
+def test_the_fp64_device_forms_refuse_a_tensor_in_the_words_they_always_had(built):
+    """the three messages as the methods spelled them before they shared _dev_arg; the check comes before the library is called"""
+    sc, t = api.Scene(type("NoContext", (), {"lib": L.load()})(), None), NotOnTheGpu()
+    for call, msg in [(lambda: sc.mesh_update(1, t), "mesh_update: verts must be a contiguous CUDA torch.float64 tensor of 3 values per row"),
+                      (lambda: sc.bih_update(1, t), "bih_update: pts9 must be a contiguous CUDA torch.float64 tensor of 9 values per row"),
+                      (lambda: sc.sphere_bih_update(1, t), "sphere_bih_update: c3r must be a contiguous CUDA torch.float64 tensor of 4 values per row")]:
+        with pytest.raises(api.GlomeError) as e:
+            call()
+        assert str(e.value) == msg
