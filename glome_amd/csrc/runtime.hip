@@ -851,7 +851,9 @@ static int render_impl(glome_scene* s, const glome_camera* cam, const glome_ligh
     const bool pooled = launch_events(ctx, ev_start, ev_stop), timed = stats || pooled;
     if (timed) HIPCHK(ctx, hipEventRecord(ev_start, ctx->stream));
     if (ch.two_rows) {
-      // one block per chunk of the launch's item order (padding chunks of the last round of heads hold nothing and are not visited)
+      // one block per chunk of the launch's item order (padding chunks of the last round of heads hold nothing and are not visited);
+      // a chunk lies in one frame, which the block reads once (cull_kernels.hpp chunk_position)
+      if (nframes > 1 && !A.chunks_per_frame) { ctx->err = "a flagship launch of several frames is interleaved by chunks"; return GLOME_E_INVALID; }
       const uint32_t nchunks = A.chunks_per_frame ? A.chunks_per_frame * (uint32_t)nframes : (items + kQueueChunk - 1) / kQueueChunk;
       glome_ctx::Slot& sl = ctx->slot();
       hipLaunchKernelGGL(k_cull_items, dim3(nchunks), dim3(kCullThreads), 0, ctx->stream, A, sl.d_list, sl.d_list + sl.list_items, nchunks);

@@ -4,7 +4,7 @@ misses the scene's root box -- an all-sky frame, whose items walk nothing: its t
 item -> pixel, pixel -> ray, the root box test, the stores).
 
   python tools/probe/item_overhead.py                       ms per frame and launch time per item, both kinds
-  KIND=sky|scene python tools/probe/item_overhead.py        one kind only: the workload for a counter pass, e.g.
+  KIND=sky|scene|down python tools/probe/item_overhead.py   one kind only (down: from straight above, every item live): the workload for a counter pass, e.g.
       PMC_SCRIPT=tools/probe/item_overhead.py KIND=sky tools/pmc_pass.sh OUT "SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_SMEM SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR SQ_INSTS_LDS SQ_INSTS_BRANCH"
   python tools/probe/item_overhead.py --pmc OUT/pass1       instructions per item by kind from that pass's counter_collection.csv
   python tools/probe/item_overhead.py --pmc OUT/pass1 --live N     the same per LIVE item: N = live_items_per_launch of a KIND=scene run (what the
@@ -89,10 +89,12 @@ def main():
     pos = sd.cam[0]
     cams = {"scene": api.camera(*sd.cam),
             # straight up from above everything: a ray's y component is fwd's 1 whatever the pixel, and the heightfield ends at y = 1.6
-            "sky": api.camera_from_vectors((pos[0], max(float(pos[1]), 3.0), pos[2]), (0, 1, 0), (0, 0, 1), (1, 0, 0))}
+            "sky": api.camera_from_vectors((pos[0], max(float(pos[1]), 3.0), pos[2]), (0, 1, 0), (0, 0, 1), (1, 0, 0)),
+            # cull_cost.py's view from straight above (KIND=down only): every item live, the cull pass's probe proves them all
+            "down": api.camera_from_vectors((0.0, 4.5, 0.0), (0, -1, 0), (0, 0, -1), (1, 0, 0))}
     buf = torch.zeros((GROUP, H, W), dtype=torch.int32, device=torch.device("cuda:0"))
     reps = int(os.environ.get("REPS", "20"))
-    kinds = [k for k in ("scene", "sky") if os.environ.get("KIND", "both") in (k, "both")]
+    kinds = [k for k in ("scene", "sky") if os.environ.get("KIND", "both") in (k, "both")] + (["down"] if os.environ.get("KIND") == "down" else [])
     for kind in kinds:
         ca = (L.Camera * GROUP)(*([cams[kind]] * GROUP))
         for i in range(reps + 3):
