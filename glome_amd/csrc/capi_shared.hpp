@@ -24,6 +24,11 @@ inline CommitRules commit_rules(const glome::Graph& G, const glome::FlatScene& F
   glome::SceneTraits& t = R.traits;
   t.tier = (int)F.tier; t.cls_mask = R.caps.cls_mask; t.stack_cap = R.caps.stack_cap; t.pk_all = F.pk_all;
   t.n_bih_nodes = (int64_t)F.bihnodes.size(); t.n_mesh_nodes = (int64_t)F.meshnodes.size() / 4;
+  // The flagship render instance and its cull pass take a root entry from the walk-entry table (rt_types.h DScene::walk) and walk it as a triangle
+  // bih without looking at its record's kind.  scene_caps gives a void record no class bit, so the class CLS_BIH_TRI alone does not
+  // rule one out: an entry of any other kind than a bih keeps the scene off the two-row kernels here (use_two_rows asks for pk_all).
+  if (F.tier == 0 && glome::scene_class(t.cls_mask) == glome::CLS_BIH_TRI)
+    for (const glome::U4& e : F.entries) if ((F.recs[e.x].x & glome::RF_KINDMASK) != glome::R_BIH) t.pk_all = false;
   for (const glome::Mat& m : G.mats) {
     if (m.kind == glome::MAT_REFLECT || m.kind == glome::MAT_REFRACT || m.kind == glome::MAT_WARP) t.has_secondary_mats = true;
     if (m.kind == glome::MAT_REFRACT) t.has_refract = true;

@@ -71,13 +71,11 @@ __device__ __forceinline__ DItem ld_item(const DItem* p, uint32_t i) {
 __device__ __forceinline__ bool lane_enters(const DScene& S, const Ray& r, bool valid) {
   bool in = false;
   for (uint32_t e = 0; e < S.n_entries; e++) {
-    U4 ent = ldu4(S.entries, e);
-    ent.x = uni(ent.x); ent.z = uni(ent.z);
-    if (ent.z & RF_NOVIS) continue;
-    U4 rec = ldu4(S.recs, ent.x);
-    rec.x = uni(rec.x); rec.y = uni(rec.y);
-    if ((rec.x & RF_KINDMASK) != R_BIH) return true;  // (no such entry in a scene of class CLS_BIH_TRI; live is always right)
-    const F4 h0 = ld4u(S.bihhdr, 3 * rec.y), h1 = ld4u(S.bihhdr, 3 * rec.y + 1);
+    // the entry as the launch's walk reads it: the same record of the walk-entry table, the same words of it (closest_flat, TABLE) -- an
+    // entry of a flagship launch's scene is a triangle bih (commit_rules)
+    const U4 w = ld_walk_u(S.walk, e);
+    if (w.x & RF_NOVIS) continue;
+    const F4 h0 = ld4u(S.bihhdr, 3 * w.y), h1 = ld4u(S.bihhdr, 3 * w.y + 1);
     if (uni(as_u(h0.w)) & BREF_LEAF) return true;     // a root that is a single leaf is tested regardless of its interval (Bih.hs:339)
     float nearv, farv;
     bih_root_interval(r, h0, h1, kInf, nearv, farv);

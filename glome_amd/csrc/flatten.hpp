@@ -117,6 +117,7 @@ struct FlatScene {
   std::vector<U4> recs;
   std::vector<F4> spheres, tris, trinorms, boxes, planes, discs, quadrics, xfms, bihhdr, bihnodes, meshhdr, meshnodes, mtris, mats, wlights;
   std::vector<U4> mtrimeta, entries;
+  std::vector<U4> walk;  // the walk-entry table: one record per entry of `entries` (emit_walk; rt_types.h DScene::walk)
   std::vector<uint32_t> matkids;
   std::vector<float> tripairs;  // the pair records of the triangle BIHs' leaves (emit_pairs; bih_packet_asm.hpp)
   std::vector<F4> pknodes;      // the packet walk's copy of the triangle BIHs' branch nodes: same slots as bihnodes, child references in its own form
@@ -127,7 +128,7 @@ struct FlatScene {
   uint32_t tex_bits = 16;   // bits per id of a TexStack (rt_types.h): 8 when the scene has at most 254 materials
   int64_t n_other_prims = 0;
   std::string why_generic;  // why the flat tier was not chosen
-  bool pk_all = true;       // every triangle BIH has the packet walk's node form (emit_bih)
+  bool pk_all = true;       // every triangle BIH has the packet walk's node form (emit_bih); the trait of the same name asks for more (capi_shared.hpp commit_rules)
   std::vector<MeshUpdateInfo> mesh_updates;  // one per emitted mesh (emit_mesh), in emission order
   std::vector<LeafBihUpdateInfo> leaf_bih_updates;  // one per emitted triangle or sphere bih (emit_bih), in emission order
   std::vector<InstanceUpdateInfo> inst_updates;  // one per emitted Instance node (emit), in emission order
@@ -177,6 +178,7 @@ class Flattener {
     mark_updatable(root);
     mark_nested(root);
     pad();
+    emit_walk();
   }
 
  private:
@@ -204,6 +206,17 @@ class Flattener {
       F.tripairs.insert(F.tripairs.end(), r, r + kPairWords);
     }
     return at * 4u;  // byte offset of the leaf's first record
+  }
+
+  // The walk-entry table (rt_types.h DScene::walk): per entry the words the entry loops read from `entries` and `recs` before a walk
+  // starts.  Every scene gets one, the padding entry of a scene without a root program included; only the flagship render instance and its
+  // cull pass read it.  After pad(): one record per entry as the device sees them.
+  void emit_walk() {
+    F.walk.clear();
+    for (const U4& e : F.entries) {
+      const U4& r = F.recs[e.x];
+      F.walk.push_back(U4{e.z, r.y, e.y, r.x});
+    }
   }
 
   void pad() {  // never hand a null pool to a kernel

@@ -75,7 +75,8 @@ struct SceneTraits {
   int cls_mask = CLS_ALL;  // which entry classes the flat root program contains
   bool has_secondary_mats = false, has_nested_mats = false;
   bool has_refract = false;  // a Refract material: its transmitted rays are not unit length (Shader.hs:141) -- see exact_traversal
-  bool pk_all = false;       // every triangle BIH of the scene has the hand-written walk's node form (flatten.hpp emit_bih)
+  bool pk_all = false;       // the hand-written walk can take every root entry it would be given: every triangle BIH of the scene has its
+                             // node form (flatten.hpp emit_bih) and, in a scene of class CLS_BIH_TRI, every root entry is a bih (commit_rules)
   int stack_cap = 8;         // stack entries per lane in LDS
   int64_t n_bih_nodes = 0, n_mesh_nodes = 0;
 };

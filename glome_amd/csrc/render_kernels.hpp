@@ -28,7 +28,7 @@
 // FAITHFUL = the reference's exact node-visit order (no ordered early-out, Bih.hs:332-368); COUNT = node / primitive
 // work counters.  They back the `faithful` / `count_work` render params (byte-model measurement, parity tests).
 // The production variant traverses with early-out and counts rays only.
-template <bool FAITHFUL, bool COUNT_, bool FULL_, int CLS = CLS_ALL, bool SURFACE_ONLY_ = false>
+template <bool FAITHFUL, bool COUNT_, bool FULL_, int CLS = CLS_ALL, bool SURFACE_ONLY_ = false, bool TABLE_ = false>
 struct FlatTier {
   static constexpr bool FULL = FULL_;  // false: lean kernel (no secondary rays, no Blend / Layers)
   // every material of the scene is a Surface: the two-row kernels, whose admission rule (instances.hpp use_two_rows over capi_shared.hpp
@@ -36,6 +36,13 @@ struct FlatTier {
   // trace_primary, postshade_lean)
   static constexpr bool SURFACE_ONLY = SURFACE_ONLY_;
   static_assert(!SURFACE_ONLY_ || !FULL_, "a full kernel shades every material kind");
+  // ... and every root entry is a triangle bih (commit_rules), so the wave-wide entry loops of such a kernel may read the walk-entry table
+  // (rt_device.hpp closest_flat, TABLE).  The flagship render instance does, as does the cull pass in front of it (cull_kernels.hpp
+  // lane_enters).  The two-row samplers do not: they spill already, the table's reads moved their spills, and the five-wave instance lost
+  // 4.8 % on the million-triangle scene (0.968 -> 1.015 ms per frame) where the four-wave one gained nothing.
+  static constexpr bool TABLE = TABLE_;
+  static_assert(!TABLE_ || SURFACE_ONLY_, "the walk-entry table serves kernels whose every root entry is a triangle bih");
+  static_assert(!SURFACE_ONLY_ || CLS == CLS_BIH_TRI, "the two-row kernels are instances of the triangle class");
   static constexpr bool COUNT = COUNT_;  // (rt_device.hpp tier_counts: a counting tier counts every ray per lane and keeps the primary ray's snapshot)
   static constexpr bool WARP = false;  // scenes with a Warp material (traces over other roots, Shader.hs:157-175) render on the generic tier
   const DScene& S;
@@ -60,14 +67,14 @@ struct FlatTier {
   __device__ __forceinline__ HitG closest_wave(const Ray& r, float tmax, bool valid, uint32_t = 0) {
     if constexpr (PACKETS) {
       HitG ch;
-      Cand c = closest_flat<FAITHFUL, COUNT, CLS, true>(S, r, tmax, stk, cnt, valid, &ch, &err);
+      Cand c = closest_flat<FAITHFUL, COUNT, CLS, true, TABLE>(S, r, tmax, stk, cnt, valid, &ch, &err);
       return valid ? finalize_flat<CLS>(S, r, c, &ch) : hit_miss();
     } else {
       return valid ? closest(r, tmax) : hit_miss();
     }
   }
   __device__ __forceinline__ bool occluded_wave(const Ray& r, float d, bool valid) {
-    if constexpr (PACKETS) return occluded_flat<COUNT, CLS, true>(S, r, d, stk, cnt, valid, &err);
+    if constexpr (PACKETS) return occluded_flat<COUNT, CLS, true, TABLE>(S, r, d, stk, cnt, valid, &err);
     else return valid && occluded(r, d);
   }
 };
@@ -322,7 +329,7 @@ __device__ __forceinline__ void render_loop(const DRenderArgs& A_, TIER& Tk) {
 template <bool FAITHFUL, bool COUNT, bool FULL, int CLS, int LB = 1, bool TWO_ROWS = false>
 __global__ void __launch_bounds__(64, LB) k_render_flat(DRenderArgs A, int stack_cap, uint32_t* ovf, int ovf_cap) {
   extern __shared__ uint32_t lds[];
-  FlatTier<FAITHFUL, COUNT, FULL, CLS, TWO_ROWS> T{A.S, A.lights, A.nlights, lane_stack<TWO_ROWS>(lds, stack_cap, ovf, ovf_cap), Cnt()};
+  FlatTier<FAITHFUL, COUNT, FULL, CLS, TWO_ROWS, TWO_ROWS> T{A.S, A.lights, A.nlights, lane_stack<TWO_ROWS>(lds, stack_cap, ovf, ovf_cap), Cnt()};
   render_loop<TWO_ROWS, TWO_ROWS>(A, T);
   if (A.want_counters) flush_counters(A.counters, T.cnt, T.err);
   else if ((CLS & (CLS_CSG | CLS_MESH)) && __builtin_amdgcn_ballot_w64(T.err != 0) && (threadIdx.x & 63) == 0) atomicOr(&A.counters->error, 1u);

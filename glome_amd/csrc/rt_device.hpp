@@ -120,6 +120,11 @@ GD uint32_t ld_word_u(const uint32_t* p, uint32_t i) {  // one word at a wave-un
   const char __attribute__((address_space(4)))* b = (const char __attribute__((address_space(4)))*)(uintptr_t)p;
   return *(const uint32_t __attribute__((address_space(4)))*)(b + (uint32_t)(uni(i) << 2));
 }
+GD U4 ld_walk_u(const U4* p, uint32_t e) {  // record e of the walk-entry table (DScene::walk; commit writes it, no launch and no update does)
+  const char __attribute__((address_space(4)))* b = (const char __attribute__((address_space(4)))*)(uintptr_t)p;
+  u32x4 v = *(const u32x4 __attribute__((address_space(4)))*)(b + (uint32_t)(uni(e) << 4));
+  U4 r; r.x = v.x; r.y = v.y; r.z = v.z; r.w = v.w; return r;
+}
 typedef float f32x4_a4 __attribute__((ext_vector_type(4), aligned(4)));  // (the cameras sit at 4-byte aligned offsets of the argument segment; s_load_dwordx4 needs no more)
 GD DCamera ld_camera_u(const void __attribute__((address_space(4)))* base, uint32_t byte_off) {  // both wave-uniform
   const f32x4_a4 __attribute__((address_space(4)))* q = (const f32x4_a4 __attribute__((address_space(4)))*)((const char __attribute__((address_space(4)))*)base + byte_off);
@@ -129,6 +134,8 @@ GD DCamera ld_camera_u(const void __attribute__((address_space(4)))* base, uint3
   r.up[0] = b.z; r.up[1] = b.w; r.up[2] = c.x; r.right[0] = c.y; r.right[1] = c.z; r.right[2] = c.w;
   return r;
 }
+#else
+GD U4 ld_walk_u(const U4* p, uint32_t e) { return p[e]; }  // (the host build: no instance of it reads the table, the name has to exist)
 #endif
 
 // texture stacks: ids of B = DScene::tex_bits bits, innermost first, id+1 (rt_types.h)
@@ -1433,15 +1440,29 @@ constexpr uint32_t CAND_CSG = 0x40000000u;  // aux flag: the candidate is a CSG 
 // walked as one packet (bih_tri_wave), everything else per lane as before.
 // CSGH: where the full hit of a CSG item goes (its normal, position and textures come out of the evaluation and cannot be
 // re-derived from a record like a primitive's); null in kernels without CLS_CSG.
-template <bool FAITHFUL, bool COUNT, int CLS, bool WAVE = false, class STK>
+// TABLE: the entry's flags and header index come from the walk-entry table (DScene::walk), one scalar load, and the entry IS a triangle
+// bih: the flagship render instance, whose admission rule (instances.hpp use_two_rows over capi_shared.hpp commit_rules) takes scenes of class
+// CLS_BIH_TRI whose every root entry is a bih -- so no look at the record's kind (the class word was dead under CLS == CLS_BIH_TRI
+// already).  `ent` and `rec` are filled in as the shared code below expects them; of the record's other two words nothing is read here
+// (ent.y serves the CSG class alone).  Every other instance reads `entries` and `recs` as before.
+template <bool FAITHFUL, bool COUNT, int CLS, bool WAVE = false, bool TABLE = false, class STK>
 GD Cand closest_flat(const DScene& S, const Ray& r, float d, STK& stk, Cnt& cnt, bool valid = true, HitG* csgh = nullptr, unsigned int* err = nullptr) {
+  static_assert(!TABLE || (WAVE && CLS == CLS_BIH_TRI), "the walk-entry table serves the wave-wide loops of the triangle class");
   Cand best; best.t = kInf; best.id = CAND_NONE; best.aux = 0;
   for (uint32_t e = 0; e < S.n_entries; e++) {
-    U4 ent = ldu4(S.entries, e);
-    if (WAVE) { ent.x = uni(ent.x); ent.z = uni(ent.z); }
-    if (ent.z & RF_NOVIS) continue;
-    U4 rec = ldu4(S.recs, ent.x);
-    if (WAVE) { rec.x = uni(rec.x); rec.y = uni(rec.y); }
+    U4 ent, rec;
+    if constexpr (TABLE) {
+      const U4 w = ld_walk_u(S.walk, e);
+      if (w.x & RF_NOVIS) continue;
+      ent.x = 0; ent.y = w.z; ent.z = w.x; ent.w = 0;
+      rec.x = R_BIH; rec.y = w.y; rec.z = 0; rec.w = 0;
+    } else {
+      ent = ldu4(S.entries, e);
+      if (WAVE) { ent.x = uni(ent.x); ent.z = uni(ent.z); }
+      if (ent.z & RF_NOVIS) continue;
+      rec = ldu4(S.recs, ent.x);
+      if (WAVE) { rec.x = uni(rec.x); rec.y = uni(rec.y); }
+    }
     uint32_t kind = rec.x & RF_KINDMASK;
     uint32_t cls = 0;
     if (kind == R_BIH) { cls = as_u(ld4(S.bihhdr, 3 * rec.y + 1).w); if (WAVE) cls = uni(cls); }
@@ -1550,15 +1571,24 @@ GD HitG finalize_flat(const DScene& S, const Ray& r, const Cand& c, const HitG* 
 }
 
 // shadow over the flat root program: `foldl' (||) False (map shadow xs)` (Solid.hs:330); Mesh casts none (Mesh.hs:210)
-template <bool COUNT, int CLS, bool WAVE = false, class STK>
+template <bool COUNT, int CLS, bool WAVE = false, bool TABLE = false, class STK>  // (TABLE: see closest_flat)
 GD bool occluded_flat(const DScene& S, const Ray& r, float d, STK& stk, Cnt& cnt, bool valid = true, unsigned int* err = nullptr) {
+  static_assert(!TABLE || (WAVE && CLS == CLS_BIH_TRI), "the walk-entry table serves the wave-wide loops of the triangle class");
   bool result = false;  // WAVE: an occluded lane stays in the entry loop without a ray until the wave is through
   for (uint32_t e = 0; e < S.n_entries; e++) {
-    U4 ent = ldu4(S.entries, e);
-    if (WAVE) { ent.x = uni(ent.x); ent.z = uni(ent.z); }
-    if (ent.z & RF_NOSHADOW) continue;
-    U4 rec = ldu4(S.recs, ent.x);
-    if (WAVE) { rec.x = uni(rec.x); rec.y = uni(rec.y); }
+    U4 ent, rec;
+    if constexpr (TABLE) {
+      const U4 w = ld_walk_u(S.walk, e);
+      if (w.x & RF_NOSHADOW) continue;
+      ent.x = 0; ent.y = w.z; ent.z = w.x; ent.w = 0;
+      rec.x = R_BIH; rec.y = w.y; rec.z = 0; rec.w = 0;
+    } else {
+      ent = ldu4(S.entries, e);
+      if (WAVE) { ent.x = uni(ent.x); ent.z = uni(ent.z); }
+      if (ent.z & RF_NOSHADOW) continue;
+      rec = ldu4(S.recs, ent.x);
+      if (WAVE) { rec.x = uni(rec.x); rec.y = uni(rec.y); }
+    }
     uint32_t kind = rec.x & RF_KINDMASK;
     uint32_t cls = 0;
     if (kind == R_BIH) { cls = as_u(ld4(S.bihhdr, 3 * rec.y + 1).w); if (WAVE) cls = uni(cls); }

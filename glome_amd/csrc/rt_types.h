@@ -130,6 +130,25 @@ struct DScene {
   uint32_t tex_bits;  // 8 or 16: bits per id of a TexStack in this scene
   uint32_t pk_generic_cap;  // generic tier: entries of the per-wave LDS stack its kernels carry for packet walks of sphere BIHs
                             // (rt_generic.hpp, the packet service of vm_run); 0 = the scene has none
+  // The walk-entry table: one record per root entry, in entry order, made by the flattener at commit (flatten.hpp emit_walk) for every
+  // scene -- what the entry loops take from entries[e] and recs[entries[e].x] before a walk starts, side by side, so that a wave has it
+  // with one scalar load where it made two dependent vector round trips:
+  //   x = entries[e].z   the RF_NOVIS / RF_NOSHADOW flags the loops test
+  //   y = recs[..].y     the index of the entry's BIH header (bihhdr[3 y ..]); whatever else the record of another kind keeps there
+  //   z = entries[e].y   the entry's tex prefix (one or two 16-bit ids)
+  //   w = recs[..].x     the record's kind | flags word
+  // The device reads x and y.  z and w complete the record and no kernel reads them today: a triangle-class kernel has no use for the
+  // prefix before shading (finalize_flat still takes it from `entries`, by the hit's entry index), and the kind is what the admission
+  // rule guarantees.
+  // No update call rewrites a word of `entries` or `recs`.  What the update and refit kernels store to: bihhdr rows 0 and 1 -- the box,
+  // with .w (root reference, leaf class) stored back as read (update_common.hpp k_bound_store) -- and never row 2; bihnodes and pknodes
+  // (bih_update_kernels.hpp, item_bih_update_kernels.hpp); tris, tripairs, spheres (bih_update_kernels.hpp,
+  // sphere_bih_update_kernels.hpp); mtris, trinorms, meshnodes, meshhdr (mesh_update_kernels.hpp); xfms (item_bih_update_kernels.hpp).
+  // So the box and the root reference stay in bihhdr, where the walks go on reading them.
+  // Read by the flagship render instance (rt_device.hpp closest_flat / occluded_flat with TABLE; render_kernels.hpp FlatTier says why the
+  // two-row samplers are not among its readers) and its cull pass (cull_kernels.hpp) only.
+  const U4* walk;
+  uint64_t walk_pad;  // (the struct grows by a whole 16 bytes: what lies behind it in a launch's arguments keeps its alignment)
 };
 
 struct DCamera { float pos[3], fwd[3], up[3], right[3]; };

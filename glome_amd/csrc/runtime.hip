@@ -562,7 +562,7 @@ glome_scene* glome_scene_commit(glome_ctx* ctx, glome_sb* sb, int32_t root) {
   rc |= upload(s, F.bihhdr, &D.bihhdr); rc |= upload(s, F.bihnodes, &D.bihnodes); rc |= upload(s, F.pknodes, &D.pknodes); D.pknodes_bytes = (uint32_t)(F.pknodes.size() * sizeof(F4));
   rc |= upload(s, F.meshhdr, &D.meshhdr); rc |= upload(s, F.meshnodes, &D.meshnodes); rc |= upload(s, F.mtris, &D.mtris);
   rc |= upload(s, F.mtrimeta, &D.mtrimeta); rc |= upload(s, F.mats, &D.mats); rc |= upload(s, F.wlights, &D.wlights); rc |= upload(s, F.matkids, &D.matkids);
-  rc |= upload(s, F.entries, &D.entries);
+  rc |= upload(s, F.entries, &D.entries); rc |= upload(s, F.walk, &D.walk); D.walk_pad = 0;
   if (rc) { glome_scene_release(s); return nullptr; }
   D.n_entries = F.tier == 0 ? (uint32_t)F.entries.size() : 0;
   D.root_rec = F.root_rec; D.tier = F.tier; D.n_mats = (uint32_t)sb_graph(sb).mats.size(); D.tex_bits = F.tex_bits;

@@ -731,7 +731,8 @@ int64_t glome_items_layout(const glome_render_params*, int tile_first, int tile_
  * Returns n, or GLOME_E_INVALID for a null array or an unknown mode. */
 int64_t glome_kernel_choice(int64_t n, const int64_t* in14, int32_t* out4);
 /* Host-only: what a commit of `root` would derive for that choice.  out11: the first eight inputs above, then ovf_cap, pk_generic_cap
- * (without the debug switch of the environment) and n_mesh_nodes. */
+ * (without the debug switch of the environment) and n_mesh_nodes.  pk_all: every triangle bih of the scene has the hand-written walk's
+ * node form and, where triangle bihs are the scene's only entry class, every root entry is a bih. */
 int glome_sb_scene_traits(glome_sb*, int32_t root, int64_t* out11);
 /* The lean render loop's pixel-coordinate tables of a frame size (xc[width], yc[height]; made on the device, once per context), or with
  * direct != 0 the same values evaluated per pixel by the coordinate function itself. */

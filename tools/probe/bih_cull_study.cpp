@@ -37,6 +37,11 @@ struct Study {
   bool origin_clip = false;         // variant `origin`
   long pushes = 0;
   std::vector<int>* visited = nullptr;  // when set: every branch node entered is appended
+  // the per-packet events of item_breakdown.py: every non-empty leaf entered; per branch node entered, which children the ray goes into
+  // (1 = the near child, 2 = the far child); did the ray pass the root's entry test
+  std::vector<int>* leaves = nullptr;
+  std::vector<std::pair<int, int>>* went = nullptr;
+  bool entered = false;
   bool tri_hit(const Tri& t, D3 o, D3 d, double tmax, double& tt) const {
     D3 s1 = cross(d, t.e2);
     double div = dot(s1, t.e1);
@@ -78,6 +83,7 @@ struct Study {
       }
       nearv = tn; farv = std::min(dmax, tf);
       if (origin_clip) nearv = std::max(nearv, -(double)FLT_MIN);
+      entered = !(nearv > farv);
       if (nearv > farv) return -1;
     }
     struct E { int k; double n, f; };
@@ -90,6 +96,7 @@ struct Study {
       if (!(nearv > farv) && clip(k, o, rcp, nearv, farv)) {
         const BihTree::Node& n = T->nodes[k];
         if (n.leaf) {
+          if (leaves && !n.items.empty()) leaves->push_back(k);
           for (int it : n.items) {
             tests++;
             double tt;
@@ -108,6 +115,7 @@ struct Study {
           double t1 = fwd ? dl : dr, t2 = fwd ? dr : dl;
           bool e1 = T->nodes[c1].leaf && T->nodes[c1].items.empty(), e2 = T->nodes[c2].leaf && T->nodes[c2].items.empty();
           bool go1 = nearv < t1 && !e1, go2 = t2 < farv && !e2;
+          if (went) went->push_back({k, (go1 ? 1 : 0) | (go2 ? 2 : 0)});
           if (go1) {
             if (go2) { st.push_back({c2, std::max(t2, nearv), farv}); pushes++; }
             k = c1; farv = std::min(t1, farv); pop = false;
@@ -206,22 +214,47 @@ int main(int argc, char** argv) {
     const int BSTRIDE = argc > 3 ? atoi(argv[3]) : 3;
     std::vector<long> pu, su, ptot;
     std::vector<int> vis, all;
+    // events of the wave-wide walks per LIVE item (an item one of whose rays enters the root), for tools/probe/item_breakdown.py: a
+    // packet steps through the union of its rays' branch nodes, pushes where one ray goes near and one goes far (and pops what it
+    // pushed), and visits the union of its rays' leaves, testing a leaf of n triangles as ceil(n / 2) pairs
+    struct Ev { double items = 0, live = 0, walks = 0, steps = 0, pushes = 0, leaf_visits = 0, pair_tests = 0; } ev[2];  // [0] primary, [1] shadow
+    std::vector<int> lv;
+    std::vector<std::pair<int, int>> wv;
+    auto tally = [&](Ev& e) {
+      std::sort(lv.begin(), lv.end()); lv.erase(std::unique(lv.begin(), lv.end()), lv.end());
+      std::sort(wv.begin(), wv.end());
+      long steps = 0, pushes = 0;
+      for (size_t a = 0; a < wv.size();) {
+        size_t b = a; int m = 0;
+        for (; b < wv.size() && wv[b].first == wv[a].first; b++) m |= wv[b].second;
+        steps++; pushes += m == 3; a = b;
+      }
+      e.steps += steps; e.pushes += pushes; e.leaf_visits += (double)lv.size();
+      for (int k : lv) e.pair_tests += (double)((S.T->nodes[k].items.size() + 1) / 2);
+      if (steps || !lv.empty()) e.walks += 1;
+    };
     for (int by = 0; by + 8 <= H; by += 8 * BSTRIDE) for (int bx = 0; bx + 8 <= W; bx += 8 * BSTRIDE) {
       std::vector<D3> so, sdv; std::vector<double> sl;
       all.clear();
       long own_max = 0;
+      bool live = false;
+      lv.clear(); wv.clear(); S.leaves = &lv; S.went = &wv;
       for (int j = 0; j < 64; j++) {
         int px = bx + j % 8, py = by + j / 8;
         double xc = ((double(px) / W) * 2 - 1) * (double(W) / H), yc = -((double(py) / H) * 2 - 1);
         D3 d = normalize(fwd + right * (-xc) + up_ * yc);
         vis.clear(); S.visited = &vis;
         double t = S.walk(pos, d, 1e6, 1);
+        live = live || S.entered;
         all.insert(all.end(), vis.begin(), vis.end());
         if (t >= 0) { D3 p = pos + d * t; D3 lv = light - p; double ll = std::sqrt(dot(lv, lv)); so.push_back(p + D3{0, 1e-4, 0}); sdv.push_back(lv * (1.0 / ll)); sl.push_back(ll - 2e-4); }
       }
       std::sort(all.begin(), all.end()); all.erase(std::unique(all.begin(), all.end()), all.end());
       long pun = (long)all.size();
       all.clear();
+      ev[0].items += 1; ev[0].live += live;
+      if (live) tally(ev[0]);
+      lv.clear(); wv.clear();
       for (size_t j = 0; j < so.size(); j++) {
         vis.clear(); S.visited = &vis;
         S.walk(so[j], sdv[j], sl[j], 2);
@@ -231,8 +264,18 @@ int main(int argc, char** argv) {
       std::sort(all.begin(), all.end()); all.erase(std::unique(all.begin(), all.end()), all.end());
       pu.push_back(pun); su.push_back((long)all.size()); ptot.push_back(pun + (long)all.size());
       (void)own_max;
+      if (live) tally(ev[1]);
     }
-    S.visited = nullptr;
+    S.visited = nullptr; S.leaves = nullptr; S.went = nullptr;
+    if (clipped) {  // one JSON line: means per live item
+      const double n = std::max(1.0, ev[0].live);
+      printf("EVENTS {\"walk\": \"origin\", \"items_sampled\": %.0f, \"live_items\": %.0f", ev[0].items, ev[0].live);
+      const char* nm[2] = {"primary", "shadow"};
+      for (int w = 0; w < 2; w++)
+        printf(", \"%s\": {\"walks\": %.4f, \"branch_steps\": %.3f, \"pushes\": %.3f, \"leaf_visits\": %.3f, \"pair_tests\": %.3f}", nm[w], ev[w].walks / n, ev[w].steps / n,
+               ev[w].pushes / n, ev[w].leaf_visits / n, ev[w].pair_tests / n);
+      printf("}\n");
+    }
     auto q = [](std::vector<long> v, double f) { std::sort(v.begin(), v.end()); return v[(size_t)(f * (v.size() - 1))]; };
     auto mean = [](const std::vector<long>& v) { double s = 0; for (long x : v) s += x; return s / v.size(); };
     printf("%-7s packets (%zu sampled): branch steps per item  primary walk mean %.0f p50 %ld p99 %ld max %ld | shadow walk mean %.0f p50 %ld p90 %ld p99 %ld p999 %ld max %ld | item mean %.0f p50 %ld p99 %ld max %ld (max / mean %.1f)\n",
