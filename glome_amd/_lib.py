@@ -55,6 +55,13 @@ class SceneInfo(C.Structure):  # glome_scene_info
                 ("max_bih_depth", C.c_int32), ("max_mesh_depth", C.c_int32), ("device_bytes", C.c_int64)]
 
 
+class XfmSource(C.Structure):  # glome_xfm_source
+    _fields_ = [("data", C.c_void_p), ("base", C.c_void_p), ("dtype", C.c_int32), ("form", C.c_int32), ("stride", C.c_int64)]
+
+
+XFM_PAIR, XFM_FORWARD, XFM_POSE = 0, 1, 2  # GLOME_XFM_*
+F64, F32 = 0, 1                            # GLOME_F64 / GLOME_F32
+
 # every symbol include/glome_hip.h declares: (name, restype, argtypes)
 vp = C.c_void_p
 SYMBOLS = [
@@ -86,6 +93,9 @@ SYMBOLS = [
     ("glome_xfm_rotate", C.c_int, [c_dp, C.c_double, c_dp]),
     ("glome_xfm_xyz_to_uvw", C.c_int, [c_dp, c_dp, c_dp, c_dp]),
     ("glome_xfm_compose", C.c_int, [c_dp, C.c_int, c_dp]),
+    ("glome_xfm_from_forward", C.c_int, [c_dp, c_dp]),
+    ("glome_xfm_from_pose", C.c_int, [c_dp, c_dp, C.c_double, c_dp]),
+    ("glome_xfm_mult", C.c_int, [c_dp, c_dp, c_dp]),
     ("glome_sb_new", vp, []),
     ("glome_sb_free", None, [vp]),
     ("glome_sb_last_error", C.c_char_p, [vp]),
@@ -110,6 +120,7 @@ SYMBOLS = [
     ("glome_sb_bih_set_triangles_indexed", C.c_int, [vp, C.c_int32, c_dp, C.c_int, c_ip, C.c_int]),
     ("glome_sb_bih_set_spheres", C.c_int, [vp, C.c_int32, c_dp, C.c_int]),
     ("glome_sb_instance_set_transforms", C.c_int, [vp, c_ip, c_dp, C.c_int]),
+    ("glome_sb_instance_transform", C.c_int, [vp, C.c_int32, c_dp]),
     ("glome_sb_bih_items", C.c_int32, [vp, C.c_int32, c_ip, C.c_int32]),
     ("glome_sb_bih_refit", C.c_int, [vp, C.c_int32]),
     ("glome_sb_bihs_above", C.c_int32, [vp, C.c_int32, C.c_int32, c_ip, C.c_int32]),
@@ -158,6 +169,9 @@ SYMBOLS = [
     ("glome_scene_sphere_bih_update_f32_dev", C.c_int, [vp, C.c_int32, vp, vp, C.c_int]),
     ("glome_scene_instance_update", C.c_int, [vp, c_ip, c_dp, C.c_int, C.POINTER(C.c_float)]),
     ("glome_scene_instance_update_dev", C.c_int, [vp, c_ip, vp, C.c_int]),
+    ("glome_xfm_source_size", C.c_size_t, []),
+    ("glome_scene_instance_update_from", C.c_int, [vp, c_ip, C.POINTER(XfmSource), C.c_int, C.POINTER(C.c_float)]),
+    ("glome_scene_instance_update_from_dev", C.c_int, [vp, c_ip, C.POINTER(XfmSource), C.c_int]),
     ("glome_scene_nested_updates", C.c_int, [vp, C.c_int]),
     ("glome_scene_bih_refit", C.c_int, [vp, C.c_int32, C.POINTER(C.c_float)]),
     ("glome_scene_bih_refit_dev", C.c_int, [vp, C.c_int32]),

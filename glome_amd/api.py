@@ -68,6 +68,60 @@ def compose(xfms):
     return out
 
 
+def xfm_from_pose(t, q_xyzw, s=1.0):
+    """The Xfm of the rigid pose p -> t + s R(q) p (glome_xfm_from_pose): q = (qx, qy, qz, qw), the scalar last, any length but 0; s a
+    uniform scale > 0.  The arithmetic is stated in glome_hip.h and is what Scene.instance_update_from computes on the device."""
+    lib = L.load()
+    (_, pt), (_, pq) = L.dvec(t), L.dvec(q_xyzw)
+    out = np.zeros(24, dtype=np.float64)
+    rc = lib.glome_xfm_from_pose(pt, pq, float(s), out.ctypes.data_as(L.c_dp))
+    if rc != 0:
+        raise GlomeError(f"xfm_from_pose: a value that is not finite, a quaternion of length 0 or a scale that is not positive (status {rc})")
+    return out
+
+
+def xfm_from_forward(m):
+    """The Xfm of a row-major 3x4 forward matrix, 12 values, its inverse by cofactors (glome_xfm_from_forward)."""
+    lib = L.load()
+    a = np.ascontiguousarray(np.asarray(m, dtype=np.float64).ravel())
+    if a.size != 12:
+        raise GlomeError(f"xfm_from_forward: 12 values, not {a.size}")
+    out = np.zeros(24, dtype=np.float64)
+    rc = lib.glome_xfm_from_forward(a.ctypes.data_as(L.c_dp), out.ctypes.data_as(L.c_dp))
+    if rc != 0:
+        raise GlomeError(f"xfm_from_forward: {'a singular matrix' if rc == L.E_SCENE else 'a value that is not finite'} (status {rc})")
+    return out
+
+
+def xfm_mult(a, b):
+    """a applied after b (glome_xfm_mult): compose([b, a]) without the identity it starts from and without check_xfm."""
+    lib = L.load()
+    (xa, pa), (xb, pb) = L.dvec(a), L.dvec(b)
+    if xa.size != 24 or xb.size != 24:
+        raise GlomeError("xfm_mult: two transforms of 24 values")
+    out = np.zeros(24, dtype=np.float64)
+    if lib.glome_xfm_mult(pa, pb, out.ctypes.data_as(L.c_dp)) != 0:
+        raise GlomeError("xfm_mult: invalid arguments")
+    return out
+
+
+XFM_FORMS = {"pair": (L.XFM_PAIR, 24), "forward": (L.XFM_FORWARD, 12), "pose": (L.XFM_POSE, 8)}
+
+
+def _xfm_stride(call, form, shape, strides):
+    """The element stride between the items of an array / tensor of `shape` and element `strides` handed to instance_update_from: [n, w],
+    or for "forward" [n, 3, 4] / [n, 4, 4], the inner dimensions contiguous; None when the layout is not one the library reads in place."""
+    w = XFM_FORMS[form][1]
+    inner = tuple(shape[1:])
+    if not (inner == (w,) or (form == "forward" and inner in ((3, 4), (4, 4)))):
+        raise GlomeError(f"{call}: a {form} source is [n, {w}]" + (", [n, 3, 4] or [n, 4, 4]" if form == "forward" else "") + f", not {list(shape)}")
+    if tuple(strides[1:]) != ((1,) if len(inner) == 1 else (4, 1)):
+        return None
+    if shape[0] <= 1:
+        return 0
+    return strides[0] if strides[0] >= w else None
+
+
 def deg(x):  # Vec.hs:17-18 (note the truncated pi, as written in the reference)
     return (x * 3.1415926535897) / 180
 
@@ -277,6 +331,13 @@ class Builder:
         if x.shape[0] != len(i):
             raise GlomeError(f"instance_set_transforms: {len(i)} ids but {x.shape[0]} matrices")
         self._chk(self.lib.glome_sb_instance_set_transforms(self.h, pi if len(i) else None, x.ctypes.data_as(L.c_dp) if len(i) else None, len(i)), "glome_sb_instance_set_transforms")
+
+    def instance_transform(self, node):
+        """The 24 doubles of Instance `node` as it stands (glome_sb_instance_transform): the placement a `cylinder` or `cone` carries, the
+        product a `transform` made.  xfm_mult(motion, this) moves the Instance rigidly."""
+        out = np.zeros(24, dtype=np.float64)
+        self._chk(self.lib.glome_sb_instance_transform(self.h, int(node), out.ctypes.data_as(L.c_dp)), "glome_sb_instance_transform")
+        return out
 
     def bih_refit(self, node):
         """What `bih` derives from its items' bounds, made again for the tree as it stands (glome_sb_bih_refit): after mesh_set_vertices /
@@ -617,6 +678,59 @@ class Scene:
         if not hasattr(t, "data_ptr") or not t.is_cuda or str(t.dtype) != "torch.float64" or not t.is_contiguous() or t.numel() != 24 * len(i):
             raise GlomeError("instance_update_dev: the matrices must be a contiguous CUDA torch.float64 tensor of 24 values per id")
         self._chk(self.lib.glome_scene_instance_update_dev(self.h, pi if len(i) else None, C.c_void_p(t.data_ptr()) if len(i) else None, len(i)), "glome_scene_instance_update_dev")
+
+    def instance_update_from(self, ids, data, form, base=None):
+        """instance_update from what a rigid-body step holds (glome_scene_instance_update_from): form "pose" -- 8 values tx ty tz qx qy qz qw
+        s per id --, "forward" -- a row-major 3x4 matrix, [n, 12], [n, 3, 4] or [n, 4, 4] (the fourth row is not read) --, or "pair" -- the
+        24 values of instance_update.  The scene instance_update gives for xfm_from_pose / xfm_from_forward of the widened items, bit for
+        bit.  base: None, or 24 float64 values per id; the item is then applied after it, xfm_mult(item, base[k]).  The inner dimensions
+        must be contiguous; the stride between items is the array's own, so a column slice of a wider state array is read in place, and
+        what lies between the items may be anything.  NumPy arrays take the host form (a float32 array is staged as float32, anything else
+        as float64) and return the device milliseconds; CUDA torch tensors, float32 or float64 (base: float64, contiguous), take the
+        device form, asynchronous on the context's stream (returns None; the tensors must stay alive until it has run)."""
+        call = "instance_update_from"
+        if form not in XFM_FORMS:
+            raise GlomeError(f"{call}: form {form!r} is none of {sorted(XFM_FORMS)}")
+        i, pi = L.ivec(ids)
+        n = len(i)
+        src = L.XfmSource()
+        src.form = XFM_FORMS[form][0]
+        if hasattr(data, "data_ptr") or hasattr(base, "data_ptr"):  # torch tensors: the device form
+            t = data
+            if not hasattr(t, "data_ptr") or not t.is_cuda or str(t.dtype) not in ("torch.float32", "torch.float64") or t.dim() < 2:
+                raise GlomeError(f"{call}: data must be a CUDA torch.float32 or torch.float64 tensor of one row per id")
+            stride = _xfm_stride(call, form, tuple(t.shape), tuple(t.stride()))
+            if stride is None:
+                raise GlomeError(f"{call}: the inner dimensions of data must be contiguous and its rows must not overlap (strides {tuple(t.stride())})")
+            if base is not None:
+                if not hasattr(base, "data_ptr") or not base.is_cuda or str(base.dtype) != "torch.float64" or not base.is_contiguous() or base.numel() != 24 * n:
+                    raise GlomeError(f"{call}: base must be a contiguous CUDA torch.float64 tensor of 24 values per id")
+                src.base = base.data_ptr() if n else None
+            if t.shape[0] != n:
+                raise GlomeError(f"{call}: {n} ids but {t.shape[0]} items")
+            src.data, src.dtype, src.stride = (t.data_ptr() if n else None), (L.F32 if str(t.dtype) == "torch.float32" else L.F64), stride
+            self._chk(self.lib.glome_scene_instance_update_from_dev(self.h, pi if n else None, C.byref(src), n), "glome_scene_instance_update_from_dev")
+            return None
+        a = np.asarray(data)
+        a = np.asarray(a, dtype=np.float32 if a.dtype == np.float32 else np.float64)
+        if a.ndim < 2:
+            a = a.reshape(-1, XFM_FORMS[form][1])
+        stride = _xfm_stride(call, form, a.shape, tuple(s // a.itemsize if s % a.itemsize == 0 else -1 for s in a.strides))
+        if stride is None:  # (a layout the library does not read in place: a dense copy)
+            a = np.ascontiguousarray(a)
+            stride = 0
+        if a.shape[0] != n:
+            raise GlomeError(f"{call}: {n} ids but {a.shape[0]} items")
+        held = None
+        if base is not None:
+            held = np.ascontiguousarray(np.asarray(base, dtype=np.float64).reshape(-1, 24))
+            if held.shape[0] != n:
+                raise GlomeError(f"{call}: {n} ids but {held.shape[0]} base matrices")
+            src.base = held.ctypes.data if n else None
+        src.data, src.dtype, src.stride = (a.ctypes.data if n else None), (L.F32 if a.dtype == np.float32 else L.F64), stride
+        ms = C.c_float(0)
+        self._chk(self.lib.glome_scene_instance_update_from(self.h, pi if n else None, C.byref(src), n, C.byref(ms)), "glome_scene_instance_update_from")
+        return ms.value
 
     def nested_updates(self, on=True):
         """The switch of glome_scene_nested_updates: with it on, the three updates accept objects that lie under bihs, leave the trees above

@@ -11,6 +11,7 @@
 #include "capi_shared.hpp"
 #include "show_format.hpp"
 #include "tiles.hpp"
+#include "xfm_sources.hpp"
 
 using namespace glome;
 
@@ -78,6 +79,35 @@ int glome_xfm_rotate(const double axis[3], double angle, double out[24]) { retur
 int glome_xfm_xyz_to_uvw(const double u[3], const double v[3], const double w[3], double out[24]) { return xguard([&] { xf_to(xf_xyz_to_uvw(d3(u), d3(v), d3(w)), out); }); }
 int glome_xfm_compose(const double* xfms, int n, double out[24]) {
   return xguard([&] { std::vector<Xf> xs; for (int k = 0; k < n; k++) xs.push_back(xf_from(xfms + 24 * k)); xf_to(xf_compose(xs), out); });
+}
+// The matrices of glome_scene_instance_update_from's forms (xfm_sources.hpp: the conversion kernel's own bodies).
+int glome_xfm_from_forward(const double m12[12], double out[24]) {
+  if (!m12 || !out) return GLOME_E_INVALID;
+  for (int q = 0; q < 12; q++) if (!std::isfinite(m12[q])) return GLOME_E_INVALID;
+  double o[24];
+  const double det = xfm::from_forward(m12, o);
+  bool finite = true;
+  for (int q = 12; q < 24; q++) finite = finite && std::isfinite(o[q]);
+  if (det == 0.0 || !finite) return GLOME_E_SCENE;
+  std::copy(o, o + 24, out);
+  return 0;
+}
+int glome_xfm_from_pose(const double t[3], const double q_xyzw[4], double s, double out[24]) {
+  if (!t || !q_xyzw || !out) return GLOME_E_INVALID;
+  const double p[8] = {t[0], t[1], t[2], q_xyzw[0], q_xyzw[1], q_xyzw[2], q_xyzw[3], s};
+  for (int q = 0; q < 8; q++) if (!std::isfinite(p[q])) return GLOME_E_INVALID;
+  double o[24];
+  if (!xfm::from_pose(p, o)) return GLOME_E_INVALID;
+  for (int q = 0; q < 24; q++) if (!std::isfinite(o[q])) return GLOME_E_INVALID;
+  std::copy(o, o + 24, out);
+  return 0;
+}
+int glome_xfm_mult(const double a[24], const double b[24], double out[24]) {
+  if (!a || !b || !out) return GLOME_E_INVALID;
+  double o[24];
+  xfm::mult(a, b, o);
+  std::copy(o, o + 24, out);
+  return 0;
 }
 int glome_camera_lookat(const double pos[3], const double at[3], const double up[3], double angle_deg, glome_camera* out) {  // Scene.hs:48-57
   if (!out) return GLOME_E_INVALID;
@@ -160,6 +190,15 @@ int glome_sb_instance_set_transforms(glome_sb* sb, const int32_t* ids, const dou
     std::vector<Xf> X;
     for (int k = 0; k < n; k++) X.push_back(xf_from(xfms + 24 * (size_t)k));
     sb->graph.instance_set_transforms(std::vector<int>(ids, ids + n), X);
+    return 0;
+  });
+}
+int glome_sb_instance_transform(glome_sb* sb, int32_t id, double out[24]) {
+  return guard(sb, [&] {
+    if (!out) throw std::invalid_argument("instance_transform: null output");
+    const Node& n = sb->graph.at(id);
+    if (n.kind != K_INSTANCE) throw std::invalid_argument("instance_transform: node " + std::to_string(id) + " is a " + kind_name(n.kind) + ", not an Instance");
+    xf_to(n.xf, out);
     return 0;
   });
 }

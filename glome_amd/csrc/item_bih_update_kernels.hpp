@@ -24,6 +24,9 @@
 // (fmin / fmax of +0 and -0 may return either: -0 arises only from a matrix product, and only a tie with it could show); the stored sign
 // is the fold's, and the tests keep their coordinates away from it.
 //   k_inst_xfm          one lane per (Instance, slot): the six float4; raises kErrBadVertex for an entry that is not finite
+//   k_xfm_convert       one lane per named Instance: its 24 doubles from a matrix source (XfmSrc: a pair, a forward matrix or a pose,
+//                       fp64 or fp32, strided, after a base matrix or not) into the scene's table, which the two kernels around it
+//                       in this list then read as they read a caller's fp64 array (glome_scene_instance_update_from)
 //   k_nest_inst_named   one lane per named Instance that is an item of the tree: its two fp32 boxes into the tree's workspace rows; as
 //                       <true>, with the child's bound taken from the bounds table when the child is live, and the matrix and the
 //                       fp64 box kept in the tree's tables (<false>: a tree without live items while the switch is off)
@@ -45,6 +48,7 @@
 #include "bih_update_kernels.hpp"
 #include "flatten.hpp"
 #include "update_common.hpp"
+#include "xfm_sources.hpp"
 
 namespace glome {
 namespace itemupd {
@@ -96,6 +100,47 @@ __global__ void __launch_bounds__(64) k_inst_xfm(DXfmArgs A) {
       bad = bad || !(isfinite(a) && isfinite(b) && isfinite(c) && isfinite(d));
       o[q] = make_float4((float)a, (float)b, (float)c, (float)d);
     }
+    if (bad) atomicOr(A.error, kErrBadVertex);
+  });
+}
+
+// A matrix source: load(k, m) gives the matrix of the k-th named Instance as 24 doubles, whatever the caller holds -- the point sources
+// of update_common.hpp, for matrices.  Item k is the width_of(FORM) values of T from data + k * stride (stride in elements, at least the
+// width: the index is 64-bit, and nothing outside the item is read, so what lies between two items may be anything); xfm::convert
+// (xfm_sources.hpp, the host functions' own body) makes the 24 doubles of them, and with a base the result is xfm::mult(item, base[k]):
+// the item applied after the base.  fp32 -> fp64 is exact, so an fp32 source gives what the fp64 source gives for the widened array.
+// False for what the POSE form refuses (a quaternion of length 0, s <= 0).
+template <class T, int FORM> struct XfmSrc {
+  const T* data;
+  const double* base;  // null, or 24 doubles per item, contiguous
+  int64_t stride;
+  __device__ __forceinline__ bool load(uint32_t k, double m[24]) const {
+    constexpr int W = FORM == xfm::kPair ? 24 : FORM == xfm::kForward ? 12 : 8;
+    const T* p = data + (int64_t)k * stride;
+    double v[W];
+    for (int q = 0; q < W; q++) v[q] = (double)p[q];
+    if (!base) return xfm::convert(FORM, v, m);
+    double item[24], b[24];
+    const bool ok = xfm::convert(FORM, v, item);
+    for (int q = 0; q < 24; q++) b[q] = base[24 * (size_t)k + q];
+    xfm::mult(item, b, m);
+    return ok;
+  }
+};
+template <class Src> struct DConvertArgs {
+  Src src;
+  double* table;         // 24 per named Instance: what k_inst_xfm and k_nest_inst_named read as `xfms`
+  uint32_t n;            // named Instances
+  unsigned int* error;   // the slot's sticky error word
+};
+// Raises kErrBadVertex for a lane whose source refuses its item or whose 24 results are not all finite (an input that is not finite, a
+// singular forward matrix: 0 / 0 and x / 0 are not finite); the row is stored all the same, and the readers raise the bit again.
+template <class Src> __global__ void __launch_bounds__(64) k_xfm_convert(DConvertArgs<Src> A) {
+  upd::for_lanes(A.n, [&](uint32_t k) {
+    double m[24];
+    bool bad = !A.src.load(k, m);
+    double* o = A.table + 24 * (size_t)k;
+    for (int q = 0; q < 24; q++) { bad = bad || !isfinite(m[q]); o[q] = m[q]; }
     if (bad) atomicOr(A.error, kErrBadVertex);
   });
 }

@@ -213,6 +213,10 @@ struct glome_scene {
   int inst_stage_next = 0;
   uint2* d_inst_rows = nullptr;
   size_t inst_rows_cap = 0;
+  // glome_scene_instance_update_from: the 24 doubles per named Instance its conversion kernel makes of the caller's source, which the
+  // update's kernels then read.  One per scene, grown like d_inst_rows and ordered like it
+  double* d_xfm_table = nullptr;
+  size_t xfm_table_cap = 0;  // matrices
 };
 
 static std::string g_global_error;
@@ -608,6 +612,7 @@ void glome_scene_release(glome_scene* s) {
   for (void* p : s->allocs) (void)hipFree(p);
   for (auto& st : s->inst_stage) { if (st.h) (void)hipHostFree(st.h); if (st.ev) (void)hipEventDestroy(st.ev); }
   if (s->d_inst_rows) (void)hipFree(s->d_inst_rows);
+  if (s->d_xfm_table) (void)hipFree(s->d_xfm_table);
   delete s;
 }
 int glome_scene_get_info(const glome_scene* s, glome_scene_info* out) {
@@ -703,7 +708,9 @@ static int device_error_status(glome_ctx* ctx, unsigned int e) {
                " refit, glome_scene_bih_refit, met an item box or joined box that reaches infinity: then that bih and the bihs above it are;"
                " or a sphere bih update, glome_scene_sphere_bih_update, met a value that is not finite or a radius that is not positive: then"
                " that bih is); or an indexed bih update, glome_scene_bih_update_indexed_dev, met a vertex index outside [0, nv), read vertex 0 in"
-               " its place, and left that bih unspecified";
+               " its place, and left that bih unspecified; or an Instance update from a source, glome_scene_instance_update_from_dev, met an"
+               " item that gives no finite matrix (a value that is not finite, a quaternion of length 0, a scale that is not positive, a"
+               " singular forward matrix): then those Instances and the bih that holds them are unspecified";
     return GLOME_E_INVALID;
   }
   ctx->err = "device-side limit hit (traversal stack or CSG advance cap)";
@@ -1539,13 +1546,10 @@ static int instance_update_check(glome_scene* s, const int32_t* ids, const void*
   if (dup != sorted.end()) { ctx->err = "instance update: node " + std::to_string(*dup) + " is named more than once"; return GLOME_E_INVALID; }
   return 0;
 }
-int glome_scene_instance_update_dev(glome_scene* s, const int32_t* ids, const double* xfms_dev, int n) {
-  if (!s) return GLOME_E_INVALID;
+// The launches of an accepted update of n > 0 Instances U, on the current stream, their matrices 24 doubles each at xfms_dev.  first():
+// what the call enqueues inside its event pair before its kernels -- nothing, or the conversion that fills xfms_dev.
+template <class First> static int instance_update_launch(glome_scene* s, const std::vector<const InstanceUpdateInfo*>& U, const double* xfms_dev, int n, First first) {
   glome_ctx* ctx = s->ctx;
-  std::vector<const InstanceUpdateInfo*> U;
-  if (int rc = instance_update_check(s, ids, xfms_dev, n, U)) return rc;
-  if (n == 0) return 0;
-  HIPCHK(ctx, hipSetDevice(ctx->device));
   hipStream_t st = ctx->stream;
   // this call's rows: (matrix, xfm slot) of every slot, then per bih (matrix, item) of its named items
   std::vector<uint2> rows;
@@ -1575,6 +1579,7 @@ int glome_scene_instance_update_dev(glome_scene* s, const int32_t* ids, const do
   for (auto& pb : per_bih) if (int rc = ensure_tree_ws(s, s->ibihs.at(pb.first))) return rc;
   UpdateSpan span(ctx, nullptr);
   HIPCHK(ctx, span.begin());
+  first();
   HIPCHK(ctx, hipMemcpyAsync(s->d_inst_rows, stage.h, rows.size() * sizeof(uint2), hipMemcpyHostToDevice, st));
   HIPCHK(ctx, hipEventRecord(stage.ev, st));
   stage.pending = true;
@@ -1609,33 +1614,144 @@ int glome_scene_instance_update_dev(glome_scene* s, const int32_t* ids, const do
   mark_launched(ctx);  // (a matrix entry that is not finite is reported at the next synchronize)
   return 0;
 }
+int glome_scene_instance_update_dev(glome_scene* s, const int32_t* ids, const double* xfms_dev, int n) {
+  if (!s) return GLOME_E_INVALID;
+  glome_ctx* ctx = s->ctx;
+  std::vector<const InstanceUpdateInfo*> U;
+  if (int rc = instance_update_check(s, ids, xfms_dev, n, U)) return rc;
+  if (n == 0) return 0;
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  return instance_update_launch(s, U, xfms_dev, n, [] {});
+}
+// what the host forms check of the matrix m (24 doubles) they would give Instance `id`, whose tables are u: 0, or the refusal
+static int instance_matrix_check(glome_scene* s, int32_t id, const InstanceUpdateInfo* u, const double* m) {
+  glome_ctx* ctx = s->ctx;
+  for (int q = 0; q < 24; q++) if (!std::isfinite(m[q])) { ctx->err = "instance update: a matrix entry of node " + std::to_string(id) + " is not finite"; return GLOME_E_INVALID; }
+  Xf x;
+  for (int q = 0; q < 12; q++) { x.f.m[q] = m[q]; x.i.m[q] = m[12 + q]; }
+  try { xf_check(x); } catch (const scene_error& e) { ctx->err = "instance update: node " + std::to_string(id) + ": " + e.what(); return GLOME_E_INVALID; }
+  if (u->bih < 0) return 0;
+  // the item's new box, as `bound` makes it: `bih` refuses one that reaches the reference's infinity
+  const double* cb = &s->ibihs.at(u->bih).info.child_bound[6 * (size_t)u->item];
+  D3 pts[8];
+  int q = 0;
+  for (double px : {cb[0], cb[3]}) for (double py : {cb[1], cb[4]}) for (double pz : {cb[2], cb[5]}) pts[q++] = xf_point(x, D3{px, py, pz});
+  const Box3 b = box_of_points(pts, 8);
+  if (b.lo.x == -kInfinity || b.lo.y == -kInfinity || b.lo.z == -kInfinity || b.hi.x == kInfinity || b.hi.y == kInfinity || b.hi.z == kInfinity) {
+    ctx->err = "instance update: node " + std::to_string(id) + " in bih " + std::to_string(u->bih) + ": bih: infinite bounding box";
+    return GLOME_E_SCENE;
+  }
+  return 0;
+}
 int glome_scene_instance_update(glome_scene* s, const int32_t* ids, const double* xfms, int n, float* gpu_ms) {
   std::vector<const InstanceUpdateInfo*> U;
   auto validate = [&]() -> int {
-    glome_ctx* ctx = s->ctx;
-    for (int k = 0; k < n; k++) {
-      const double* m = xfms + 24 * (size_t)k;
-      for (int q = 0; q < 24; q++) if (!std::isfinite(m[q])) { ctx->err = "instance update: a matrix entry of node " + std::to_string(ids[k]) + " is not finite"; return GLOME_E_INVALID; }
-      Xf x;
-      for (int q = 0; q < 12; q++) { x.f.m[q] = m[q]; x.i.m[q] = m[12 + q]; }
-      try { xf_check(x); } catch (const scene_error& e) { ctx->err = "instance update: node " + std::to_string(ids[k]) + ": " + e.what(); return GLOME_E_INVALID; }
-      if (U[(size_t)k]->bih < 0) continue;
-      // the item's new box, as `bound` makes it: `bih` refuses one that reaches the reference's infinity
-      const double* cb = &s->ibihs.at(U[(size_t)k]->bih).info.child_bound[6 * (size_t)U[(size_t)k]->item];
-      D3 pts[8];
-      int q = 0;
-      for (double px : {cb[0], cb[3]}) for (double py : {cb[1], cb[4]}) for (double pz : {cb[2], cb[5]}) pts[q++] = xf_point(x, D3{px, py, pz});
-      const Box3 b = box_of_points(pts, 8);
-      if (b.lo.x == -kInfinity || b.lo.y == -kInfinity || b.lo.z == -kInfinity || b.hi.x == kInfinity || b.hi.y == kInfinity || b.hi.z == kInfinity) {
-        ctx->err = "instance update: node " + std::to_string(ids[k]) + " in bih " + std::to_string(U[(size_t)k]->bih) + ": bih: infinite bounding box";
-        return GLOME_E_SCENE;
-      }
-    }
+    for (int k = 0; k < n; k++) if (int rc = instance_matrix_check(s, ids[k], U[(size_t)k], xfms + 24 * (size_t)k)) return rc;
     return 0;
   };
   return blocking_update(s, gpu_ms, [&] { return instance_update_check(s, ids, xfms, n, U); }, validate, [&](StageIn& in) {
     double* dx = in(xfms, 24 * (size_t)n);
     return [=] { return glome_scene_instance_update_dev(s, ids, dx, n); };
+  }, n == 0);
+}
+
+// ---- the same from a matrix source: pairs, forward matrices or poses, fp64 or fp32, strided, after a base (xfm_sources.hpp) ----
+size_t glome_xfm_source_size(void) { return sizeof(glome_xfm_source); }
+static_assert((int)GLOME_XFM_PAIR == xfm::kPair && (int)GLOME_XFM_FORWARD == xfm::kForward && (int)GLOME_XFM_POSE == xfm::kPose, "the header's forms are the kernels' (xfm_sources.hpp)");
+// what both forms refuse of the source before anything is launched, once instance_update_check has passed; *stride = elements per item
+static int xfm_source_check(glome_scene* s, const glome_xfm_source* src, int n, int64_t* stride) {
+  glome_ctx* ctx = s->ctx;
+  auto refuse = [&](const std::string& why) { ctx->err = "instance update: " + why; return GLOME_E_INVALID; };
+  *stride = 0;
+  if (n == 0) return 0;
+  if (!src || !src->data) return refuse("bad count or null array");  // (instance_update_check's words for its own null array)
+  const int w = xfm::width_of(src->form);
+  if (!w) return refuse("form " + std::to_string(src->form) + " is none of GLOME_XFM_PAIR, GLOME_XFM_FORWARD, GLOME_XFM_POSE");
+  if (src->dtype != GLOME_F64 && src->dtype != GLOME_F32) return refuse("dtype " + std::to_string(src->dtype) + " is neither GLOME_F64 nor GLOME_F32");
+  if (src->stride < 0) return refuse("stride " + std::to_string(src->stride) + " is negative");
+  if (src->stride != 0 && src->stride < w) return refuse("stride " + std::to_string(src->stride) + " is less than the form's " + std::to_string(w) + " values");
+  *stride = src->stride ? src->stride : w;
+  return 0;
+}
+template <class T, int FORM> static void launch_xfm_convert(glome_scene* s, const glome_xfm_source& src, int64_t stride, int n) {
+  using Src = itemupd::XfmSrc<T, FORM>;
+  itemupd::DConvertArgs<Src> A;
+  A.src = Src{(const T*)src.data, src.base, stride};
+  A.table = s->d_xfm_table; A.n = (uint32_t)n; A.error = &s->ctx->slot().d_counters->error;
+  launch_lanes(s->ctx, itemupd::k_xfm_convert<Src>, (uint32_t)n, A);
+}
+int glome_scene_instance_update_from_dev(glome_scene* s, const int32_t* ids, const glome_xfm_source* src_in, int n) {
+  if (!s) return GLOME_E_INVALID;
+  glome_ctx* ctx = s->ctx;
+  std::vector<const InstanceUpdateInfo*> U;
+  // (the array instance_update_check asks for: a null source is a null array)
+  if (int rc = instance_update_check(s, ids, src_in ? src_in->data : nullptr, n, U)) return rc;
+  int64_t stride = 0;
+  if (int rc = xfm_source_check(s, src_in, n, &stride)) return rc;
+  if (n == 0) return 0;
+  const glome_xfm_source src = *src_in;
+  // the layout the existing call takes: that call, and no table
+  if (src.form == GLOME_XFM_PAIR && src.dtype == GLOME_F64 && stride == 24 && !src.base) return glome_scene_instance_update_dev(s, ids, (const double*)src.data, n);
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  if ((size_t)n > s->xfm_table_cap) {  // (grown like d_inst_rows: the kernels of an earlier call may still read the old one)
+    if (s->d_xfm_table) { HIPCHK(ctx, hipStreamSynchronize(ctx->stream)); HIPCHK(ctx, hipFree(s->d_xfm_table)); s->d_xfm_table = nullptr; s->xfm_table_cap = 0; }
+    HIPCHK(ctx, hipMalloc((void**)&s->d_xfm_table, 24 * (size_t)n * sizeof(double)));
+    s->xfm_table_cap = (size_t)n;
+  }
+  return instance_update_launch(s, U, s->d_xfm_table, n, [&] {
+    const bool f32 = src.dtype == GLOME_F32;
+    if (src.form == GLOME_XFM_POSE) f32 ? launch_xfm_convert<float, xfm::kPose>(s, src, stride, n) : launch_xfm_convert<double, xfm::kPose>(s, src, stride, n);
+    else if (src.form == GLOME_XFM_FORWARD) f32 ? launch_xfm_convert<float, xfm::kForward>(s, src, stride, n) : launch_xfm_convert<double, xfm::kForward>(s, src, stride, n);
+    else f32 ? launch_xfm_convert<float, xfm::kPair>(s, src, stride, n) : launch_xfm_convert<double, xfm::kPair>(s, src, stride, n);
+  });
+}
+int glome_scene_instance_update_from(glome_scene* s, const int32_t* ids, const glome_xfm_source* src, int n, float* gpu_ms) {
+  std::vector<const InstanceUpdateInfo*> U;
+  int64_t stride = 0;
+  auto check = [&]() -> int {
+    if (int rc = instance_update_check(s, ids, src ? src->data : nullptr, n, U)) return rc;
+    return xfm_source_check(s, src, n, &stride);
+  };
+  // every item converted on the host, by the device's own expressions (xfm_sources.hpp), and held to what the existing host form checks
+  auto validate = [&]() -> int {
+    glome_ctx* ctx = s->ctx;
+    if (n == 0) return 0;
+    const int w = xfm::width_of(src->form);
+    for (int k = 0; k < n; k++) {
+      const std::string node = "node " + std::to_string(ids[k]);
+      double v[24], item[24], m[24];
+      for (int q = 0; q < w; q++) {
+        const size_t at = (size_t)k * (size_t)stride + (size_t)q;
+        v[q] = src->dtype == GLOME_F32 ? (double)((const float*)src->data)[at] : ((const double*)src->data)[at];
+        if (!std::isfinite(v[q])) { ctx->err = "instance update: a value of the item of " + node + " is not finite"; return GLOME_E_INVALID; }
+      }
+      if (src->form == GLOME_XFM_POSE) {
+        if (!xfm::from_pose(v, item)) {
+          ctx->err = "instance update: " + node + ": " + (v[7] > 0.0 ? "the quaternion has length 0" : "the scale is not positive");
+          return GLOME_E_INVALID;
+        }
+      } else if (src->form == GLOME_XFM_FORWARD) {
+        const double det = xfm::from_forward(v, item);
+        bool finite = true;
+        for (int q = 12; q < 24; q++) finite = finite && std::isfinite(item[q]);
+        if (det == 0.0 || !finite) { ctx->err = "instance update: " + node + ": the forward matrix is singular (its determinant is 0 or its inverse is not finite)"; return GLOME_E_SCENE; }
+      } else {
+        xfm::convert(xfm::kPair, v, item);
+      }
+      if (src->base) xfm::mult(item, src->base + 24 * (size_t)k, m);
+      else std::copy(item, item + 24, m);
+      if (int rc = instance_matrix_check(s, ids[k], U[(size_t)k], m)) return rc;
+    }
+    return 0;
+  };
+  return blocking_update(s, gpu_ms, check, validate, [&](StageIn& in) {
+    // the caller's array as it is, in its own dtype and stride (the tail after the last item is not the call's to read)
+    const size_t elems = (size_t)(n - 1) * (size_t)stride + (size_t)xfm::width_of(src->form);
+    glome_xfm_source d = *src;
+    d.data = in((const char*)src->data, elems * (src->dtype == GLOME_F32 ? sizeof(float) : sizeof(double)));
+    d.base = src->base ? in(src->base, 24 * (size_t)n) : nullptr;
+    d.stride = stride;
+    return [=] { return glome_scene_instance_update_from_dev(s, ids, &d, n); };
   }, n == 0);
 }
 

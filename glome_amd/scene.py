@@ -174,6 +174,8 @@ class DescScene:
     def bih_update(self, node, pts9): return self.scene.bih_update(self.nmap[node], pts9)
     def sphere_bih_update(self, node, c3r): return self.scene.sphere_bih_update(self.nmap[node], c3r)
     def instance_update(self, nodes, xfms): return self.scene.instance_update([self.nmap[n] for n in nodes], xfms)
+    def instance_update_from(self, nodes, data, form, base=None): return self.scene.instance_update_from([self.nmap[n] for n in nodes], data, form, base)
+    def instance_transform(self, node): return self.builder.instance_transform(self.nmap[node])
     def bih_refit(self, node): return self.scene.bih_refit(self.nmap[node])
 
     def _ids(self, builder_ids):

@@ -80,6 +80,31 @@ int glome_xfm_scale(const double v[3], double out[24]);                         
 int glome_xfm_rotate(const double axis[3], double angle_rad, double out[24]);        /* Vec.hs:577-598 */
 int glome_xfm_xyz_to_uvw(const double u[3], const double v[3], const double w[3], double out[24]); /* Vec.hs:602-622 */
 int glome_xfm_compose(const double* xfms /* n*24 */, int n, double out[24]);         /* Vec.hs:461-462 */
+/* An Xfm from what a producer of rigid motion holds, and the product of two.  Host only: the specification of
+ * glome_scene_instance_update_from, whose device side evaluates the same expressions.  Every operation below is one round-to-nearest
+ * fp64 operation, in the order written, sums left to right, and nothing contracts: the results are defined to the bit.
+ *   glome_xfm_from_pose(t, q, s): the forward map p -> t + s R(q) p, q = (qx, qy, qz, qw) with the scalar LAST, any length but 0, s a
+ *     uniform scale.
+ *       inv = 1 / sqrt(((qx qx + qy qy) + qz qz) + qw qw);   x, y, z, w = qx inv, qy inv, qz inv, qw inv
+ *       R = [[1 - 2 (yy + zz), 2 (xy - zw), 2 (xz + yw)], [2 (xy + zw), 1 - 2 (xx + zz), 2 (yz - xw)], [2 (xz - yw), 2 (yz + xw), 1 - 2 (xx + yy)]]
+ *     (xx = x x and so on, each product made once; the products by 2 are exact).
+ *       forward row r: (s R[r][0], s R[r][1], s R[r][2], t[r])
+ *       inverse row r: i[r][c] = R[c][r] / s for c < 3 -- a division, not a product by 1 / s --, i[r][3] = -(((i[r][0] tx) + (i[r][1] ty)) + (i[r][2] tz))
+ *     GLOME_E_INVALID, out untouched: a value that is not finite, q of length 0 (the sum of squares is 0), s <= 0, a result that is not finite.
+ *   glome_xfm_from_forward(m12): m12 a row-major 3x4 forward matrix, A = a[r][c] its 3x3 part, t its column 3.  The forward rows are m12.
+ *       c00 = a11 a22 - a12 a21   c01 = a12 a20 - a10 a22   c02 = a10 a21 - a11 a20
+ *       c10 = a02 a21 - a01 a22   c11 = a00 a22 - a02 a20   c12 = a01 a20 - a00 a21
+ *       c20 = a01 a12 - a02 a11   c21 = a02 a10 - a00 a12   c22 = a00 a11 - a01 a10
+ *       det = ((a00 c00) + (a01 c01)) + (a02 c02)
+ *       inverse row r: i[r][c] = c[c][r] / det for c < 3 (the transposed cofactor matrix, each entry DIVIDED by det), i[r][3] as for the pose.
+ *     GLOME_E_INVALID for a value that is not finite; GLOME_E_SCENE when det is 0 or an entry of the inverse is not finite; out untouched.
+ *   glome_xfm_mult(a, b): a applied AFTER b, xfm_mult a b (Vec.hs:447-449): forward = mat_mult a.forward b.forward, inverse = mat_mult
+ *     b.inverse a.inverse, mat_mult (Vec.hs:426-443) with every entry ((x0 y0 + x1 y1) + x2 y2) and column 3 (((x0 y0 + x1 y1) + x2 y2) + x3).
+ *     It is the step glome_xfm_compose folds from an identity; without the identity it never changes the sign of a zero, and it does not
+ *     run check_xfm.  out may be a or b. */
+int glome_xfm_from_forward(const double m12[12], double out[24]);
+int glome_xfm_from_pose(const double t[3], const double q_xyzw[4], double s, double out[24]);
+int glome_xfm_mult(const double a[24], const double b[24], double out[24]);
 
 /* ---- scene builder: one call per reference constructor ---- */
 glome_sb* glome_sb_new(void);
@@ -164,6 +189,10 @@ int32_t glome_sb_bih_items(glome_sb*, int32_t bih_id, int32_t* out, int32_t cap)
  * box would be infinite, as glome_sb_bih refuses it) with a message naming the node, and nothing is touched.  Host only; the
  * specification of glome_scene_instance_update. */
 int glome_sb_instance_set_transforms(glome_sb*, const int32_t* ids, const double* xfms, int n);
+/* The matrix of Instance `id` as it stands, 24 doubles (forward rows, inverse rows): the placement `cylinder` and `cone` gave the node
+ * they return, the product `transform` made, what glome_sb_instance_set_transforms last set.  With it a caller moves such an Instance
+ * rigidly: glome_xfm_mult(motion, this).  GLOME_E_INVALID for a node that is not an Instance. */
+int glome_sb_instance_transform(glome_sb*, int32_t id, double out[24]);
 /* What `bih` derives from its items' bounds, made again for the tree as it stands: every branch's planes and the tree's box from
  * glome_sb_bound of the items' current state -- the last step of glome_sb_bih_set_triangles and glome_sb_instance_set_transforms, on its
  * own.  Topology stays.  With it the host spells the nested case: glome_sb_mesh_set_vertices / _bih_set_triangles /
@@ -420,6 +449,59 @@ int glome_scene_sphere_bih_update_f32_dev(glome_scene*, int32_t bih_id, const fl
  * stream once, to grow its table. */
 int glome_scene_instance_update(glome_scene*, const int32_t* ids, const double* xfms, int n, float* gpu_ms);
 int glome_scene_instance_update_dev(glome_scene*, const int32_t* ids, const double* xfms_dev, int n);
+
+/* ---- the same update from what a rigid-body or skinning step holds: poses, 3x4 / 4x4 forward matrices, fp32, strided ----
+ * glome_scene_instance_update takes 24 contiguous doubles per Instance, the inverse included.  These calls read a SOURCE instead: item k
+ * of the source is the matrix of ids[k], and the library makes the 24 doubles on the device.  The contract is the other updates': the
+ * call leaves the committed scene, bit for bit, as glome_scene_instance_update leaves it when given the table the host functions above
+ * (glome_xfm_from_pose, glome_xfm_from_forward, glome_xfm_mult) yield for the widened items.  fp32 -> fp64 is exact and the device
+ * evaluates those functions' own expressions with explicit round-to-nearest operations: there is no tolerance.  (An fp32 input that is
+ * subnormal may be read as zero, as in the other fp32 forms.)
+ *   data    item k starts k * stride ELEMENTS of dtype after data; GLOME_F64 or GLOME_F32.
+ *   stride  elements between the starts of two items: 0 = dense (the form's width), otherwise at least the width.  Only the values
+ *           [k * stride, k * stride + width) are ever read, k < n: what lies between two items, and after the last one, may be anything,
+ *           NaN included, and need not exist after the last item.  All index arithmetic is 64-bit.
+ *   form    GLOME_XFM_PAIR: 24 values, forward rows then inverse rows -- the existing layout, now also fp32 and strided.
+ *           GLOME_XFM_FORWARD: 12 values, a row-major 3x4 forward matrix (glome_xfm_from_forward); stride 16 reads a row-major 4x4
+ *             [n, 4, 4] array, whose fourth row is never read.
+ *           GLOME_XFM_POSE: 8 values tx ty tz qx qy qz qw s (glome_xfm_from_pose): the quaternion's scalar last, a uniform scale.
+ *   base    NULL, or 24 doubles per id, contiguous (fp64 whatever dtype is): the item is applied AFTER base[k], the result being
+ *           glome_xfm_mult(item, base[k]) -- NOT glome_xfm_compose, which starts from an identity and can change the sign of a zero.  With
+ *           base[k] = glome_sb_instance_transform of a `cylinder` or `cone`, a pose moves that primitive rigidly from where it was built.
+ * ids is a HOST array in both forms, and the struct is host memory read during the call.  Everything glome_scene_instance_update
+ * refuses stays refused, with its messages, before anything is launched (what is updatable, an id twice, the nested rule); also
+ * GLOME_E_INVALID before anything is launched: a null source or null data with n > 0, an unknown form or dtype, a negative stride, a
+ * stride that is neither 0 nor at least the form's width.
+ *   glome_scene_instance_update_from: data and base are HOST arrays.  It converts every item on the host first and refuses, the scene
+ * untouched and the message naming the node: a value of an item that is not finite, a quaternion of length 0 or s <= 0
+ * (GLOME_E_INVALID); a forward matrix whose det is 0 or whose inverse is not finite (GLOME_E_SCENE); then, on the converted matrix,
+ * exactly what glome_scene_instance_update checks (an entry that is not finite, check_xfm, an item box that reaches 1e6).  Then it
+ * waits for every launch of the context, stages the caller's array AS IT IS -- its own dtype and stride, (n - 1) * stride + width
+ * elements -- and base, runs the _dev form and returns when the update is complete; *gpu_ms (may be NULL) = HIP-event time.
+ *   glome_scene_instance_update_from_dev: data and base are DEVICE pointers; asynchronous on the current stream and slot like
+ * glome_scene_instance_update_dev, whose first-update, workspace and nested-updates behaviour it inherits (with
+ * glome_scene_nested_updates on, the trees' tables keep the CONVERTED 24 doubles and the trees above are marked stale).  It takes part
+ * in glome_ctx_timing_begin / _end with ONE event pair per call, the conversion inside it.  The same defects are found on the device:
+ * a lane whose 24 results are not all finite (a value that is not finite, a singular forward matrix), or whose quaternion has length 0
+ * or s <= 0, raises the updates' error word; the next glome_ctx_synchronize returns GLOME_E_INVALID (its message names this call too),
+ * and the named Instances and their bih are unspecified, never out of bounds, until a valid update.  A matrix that merely fails
+ * check_xfm is the caller's error there, as it is in glome_scene_instance_update_dev.
+ *   The conversion writes the 24 doubles into ONE table per scene, which the update's kernels then read as they read a caller's array;
+ * a call that names more Instances than any _from call before it waits for the stream once, to grow the table (192 bytes per
+ * Instance, kept until glome_scene_release).  So the ordering rule of the Instance updates holds here too and covers the table: two
+ * _dev Instance updates of one scene, of either entry, must not run at the same time on different streams / slots; order them on one
+ * stream or with events.  PAIR + GLOME_F64 + dense + no base is glome_scene_instance_update_dev itself, with no table. */
+enum { GLOME_XFM_PAIR = 0, GLOME_XFM_FORWARD = 1, GLOME_XFM_POSE = 2 };
+typedef struct glome_xfm_source {
+  const void* data;   /* item k starts k * stride ELEMENTS of dtype after data */
+  const double* base; /* NULL, or 24 doubles per id, contiguous: the item is applied AFTER base[k] */
+  int32_t dtype;      /* GLOME_F64 / GLOME_F32 */
+  int32_t form;       /* GLOME_XFM_* */
+  int64_t stride;     /* elements between items; 0 = dense: 24 / 12 / 8 */
+} glome_xfm_source;
+size_t glome_xfm_source_size(void);
+int glome_scene_instance_update_from(glome_scene*, const int32_t* ids, const glome_xfm_source*, int n, float* gpu_ms);
+int glome_scene_instance_update_from_dev(glome_scene*, const int32_t* ids, const glome_xfm_source*, int n);
 
 /* ---- update objects under a bih: the chain of bihs above refitted on the GPU, one call per tree ----
  * The three updates above refuse an object as soon as a bih lies above it (a second one for an Instance): that tree's planes and box
