@@ -16,20 +16,45 @@
 //   lanes        the set of lanes whose interval reaches the current node lives in EXEC, not in a scalar pair: a vote is a
 //                v_cmp into VCC or a v_cmpx (which narrows EXEC itself) followed by s_cbranch_vccz / s_cbranch_execz -- no
 //                s_and, no s_cmp, no mask moves.  Lanes outside EXEC keep stale intervals that nobody reads.
-//   branch step  9-12 scalar-type instructions (round 2: 21).  The walk reads its own copy of the nodes (DScene::pknodes,
+//   branch step  by which children the packet enters (instructions as listed, the dispatch at its longest; per live item of the
+//                flagship frame, both walks, tools/probe/bih_cull_study.cpp): the near one only 15 (32.2 steps), the far one
+//                only 18 (36.5), both 27 (26.8), neither 8 and a pop (9.1).  Round 2's step was 21 scalar-type instructions
+//                alone.  The walk reads its own copy of the nodes (DScene::pknodes,
 //                flatten.hpp): a branch child's reference is its byte offset with the child's AXIS in the two low bits, a leaf
 //                child's is the byte offset of its first pair record with both low bits set, so two bit tests pick the next
 //                piece of code and nothing is shifted or masked.  As soon as a node has arrived the NEAR child's node -- the
-//                next step seven times in ten -- is asked for into the other of two register sets (A / B), through a buffer
-//                descriptor over the pool: a leaf reference reads something harmless or, out of range, nothing, so the
-//                prefetch needs no test.  The two plane distances are one packed pair: (lsplit, rsplit) sit in an aligned
+//                next step in 56 % of the steps (near only or both) -- is asked for into the other of two register sets (A / B),
+//                through a buffer descriptor over the pool: a leaf reference reads something harmless or, out of range, nothing,
+//                so the prefetch needs no test.  The two plane distances are one packed pair: (lsplit, rsplit) sit in an aligned
 //                scalar pair, v_pk_add_f32 / v_pk_mul_f32 give ((l - o) * r, (r - o) * r) -- the same IEEE operations per
-//                element.  The far child is pushed as soon as some lane reaches it (before the near vote narrows EXEC) and
-//                taken straight back in the rare case that no lane enters the near child.  The stack pointer lives in m0
-//                for the whole walk (v_writelane / v_readlane take it from there; v_lshl_add_u32 makes the LDS address from
-//                it, so no per-lane address register can drift under a partial EXEC).
-//                At most one prefetch is ever in flight, and a fetch that was not prefetched (a far child entered alone, a
-//                popped entry, the root) is only issued behind an s_waitcnt, so two loads never race for one register set.
+//                element.
+//   votes        (round 11) far first, into VCC.  Empty: v_cmpx takes the near vote into EXEC, and the step goes on to the near
+//                child or to the pops.  Not empty: the near vote is taken WITHOUT touching EXEC (v_cmp_lt_f32_e64 into
+//                s[K28:K29]: under EXEC = the node's lanes the bits are v_cmpx's) and one scalar compare of that pair picks
+//                between the two remaining kinds.  BOTH children entered is the only step that pushes: capacity test, the
+//                entry (EXEC still the node's lanes, the entry's mask VCC), then EXEC = s[K28:K29], known not to be empty.  THE
+//                FAR CHILD ALONE is a third of all steps, not a rare case: descending to where a packet lies picks the far side
+//                about as often as the near side, and a near child that is an empty leaf (plane at -+inf, flatten.hpp) makes
+//                12 of the 36.5 static.  It costs no capacity test, no writelane, no LDS write and no m0 traffic (until round
+//                11 it was pushed before the near vote and taken back after it, and its node fetched late behind a wait of
+//                its own: 30 instructions): EXEC = VCC, near = maximum3(t2, near, near), and the far child's node is asked for
+//                into the CURRENT set -- dead once %[ref] holds the far reference -- so that the next step's own wait covers
+//                it together with the unused prefetch, which lands in the other set.
+//                Consequences: L_slow / PKW_PUSH_OVERFLOW is reached by real pushes only (the `g1 == false` branch of the
+//                C++ step in bih_tri_packet_hw is unreachable from this block, not wrong); a far-only step taken at sp >= CAP
+//                leaves the overflow entries where they are and m0 as it is, so the next pop still goes through L_popslow.
+//   stack        The stack pointer lives in m0 for the whole walk (v_writelane / v_readlane take it from there;
+//                v_lshl_add_u32 makes the LDS address from it, so no per-lane address register can drift under a partial EXEC).
+//   loads        Two loads never race for one register set: a prefetch goes to the other set, a far child's fetch to the
+//                current one (so at most two node loads are in flight, one per set), and every step starts with
+//                s_waitcnt lgkmcnt(0) before it asks for anything; a fetch after a pop or at the root goes to set A behind a
+//                wait (the pop's own, for its LDS reads; L_node's).
+//   hazards      Inline assembly gets no hazard recogniser.  The new pair VALU-writes-SGPR -> SALU-reads-it (v_cmp_lt_f32_e64
+//                s[K28:K29] -> s_cmp_lg_u64, s_mov_b64 exec) needs no wait state on gfx950: the ISA manual's table of manually
+//                inserted wait states lists a VALU write of an SGPR only against v_readlane / v_writelane taking it as the lane
+//                select (4), a VMEM instruction reading it (5) and v_div_fmas reading VCC (4); an SALU read is interlocked.
+//                The pop path has relied on the same pair since round 2 (v_readlane -> s_mov_b64 exec).  The lane selects of
+//                the writelanes are m0, which no VALU writes.
 //   triangles    TWO per test, any number per leaf: a leaf's triangles come as 80-byte pair records (DScene::tripairs,
 //                flatten.hpp emit_pairs: every component of p1, e1, e2 of two triangles as (A, B) in an aligned scalar pair,
 //                then the number of triangles left in the leaf; five of six leaves of the flagship tree hold exactly two)
@@ -406,15 +431,19 @@ constexpr uint32_t PKREF_LEAF = 3u;  // low bits of a reference in the walk's ow
 // pairs (P0 = (ox, oy), P1 = (oz, dx); R0 = (rx, ry), R1 = (rz, .)): the pair operand and the op_sel bit that broadcasts its
 // low or high half.  TN / TF: which half of (T0, T1) = ((lsplit - o) * r, (rsplit - o) * r) ends the near child's interval
 // and which starts the far child's.
-#define GLOME_PKW_STEP(SET, TAG, PL, NC, FC, OTH, ON, OP, RP, H, TN, TF)                                 \
+#define GLOME_PKW_STEP(SET, CUR, TAG, PL, NC, FC, OTH, ON, OP, RP, H, TN, TF)                            \
   "L_st" SET TAG "_%=:\n"                                                                               \
-  "  s_waitcnt lgkmcnt(0)\n"                /* the node is here */                                      \
+  "  s_waitcnt lgkmcnt(0)\n"                /* the node is here (and whatever else was asked for) */    \
   PKW_PREFETCH(OTH, NC)                                                                                 \
   PKW_EXP_STEP_(SET TAG)                                                                                \
   "  v_pk_add_f32 v[" T0 ":" T1 "], " PL ", %[" OP "] op_sel:[0," H "] op_sel_hi:[1," H "] neg_lo:[0,1] neg_hi:[0,1]\n" \
   "  v_pk_mul_f32 v[" T0 ":" T1 "], v[" T0 ":" T1 "], %[" RP "] op_sel:[0," H "] op_sel_hi:[1," H "]\n" \
   "  v_cmp_lt_f32 vcc, " TF ", %[far]\n"    /* lanes that reach the far child */                        \
   "  s_cbranch_vccz L_nf" SET TAG "_%=\n"                                                               \
+  "  v_cmp_lt_f32_e64 s[" K28 ":" K29 "], %[near], " TN "\n"  /* the near vote with EXEC left alone: the bits v_cmpx would give */ \
+  "  s_cmp_lg_u64 s[" K28 ":" K29 "], 0\n"                                                               \
+  "  s_cbranch_scc0 L_fo" SET TAG "_%=\n"   /* the far child alone: a step, not a push */               \
+  /* ---- both children are entered: the one case that pushes */                                        \
   "  s_cmp_ge_u32 m0, %[cap]\n"                                                                         \
   "  s_cbranch_scc1 L_slow_%=\n"                                                                        \
   /* the far child's interval starts at `fmax t2 near`; a NaN near (bbclip_ub's, Q1) must stay NaN, which v_max_f32 dropped.  gfx950's IEEE */ \
@@ -428,28 +457,37 @@ constexpr uint32_t PKREF_LEAF = 3u;  // low bits of a reference in the walk's ow
   "  ds_write_b32 v" T2 ", " TF "\n"        /* this lane's (near, far) of the far child */              \
   "  ds_write_b32 v" T2 ", %[far] offset:%[row1]\n"                                                     \
   "  s_add_u32 m0, m0, 1\n"                                                                             \
-  "L_nf" SET TAG "_%=:\n"                                                                               \
-  "  v_cmpx_lt_f32_e64 s[" K28 ":" K29 "], %[near], " TN "\n"  /* EXEC = the lanes that reach the near child */ \
-  "  s_cbranch_execz L_n1" SET TAG "_%=\n"                                                              \
+  "  s_mov_b64 exec, s[" K28 ":" K29 "]\n"  /* EXEC = the lanes that reach the near child: not empty */ \
   "  v_min_f32 %[far], " TN ", %[far]\n"                                                                \
   "  s_mov_b32 %[ref], " NC "\n"                                                                        \
   PKW_LATE_FETCH(OTH, NC)                                                                               \
   GLOME_PKW_DISPATCH(ON)                                                                                \
-  "L_n1" SET TAG "_%=:\n"                   /* nobody enters the near child */                          \
-  "  s_cbranch_vccz L_pop_%=\n"             /* nor the far one */                                       \
-  "  s_sub_u32 m0, m0, 1\n"                 /* the far child alone: it was pushed a moment ago, take it back */ \
-  "  s_mov_b64 exec, vcc\n"                                                                             \
-  "  v_mov_b32 %[near], " TF "\n"                                                                       \
+  /* ---- nobody reaches the far child (VCC = 0): the near one, or neither */                           \
+  "L_nf" SET TAG "_%=:\n"                                                                               \
+  "  v_cmpx_lt_f32_e64 s[" K28 ":" K29 "], %[near], " TN "\n"  /* EXEC = the lanes that reach the near child */ \
+  "  s_cbranch_execz L_pop_%=\n"                                                                        \
+  "  v_min_f32 %[far], " TN ", %[far]\n"                                                                \
+  "  s_mov_b32 %[ref], " NC "\n"                                                                        \
+  PKW_LATE_FETCH(OTH, NC)                                                                               \
+  GLOME_PKW_DISPATCH(ON)                                                                                \
+  /* ---- the far child alone (VCC = its lanes): nothing is pushed, m0 and the LDS rows are not touched, whatever the stack   */ \
+  /* holds.  Its node is asked for into THIS set, which is dead once %[ref] holds FC (the planes were read by v_pk_add, NC by */ \
+  /* the prefetch, FC by the s_mov); the prefetch, if still in flight, lands in the OTHER set, and the next step's own wait   */ \
+  /* covers both.  near = `fmax t2 near` on the far child's lanes, a NaN near staying NaN (see above)                         */ \
+  "L_fo" SET TAG "_%=:\n"                                                                               \
   "  s_mov_b32 %[ref], " FC "\n"                                                                        \
-  "  s_branch L_node_%=\n"
+  "  s_buffer_load_dwordx4 " CUR ", s[" K36 ":" K39 "], %[ref]\n"                                        \
+  "  s_mov_b64 exec, vcc\n"                                                                             \
+  "  v_maximum3_f32 %[near], " TF ", %[near], %[near]\n"                                                \
+  GLOME_PKW_DISPATCH(SET)
 
 // rays running towards +axis take the left child first (it ends at lsplit -> T0), the others the right one (rsplit -> T1)
-#define GLOME_PKW_STEP_FWD(SET, TAG, PL, L, R, OTH, ON, OP, RP, H) GLOME_PKW_STEP(SET, TAG, PL, L, R, OTH, ON, OP, RP, H, "v" T0, "v" T1)
-#define GLOME_PKW_STEP_BWD(SET, TAG, PL, L, R, OTH, ON, OP, RP, H) GLOME_PKW_STEP(SET, TAG, PL, R, L, OTH, ON, OP, RP, H, "v" T1, "v" T0)
-#define GLOME_PKW_STEPS(SET, PL, L, R, OTH, ON, AX, AY, AZ)                                             \
-  GLOME_PKW_STEP_##AX(SET, "X", PL, L, R, OTH, ON, "P0", "R0", "0")                                     \
-  GLOME_PKW_STEP_##AY(SET, "Y", PL, L, R, OTH, ON, "P0", "R0", "1")                                     \
-  GLOME_PKW_STEP_##AZ(SET, "Z", PL, L, R, OTH, ON, "P1", "R1", "0")                                     \
+#define GLOME_PKW_STEP_FWD(SET, CUR, TAG, PL, L, R, OTH, ON, OP, RP, H) GLOME_PKW_STEP(SET, CUR, TAG, PL, L, R, OTH, ON, OP, RP, H, "v" T0, "v" T1)
+#define GLOME_PKW_STEP_BWD(SET, CUR, TAG, PL, L, R, OTH, ON, OP, RP, H) GLOME_PKW_STEP(SET, CUR, TAG, PL, R, L, OTH, ON, OP, RP, H, "v" T1, "v" T0)
+#define GLOME_PKW_STEPS(SET, CUR, PL, L, R, OTH, ON, AX, AY, AZ)                                        \
+  GLOME_PKW_STEP_##AX(SET, CUR, "X", PL, L, R, OTH, ON, "P0", "R0", "0")                                \
+  GLOME_PKW_STEP_##AY(SET, CUR, "Y", PL, L, R, OTH, ON, "P0", "R0", "1")                                \
+  GLOME_PKW_STEP_##AZ(SET, CUR, "Z", PL, L, R, OTH, ON, "P1", "R1", "0")                                \
   GLOME_PKW_DISPATCH_TAIL(SET)
 #if defined(GLOME_PKW_EXP_NOPF)  // the near child's fetch at the END of the step: the same instructions, nothing overlapped
 #define PKW_PREFETCH(OTH, NC) ""
@@ -592,8 +630,8 @@ constexpr uint32_t PKREF_LEAF = 3u;  // low bits of a reference in the walk's ow
       "  s_buffer_load_dwordx4 " PKW_SETA ", s[" K36 ":" K39 "], %[ref]\n"   /* (the reference is the byte offset; its two low bits do not address) */ \
       GLOME_PKW_DISPATCH_FALL("A")                                                                                                \
       /* ------------------------------------------------------------ branch steps */                                          \
-      GLOME_PKW_STEPS("A", "s[" K0 ":" K1 "]", "s" K2, "s" K3, PKW_SETB, "B", AX, AY, AZ)                                        \
-      GLOME_PKW_STEPS("B", "s[" K4 ":" K5 "]", "s" K6, "s" K7, PKW_SETA, "A", AX, AY, AZ)                                        \
+      GLOME_PKW_STEPS("A", PKW_SETA, "s[" K0 ":" K1 "]", "s" K2, "s" K3, PKW_SETB, "B", AX, AY, AZ)                              \
+      GLOME_PKW_STEPS("B", PKW_SETB, "s[" K4 ":" K5 "]", "s" K6, "s" K7, PKW_SETA, "A", AX, AY, AZ)                              \
       /* ------------------------------------------------------------ a leaf: two triangles per test */                        \
       "L_leaf_%=:\n"                        /* %[ref] = byte offset of the first pair record | 3 */                             \
       "  s_mov_b64 s[" K34 ":" K35 "], exec\n"   /* the leaf's lanes */                                                         \

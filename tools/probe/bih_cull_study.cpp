@@ -217,7 +217,8 @@ int main(int argc, char** argv) {
     // events of the wave-wide walks per LIVE item (an item one of whose rays enters the root), for tools/probe/item_breakdown.py: a
     // packet steps through the union of its rays' branch nodes, pushes where one ray goes near and one goes far (and pops what it
     // pushed), and visits the union of its rays' leaves, testing a leaf of n triangles as ceil(n / 2) pairs
-    struct Ev { double items = 0, live = 0, walks = 0, steps = 0, pushes = 0, leaf_visits = 0, pair_tests = 0; } ev[2];  // [0] primary, [1] shadow
+    // (kind[m]: the steps by which children the packet's rays go into -- 0 neither, 1 the near one only, 2 the far one only, 3 both: the one kind that pushes)
+    struct Ev { double items = 0, live = 0, walks = 0, steps = 0, pushes = 0, leaf_visits = 0, pair_tests = 0, kind[4] = {0, 0, 0, 0}; } ev[2];  // [0] primary, [1] shadow
     std::vector<int> lv;
     std::vector<std::pair<int, int>> wv;
     auto tally = [&](Ev& e) {
@@ -227,7 +228,7 @@ int main(int argc, char** argv) {
       for (size_t a = 0; a < wv.size();) {
         size_t b = a; int m = 0;
         for (; b < wv.size() && wv[b].first == wv[a].first; b++) m |= wv[b].second;
-        steps++; pushes += m == 3; a = b;
+        steps++; pushes += m == 3; e.kind[m] += 1; a = b;
       }
       e.steps += steps; e.pushes += pushes; e.leaf_visits += (double)lv.size();
       for (int k : lv) e.pair_tests += (double)((S.T->nodes[k].items.size() + 1) / 2);
@@ -272,8 +273,9 @@ int main(int argc, char** argv) {
       printf("EVENTS {\"walk\": \"origin\", \"items_sampled\": %.0f, \"live_items\": %.0f", ev[0].items, ev[0].live);
       const char* nm[2] = {"primary", "shadow"};
       for (int w = 0; w < 2; w++)
-        printf(", \"%s\": {\"walks\": %.4f, \"branch_steps\": %.3f, \"pushes\": %.3f, \"leaf_visits\": %.3f, \"pair_tests\": %.3f}", nm[w], ev[w].walks / n, ev[w].steps / n,
-               ev[w].pushes / n, ev[w].leaf_visits / n, ev[w].pair_tests / n);
+        printf(", \"%s\": {\"walks\": %.4f, \"branch_steps\": %.3f, \"pushes\": %.3f, \"leaf_visits\": %.3f, \"pair_tests\": %.3f, \"near_only\": %.3f, \"far_only\": %.3f, \"both\": %.3f, "
+               "\"neither\": %.3f}", nm[w], ev[w].walks / n, ev[w].steps / n, ev[w].pushes / n, ev[w].leaf_visits / n, ev[w].pair_tests / n, ev[w].kind[1] / n, ev[w].kind[2] / n, ev[w].kind[3] / n,
+               ev[w].kind[0] / n);
       printf("}\n");
     }
     auto q = [](std::vector<long> v, double f) { std::sort(v.begin(), v.end()); return v[(size_t)(f * (v.size() - 1))]; };

@@ -2,9 +2,21 @@
 events of the wave-wide walks per live item of the S3 frame (tools/probe/bih_cull_study.cpp, its EVENTS line: branch steps, pushes, leaf
 visits and pair tests of the primary and of the shadow walk, counted on the CPU per 8 x 8 packet) times the instructions each event
 costs, read here from the flagship kernel's listing (tools/kernel_mix.py 1 leaves it in its output directory): the labels of an inlined
-walk block (bih_packet_asm.hpp) cut it into the step variants L_st* / L_nf* / L_n1*, the pair test L_tri .. L_pop and the pop
-L_pop .. L_empty.  What the counters give for a live item (tools/probe/item_overhead.py --pmc ... --live N) less the model's walks is
-what lies outside them.
+walk block (bih_packet_asm.hpp) cut it into the step variants L_st* / L_nf* / L_fo* (before round 11: L_n1*, and L_node for the far
+child's fetch), the pair test L_tri .. L_pop and the pop L_pop .. L_empty.  What the counters give for a live item
+(tools/probe/item_overhead.py --pmc ... --live N) less the model's walks is what lies outside them.
+
+A branch step is priced by its KIND, each by its own path through the listing (the EVENTS line's near_only / far_only / both / neither:
+which children the packet's rays go into):
+  near only   L_st up to the far vote, then L_nf
+  neither     L_st up to the far vote, the near vote and its branch to the pop (the pop itself is not charged: see below)
+  both        the whole of L_st: both votes, the capacity test, the push, the near child's dispatch (before round 11: L_st with its push,
+              then L_nf)
+  far only    L_st up to the near vote's branch, then L_fo (before round 11: L_st WITH its push, the near vote, L_n1 which takes the push
+              back, L_node's wait and fetch and its dispatch)
+A dispatch is counted at its longest path (five instructions; four or two are executed for three of the four targets).  An EVENTS line
+without the four kinds (older than round 11) is priced as before: one figure per step, the push where both children are entered -- which
+charged the parent's far-only steps 15 instructions too few each and put them into "outside the walks".
 
 Pops are charged per push (pops = pushes): every entry pushed is popped once.  The pop that finds the stack empty and ends a walk -- one
 per walk that left its root branch -- is charged nowhere, so the model's walks are short by up to one pop (20 instructions) per walk,
@@ -63,7 +75,7 @@ def main():
             if s == f"L_end_{cur}:":
                 cur = None
     # one block's segments (every block has the same shape; the mean over the blocks is reported)
-    cost = {"step": [], "push": [], "pair": [], "pop": [], "leaf_entry": []}
+    cost = {"step": [], "push": [], "near_only": [], "far_only": [], "both": [], "neither": [], "pair": [], "pop": [], "leaf_entry": []}
     for n, b in blocks.items():
         seg, name = {}, None
         for s in b:
@@ -78,8 +90,21 @@ def main():
             tag = k[len("L_st"):]
             body = seg[k]
             cut = next(i for i, s in enumerate(body) if s.startswith("s_cbranch_vccz L_nf")) + 1  # up to the vote "does any lane enter the far child"
-            cost["step"].append(cut + len(seg["L_nf" + tag]))
-            cost["push"].append(len(body) - cut)
+            nf = seg["L_nf" + tag]
+            vote = next(i for i, s in enumerate(nf) if s.startswith("s_cbranch_execz")) + 1  # the near vote and its branch
+            cost["step"].append(cut + len(nf))
+            cost["near_only"].append(cut + len(nf))
+            if "L_fo" + tag in seg:  # the far child entered alone is a step of its own
+                fo = next(i for i, s in enumerate(body) if s.startswith("s_cbranch_scc0 L_fo")) + 1
+                cost["push"].append(len(body) - cut - (len(nf) - vote))  # (what a step that pushes costs beyond a near-only one)
+                cost["both"].append(len(body))
+                cost["far_only"].append(fo + len(seg["L_fo" + tag]))
+                cost["neither"].append(cut + vote)
+            else:  # it is pushed and taken back, and its node fetched through L_node
+                cost["push"].append(len(body) - cut)
+                cost["both"].append(len(body) + len(nf))
+                cost["far_only"].append(len(body) + vote + len(seg["L_n1" + tag]) + len(seg[f"L_node_{n}"]) + len(seg[f"L_node2_{n}"]))
+                cost["neither"].append(cut + vote + 1)
         cost["pair"].append(len(seg[f"L_tri_{n}"]))
         cost["pop"].append(len(seg[f"L_pop_{n}"]))
         cost["leaf_entry"].append(len(seg[f"L_leaf_{n}"]) + len(seg.get(f"L_zlA_{n}", [])))
@@ -87,15 +112,19 @@ def main():
     rows, walks = [], 0.0
     for w in ("primary", "shadow"):
         e = ev[w]
-        parts = {"branch steps": e["branch_steps"] * c["step"], "pushes": e["pushes"] * c["push"], "pops": e["pushes"] * c["pop"],
-                 "pair tests": e["pair_tests"] * c["pair"], "leaf entries": e["leaf_visits"] * c["leaf_entry"]}
+        if "far_only" in e:
+            parts = {k.replace("_", " ") + " steps": e[k] * c[k] for k in ("near_only", "far_only", "both", "neither")}
+        else:
+            parts = {"branch steps": e["branch_steps"] * c["step"], "pushes": e["pushes"] * c["push"]}
+        parts.update({"pops": e["pushes"] * c["pop"], "pair tests": e["pair_tests"] * c["pair"], "leaf entries": e["leaf_visits"] * c["leaf_entry"]})
         rows.append((w, e, parts))
         walks += sum(parts.values())
     print(f"listing: {total} instructions, {inside} inside the {len(blocks)} walk blocks, {total - inside} outside")
     print("per event (listing): " + ", ".join(f"{k} {v:.1f}" for k, v in c.items()))
     print(f"events per live item ({ev['live_items']} live of {ev['items_sampled']} sampled items):")
     for w, e, parts in rows:
-        print(f"  {w:8s} walks {e['walks']:.2f}  steps {e['branch_steps']:.1f}  pushes = pops {e['pushes']:.1f}  leaf visits {e['leaf_visits']:.1f}  pair tests {e['pair_tests']:.1f}")
+        kinds = "  (near only {near_only:.1f}, far only {far_only:.1f}, both {both:.1f}, neither {neither:.1f})".format(**e) if "far_only" in e else ""
+        print(f"  {w:8s} walks {e['walks']:.2f}  steps {e['branch_steps']:.1f}{kinds}  pushes = pops {e['pushes']:.1f}  leaf visits {e['leaf_visits']:.1f}  pair tests {e['pair_tests']:.1f}")
         print("           instructions: " + ", ".join(f"{k} {v:.0f}" for k, v in parts.items()) + f"  = {sum(parts.values()):.0f}")
     print(f"in the walks (model): {walks:.0f} per live item")
     if "--counted" in sys.argv:
