@@ -16,11 +16,12 @@
 //   lanes        the set of lanes whose interval reaches the current node lives in EXEC, not in a scalar pair: a vote is a
 //                v_cmp into VCC or a v_cmpx (which narrows EXEC itself) followed by s_cbranch_vccz / s_cbranch_execz -- no
 //                s_and, no s_cmp, no mask moves.  Lanes outside EXEC keep stale intervals that nobody reads.
-//   branch step  by which children the packet enters (instructions as listed, the dispatch at its longest; per live item of the
-//                flagship frame, both walks, tools/probe/bih_cull_study.cpp): the near one only 15 (32.2 steps), the far one
-//                only 18 (36.5), both 27 (26.8), neither 8 and a pop (9.1).  Round 2's step was 21 scalar-type instructions
-//                alone.  The walk reads its own copy of the nodes (DScene::pknodes,
-//                flatten.hpp): a branch child's reference is its byte offset with the child's AXIS in the two low bits, a leaf
+//   branch step  by which children the packet enters (instructions without the dispatch that ends the step; per live item of the
+//                flagship frame, both walks, tools/probe/bih_cull_study.cpp): the near one only 10 (32.2 steps), the far one
+//                only 13 (36.5), both 21 (26.8), neither 8 and a pop (9.1).  Round 2's step was 21 scalar-type instructions
+//                alone.  The dispatch -- 2 to 7 instructions by the site it leaves from and the kind of node it goes to, 3.8 on
+//                average where the one form of rounds 2 to 11 took 4.6 -- is priced at GLOME_PKW_AFTER_X below.  The walk
+//                reads its own copy of the nodes (DScene::pknodes, flatten.hpp): a branch child's reference is its byte offset with the child's AXIS in the two low bits, a leaf
 //                child's is the byte offset of its first pair record with both low bits set, so two bit tests pick the next
 //                piece of code and nothing is shifted or masked.  As soon as a node has arrived the NEAR child's node -- the
 //                next step in 56 % of the steps (near only or both) -- is asked for into the other of two register sets (A / B),
@@ -32,7 +33,8 @@
 //                child or to the pops.  Not empty: the near vote is taken WITHOUT touching EXEC (v_cmp_lt_f32_e64 into
 //                s[K28:K29]: under EXEC = the node's lanes the bits are v_cmpx's) and one scalar compare of that pair picks
 //                between the two remaining kinds.  BOTH children entered is the only step that pushes: capacity test, the
-//                entry (EXEC still the node's lanes, the entry's mask VCC), then EXEC = s[K28:K29], known not to be empty.  THE
+//                entry (EXEC still the node's lanes, the entry's mask VCC; the lane's near and far go to their two LDS rows in one
+//                ds_write2st64_b32: the rows lie CAP * 256 bytes apart), then EXEC = s[K28:K29], known not to be empty.  THE
 //                FAR CHILD ALONE is a third of all steps, not a rare case: descending to where a packet lies picks the far side
 //                about as often as the near side, and a near child that is an empty leaf (plane at -+inf, flatten.hpp) makes
 //                12 of the 36.5 static.  It costs no capacity test, no writelane, no LDS write and no m0 traffic (until round
@@ -64,8 +66,12 @@
 //                register pairs ((ox, oy) (oz, dx) (dy, dz)) through op_sel, which broadcasts either half.  The rejection
 //                tests are two chains of v_cmpx, A's first (its update moves `far`, which B's last test reads: `nearest`,
 //                ties -> later item); a leaf's odd last triangle is a pair whose B half is computed and ignored.  A hit
-//                records the triangle's record index, which the pair record carries.
-//   pop          7 scalar-type.
+//                records the triangle's record index: the pair record carries A's, B's is the next (one v_add_u32 on the lanes
+//                that hit; until round 12 an s_add_u32 per pair test and a v_mov).
+//   pop          6 scalar-type and the dispatch.  ONE test of the stack pointer: m0 - 1 is >= CAP, unsigned, for an entry beyond
+//                the LDS part and for the empty stack alike (0xffffffff); L_popslow tells them apart, two instructions on the one
+//                pop that ends a walk instead of one on every pop.  Entered with phase != 0 and sp = 0 the block so leaves through
+//                L_empty: status 0, am = 0, sp = 0.
 //
 // What it declines goes back to the C++ loop for one step (status codes below): pushes and pops beyond the LDS part of the
 // stack (global overflow columns).  The wave-uniform part of the stack (reference and lane mask of entry k in lane k of three
@@ -93,7 +99,7 @@ namespace glome {
 // destinations), K0 .. K39 below.
 //   K0..K3 node set A, K4..K7 node set B (lsplit, rsplit, left, right) | K8..K25 a pair record (p1x p1y p1z e1x e1y e1z e2x e2y
 //   e2z, each as (A, B)), K26 the triangles left in its leaf, K27 the first one's record index | K28 K29 a popped entry's mask, v_cmpx's other
-//   destination | K30 K31 EXEC at entry | K32 the caller's m0 | K33 the second triangle's record | K34 K35 a leaf's lanes |
+//   destination | K30 K31 EXEC at entry | K32 the caller's m0 | K33 the destination of a dispatch's s_and (nothing reads it) | K34 K35 a leaf's lanes |
 //   K36..K39 buffer descriptor over the node pool
 #ifndef GLOME_PKW_BASE
 #define GLOME_PKW_BASE 36
@@ -390,23 +396,56 @@ namespace glome {
 enum : int { PKW_DONE = 0, PKW_PUSH_OVERFLOW = 1, PKW_POP_OVERFLOW = 3 };
 constexpr uint32_t PKREF_LEAF = 3u;  // low bits of a reference in the walk's own form: 0 / 1 / 2 = a branch splitting x / y / z, 3 = a leaf
 
-// where to go with the reference in %[ref]: 00 / 01 / 10 = a branch along x / y / z whose node is arriving in set S, 11 = a leaf
-#define GLOME_PKW_DISPATCH(S)                                                                           \
+// Where to go with the reference in %[ref]: 00 / 01 / 10 = a branch along x / y / z whose node is arriving in set S, 11 = a leaf.
+// One form per SITE (round 12), its test order taken from where the dispatches of that site go (tools/probe/bih_cull_study.cpp's
+// TRANS line; the tree cycles through its axes: Z is followed by X in 57 % of the cases, X by Y or Z in 76 %, X by X and Z by Z
+// almost never).  A bit test and its branch cost 2, `s_and_b32 tmp, ref, 3` sets SCC = (kind != 0), which takes X out in 2; a target
+// that follows physically needs no s_branch: the (Z, leaf) tail of a set stands in front of its Z step and the (X, Y) tail of set A
+// in front of its X step, so whoever reaches them pays 4 for either target.
+//   after an X step   Y 4, Z 4, leaf 4, X 5     (X follows X least)
+//   after a Y step    X 2, Z 4, leaf 6, Y 7
+//   after a Z step    X 2, Y 4, leaf 6, Z 7
+//   after a pop       X 4, Y 4, Z 4, leaf 5     (always into set A)
+//   at the root       X 4, Y 4, Z 4, leaf 4     (L_node / L_node2: a fresh walk, and a re-entry after a C++ step)
+// s[K33] is the s_and's destination, nothing reads it.
+#define GLOME_PKW_AFTER_X(S)                                                                            \
   "  s_bitcmp1_b32 %[ref], 1\n"                                                                         \
   "  s_cbranch_scc1 L_zl" S "_%=\n"                                                                     \
   "  s_bitcmp1_b32 %[ref], 0\n"                                                                         \
   "  s_cbranch_scc1 L_st" S "Y_%=\n"                                                                    \
   "  s_branch L_st" S "X_%=\n"
-#define GLOME_PKW_DISPATCH_FALL(S) /* ... and the X piece follows */                                     \
-  "  s_bitcmp1_b32 %[ref], 1\n"                                                                         \
-  "  s_cbranch_scc1 L_zl" S "_%=\n"                                                                     \
+#define GLOME_PKW_AFTER_Y(S)                                                                            \
+  "  s_and_b32 s" K33 ", %[ref], 3\n"                                                                   \
+  "  s_cbranch_scc0 L_st" S "X_%=\n"                                                                    \
   "  s_bitcmp1_b32 %[ref], 0\n"                                                                         \
-  "  s_cbranch_scc1 L_st" S "Y_%=\n"
-#define GLOME_PKW_DISPATCH_TAIL(S)                                                                      \
-  "L_zl" S "_%=:\n"                                                                                     \
+  "  s_cbranch_scc0 L_st" S "Z_%=\n"                                                                    \
+  "  s_bitcmp1_b32 %[ref], 1\n"                                                                         \
+  "  s_cbranch_scc1 L_leaf_%=\n"                                                                        \
+  "  s_branch L_st" S "Y_%=\n"
+#define GLOME_PKW_AFTER_Z(S)                                                                            \
+  "  s_and_b32 s" K33 ", %[ref], 3\n"                                                                   \
+  "  s_cbranch_scc0 L_st" S "X_%=\n"                                                                    \
+  "  s_bitcmp1_b32 %[ref], 1\n"                                                                         \
+  "  s_cbranch_scc0 L_st" S "Y_%=\n"                                                                    \
   "  s_bitcmp1_b32 %[ref], 0\n"                                                                         \
   "  s_cbranch_scc1 L_leaf_%=\n"                                                                        \
   "  s_branch L_st" S "Z_%=\n"
+#define GLOME_PKW_AFTER_POP /* into set A, whose (X, Y) tail stands at the root */                       \
+  "  s_bitcmp1_b32 %[ref], 1\n"                                                                         \
+  "  s_cbranch_scc0 L_xyA_%=\n"                                                                         \
+  "  s_bitcmp1_b32 %[ref], 0\n"                                                                         \
+  "  s_cbranch_scc0 L_stAZ_%=\n"                                                                        \
+  "  s_branch L_leaf_%=\n"
+#define GLOME_PKW_AT_ROOT /* ... and set A's X step follows */                                           \
+  "  s_bitcmp1_b32 %[ref], 1\n"                                                                         \
+  "  s_cbranch_scc1 L_zlA_%=\n"                                                                         \
+  "L_xyA_%=:\n"                                                                                         \
+  "  s_bitcmp1_b32 %[ref], 0\n"                                                                         \
+  "  s_cbranch_scc1 L_stAY_%=\n"
+#define GLOME_PKW_ZL_TAIL(S) /* ... and the set's Z step follows */                                      \
+  "L_zl" S "_%=:\n"                                                                                     \
+  "  s_bitcmp1_b32 %[ref], 0\n"                                                                         \
+  "  s_cbranch_scc1 L_leaf_%=\n"
 
 
 // Sensitivity experiments (measurement builds only, tools/build_variants.py): extra work of one kind per branch step or per
@@ -431,7 +470,7 @@ constexpr uint32_t PKREF_LEAF = 3u;  // low bits of a reference in the walk's ow
 // pairs (P0 = (ox, oy), P1 = (oz, dx); R0 = (rx, ry), R1 = (rz, .)): the pair operand and the op_sel bit that broadcasts its
 // low or high half.  TN / TF: which half of (T0, T1) = ((lsplit - o) * r, (rsplit - o) * r) ends the near child's interval
 // and which starts the far child's.
-#define GLOME_PKW_STEP(SET, CUR, TAG, PL, NC, FC, OTH, ON, OP, RP, H, TN, TF)                            \
+#define GLOME_PKW_STEP(SET, CUR, TAG, DSP, PL, NC, FC, OTH, ON, OP, RP, H, TN, TF)                            \
   "L_st" SET TAG "_%=:\n"                                                                               \
   "  s_waitcnt lgkmcnt(0)\n"                /* the node is here (and whatever else was asked for) */    \
   PKW_PREFETCH(OTH, NC)                                                                                 \
@@ -454,14 +493,13 @@ constexpr uint32_t PKREF_LEAF = 3u;  // low bits of a reference in the walk's ow
   "  v_writelane_b32 %[ulo], vcc_lo, m0\n"                                                              \
   "  v_writelane_b32 %[uhi], vcc_hi, m0\n"                                                              \
   "  v_lshl_add_u32 v" T2 ", m0, 8, %[lds]\n"                                                           \
-  "  ds_write_b32 v" T2 ", " TF "\n"        /* this lane's (near, far) of the far child */              \
-  "  ds_write_b32 v" T2 ", %[far] offset:%[row1]\n"                                                     \
+  "  ds_write2st64_b32 v" T2 ", " TF ", %[far] offset0:0 offset1:%[cap]\n"  /* this lane's (near, far) of the far child: the far row lies CAP * 256 bytes on */ \
   "  s_add_u32 m0, m0, 1\n"                                                                             \
   "  s_mov_b64 exec, s[" K28 ":" K29 "]\n"  /* EXEC = the lanes that reach the near child: not empty */ \
   "  v_min_f32 %[far], " TN ", %[far]\n"                                                                \
   "  s_mov_b32 %[ref], " NC "\n"                                                                        \
   PKW_LATE_FETCH(OTH, NC)                                                                               \
-  GLOME_PKW_DISPATCH(ON)                                                                                \
+  DSP(ON)                                                                                               \
   /* ---- nobody reaches the far child (VCC = 0): the near one, or neither */                           \
   "L_nf" SET TAG "_%=:\n"                                                                               \
   "  v_cmpx_lt_f32_e64 s[" K28 ":" K29 "], %[near], " TN "\n"  /* EXEC = the lanes that reach the near child */ \
@@ -469,7 +507,7 @@ constexpr uint32_t PKREF_LEAF = 3u;  // low bits of a reference in the walk's ow
   "  v_min_f32 %[far], " TN ", %[far]\n"                                                                \
   "  s_mov_b32 %[ref], " NC "\n"                                                                        \
   PKW_LATE_FETCH(OTH, NC)                                                                               \
-  GLOME_PKW_DISPATCH(ON)                                                                                \
+  DSP(ON)                                                                                               \
   /* ---- the far child alone (VCC = its lanes): nothing is pushed, m0 and the LDS rows are not touched, whatever the stack   */ \
   /* holds.  Its node is asked for into THIS set, which is dead once %[ref] holds FC (the planes were read by v_pk_add, NC by */ \
   /* the prefetch, FC by the s_mov); the prefetch, if still in flight, lands in the OTHER set, and the next step's own wait   */ \
@@ -479,16 +517,16 @@ constexpr uint32_t PKREF_LEAF = 3u;  // low bits of a reference in the walk's ow
   "  s_buffer_load_dwordx4 " CUR ", s[" K36 ":" K39 "], %[ref]\n"                                        \
   "  s_mov_b64 exec, vcc\n"                                                                             \
   "  v_maximum3_f32 %[near], " TF ", %[near], %[near]\n"                                                \
-  GLOME_PKW_DISPATCH(SET)
+  DSP(SET)
 
 // rays running towards +axis take the left child first (it ends at lsplit -> T0), the others the right one (rsplit -> T1)
-#define GLOME_PKW_STEP_FWD(SET, CUR, TAG, PL, L, R, OTH, ON, OP, RP, H) GLOME_PKW_STEP(SET, CUR, TAG, PL, L, R, OTH, ON, OP, RP, H, "v" T0, "v" T1)
-#define GLOME_PKW_STEP_BWD(SET, CUR, TAG, PL, L, R, OTH, ON, OP, RP, H) GLOME_PKW_STEP(SET, CUR, TAG, PL, R, L, OTH, ON, OP, RP, H, "v" T1, "v" T0)
+#define GLOME_PKW_STEP_FWD(SET, CUR, TAG, DSP, PL, L, R, OTH, ON, OP, RP, H) GLOME_PKW_STEP(SET, CUR, TAG, DSP, PL, L, R, OTH, ON, OP, RP, H, "v" T0, "v" T1)
+#define GLOME_PKW_STEP_BWD(SET, CUR, TAG, DSP, PL, L, R, OTH, ON, OP, RP, H) GLOME_PKW_STEP(SET, CUR, TAG, DSP, PL, R, L, OTH, ON, OP, RP, H, "v" T1, "v" T0)
 #define GLOME_PKW_STEPS(SET, CUR, PL, L, R, OTH, ON, AX, AY, AZ)                                        \
-  GLOME_PKW_STEP_##AX(SET, CUR, "X", PL, L, R, OTH, ON, "P0", "R0", "0")                                \
-  GLOME_PKW_STEP_##AY(SET, CUR, "Y", PL, L, R, OTH, ON, "P0", "R0", "1")                                \
-  GLOME_PKW_STEP_##AZ(SET, CUR, "Z", PL, L, R, OTH, ON, "P1", "R1", "0")                                \
-  GLOME_PKW_DISPATCH_TAIL(SET)
+  GLOME_PKW_STEP_##AX(SET, CUR, "X", GLOME_PKW_AFTER_X, PL, L, R, OTH, ON, "P0", "R0", "0")             \
+  GLOME_PKW_STEP_##AY(SET, CUR, "Y", GLOME_PKW_AFTER_Y, PL, L, R, OTH, ON, "P0", "R0", "1")             \
+  GLOME_PKW_ZL_TAIL(SET)                                                                                \
+  GLOME_PKW_STEP_##AZ(SET, CUR, "Z", GLOME_PKW_AFTER_Z, PL, L, R, OTH, ON, "P1", "R1", "0")
 #if defined(GLOME_PKW_EXP_NOPF)  // the near child's fetch at the END of the step: the same instructions, nothing overlapped
 #define PKW_PREFETCH(OTH, NC) ""
 #define PKW_LATE_FETCH(OTH, NC) "  s_buffer_load_dwordx4 " OTH ", s[" K36 ":" K39 "], " NC "\n"
@@ -578,12 +616,14 @@ constexpr uint32_t PKREF_LEAF = 3u;  // low bits of a reference in the walk's ow
 #define GLOME_PKW_CHAIN_A GLOME_PKW_CHAIN(T12, T6, T8, T2)
 #define GLOME_PKW_CHAIN_B GLOME_PKW_CHAIN(T13, T7, T9, T3)
 
-// what the lanes that hit do (EXEC = those lanes; TT = the half that holds their t, REC = the scalar register that names the
-// triangle: its pair record's byte offset).  MODE 2 goes on to the pops when no lane of the leaf is left.
+// what the lanes that hit do (EXEC = those lanes; TT = the half that holds their t, REC = the instruction that names the triangle:
+// the pair record carries A's record index, B's is the next).  MODE 2 goes on to the pops when no lane of the leaf is left.
+#define PKW_REC_A "  v_mov_b32 %[best_rec], s" K27 "\n"
+#define PKW_REC_B "  v_add_u32_e64 %[best_rec], s" K27 ", 1\n"
 #define GLOME_PKW_UPDATE_1(TT, REC)                                                                   \
   "  v_mov_b32 %[best_t], v" TT "\n"                                                                  \
   "  v_mov_b32 %[far], v" TT "\n"           /* far = min(far, t) = t: the test just passed t <= far */ \
-  "  v_mov_b32 %[best_rec], " REC "\n"
+  REC
 #define GLOME_PKW_UPDATE_2(TT, REC)                                                                   \
   "  s_or_b64 %[occ], %[occ], exec\n"                                                                 \
   "  s_andn2_b64 s[" K34 ":" K35 "], s[" K34 ":" K35 "], exec\n"   /* an occluded ray is finished; SCC = rays left in this leaf */ \
@@ -628,7 +668,7 @@ constexpr uint32_t PKREF_LEAF = 3u;  // low bits of a reference in the walk's ow
       "  s_waitcnt lgkmcnt(0)\n"            /* a prefetch that was not used has landed: the set is free */                      \
       "L_node2_%=:\n"                                                                                                           \
       "  s_buffer_load_dwordx4 " PKW_SETA ", s[" K36 ":" K39 "], %[ref]\n"   /* (the reference is the byte offset; its two low bits do not address) */ \
-      GLOME_PKW_DISPATCH_FALL("A")                                                                                                \
+      GLOME_PKW_AT_ROOT                                                                                                          \
       /* ------------------------------------------------------------ branch steps */                                          \
       GLOME_PKW_STEPS("A", PKW_SETA, "s[" K0 ":" K1 "]", "s" K2, "s" K3, PKW_SETB, "B", AX, AY, AZ)                              \
       GLOME_PKW_STEPS("B", PKW_SETB, "s[" K4 ":" K5 "]", "s" K6, "s" K7, PKW_SETA, "A", AX, AY, AZ)                              \
@@ -639,15 +679,14 @@ constexpr uint32_t PKREF_LEAF = 3u;  // low bits of a reference in the walk's ow
       "  s_load_dwordx16 s[" K8 ":" K23 "], %[pairs], %[ref]\n"                                                                 \
       "  s_load_dwordx4 s[" K24 ":" K27 "], %[pairs], %[ref] offset:0x40\n"                                                     \
       "  s_waitcnt lgkmcnt(0)\n"                                                                                                \
-      "  s_add_u32 s" K33 ", s" K27 ", 1\n" /* the second triangle's record index */                                           \
       GLOME_PKW_PAIR_ARITH                                                                                                      \
       GLOME_PKW_CHAIN_A                                                                                                         \
-      GLOME_PKW_UPDATE_##M(T2, "s" K27)                                                                                        \
+      GLOME_PKW_UPDATE_##M(T2, PKW_REC_A)                                                                                   \
       "  s_cmp_eq_u32 s" K26 ", 1\n"                                                                                            \
       "  s_cbranch_scc1 L_pop_%=\n"         /* that was the leaf's last */                                                      \
       "  s_mov_b64 exec, s[" K34 ":" K35 "]\n"                                                                                  \
       GLOME_PKW_CHAIN_B                                                                                                         \
-      GLOME_PKW_UPDATE_##M(T3, "s" K33)                                                                                         \
+      GLOME_PKW_UPDATE_##M(T3, PKW_REC_B)                                                                                        \
       "  s_cmp_eq_u32 s" K26 ", 2\n"                                                                                            \
       "  s_cbranch_scc1 L_pop_%=\n"                                                                                             \
       "  s_add_u32 %[ref], %[ref], 80\n"                                                                                        \
@@ -655,8 +694,7 @@ constexpr uint32_t PKREF_LEAF = 3u;  // low bits of a reference in the walk's ow
       "  s_branch L_tri_%=\n"                                                                                                   \
       /* ------------------------------------------------------------ pop until an entry some lane still wants */              \
       "L_pop_%=:\n"                                                                                                             \
-      "  s_sub_u32 m0, m0, 1\n"             /* SCC = the stack was empty */                                                     \
-      "  s_cbranch_scc1 L_empty_%=\n"                                                                                           \
+      "  s_sub_u32 m0, m0, 1\n"             /* an empty stack leaves 0xffffffff: one test for that and for an entry beyond the LDS part */ \
       "  s_cmp_ge_u32 m0, %[cap]\n"                                                                                             \
       "  s_cbranch_scc1 L_popslow_%=\n"                                                                                         \
       "  v_readlane_b32 %[ref], %[ur], m0\n"                                                                                    \
@@ -669,7 +707,7 @@ constexpr uint32_t PKREF_LEAF = 3u;  // low bits of a reference in the walk's ow
       "  s_waitcnt lgkmcnt(0)\n"                                                                                                \
       GLOME_PKW_FILTER_##M                                                                                                      \
       "  s_buffer_load_dwordx4 " PKW_SETA ", s[" K36 ":" K39 "], %[ref]\n"   /* (as at L_node2: nothing is in flight behind that wait) */ \
-      GLOME_PKW_DISPATCH("A")                                                                                                   \
+      GLOME_PKW_AFTER_POP                                                                                                      \
       /* ------------------------------------------------------------ exits */                                                 \
       "L_empty_%=:\n"                                                                                                           \
       "  s_mov_b32 m0, 0\n"                                                                                                     \
@@ -680,7 +718,9 @@ constexpr uint32_t PKREF_LEAF = 3u;  // low bits of a reference in the walk's ow
       "  s_mov_b64 %[am], exec\n"                                                                                               \
       "  s_mov_b32 %[status], 1\n"                                                                                              \
       "  s_branch L_dump_%=\n"                                                                                                  \
-      "L_popslow_%=:\n"                       /* the top entry lives in the overflow columns */                                 \
+      "L_popslow_%=:\n"                       /* the stack was empty, or the top entry lives in the overflow columns */        \
+      "  s_cmp_eq_u32 m0, -1\n"                                                                                                 \
+      "  s_cbranch_scc1 L_empty_%=\n"                                                                                           \
       "  s_add_u32 m0, m0, 1\n"                                                                                                 \
       "  s_mov_b32 %[status], 3\n"                                                                                              \
       "L_dump_%=:\n"                          /* a C++ step follows: the entries (lane k = entry k) leave the registers */       \
@@ -717,6 +757,7 @@ template <int MODE, bool XF, bool YF, bool ZF, int CAP>
 __device__ __forceinline__ int bih_walk_asm(const F4* nodes, uint32_t nbytes, const float* pairs, int phase, uint32_t& ref, LaneMask& am, int& sp, float& nearv, float& farv,
                                             float& best_t, uint32_t& best_rec, LaneMask& occm, V3 o, V3 rcp, V3 d, uint32_t lds_row, uint32_t* dump) {
   static_assert(MODE == 1 || MODE == 2, "the hand-written walk covers the production traversals only");
+  static_assert(CAP > 0 && CAP < 256, "the push reaches the far row through ds_write2st64's 8-bit offset");
   int status;
   uint32_t ur, ulo, uhi;  // the wave-uniform part of the stack, entry k in lane k -- alive inside the asm block only
   // the ray as aligned register pairs (op_sel picks a half): origin and direction for the triangle tests, origin and

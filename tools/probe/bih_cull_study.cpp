@@ -10,6 +10,8 @@
 //   origin   the walk as it is, but the root interval starts at the ray's origin: near = max(near, -FLT_MIN) (bih_clip_root_at_origin,
 //            rt_device.hpp) -- in the closest-hit walk and in the any-hit walk.  Every shadow result is compared with the unclipped walk's.
 // A cull only ever drops nodes in which nothing can be hit: results are unchanged (checked: same hits).
+// Per 8 x 8 packet of the `origin` walk it also prints, per live item, the events of the wave-wide walks (EVENTS) and where the dispatches
+// of the hand-written walk go, by the site they leave from (TRANS): what tools/probe/item_breakdown.py prices.
 //
 //   g++ -O2 -std=c++17 -I glome_amd/csrc -I include tools/probe/bih_cull_study.cpp -o /tmp/bih_cull_study && /tmp/bih_cull_study 224 8 3
 //   (S5: 708 8 3 -- N > 300 selects the 3840 x 2160 frame)
@@ -38,7 +40,8 @@ struct Study {
   long pushes = 0;
   std::vector<int>* visited = nullptr;  // when set: every branch node entered is appended
   // the per-packet events of item_breakdown.py: every non-empty leaf entered; per branch node entered, which children the ray goes into
-  // (1 = the near child, 2 = the far child); did the ray pass the root's entry test
+  // (1 = the near child, 2 = the far child; 4 = the ray runs towards +axis there, so the near child is the left one); did the ray pass
+  // the root's entry test
   std::vector<int>* leaves = nullptr;
   std::vector<std::pair<int, int>>* went = nullptr;
   bool entered = false;
@@ -115,7 +118,7 @@ struct Study {
           double t1 = fwd ? dl : dr, t2 = fwd ? dr : dl;
           bool e1 = T->nodes[c1].leaf && T->nodes[c1].items.empty(), e2 = T->nodes[c2].leaf && T->nodes[c2].items.empty();
           bool go1 = nearv < t1 && !e1, go2 = t2 < farv && !e2;
-          if (went) went->push_back({k, (go1 ? 1 : 0) | (go2 ? 2 : 0)});
+          if (went) went->push_back({k, (go1 ? 1 : 0) | (go2 ? 2 : 0) | (fwd ? 4 : 0)});
           if (go1) {
             if (go2) { st.push_back({c2, std::max(t2, nearv), farv}); pushes++; }
             k = c1; farv = std::min(t1, farv); pop = false;
@@ -218,18 +221,36 @@ int main(int argc, char** argv) {
     // packet steps through the union of its rays' branch nodes, pushes where one ray goes near and one goes far (and pops what it
     // pushed), and visits the union of its rays' leaves, testing a leaf of n triangles as ceil(n / 2) pairs
     // (kind[m]: the steps by which children the packet's rays go into -- 0 neither, 1 the near one only, 2 the far one only, 3 both: the one kind that pushes)
-    struct Ev { double items = 0, live = 0, walks = 0, steps = 0, pushes = 0, leaf_visits = 0, pair_tests = 0, kind[4] = {0, 0, 0, 0}; } ev[2];  // [0] primary, [1] shadow
+    // trans[s][t]: the dispatches of the hand-written walk (bih_packet_asm.hpp: the branch on a reference's two low bits that ends every step
+    // and every pop) by the SITE they leave from -- 0 / 1 / 2 after a step of a node that splits x / y / z, 3 after a pop, 4 at the root --
+    // and the kind of node they go to: 0 / 1 / 2 a branch along x / y / z, 3 a leaf.  A step dispatches to the child the packet goes on
+    // with: the near one when any ray enters it, else the far one; the far child of a both-step is reached by the pop of its entry, when a
+    // ray still enters it then (a ray that has found a nearer hit, or an occluder, does not); a step that enters neither child dispatches nothing.
+    struct Ev { double items = 0, live = 0, walks = 0, steps = 0, pushes = 0, leaf_visits = 0, pair_tests = 0, kind[4] = {0, 0, 0, 0}, trans[5][4] = {}; } ev[2];  // [0] primary, [1] shadow
     std::vector<int> lv;
     std::vector<std::pair<int, int>> wv;
     auto tally = [&](Ev& e) {
       std::sort(lv.begin(), lv.end()); lv.erase(std::unique(lv.begin(), lv.end()), lv.end());
       std::sort(wv.begin(), wv.end());
       long steps = 0, pushes = 0;
+      const auto& N = S.T->nodes;
+      auto kind_of = [&](int k) { return N[k].leaf ? 3 : N[k].axis; };
+      auto entered = [&](int k) {  // by any ray of the packet: a branch node has a record in wv, a leaf one in lv
+        if (N[k].leaf) return std::binary_search(lv.begin(), lv.end(), k);
+        auto it = std::lower_bound(wv.begin(), wv.end(), std::make_pair(k, 0));
+        return it != wv.end() && it->first == k;
+      };
       for (size_t a = 0; a < wv.size();) {
         size_t b = a; int m = 0;
         for (; b < wv.size() && wv[b].first == wv[a].first; b++) m |= wv[b].second;
+        const int k = wv[a].first, fwd = (wv[a].second & 4) != 0, c1 = fwd ? N[k].left : N[k].right, c2 = fwd ? N[k].right : N[k].left;
+        m &= 3;
         steps++; pushes += m == 3; e.kind[m] += 1; a = b;
+        if (m & 1) e.trans[N[k].axis][kind_of(c1)] += 1;
+        else if (m == 2) e.trans[N[k].axis][kind_of(c2)] += 1;
+        if (m == 3 && entered(c2)) e.trans[3][kind_of(c2)] += 1;
       }
+      if (steps || !lv.empty()) e.trans[4][kind_of(0)] += 1;
       e.steps += steps; e.pushes += pushes; e.leaf_visits += (double)lv.size();
       for (int k : lv) e.pair_tests += (double)((S.T->nodes[k].items.size() + 1) / 2);
       if (steps || !lv.empty()) e.walks += 1;
@@ -276,6 +297,14 @@ int main(int argc, char** argv) {
         printf(", \"%s\": {\"walks\": %.4f, \"branch_steps\": %.3f, \"pushes\": %.3f, \"leaf_visits\": %.3f, \"pair_tests\": %.3f, \"near_only\": %.3f, \"far_only\": %.3f, \"both\": %.3f, "
                "\"neither\": %.3f}", nm[w], ev[w].walks / n, ev[w].steps / n, ev[w].pushes / n, ev[w].leaf_visits / n, ev[w].pair_tests / n, ev[w].kind[1] / n, ev[w].kind[2] / n, ev[w].kind[3] / n,
                ev[w].kind[0] / n);
+      printf("}\n");
+      printf("TRANS {\"walk\": \"origin\", \"live_items\": %.0f, \"targets\": [\"x\", \"y\", \"z\", \"leaf\"]", ev[0].live);
+      const char* site[5] = {"after_x", "after_y", "after_z", "after_pop", "at_root"};
+      for (int w = 0; w < 2; w++) {
+        printf(", \"%s\": {", nm[w]);
+        for (int s = 0; s < 5; s++) printf("%s\"%s\": [%.3f, %.3f, %.3f, %.3f]", s ? ", " : "", site[s], ev[w].trans[s][0] / n, ev[w].trans[s][1] / n, ev[w].trans[s][2] / n, ev[w].trans[s][3] / n);
+        printf("}");
+      }
       printf("}\n");
     }
     auto q = [](std::vector<long> v, double f) { std::sort(v.begin(), v.end()); return v[(size_t)(f * (v.size() - 1))]; };

@@ -14,7 +14,11 @@ which children the packet's rays go into):
               then L_nf)
   far only    L_st up to the near vote's branch, then L_fo (before round 11: L_st WITH its push, the near vote, L_n1 which takes the push
               back, L_node's wait and fetch and its dispatch)
-A dispatch is counted at its longest path (five instructions; four or two are executed for three of the four targets).  An EVENTS line
+A dispatch -- the branch on a reference's two low bits that ends every step and every pop -- is priced by WHERE IT GOES when the study's
+TRANS line is given (--trans FILE: per site -- after an X / Y / Z step, after a pop, at the root -- how many dispatches go to an X, Y, Z
+branch and to a leaf, per live item): the instructions executed on that path through the site's own form (DISPATCH_PATHS below, read off
+bih_packet_asm.hpp: since round 12 every site has its own test order; before, one form served all), and the step kinds and the pop are
+priced WITHOUT their dispatch.  Without --trans a dispatch is counted at its full length inside the step, as until round 11.  An EVENTS line
 without the four kinds (older than round 11) is priced as before: one figure per step, the push where both children are entered -- which
 charged the parent's far-only steps 15 instructions too few each and put them into "outside the walks".
 
@@ -24,7 +28,7 @@ about 40 per live item, which the "outside" figure holds instead.
 
   g++ -O2 -std=c++17 -I glome_amd/csrc -I include tools/probe/bih_cull_study.cpp -o BUILD/bih_cull_study && BUILD/bih_cull_study 224 8 3 | grep EVENTS > BUILD/events.txt
   python tools/kernel_mix.py 1 > /dev/null
-  python tools/probe/item_breakdown.py BUILD/events.txt [--listing FILE.s] [--kernel MANGLED] [--counted 4636.2]
+  python tools/probe/item_breakdown.py BUILD/events.txt [--trans BUILD/trans.txt] [--listing FILE.s] [--kernel MANGLED] [--counted 4636.2]
 (BUILD: any directory outside the tree's tracked files)
 """
 import json
@@ -33,6 +37,14 @@ import sys
 
 LISTING = "/tmp/kernel_mix/p1/kernel_parts-hip-amdgcn-amd-amdhsa-gfx950.s"  # where tools/kernel_mix.py 1 writes it
 KERNEL = "_Z13k_render_flatILb0ELb0ELb0ELi1ELi6ELb1EEvN5glome11DRenderArgsEiPji"  # the flagship instance
+
+
+# instructions executed by a dispatch, by site and target (x, y, z, leaf), and the site's length in the listing.  "r12": the per-site forms
+# (a block that has the label L_xyA); "r11": the one form of rounds 2 to 11 (bit 1, then bit 0; s_branch to X and to Z).
+DISPATCH_PATHS = {"r12": {"after_x": (5, 4, 4, 4), "after_y": (2, 7, 4, 6), "after_z": (2, 4, 7, 6), "after_pop": (4, 4, 4, 5), "at_root": (4, 4, 4, 4)},
+                  "r11": {k: (5, 4, 5, 4) for k in ("after_x", "after_y", "after_z", "after_pop")}}
+DISPATCH_PATHS["r11"]["at_root"] = (4, 4, 5, 4)  # (the root's form fell through into the X step)
+DISPATCH_LEN = {"r12": {"X": 5, "Y": 7, "Z": 7, "pop": 5}, "r11": {"X": 5, "Y": 5, "Z": 5, "pop": 5}}
 
 
 def arg(name, default):
@@ -59,7 +71,8 @@ def is_label(s):
 
 
 def main():
-    ev = json.loads(open(sys.argv[1]).read().split("EVENTS", 1)[1])
+    ev = json.loads(open(sys.argv[1]).read().split("EVENTS", 1)[1].splitlines()[0])
+    trans = json.loads(open(arg("--trans", "")).read().split("TRANS", 1)[1].splitlines()[0]) if "--trans" in sys.argv else None
     lines = kernel_lines(arg("--listing", LISTING), arg("--kernel", KERNEL))
     total = sum(1 for s in lines if not is_label(s))
     # the walk blocks: L_fresh_N .. L_end_N
@@ -86,9 +99,13 @@ def main():
         st = [k for k in seg if k.startswith("L_st")]
         if not st:
             continue
+        form = "r12" if f"L_xyA_{n}" in seg else "r11"
         for k in st:
             tag = k[len("L_st"):]
             body = seg[k]
+            if trans:  # the three dispatches of a step (both, near only, far only) leave: they are priced by where they go
+                cutd = DISPATCH_LEN[form][tag[1]]
+                seg["L_nf" + tag] = seg["L_nf" + tag][:-cutd]; seg["L_fo" + tag] = seg["L_fo" + tag][:-cutd]; body = body[:-cutd]
             cut = next(i for i, s in enumerate(body) if s.startswith("s_cbranch_vccz L_nf")) + 1  # up to the vote "does any lane enter the far child"
             nf = seg["L_nf" + tag]
             vote = next(i for i, s in enumerate(nf) if s.startswith("s_cbranch_execz")) + 1  # the near vote and its branch
@@ -106,8 +123,8 @@ def main():
                 cost["far_only"].append(len(body) + vote + len(seg["L_n1" + tag]) + len(seg[f"L_node_{n}"]) + len(seg[f"L_node2_{n}"]))
                 cost["neither"].append(cut + vote + 1)
         cost["pair"].append(len(seg[f"L_tri_{n}"]))
-        cost["pop"].append(len(seg[f"L_pop_{n}"]))
-        cost["leaf_entry"].append(len(seg[f"L_leaf_{n}"]) + len(seg.get(f"L_zlA_{n}", [])))
+        cost["pop"].append(len(seg[f"L_pop_{n}"]) - (DISPATCH_LEN[form]["pop"] if trans else 0))
+        cost["leaf_entry"].append(len(seg[f"L_leaf_{n}"]) + (0 if trans else len(seg.get(f"L_zlA_{n}", []))))
     c = {k: sum(v) / len(v) for k, v in cost.items()}
     rows, walks = [], 0.0
     for w in ("primary", "shadow"):
@@ -117,6 +134,8 @@ def main():
         else:
             parts = {"branch steps": e["branch_steps"] * c["step"], "pushes": e["pushes"] * c["push"]}
         parts.update({"pops": e["pushes"] * c["pop"], "pair tests": e["pair_tests"] * c["pair"], "leaf entries": e["leaf_visits"] * c["leaf_entry"]})
+        if trans:
+            parts["dispatches"] = sum(n_ * p_ for site, paths in DISPATCH_PATHS[form].items() for n_, p_ in zip(trans[w][site], paths))
         rows.append((w, e, parts))
         walks += sum(parts.values())
     print(f"listing: {total} instructions, {inside} inside the {len(blocks)} walk blocks, {total - inside} outside")
@@ -126,6 +145,10 @@ def main():
         kinds = "  (near only {near_only:.1f}, far only {far_only:.1f}, both {both:.1f}, neither {neither:.1f})".format(**e) if "far_only" in e else ""
         print(f"  {w:8s} walks {e['walks']:.2f}  steps {e['branch_steps']:.1f}{kinds}  pushes = pops {e['pushes']:.1f}  leaf visits {e['leaf_visits']:.1f}  pair tests {e['pair_tests']:.1f}")
         print("           instructions: " + ", ".join(f"{k} {v:.0f}" for k, v in parts.items()) + f"  = {sum(parts.values()):.0f}")
+    if trans:
+        for site, paths in DISPATCH_PATHS[form].items():
+            counts = [trans["primary"][site][t] + trans["shadow"][site][t] for t in range(4)]
+            print(f"  dispatches {site:9s} -> x {counts[0]:.2f} y {counts[1]:.2f} z {counts[2]:.2f} leaf {counts[3]:.2f}  at {paths}: {sum(a * b for a, b in zip(counts, paths)):.1f}")
     print(f"in the walks (model): {walks:.0f} per live item")
     if "--counted" in sys.argv:
         counted = float(arg("--counted", "0"))
