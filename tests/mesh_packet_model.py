@@ -24,7 +24,7 @@ import collections
 
 import numpy as np
 
-from packet_model import NS_fmax3, NS_fmin3, tri_hits
+from packet_walk_model import NS_fmax3, NS_fmin3, tri_hits
 
 MUTANTS = ("no_third_pass", "high_lanes_lost_beyond_lds", "later_left_interval_from_the_right")
 LDS_CAP = 12  # kAsmLdsCap (rt_types.h): stack entries 0..11 live in LDS, entry 12 and beyond in the overflow columns

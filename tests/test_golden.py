@@ -12,7 +12,8 @@ from helpers import HostSim, oracle_for, product_camera_lights
 from glome_amd import api
 
 GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
-NAMES = sorted(os.path.basename(p)[:-5] for p in glob.glob(os.path.join(GOLD, "*.json")))
+# (packet_walk_record.json is no golden vector: it is the record of tests/test_packet_walk_model_host.py, made by make_packet_walk_record.py)
+NAMES = sorted(os.path.basename(p)[:-5] for p in glob.glob(os.path.join(GOLD, "*.json")) if os.path.basename(p) != "packet_walk_record.json")
 
 
 def load_gold(name):

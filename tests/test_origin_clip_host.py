@@ -20,7 +20,6 @@ import zoo
 from helpers import HostSim
 from glome_amd import api, scenes
 
-FLT_MIN = np.float32(1.17549435e-38)
 KDEL = 1.0e-4  # Vec.hs:40
 
 
@@ -371,20 +370,14 @@ def test_one_leaf_trees_are_tested_regardless(built):
             assert np.array_equal(occ, hs.shadow(o, long_d, np.float32(50.0), tier=1))
 
 
-def test_the_deep_streams_of_the_ladder_keep_their_overflow(built, monkeypatch):
+def test_the_deep_streams_of_the_ladder_keep_their_overflow(built):
     """tests/test_packet_walk_edges.py reaches the overflow path of the hand-written walk with streams that hold 16 pending entries.  Their rays
     start INSIDE the ladder's bounds (between the screen and the nearest rung; the shadow rays on the screen) and run towards the far end: the
-    pending entries are far children AHEAD of the origin.  Modelled (tests/packet_model.py) with the root interval clipped as the production
+    pending entries are far children AHEAD of the origin.  Modelled (tests/packet_walk_model.py, origin_clip) with the root interval clipped as the production
     walk now clips it: the same depth, pushes and pops beyond the LDS part as with the reference interval, in every packet."""
     import ladder
-    import packet_model as PM
+    import packet_walk_model as PM
     from oracle import np_scene as NS
-    plain = PM.root_interval
-
-    def clipped(bb, o, d, dist):
-        near, far = plain(bb, o, d, dist)
-        return np.where(-float(FLT_MIN) > near, -float(FLT_MIN), near), far
-
     for v in ((0, 1), (1, -1)):
         lad = ladder.Ladder(*v)
         sc, nm = NS.load(lad.sd)
@@ -397,10 +390,8 @@ def test_the_deep_streams_of_the_ladder_keep_their_overflow(built, monkeypatch):
         so, sd_, sl = ladder.shadow_rays(lad, *lad.shadow_set()[:2], t)
         assert np.all((so >= lo) & (so <= hi))
         sref = PM.walk_stream(bih, so, sd_, sl, 2)
-        monkeypatch.setattr(PM, "root_interval", clipped)
-        got = PM.walk_stream(bih, o, d, 1e6, 1)
-        sgot = PM.walk_stream(bih, so, sd_, sl, 2)
-        monkeypatch.setattr(PM, "root_interval", plain)
+        got = PM.walk_stream(bih, o, d, 1e6, 1, origin_clip=True)
+        sgot = PM.walk_stream(bih, so, sd_, sl, 2, origin_clip=True)
         for a, b in list(zip(ref, got)) + list(zip(sref, sgot)):
             assert [(w.octant, w.lanes, w.max_depth, w.pushes_over, w.pops_over) for w in a["walks"]] == [(w.octant, w.lanes, w.max_depth, w.pushes_over, w.pops_over) for w in b["walks"]]
             assert all(w.max_depth >= 15 and w.pushes_over >= 1 and w.pops_over >= 1 for w in b["walks"])

@@ -6,7 +6,7 @@ packet that holds more than twelve pending far children.  A GPU test of those pa
 a test of the C++ walk passes for nothing; so the conditions are stated here, on the ladder scenes and ray streams of tests/ladder.py:
 
   * the commit's own rules (glome_sb_scene_traits, glome_trace_kernel_choice) send every ladder to the instances that call the walk;
-  * tests/packet_model.py walks the tree the product builds (compared through the `show` text);
+  * tests/packet_walk_model.py walks the tree the product builds (compared through the `show` text);
   * every deep packet, closest-hit and shadow, is modelled at stack depth >= 15 with pushes and pops beyond entry 12, in each of the 8
     octants over combs split on each of the 3 axes; the leaves they test hold 1 .. 9 and 13 triangles; a packet first-hits >= 10 rungs
     while >= 4 of its lanes miss everything; an octant held by one lane of a wave is walked alone and deep;
@@ -21,7 +21,7 @@ import numpy as np
 import pytest
 
 import ladder
-import packet_model as PM
+import packet_walk_model as PM
 import showfmt
 from helpers import oracle_for
 from test_trace_choice import export_choice, instance_name
@@ -254,7 +254,7 @@ def test_fp32_and_fp64_oracles_agree_on_every_ray(cases, v):
 @pytest.mark.parametrize("v", [VARIANTS[0], VARIANTS[3], VARIANTS[4]], ids=[IDS[0], IDS[3], IDS[4]])
 def test_model_finds_the_oracles_primitives_and_its_mutants_do_not(cases, v):
     """The model's per-lane hit is the fp64 oracle's on every ray of the deep and the mixed stream -- duplicates included: the later item of a tie.
-    The model's three mutants (packet_model.MUTANTS: an entry beyond the LDS part that loses the high word of its lane mask, the B half of every
+    The model's three mutants (packet_walk_model.MUTANTS: an entry beyond the LDS part that loses the high word of its lane mask, the B half of every
     pair of a leaf ignored, the early-out's clip dropped at pops from beyond the LDS part under the hand-written walk's own acceptance, t <= far
     alone) each get rays of the deep stream wrong: the streams can tell.  These are mutants of the MODEL: the hand-written walk cannot run without a GPU and the
     host build's wave is one lane; what the like changes do to the host-compiled C++ walk is recorded in DESIGN.md 4.1c."""
