@@ -48,6 +48,10 @@ class RaygenParams(C.Structure):  # glome_raygen_params
                 ("seed", C.c_uint32), ("aperture", C.c_float), ("focus_dist", C.c_float)]
 
 
+class AdaptiveParams(C.Structure):  # glome_adaptive_params
+    _fields_ = [("base_samples", C.c_int32), ("threshold", C.c_float)]
+
+
 class SceneInfo(C.Structure):  # glome_scene_info
     _fields_ = [("tier", C.c_int32), ("nesting_depth", C.c_int32), ("n_records", C.c_int64), ("n_bih_nodes", C.c_int64),
                 ("n_mesh_nodes", C.c_int64), ("n_triangles", C.c_int64), ("n_spheres", C.c_int64),
@@ -201,6 +205,14 @@ SYMBOLS = [
                                     C.POINTER(Stats)]),
     ("glome_render_lens_dev", C.c_int, [vp, C.POINTER(Camera), C.POINTER(RaygenParams), C.POINTER(Light), C.c_int, C.POINTER(TraceParams), C.c_int64, vp, vp,
                                         C.POINTER(Stats)]),
+    ("glome_adaptive_params_default", None, [C.POINTER(AdaptiveParams)]),
+    ("glome_adaptive_params_size", C.c_size_t, []),
+    ("glome_adaptive_levels", C.c_int, [C.c_int32, C.c_int32, c_ip, C.c_int]),
+    ("glome_adaptive_fold", C.c_int, [c_fp, C.c_int32, C.c_int32, C.c_float, c_ip, c_fp, c_up]),
+    ("glome_render_lens_adaptive", C.c_int, [vp, C.POINTER(Camera), C.POINTER(RaygenParams), C.POINTER(Light), C.c_int, C.POINTER(TraceParams),
+                                             C.POINTER(AdaptiveParams), C.c_int64, c_fp, c_up, C.POINTER(C.c_uint8), C.POINTER(Stats)]),
+    ("glome_render_lens_adaptive_dev", C.c_int, [vp, C.POINTER(Camera), C.POINTER(RaygenParams), C.POINTER(Light), C.c_int, C.POINTER(TraceParams),
+                                                 C.POINTER(AdaptiveParams), C.c_int64, vp, vp, vp, C.POINTER(Stats)]),
     ("glome_camera_lookat", C.c_int, [c_dp, c_dp, c_dp, C.c_double, C.POINTER(Camera)]),
     ("glome_render_params_default", None, [C.POINTER(RenderParams)]),
     ("glome_render", C.c_int, [vp, C.POINTER(Camera), C.POINTER(Light), C.c_int, C.POINTER(RenderParams), c_fp, c_up, C.POINTER(Stats)]),

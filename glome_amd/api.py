@@ -219,6 +219,47 @@ def raygen_sample(seed, pixel, s, dim):
     return int(L.load().glome_raygen_sample(seed & 0xffffffff, pixel & 0xffffffff, s & 0xffffffff, dim & 0xffffffff))
 
 
+def adaptive_params(base_samples=None, threshold=None):
+    """glome_adaptive_params of Scene.render_lens_adaptive: the first level and the most the means of a pixel's two halves may differ.
+    The defaults (4, 1/64) are the library's first guess, not tuned."""
+    p = L.AdaptiveParams()
+    L.load().glome_adaptive_params_default(C.byref(p))
+    if base_samples is not None:
+        p.base_samples = int(base_samples)
+    if threshold is not None:
+        p.threshold = float(threshold)
+    return p
+
+
+def adaptive_levels(base, max_samples):
+    """The levels base, 2 base, .. max_samples of the adaptive rule (glome_adaptive_levels); ValueError when the pair is not legal."""
+    out = (C.c_int32 * 8)()
+    n = int(L.load().glome_adaptive_levels(int(base), int(max_samples), out, 8))
+    if n < 0:
+        raise ValueError("adaptive_levels: base must be even and at least 2, max = base * 2^k, at most 64 (got %r, %r)" % (base, max_samples))
+    return [int(out[k]) for k in range(n)]
+
+
+def adaptive_fold(tuples, base, threshold):
+    """The adaptive rule on the host (glome_adaptive_fold), pixel by pixel: tuples[n, max, 5] float32 (or [max, 5]) gives
+    (counts[n] int32, rgbad[n, 5] float32, packed[n] uint32).  What Scene.render_lens_adaptive computes on the device, bit for bit."""
+    lib = L.load()
+    x = np.ascontiguousarray(tuples, dtype=np.float32)
+    if x.ndim == 2:
+        x = x[None]
+    if x.ndim != 3 or x.shape[2] != 5:
+        raise ValueError("adaptive_fold: tuples must be [n, max, 5]")
+    n, mx = x.shape[0], x.shape[1]
+    counts, out, packed = np.zeros(n, np.int32), np.zeros((n, 5), np.float32), np.zeros(n, np.uint32)
+    px, pc, po, pp = x.ctypes.data, counts.ctypes.data, out.ctypes.data, packed.ctypes.data
+    for k in range(n):
+        rc = lib.glome_adaptive_fold(C.cast(px + k * mx * 20, L.c_fp), int(base), mx, float(threshold), C.cast(pc + 4 * k, L.c_ip), C.cast(po + 20 * k, L.c_fp),
+                                     C.cast(pp + 4 * k, L.c_up))
+        if rc:
+            raise ValueError("adaptive_fold: refused (base %r, max %r, threshold %r)" % (base, mx, threshold))
+    return counts, out, packed
+
+
 # ---------------------------------------------------------------- scene builder
 class Builder:
     """One method per reference constructor; returns integer node / material ids."""
@@ -898,6 +939,34 @@ class Scene:
         self._chk(self.lib.glome_render_lens_dev(self.h, C.byref(cam), C.byref(raygen), la, len(lights), C.byref(trace), int(rays_per_pass),
                                                  C.c_void_p(rgbad_ptr) if rgbad_ptr else None, C.c_void_p(packed_ptr) if packed_ptr else None,
                                                  C.byref(st) if want_stats else None), "glome_render_lens_dev")
+        return _stats_dict(st) if want_stats else None
+
+    def render_lens_adaptive(self, cam, lights, raygen, adaptive=None, trace=None, rays_per_pass=0, want_packed=True):
+        """render_lens with raygen.samples the most a pixel gets and fewer where the halves of its samples agree
+        (glome_render_lens_adaptive): returns (rgbad[h,w,5] float32, packed[h,w] uint32 or None, counts[h,w] uint8, stats dict).  Every
+        pixel is adaptive_fold of its samples, bit for bit."""
+        w, h = raygen.width, raygen.height
+        img = np.zeros((max(h, 0), max(w, 0), 5), np.float32)
+        packed = np.zeros((max(h, 0), max(w, 0)), np.uint32) if want_packed else None
+        counts = np.zeros((max(h, 0), max(w, 0)), np.uint8)
+        trace = trace_params() if trace is None else trace
+        adaptive = adaptive_params() if adaptive is None else adaptive
+        la = (L.Light * max(1, len(lights)))(*lights)
+        st = L.Stats()
+        self._chk(self.lib.glome_render_lens_adaptive(self.h, C.byref(cam), C.byref(raygen), la, len(lights), C.byref(trace), C.byref(adaptive), int(rays_per_pass),
+                                                      img.ctypes.data_as(L.c_fp), packed.ctypes.data_as(L.c_up) if want_packed else None,
+                                                      counts.ctypes.data_as(C.POINTER(C.c_uint8)), C.byref(st)), "glome_render_lens_adaptive")
+        return img, packed, counts, _stats_dict(st)
+
+    def render_lens_adaptive_dev(self, cam, lights, raygen, adaptive, trace, rgbad_ptr, packed_ptr=None, counts_ptr=None, rays_per_pass=0, want_stats=True):
+        """Device-pointer render_lens_adaptive (whole frames; any pointer may be None / 0, rgbad_ptr and packed_ptr not both).  Not
+        asynchronous: the call waits for the stream once per round of each pass."""
+        vp = lambda p: C.c_void_p(p) if p else None
+        la = (L.Light * max(1, len(lights)))(*lights)
+        st = L.Stats()
+        self._chk(self.lib.glome_render_lens_adaptive_dev(self.h, C.byref(cam), C.byref(raygen), la, len(lights), C.byref(trace), C.byref(adaptive),
+                                                          int(rays_per_pass), vp(rgbad_ptr), vp(packed_ptr), vp(counts_ptr), C.byref(st) if want_stats else None),
+                  "glome_render_lens_adaptive_dev")
         return _stats_dict(st) if want_stats else None
 
     def render(self, cam, lights, params, want_packed=True, init=None):

@@ -73,6 +73,47 @@ int64_t glome_raygen_count(const glome_raygen_params* p) {
 }
 uint32_t glome_raygen_sample(uint32_t seed, uint32_t pixel, uint32_t s, uint32_t dim) { return raygen_word(seed, pixel, s, dim); }
 
+// ---- the adaptive rule's host-only entries (adaptive_rule.hpp: the bodies the fold kernels compile; the device path: runtime.hip) ----
+void glome_adaptive_params_default(glome_adaptive_params* p) {
+  if (!p) return;
+  memset(p, 0, sizeof(*p));
+  p->base_samples = 4; p->threshold = 1.0f / 64;  // a first guess, not tuned
+}
+size_t glome_adaptive_params_size(void) { return sizeof(glome_adaptive_params); }
+int glome_adaptive_levels(int32_t base, int32_t max, int32_t* out, int cap) {
+  if (!adaptive::legal(base, max) || cap < 0 || (cap > 0 && !out)) return GLOME_E_INVALID;
+  int k = 0;
+  for (int32_t n = base; n <= max; n *= 2, k++) if (k < cap) out[k] = n;
+  return k;
+}
+namespace {
+// rgbf (rt_device.hpp, Glome.hs:98-110) on the host: the float-to-int conversion spelled as the device's instruction performs it
+// (saturating, 0 for a NaN), the word wrapping like Word32 arithmetic
+uint32_t rgbf_channel(float x) {
+  x = x >= 1 ? 1 - 0.0001f : x;  // cap1, kDel
+  const float v = std::floor(x * 256);
+  if (v != v) return 0u;
+  if (v >= 2147483648.0f) return 0x7fffffffu;
+  if (v <= -2147483648.0f) return 0x80000000u;
+  return (uint32_t)(int32_t)v;
+}
+uint32_t rgbf_host(float r, float g, float b) { return rgbf_channel(r) * 65536u + rgbf_channel(g) * 256u + rgbf_channel(b); }
+}  // namespace
+int glome_adaptive_fold(const float* tuples, int32_t base, int32_t max, float threshold, int32_t* count, float rgbad[5], uint32_t* packed) {
+  if (!tuples || !count || !rgbad || !packed || adaptive_rule_error(base, max, threshold)) return GLOME_E_INVALID;
+  adaptive::Fold F = {};
+  int32_t s = 0, n = base;
+  for (;; n *= 2) {
+    const uint32_t h = (uint32_t)n / 2;
+    for (; s < n; s++) adaptive::take(F, (uint32_t)s, h, tuples + 5 * (size_t)s);
+    if (n == max || adaptive::agrees(F, h, threshold)) break;
+  }
+  adaptive::result(F, (uint32_t)n, rgbad);
+  *count = n;
+  *packed = rgbf_host(rgbad[0] * rgbad[3], rgbad[1] * rgbad[3], rgbad[2] * rgbad[3]);
+  return 0;
+}
+
 int glome_xfm_translate(const double v[3], double out[24]) { return xguard([&] { xf_to(xf_translate(d3(v)), out); }); }
 int glome_xfm_scale(const double v[3], double out[24]) { return xguard([&] { xf_to(xf_scale(d3(v)), out); }); }
 int glome_xfm_rotate(const double axis[3], double angle, double out[24]) { return xguard([&] { xf_to(xf_rotate(d3(axis), angle), out); }); }

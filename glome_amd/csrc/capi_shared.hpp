@@ -5,6 +5,7 @@
 #include <string>
 
 #include "../../include/glome_hip.h"
+#include "adaptive_rule.hpp"
 #include "flatten.hpp"
 #include "host_graph.hpp"
 #include "instances.hpp"
@@ -47,5 +48,11 @@ inline const char* raygen_params_error(const glome_raygen_params* p) {
   if (p->lens != GLOME_LENS_PINHOLE && p->lens != GLOME_LENS_THIN && p->lens != GLOME_LENS_LATLONG) return "unknown lens";
   if (!std::isfinite(p->aperture) || !std::isfinite(p->focus_dist)) return "aperture and focus_dist must be finite";
   if (p->lens == GLOME_LENS_THIN && (p->focus_dist <= 0 || p->aperture < 0)) return "a thin lens needs focus_dist > 0 and aperture >= 0";
+  return nullptr;
+}
+// What the adaptive rule refuses (glome_adaptive_levels / _fold on the host half, glome_render_lens_adaptive on the device half).
+inline const char* adaptive_rule_error(int32_t base, int32_t max, float threshold) {
+  if (!glome::adaptive::legal(base, max)) return "adaptive levels: base_samples must be even and at least 2, samples = base_samples * 2^k, at most 64";
+  if (!(threshold >= 0)) return "the adaptive threshold must be 0 or more (+inf allowed), not NaN";
   return nullptr;
 }

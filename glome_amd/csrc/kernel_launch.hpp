@@ -59,3 +59,7 @@ void launch_trace_generic_lean(int grid, hipStream_t st, const DTraceArgs& A);  
 constexpr int kResolveSamplesInLds = 16;
 void launch_camera_rays(int grid, hipStream_t st, const DLensArgs& A);
 void launch_resolve(int grid, hipStream_t st, const DResolveArgs& A);
+// glome_render_lens_adaptive's rounds (lens_adaptive_kernels.hpp; part 15): the raygen of listed pixels, and the fold at one level -- round 0's
+// (first) or a later round's -- with k_resolve's staging
+void launch_camera_rays_list(int grid, hipStream_t st, const DLensListArgs& A);
+void launch_adaptive_fold(int grid, hipStream_t st, bool first, const DAdaptFoldArgs& A);

@@ -1,9 +1,10 @@
 // kernel_parts.hip -- the kernel instances of the library, cut into parts that compile in parallel: -DGLOME_PART=k (k = 1..kParts-1,
 // glome_amd/build.py) keeps the instances instances.hpp lists for part k and defines the launcher that knows them (kernel_launch.hpp).
-// The device code itself is render_kernels.hpp, trace_kernels.hpp and lens_kernels.hpp; the host runtime (runtime.hip) is a unit of its own and holds none of it.
+// The device code itself is render_kernels.hpp, trace_kernels.hpp, lens_kernels.hpp and lens_adaptive_kernels.hpp; the host runtime (runtime.hip) is a unit of its own and holds none of it.
 #include "render_kernels.hpp"
 #include "trace_kernels.hpp"
 #include "lens_kernels.hpp"
+#include "lens_adaptive_kernels.hpp"
 
 #if !defined(GLOME_PART) || GLOME_PART < 1 || GLOME_PART >= GLOME_NPARTS
 #error "kernel_parts.hip is compiled once per part: -DGLOME_PART=k with k = 1..GLOME_NPARTS-1 (instances.hpp)"
@@ -116,4 +117,10 @@ void launch_trace_generic(int grid, hipStream_t st, const DTraceArgs& A) { hipLa
 #if GLOME_IN_PART(15)
 void launch_camera_rays(int grid, hipStream_t st, const DLensArgs& A) { hipLaunchKernelGGL(k_camera_rays<>, dim3(grid), dim3(64), 0, st, A); }
 void launch_resolve(int grid, hipStream_t st, const DResolveArgs& A) { hipLaunchKernelGGL(k_resolve<kResolveSamplesInLds>, dim3(grid), dim3(64), 0, st, A); }
+// glome_render_lens_adaptive's rounds (lens_adaptive_kernels.hpp)
+void launch_camera_rays_list(int grid, hipStream_t st, const DLensListArgs& A) { hipLaunchKernelGGL(k_camera_rays_list<>, dim3(grid), dim3(64), 0, st, A); }
+void launch_adaptive_fold(int grid, hipStream_t st, bool first, const DAdaptFoldArgs& A) {
+  if (first) hipLaunchKernelGGL((k_adaptive_fold<kResolveSamplesInLds, true>), dim3(grid), dim3(64), 0, st, A);
+  else hipLaunchKernelGGL((k_adaptive_fold<kResolveSamplesInLds, false>), dim3(grid), dim3(64), 0, st, A);
+}
 #endif

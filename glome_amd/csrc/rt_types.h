@@ -281,6 +281,32 @@ struct DResolveArgs {
   int32_t samples;
   int32_t vec;  // 1: samples_in is 16-byte aligned (a wave's block then is: it starts a multiple of 1280 bytes further on)
 };
+// ---- glome_render_lens_adaptive (lens_adaptive_kernels.hpp; the rule itself: adaptive_rule.hpp)
+// The arguments of a list raygen launch: ray j of the launch is sample h + j % h of the pixel first_pixel + list[j / h], L.n rays in all.
+// L.first_pixel is the pass's first pixel, L.first_s and L.samples are not read.
+struct DLensListArgs {
+  DLensArgs L;
+  const uint32_t* list;   // entries: pixels of the pass, counted from its first one
+  uint32_t pass_pixels;   // an entry is clamped below this
+  uint32_t h;             // samples per entry: half the level
+};
+// The arguments of a fold launch at one level.  Round 0 (k_adaptive_fold<SB, true>): the n entries are the pass's pixels themselves and
+// samples_in holds `level` tuples for each; a later round (<SB, false>): entry j is list_in[j], samples_in holds its level / 2 new tuples
+// and `state` what it kept.  A pixel that stops goes to the frames, one that goes on to `state` and list_out.
+struct DAdaptFoldArgs {
+  const float* samples_in;
+  float* rgbad; uint32_t* packed; uint8_t* counts;  // whole frames, any may be null
+  float* state;             // pass_pixels * 5: S and d of a pixel that goes on
+  const uint32_t* list_in;
+  uint32_t* list_out;       // pass_pixels words
+  uint32_t* counter;        // list_out's length, zero before the launch
+  uint32_t first_pixel;     // of the pass
+  uint32_t pass_pixels;
+  uint32_t n;               // entries
+  int32_t level;            // n of the rule
+  int32_t last;             // 1: the level is max -- every pixel stops
+  float threshold;
+};
 constexpr int kWorkWords = 8;  // GLOME_WORK_WORDS: bih, mesh, prim, shadow rays, secondary rays of a ray's whole trace; bih, mesh, prim of its primary ray's closest hit
 
 }  // namespace glome

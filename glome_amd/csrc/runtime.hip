@@ -132,6 +132,8 @@ struct glome_ctx {
     uint32_t cull_total = 0;     // work items of the slot's last flagship launch (its live ones: DCounters::list_len)
     float* d_lens = nullptr;     // glome_render_lens: a pass's six ray streams, then its n * 5 results (grown on demand)
     size_t lens_bytes = 0;
+    uint32_t* d_adapt = nullptr; // glome_render_lens_adaptive: a pass's list lengths, pixel states and two lists (grown on demand)
+    size_t adapt_bytes = 0;
     bool launched = false;  // a launch went out on this slot since its error word was last polled
     hipStream_t launched_on = nullptr;  // ... on this stream (a caller's own stream is the caller's to synchronise)
   };
@@ -368,6 +370,7 @@ void glome_ctx_destroy(glome_ctx* c) {
     if (sl.d_scratch) (void)hipFree(sl.d_scratch);
     if (sl.d_list) (void)hipFree(sl.d_list);
     if (sl.d_lens) (void)hipFree(sl.d_lens);
+    if (sl.d_adapt) (void)hipFree(sl.d_adapt);
   }
   if (c->ev0) (void)hipEventDestroy(c->ev0);
   if (c->ev1) (void)hipEventDestroy(c->ev1);
@@ -2169,6 +2172,147 @@ int glome_render_lens(glome_scene* s, const glome_camera* cam, const glome_rayge
   if (int rc = glome_render_lens_dev(s, cam, RP, lights, nlights, TP, rays_per_pass, d5, dp, stats ? stats : &local)) return rc;
   if (rgbad) HIPCHK(ctx, hipMemcpy(rgbad, d5, np * 5 * sizeof(float), hipMemcpyDeviceToHost));
   if (packed) HIPCHK(ctx, hipMemcpy(packed, dp, np * sizeof(uint32_t), hipMemcpyDeviceToHost));
+  return 0;
+}
+
+// ---- adaptive lens frames: a pass in rounds, one per level of the rule (adaptive_rule.hpp, lens_adaptive_kernels.hpp) ----
+// The pass's own workspace beside d_lens: kAdaptCounterWords list lengths (one per round, zeroed once a pass), 20 bytes of state per
+// pixel, two lists of a word per pixel.
+constexpr size_t kAdaptCounterWords = 16;
+static_assert(kAdaptCounterWords >= (size_t)adaptive::kMaxLevels, "a list length per round");
+static int ensure_adapt(glome_ctx* ctx, size_t pass_pixels) {
+  glome_ctx::Slot& sl = ctx->slot();
+  const size_t need = (kAdaptCounterWords + pass_pixels * 7) * sizeof(uint32_t);
+  if (need <= sl.adapt_bytes) return 0;
+  if (sl.d_adapt) { HIPCHK(ctx, hipStreamSynchronize(ctx->stream)); HIPCHK(ctx, hipFree(sl.d_adapt)); sl.d_adapt = nullptr; sl.adapt_bytes = 0; }
+  HIPCHK(ctx, hipMalloc((void**)&sl.d_adapt, need));
+  sl.adapt_bytes = need;
+  return 0;
+}
+// everything glome_render_lens_adaptive is refused for, asked before the first launch and before a frame is allocated
+static int render_lens_adaptive_check(glome_ctx* ctx, const glome_camera* cam, const glome_raygen_params* RP, const glome_light* lights, int nlights,
+                                      const glome_trace_params* TP, const glome_adaptive_params* AP, int64_t rays_per_pass, const void* rgbad,
+                                      const void* packed, DLensArgs& A) {
+  if (int rc = render_lens_check(ctx, cam, RP, lights, nlights, TP, rays_per_pass, rgbad, packed, A)) return rc;
+  if (!AP) { ctx->err = "null adaptive params"; return GLOME_E_INVALID; }
+  if (const char* why = adaptive_rule_error(AP->base_samples, RP->samples, AP->threshold)) { ctx->err = why; return GLOME_E_INVALID; }
+  return 0;
+}
+// the two launches of a round that are this path's own (timed like lens_launch_rays / _resolve)
+static int adapt_launch_rays(glome_ctx* ctx, const DLensListArgs& A) {
+  if (A.L.n == 0) return 0;
+  hipEvent_t e0, e1;
+  const bool pooled = ctx->timing && launch_events(ctx, e0, e1);
+  if (pooled) HIPCHK(ctx, hipEventRecord(e0, ctx->stream));
+  const uint32_t items = (A.L.n + 63u) >> 6;
+  launch_camera_rays_list((int)std::min<uint32_t>(items, (uint32_t)ctx->prop.multiProcessorCount * 32u * 4u), ctx->stream, A);
+  HIPCHK(ctx, hipGetLastError());
+  if (pooled) HIPCHK(ctx, hipEventRecord(e1, ctx->stream));
+  return 0;
+}
+static int adapt_launch_fold(glome_ctx* ctx, bool first, const DAdaptFoldArgs& A) {
+  if (A.n == 0) return 0;
+  hipEvent_t e0, e1;
+  const bool pooled = ctx->timing && launch_events(ctx, e0, e1);
+  if (pooled) HIPCHK(ctx, hipEventRecord(e0, ctx->stream));
+  launch_adaptive_fold((int)((A.n + 63u) / 64u), ctx->stream, first, A);  // (a wave per 64 entries: at most 2^24 blocks)
+  HIPCHK(ctx, hipGetLastError());
+  if (pooled) HIPCHK(ctx, hipEventRecord(e1, ctx->stream));
+  return 0;
+}
+int glome_render_lens_adaptive_dev(glome_scene* s, const glome_camera* cam, const glome_raygen_params* RP, const glome_light* lights, int nlights,
+                                   const glome_trace_params* TP, const glome_adaptive_params* AP, int64_t rays_per_pass, float* rgbad_dev,
+                                   uint32_t* packed_dev, uint8_t* counts_dev, glome_stats* stats) {
+  if (!s) return GLOME_E_INVALID;
+  glome_ctx* ctx = s->ctx;
+  DLensArgs A;
+  if (int rc = render_lens_adaptive_check(ctx, cam, RP, lights, nlights, TP, AP, rays_per_pass, rgbad_dev, packed_dev, A)) return rc;
+  const int64_t pixels = (int64_t)RP->width * RP->height, max = RP->samples, base = AP->base_samples;
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  const int64_t per_pass = std::min<int64_t>(pixels, std::max<int64_t>(1, (rays_per_pass ? rays_per_pass : kLensRaysPerPass) / max));  // pixels
+  const size_t round_rays = (size_t)(per_pass * std::max(base, max / 2));  // the most a round holds: round 0's, or the last round's with every pixel listed
+  if (int rc = ensure_lens(ctx, round_rays)) return rc;
+  if (int rc = ensure_adapt(ctx, (size_t)per_pass)) return rc;
+  const size_t sf = lens_stream_floats(round_rays);
+  float* w = ctx->slot().d_lens;
+  A.ox = w; A.oy = w + sf; A.oz = w + 2 * sf; A.dx = w + 3 * sf; A.dy = w + 4 * sf; A.dz = w + 5 * sf;
+  float* results = w + 6 * sf;
+  uint32_t* counters = ctx->slot().d_adapt;
+  float* state = reinterpret_cast<float*>(counters + kAdaptCounterWords);
+  uint32_t* lists[2] = {counters + kAdaptCounterWords + 5 * per_pass, counters + kAdaptCounterWords + 6 * per_pass};
+  if (stats) memset(stats, 0, sizeof(*stats));
+  for (int64_t p0 = 0; p0 < pixels; p0 += per_pass) {
+    const int64_t np = std::min(per_pass, pixels - p0);
+    HIPCHK(ctx, hipMemsetAsync(counters, 0, kAdaptCounterWords * sizeof(uint32_t), ctx->stream));
+    uint32_t len = (uint32_t)np;  // entries of the round: the pass's pixels, then the list the round before wrote
+    int round = 0;
+    for (int64_t level = base;; level *= 2, round++) {
+      const int64_t h = level / 2, n = round == 0 ? np * base : (int64_t)len * h;
+      const bool last = level == max;
+      float ms_rays = 0, ms_fold = 0;
+      glome_stats ps;
+      if (stats) HIPCHK(ctx, hipEventRecord(ctx->ev2, ctx->stream));
+      if (round == 0) {  // samples [0, base) of every pixel of the pass: k_camera_rays's own frame order at samples = base
+        A.samples = (int32_t)base; A.first_pixel = (uint32_t)p0; A.first_s = 0; A.n = (uint32_t)n;
+        if (int rc = lens_launch_rays(ctx, A)) return rc;
+      } else {
+        DLensListArgs LA;
+        LA.L = A; LA.L.first_pixel = (uint32_t)p0; LA.L.n = (uint32_t)n;
+        LA.list = lists[(round - 1) & 1]; LA.pass_pixels = (uint32_t)np; LA.h = (uint32_t)h;
+        if (int rc = adapt_launch_rays(ctx, LA)) return rc;
+      }
+      if (stats) HIPCHK(ctx, hipEventRecord(ctx->ev3, ctx->stream));
+      if (int rc = glome_trace_batch_dev(s, (size_t)n, A.ox, A.oy, A.oz, A.dx, A.dy, A.dz, nullptr, lights, nlights, TP, results, nullptr, nullptr, nullptr, nullptr,
+                                         nullptr, nullptr, stats ? &ps : nullptr)) return rc;
+      if (stats) {  // (the trace launch has synchronised the stream: the raygen pair is complete)
+        HIPCHK(ctx, hipEventElapsedTime(&ms_rays, ctx->ev2, ctx->ev3));
+        HIPCHK(ctx, hipEventRecord(ctx->ev2, ctx->stream));
+      }
+      DAdaptFoldArgs F;
+      F.samples_in = results; F.rgbad = rgbad_dev; F.packed = packed_dev; F.counts = counts_dev;
+      F.state = state; F.list_in = lists[(round - 1) & 1]; F.list_out = lists[round & 1]; F.counter = counters + round;
+      F.first_pixel = (uint32_t)p0; F.pass_pixels = (uint32_t)np; F.n = len;
+      F.level = (int32_t)level; F.last = last ? 1 : 0; F.threshold = AP->threshold;
+      if (int rc = adapt_launch_fold(ctx, round == 0, F)) return rc;
+      if (stats) {
+        HIPCHK(ctx, hipEventRecord(ctx->ev3, ctx->stream));
+        HIPCHK(ctx, hipEventSynchronize(ctx->ev3));
+        HIPCHK(ctx, hipEventElapsedTime(&ms_fold, ctx->ev2, ctx->ev3));
+        stats->rays_primary += ps.rays_primary; stats->rays_shadow += ps.rays_shadow; stats->rays_secondary += ps.rays_secondary;
+        stats->bih_nodes += ps.bih_nodes; stats->mesh_nodes += ps.mesh_nodes; stats->prim_tests += ps.prim_tests;
+        stats->kernel_ms += ms_rays + ps.kernel_ms + ms_fold;
+        stats->n_tiles += ps.n_tiles;
+      }
+      if (last) break;
+      // the next round's size: 4 bytes and one wait for the stream
+      HIPCHK(ctx, hipMemcpyAsync(&len, counters + round, sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+      HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+      if (len > (uint32_t)np) len = (uint32_t)np;  // (the fold writes no list slot beyond the pass)
+      if (len == 0) break;
+    }
+  }
+  if (stats) stats->n_pixels = (int32_t)pixels;
+  return 0;
+}
+int glome_render_lens_adaptive(glome_scene* s, const glome_camera* cam, const glome_raygen_params* RP, const glome_light* lights, int nlights,
+                               const glome_trace_params* TP, const glome_adaptive_params* AP, int64_t rays_per_pass, float* rgbad, uint32_t* packed,
+                               uint8_t* counts, glome_stats* stats) {
+  if (!s) return GLOME_E_INVALID;
+  glome_ctx* ctx = s->ctx;
+  DLensArgs A;
+  if (int rc = render_lens_adaptive_check(ctx, cam, RP, lights, nlights, TP, AP, rays_per_pass, rgbad, packed, A)) return rc;
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  const size_t np = (size_t)RP->width * RP->height;
+  Staging st{ctx, {}};
+  float* d5 = rgbad ? st.in<float>(nullptr, np * 5) : nullptr;
+  uint32_t* dp = packed ? st.in<uint32_t>(nullptr, np) : nullptr;
+  uint8_t* dc = counts ? st.in<uint8_t>(nullptr, np) : nullptr;
+  if ((rgbad && !d5) || (packed && !dp) || (counts && !dc)) { ctx->err = "staging allocation failed"; return GLOME_E_HIP; }
+  glome_stats local;
+  if (int rc = glome_render_lens_adaptive_dev(s, cam, RP, lights, nlights, TP, AP, rays_per_pass, d5, dp, dc, stats ? stats : &local)) return rc;
+  if (rgbad) HIPCHK(ctx, hipMemcpy(rgbad, d5, np * 5 * sizeof(float), hipMemcpyDeviceToHost));
+  if (packed) HIPCHK(ctx, hipMemcpy(packed, dp, np * sizeof(uint32_t), hipMemcpyDeviceToHost));
+  if (counts) HIPCHK(ctx, hipMemcpy(counts, dc, np * sizeof(uint8_t), hipMemcpyDeviceToHost));
   return 0;
 }
 

@@ -752,6 +752,56 @@ int glome_render_lens(glome_scene*, const glome_camera*, const glome_raygen_para
                       const glome_trace_params*, int64_t rays_per_pass, float* rgbad, uint32_t* packed, glome_stats*);
 int glome_render_lens_dev(glome_scene*, const glome_camera*, const glome_raygen_params*, const glome_light* lights, int nlights,
                           const glome_trace_params*, int64_t rays_per_pass, float* rgbad_dev, uint32_t* packed_dev, glome_stats*);
+
+/* ---- Adaptive sampling for lens frames: more samples only where the two halves of a pixel's samples differ.
+ * glome_raygen_params.samples is the most a pixel gets (`max`).  Levels are n_0 = base, n_{k+1} = 2 n_k, up to max: base is even and at
+ * least 2, max = base * 2^k with k >= 0, max <= 64.  For one pixel with tuples x_s = (r, g, b, a, depth) of samples s = 0 .. max - 1:
+ *   S  the running fp32 sum of r, g, b, a: a copy of sample 0, then plain fp32 additions in index order (glome_resolve_dev's sum);
+ *   d  the least depth so far (glome_resolve_dev's);
+ *   at level n with h = n / 2: A is S as it stood after sample h - 1, B a fresh sum of samples h .. n - 1 (a copy of sample h, then
+ *   additions in index order).  The pixel stops at n when fabsf(A_c - B_c) <= threshold * (float)h is true for each of the four channels
+ *   -- one fp32 subtraction and one fp32 multiplication, round to nearest, never contracted; in words, the means of the two halves
+ *   differ by at most threshold.  A comparison that is false -- one with a NaN too -- continues the pixel; at max it stops whatever the
+ *   test says.
+ * The result at count = n: r, g, b, a = S_c / (float)n correctly rounded, depth = d, the packed word rgbf(r a, g a, b a): what
+ * glome_resolve_dev gives for samples = n, bit for bit.  (The device flushes subnormals like every kernel here; the identity with the
+ * host functions holds where none arises.)
+ * The defaults -- base 4, threshold 1/64 -- are a first guess, not tuned. */
+typedef struct glome_adaptive_params {
+  int32_t base_samples;  /* the first level: even, >= 2; raygen samples = base_samples * 2^k */
+  float threshold;       /* >= 0; +inf is legal (every pixel stops at base_samples), NaN is not */
+} glome_adaptive_params;
+void glome_adaptive_params_default(glome_adaptive_params*);  /* base 4, threshold 1/64: a first guess, not tuned */
+size_t glome_adaptive_params_size(void);                     /* sizeof(glome_adaptive_params) of the loaded library */
+/* Host-only.  The levels of (base, max) into out[0 .. cap), returns how many there are (at most 6; out may be NULL with cap = 0);
+ * GLOME_E_INVALID when (base, max) is not as above, or out is NULL with cap > 0. */
+int glome_adaptive_levels(int32_t base, int32_t max, int32_t* out, int cap);
+/* Host-only.  The rule for one pixel: tuples = max * 5 floats; writes the count, the (r, g, b, a, depth) result and the packed word.
+ * GLOME_E_INVALID: a null pointer, a bad (base, max), a threshold that is NaN or negative.  The kernels below compile the same
+ * definition of the step (glome_amd/csrc/adaptive_rule.hpp). */
+int glome_adaptive_fold(const float* tuples, int32_t base, int32_t max, float threshold, int32_t* count, float rgbad[5], uint32_t* packed);
+/* A frame like glome_render_lens's in which every pixel is glome_adaptive_fold of that pixel's max tuples -- the tuples glome_camera_rays
+ * -> glome_trace_batch give for it at samples = max -- bit for bit in rgbad, packed and counts, whatever rays_per_pass is.  rgbad and
+ * packed are whole frames (either may be NULL, not both); counts, width * height bytes, receives the level each pixel stopped at and may
+ * be NULL.  Only the samples a pixel needs are made and traced.  A pass covers max(1, rays_per_pass / max) consecutive pixels
+ * (rays_per_pass = 0: glome_render_lens's default) and runs in rounds: round 0 makes and traces samples [0, base) of every pixel of the
+ * pass and folds them at level base; round k makes, traces and folds samples [n / 2, n) of the pixels the round before listed; the pass
+ * ends when a list is empty or after level max.  The workspace is the slot's, grown on demand: 44 bytes per ray for the most rays a
+ * round holds, pixels-per-pass * max(base, max / 2), and per pixel of a pass 20 bytes of state and two list words.
+ * NOT asynchronous, in either form: the length of a round's list is read back (4 bytes), so the call waits for its stream once per
+ * round of each pass -- the only blocking steps of the _dev form when stats is NULL; with stats every trace launch waits as well.  Every
+ * launch takes part in glome_ctx_timing_begin / _end (one event pair each: raygen, trace, fold).  stats are summed over all trace
+ * launches: rays_primary equals the sum of the counts, n_pixels = width * height, kernel_ms = the HIP-event time of all stages.
+ * GLOME_E_INVALID / GLOME_E_LIMIT before anything is launched, the frames untouched: everything glome_render_lens refuses (with
+ * samples = max; width * height * max > 2^31 among it), null adaptive params, what glome_adaptive_levels refuses of (base_samples,
+ * samples), a threshold that is NaN or negative. */
+int glome_render_lens_adaptive(glome_scene*, const glome_camera*, const glome_raygen_params*, const glome_light* lights, int nlights,
+                               const glome_trace_params*, const glome_adaptive_params*, int64_t rays_per_pass,
+                               float* rgbad, uint32_t* packed, uint8_t* counts, glome_stats*);
+int glome_render_lens_adaptive_dev(glome_scene*, const glome_camera*, const glome_raygen_params*, const glome_light* lights, int nlights,
+                                   const glome_trace_params*, const glome_adaptive_params*, int64_t rays_per_pass,
+                                   float* rgbad_dev, uint32_t* packed_dev, uint8_t* counts_dev, glome_stats*);
+
 /* Host-only, no device: the kernel instance a trace launch gets (choose_trace, glome_amd/csrc/instances.hpp).  n rows of 11 inputs -- the
  * eight scene traits of glome_sb_scene_traits, then faithful, count_work, maxdepth -- give n rows of 3 outputs: the instance (a flat-tier
  * key with the bits glome_kernel_choice describes, TWO_ROWS never set; -1 / -2: the generic tier's kernel that counts work / does not),
