@@ -124,6 +124,7 @@ struct FlatScene {
   uint32_t root_rec = 0;
   uint32_t tier = 1;
   int nesting_depth = 0, max_bih_depth = 0, max_mesh_depth = 0;
+  int vm_words = 0;  // the frame words run() estimated for a ray of this scene: what it held against kVmWords (host side only: tests)
   int max_sphere_bih_depth = 0;  // deepest BIH the interpreter's packet service can walk: items all plain spheres, all plain triangles, or all answered in place (0: none)
   uint32_t tex_bits = 16;   // bits per id of a TexStack (rt_types.h): 8 when the scene has at most 254 materials
   int64_t n_other_prims = 0;
@@ -163,8 +164,9 @@ class Flattener {
       throw limit_error("a primitive lies under " + std::to_string(tex_depth_of(root)) + " nested textures; the device's texture stack holds " + std::to_string(tex_cap) +
                         (tex_cap < kMaxTexDepth ? " in a scene of more than 254 materials (" + std::to_string(kMaxTexDepth) + " otherwise)" : ""));
     const bool warps = bind_warps();  // Warp materials refer to records: the frame's, and the scene's they look into
-    if (vm_words_of(root) + 2 > kVmWords)
-      throw limit_error("scene nests deeper than the device interpreter's frame memory holds (" + std::to_string(vm_words_of(root) + 2) + " of " + std::to_string(kVmWords) + " words)");
+    F.vm_words = std::max(vm_words_of(root) + 2, warp_words);
+    if (F.vm_words > kVmWords)
+      throw limit_error("scene nests deeper than the device interpreter's frame memory holds (" + std::to_string(F.vm_words) + " of " + std::to_string(kVmWords) + " words)");
     // flat tier: root program of simple entries
     F.tier = 0;
     if (warps) { F.tier = 1; F.why_generic = "a Warp material traces other roots than the scene's"; }
@@ -263,8 +265,10 @@ class Flattener {
       const uint32_t frame = slot(emit(m.wframe)), scene = m.wscene < 0 ? F.root_rec : slot(emit(m.wscene));
       F.nesting_depth = std::max(F.nesting_depth, std::max(depth_of(m.wframe), m.wscene < 0 ? 0 : depth_of(m.wscene)));
       if (std::max(tex_depth_of(m.wframe), m.wscene < 0 ? 0 : tex_depth_of(m.wscene)) > tex_cap) throw limit_error("a Warp material's frame / scene has more nested textures than the device's texture stack holds");
-      if (std::max(vm_words_of(m.wframe), m.wscene < 0 ? 0 : vm_words_of(m.wscene)) + 2 > kVmWords)
-        throw limit_error("a Warp material's frame / scene nests deeper than the device interpreter's frame memory holds");
+      // (the shader traces these roots from an empty frame memory, like the scene's own: the same estimate, and the largest goes to FlatScene::vm_words)
+      warp_words = std::max(warp_words, std::max(vm_words_of(m.wframe), m.wscene < 0 ? 0 : vm_words_of(m.wscene)) + 2);
+      if (warp_words > kVmWords)
+        throw limit_error("a Warp material's frame / scene nests deeper than the device interpreter's frame memory holds (" + std::to_string(warp_words) + " of " + std::to_string(kVmWords) + " words)");
       const uint32_t xf = (uint32_t)(F.xfms.size() / 6);
       for (int q = 0; q < 3; q++) F.xfms.push_back(mk4(m.wxf.f.m[4 * q], m.wxf.f.m[4 * q + 1], m.wxf.f.m[4 * q + 2], m.wxf.f.m[4 * q + 3]));
       for (int q = 0; q < 3; q++) F.xfms.push_back(mk4(m.wxf.i.m[4 * q], m.wxf.i.m[4 * q + 1], m.wxf.i.m[4 * q + 2], m.wxf.i.m[4 * q + 3]));
@@ -310,9 +314,15 @@ class Flattener {
   }
   // Frame words a rayint / shadow / inside call on `id` can have live at once in the generic tier's loop (rt_generic.hpp's
   // frame layouts): what the interpreter's nesting limit is now -- memory, checked here so that a scene is refused at commit
-  // rather than stopped in the middle of a frame.  An Intersection's chain of advance frames depends on the geometry; the
-  // estimate allows kVmIsectChain of them and the run-time check (GLOME_E_LIMIT) remains behind it.
+  // rather than stopped in the middle of a frame.  An Intersection's chain of frames has two parts (rt_generic.hpp VT_ISECT_HS): a frame
+  // for the rest of the list behind a child the ray starts inside of and leaves -- at most one per child but the last, with no advance
+  // at all, so commit counts the children --, and a frame per ray advance, which depends on the geometry: the estimate allows
+  // kVmIsectChain of those and the run-time check (GLOME_E_LIMIT) remains behind it.
   mutable std::unordered_map<int, int> words_memo, iwords_memo, mwords_memo;
+  int warp_words = 0;  // the largest estimate of a Warp material's roots (bind_warps)
+  // a Difference of two primitives, an Intersection of primitives that csg_isect's frames hold (emit: RF_PRIMLIST): answered in place,
+  // no frame but the word of a shadow call's VT_S_OF_R -- and what `inside` of the node itself takes, should it be a root
+  bool csg_in_place(int id) const { auto it = memo.find(id); return it != memo.end() && (it->second.x & RF_PRIMLIST) != 0; }
   int bih_items_max(const Node& n, bool inside) const {
     int d = 0;
     for (auto& bn : n.bih->nodes) for (int k : bn.items) d = std::max(d, inside ? inside_words_of(k) : vm_words_of(k));
@@ -357,9 +367,9 @@ class Flattener {
     int d = 0;
     switch (n.kind) {
       case K_LIST: { for (int k : n.kids) d = std::max(d, vm_words_of(k)); d += kVmListR; break; }
-      case K_ISECT: { for (int k : n.kids) d = std::max(d, std::max(vm_words_of(k), 1 + inside_words_of(k))); d += 1 + kVmIsectChain * kVmIsectWords; break; }
+      case K_ISECT: { if (csg_in_place(id)) { d = 1 + inside_words_of(id); break; } for (int k : n.kids) d = std::max(d, std::max(vm_words_of(k), 1 + inside_words_of(k))); d += 1 + ((int)n.kids.size() + kVmIsectChain) * kVmIsectWords; break; }
       case K_INSTANCE: d = kVmInstR + vm_words_of(n.a); break;
-      case K_DIFF: d = 1 + kVmDiffFixed + kCsgMaxAdvance + std::max(std::max(vm_words_of(n.a), vm_words_of(n.b)), 1 + std::max(std::max(inside_words_of(n.a), inside_words_of(n.b)), meta_words_of(n.a))); break;
+      case K_DIFF: if (csg_in_place(id)) { d = 1 + inside_words_of(id); break; } d = 1 + kVmDiffFixed + kCsgMaxAdvance + std::max(std::max(vm_words_of(n.a), vm_words_of(n.b)), 1 + std::max(std::max(inside_words_of(n.a), inside_words_of(n.b)), meta_words_of(n.a))); break;
       case K_BOUND: d = kVmBoundR + std::max(std::max(vm_words_of(n.a), vm_words_of(n.b)), 1 + inside_words_of(n.a)); break;
       case K_INNERBOUND: d = kVmIbR + std::max(vm_words_of(n.a), vm_words_of(n.b)); break;
       case K_BIH: d = kVmBihFixedR + 3 * n.bih->depth + bih_items_max(n, false); break;

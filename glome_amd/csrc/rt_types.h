@@ -73,7 +73,7 @@ constexpr int kGenericStack = 32;  // scratch traversal-stack entries per BIH/Me
 // the generic tier's frame stack (rt_generic.hpp): words per ray, and the frame sizes the host's commit-time estimate shares
 constexpr int kVmWords = 2048 /* 768 until round 4; measured on GlomeView's default scene: +0.2 %, adaptive +1.4 % (profiles/r04_probes/vm_words_ab.txt) */, kVmHitWords = 17, kVmListR = 7 + kVmHitWords, kVmInstR = 10, kVmBoundR = 5, kVmIbR = 4, kVmDiffFixed = 10 + kVmHitWords,
               kVmIsectWords = 11, kVmBihFixedR = 12 + kVmHitWords, kVmBihFixedS = 12;
-constexpr int kVmIsectChain = 8;   // Intersection frames the commit-time estimate allows for (a chain longer than the memory is caught at run time)
+constexpr int kVmIsectChain = 8;   // ray advances per Intersection the commit-time frame estimate allows for, a frame each, beside a frame per child (more are caught at run time)
 constexpr int kCsgMaxAdvance = 32; // ray-advance steps per Difference the generic tier's commit-time frame estimate allows for (at run time: its frame memory)
 constexpr int kCsgFlatAdvance = 256; // ray-advance steps per CSG item of the flat tier whose distances are added back in the reference's own (nested) order; a ray that
                                      // advances more often keeps going (reference: unbounded recursion) with the further advances added to the last slot -- the same

@@ -122,6 +122,49 @@ def _hs_render_subsample(self, cam, lights, width, height, maxdepth, blocksize=6
 HostSim.render_subsample = _hs_render_subsample
 
 
+def _hs_vm_words(self):
+    """(the frame words commit estimated for a ray of this scene -- FlatScene::vm_words --, kVmWords)"""
+    lim = C.c_int(0)
+    return int(self.lib.hostsim_vm_words(self.h, C.byref(lim))), int(lim.value)
+
+
+VM_CONSTS = ("kVmWords", "kVmHitWords", "kVmListR", "kVmInstR", "kVmBoundR", "kVmIbR", "kVmDiffFixed", "kVmIsectWords", "kVmBihFixedR", "kVmBihFixedS",
+             "kVmIsectChain", "kCsgMaxAdvance")
+
+
+def vm_consts():
+    """the frame sizes of rt_types.h as the host build was compiled with them (hostsim_vm_consts)"""
+    out = (C.c_int * len(VM_CONSTS))()
+    hostsim_lib().hostsim_vm_consts(out)
+    return dict(zip(VM_CONSTS, list(out)))
+
+
+PROBE_ROUTES = {"rayint": 0, "shadow": 1, "inside": 2, "trace": 3}
+
+
+def _hs_frame_probe(self, route, o, d=None, tmax=1e6, lights=(), maxdepth=1):
+    """The generic tier's interpreter over rays (route "inside": points) with its frame memory inside a larger buffer (hostsim_frame_probe).
+    Per ray: words (frame words written: a lower bound of the stack height), flag (the error flag), canary (True: nothing written past the
+    frame memory), ans (depth or -1 / shadow / inside / the trace's depth)."""
+    o = np.asarray(o, np.float32).reshape(-1, 3)
+    d = np.zeros_like(o) if d is None else d
+    n, cols = self._cols(o, d, tmax)
+    lv = np.array([list(p) + list(c) + [r, float(s)] for (p, c, r, s) in lights], np.float32).reshape(-1, 8)
+    if not len(lv):
+        lv = np.zeros((1, 8), np.float32)
+    words = np.zeros(n, np.int32); flag = np.zeros(n, np.uint8); canary = np.zeros(n, np.uint8); ans = np.zeros(n, np.float32)
+    rc = self.lib.hostsim_frame_probe(self.h, PROBE_ROUTES[route], C.c_size_t(n), *[c.ctypes.data_as(c_fp) for c in cols], lv.ctypes.data_as(c_fp), len(lights), maxdepth,
+                                      words.ctypes.data_as(C.POINTER(C.c_int)), flag.ctypes.data_as(C.POINTER(C.c_ubyte)), canary.ctypes.data_as(C.POINTER(C.c_ubyte)),
+                                      ans.ctypes.data_as(c_fp))
+    if rc != 0:
+        raise RuntimeError(f"hostsim_frame_probe rc={rc}")
+    return {"words": words, "flag": flag.astype(bool), "canary": canary.astype(bool), "ans": ans}
+
+
+HostSim.vm_words = _hs_vm_words
+HostSim.frame_probe = _hs_frame_probe
+
+
 def product_camera_lights(sd):
     """The glome_camera / glome_light structs the product gets for a SceneDesc (fp32 fields)."""
     from glome_amd import api

@@ -67,6 +67,27 @@ struct HostGenericTier {
   bool occluded_wave(const Ray& r, float d, bool valid) { return valid && occluded(r, d); }
 };
 
+// HostGenericTier with its frame memory outside it: the caller's words (hostsim_frame_probe), so that what the interpreter writes can be read
+struct ProbeGenericTier {
+  static constexpr bool FULL = true;
+  static constexpr bool WARP = true;
+  const DScene& S;
+  const DLight* lights;
+  int nlights;
+  Cnt cnt;
+  uint32_t* vm;
+  unsigned int err = 0;
+  HostStack pkmem;
+  LaneStack pk;
+  void packets() { pk = pkmem.lane((int)S.pk_generic_cap); if (S.pk_generic_cap == 0) { pk.cap = 0; pk.ovf_cap = 0; } }
+  HitG closest(const Ray& r, float tmax, uint32_t root) { return vm_closest<true>(S, cnt, err, vm, pk.cap > 0 ? &pk : (LaneStack*)nullptr, r, tmax, root); }
+  bool occluded(const Ray& r, float d, uint32_t root) { return vm_occluded<true>(S, cnt, err, vm, pk.cap > 0 ? &pk : (LaneStack*)nullptr, r, d, root); }
+  HitG closest(const Ray& r, float tmax) { return closest(r, tmax, S.root_rec); }
+  bool occluded(const Ray& r, float d) { return occluded(r, d, S.root_rec); }
+  HitG closest_wave(const Ray& r, float tmax, bool valid, uint32_t root) { return valid ? closest(r, tmax, root) : hit_miss(); }
+  bool occluded_wave(const Ray& r, float d, bool valid) { return valid && occluded(r, d); }
+};
+
 
 // has the scene a Refract material?  (What the product's rule of the faithful instance asks: instances.hpp exact_traversal, used below.)
 static bool refract_scene(const SimScene* s) {
@@ -98,6 +119,55 @@ int hostsim_info(void* sv, int* out) {  // tier, nesting, max_bih_depth, max_mes
   SimScene* s = (SimScene*)sv;
   out[0] = (int)s->F.tier; out[1] = s->F.nesting_depth; out[2] = s->F.max_bih_depth; out[3] = s->F.max_mesh_depth;
   out[4] = (int)s->D.n_entries; out[5] = (int)s->F.recs.size();
+  return 0;
+}
+// the frame words commit estimated for a ray of this scene (FlatScene::vm_words: what Flattener::run held against kVmWords), and kVmWords
+int hostsim_vm_words(void* sv, int* limit) { if (limit) *limit = kVmWords; return ((SimScene*)sv)->F.vm_words; }
+// the frame sizes the estimate and the interpreter share (rt_types.h), in the order of helpers.VM_CONSTS
+void hostsim_vm_consts(int* out) {
+  const int c[] = {kVmWords, kVmHitWords, kVmListR, kVmInstR, kVmBoundR, kVmIbR, kVmDiffFixed, kVmIsectWords, kVmBihFixedR, kVmBihFixedS, kVmIsectChain, kCsgMaxAdvance};
+  for (size_t k = 0; k < sizeof(c) / sizeof(c[0]); k++) out[k] = c[k];
+}
+// The generic tier's interpreter over the caller's rays with its frame memory inside a larger buffer: kVmWords words, then kProbeCanary more
+// that nothing may touch.  Every ray runs twice, the buffer filled with one sentinel and then with another; per ray:
+//   words[i]   one more than the index of the last frame word that differs from the sentinel, the larger of the two runs -- a LOWER bound of
+//              the interpreter's stack height (a frame reserves words it may never write; a word written with the sentinel's own value shows
+//              in the other run)
+//   flag[i]    the error flag (what the kernels OR into the context's error word)
+//   canary[i]  1: the words after kVmWords - 1 are untouched in both runs
+//   ans[i]     route 0 rayint: the depth (-1 a miss); 1 shadow: 0 / 1; 2 inside (ox, oy, oz the point): 0 / 1; 3 trace (lights, maxdepth): the depth
+// The answer is the second run's; both runs must agree in it and in the flag, or -6 is returned (the frame memory's old contents were read).
+int hostsim_frame_probe(void* sv, int route, size_t n, const float* ox, const float* oy, const float* oz, const float* dx, const float* dy, const float* dz,
+                        const float* tmax, const float* lights, int nl, int maxdepth, int* words, unsigned char* flag, unsigned char* canary, float* ans) {
+  SimScene* s = (SimScene*)sv;
+  constexpr int kProbeCanary = 64;
+  if (route < 0 || route > 3) return -5;
+  if (route == 3 && (nl < 0 || nl > kMaxLights || maxdepth < 1 || maxdepth > kMaxTraceDepth)) return -5;
+  DLight L[kMaxLights];
+  if (route == 3) for (int i = 0; i < nl; i++) { memcpy(L[i].pos, lights + 8 * i, 12); memcpy(L[i].color, lights + 8 * i + 3, 12); L[i].rad = lights[8 * i + 6]; L[i].shadow = lights[8 * i + 7] != 0; }
+  std::vector<uint32_t> buf(kVmWords + kProbeCanary);
+  const uint32_t sentinels[2] = {0xa5a5a5a5u, 0x5a5a5a5au};
+  for (size_t i = 0; i < n; i++) {
+    Ray r; r.o = v3(ox[i], oy[i], oz[i]);
+    if (route != 2) r.d = v3(dx[i], dy[i], dz[i]); else r.d = v3(0, 0, 1);
+    words[i] = 0; canary[i] = 1;
+    float a2[2] = {0, 0}; unsigned int e2[2] = {0, 0};
+    for (int k = 0; k < 2; k++) {
+      std::fill(buf.begin(), buf.end(), sentinels[k]);
+      ProbeGenericTier T{s->D, L, route == 3 ? nl : 0, Cnt(), buf.data()}; T.packets();
+      if (route == 0) { HitG h = T.closest(r, tmax[i]); a2[k] = h.hit ? h.t : -1.0f; }
+      else if (route == 1) a2[k] = T.occluded(r, tmax[i]) ? 1.0f : 0.0f;
+      else if (route == 2) a2[k] = vm_inside(s->D, T.err, buf.data(), 0, s->D.recs[s->D.root_rec], r.o) ? 1.0f : 0.0f;
+      else { HitG h; trace_primary(T, r, tmax[i], maxdepth, true, &h); a2[k] = h.hit ? h.t : kInf; }
+      e2[k] = T.err;
+      int top = kVmWords;
+      while (top > 0 && buf[top - 1] == sentinels[k]) top--;
+      if (top > words[i]) words[i] = top;
+      for (int c = 0; c < kProbeCanary; c++) if (buf[kVmWords + c] != sentinels[k]) canary[i] = 0;
+    }
+    if (memcmp(&a2[0], &a2[1], 4) != 0 || e2[0] != e2[1]) return -6;
+    flag[i] = e2[1] ? 1 : 0; ans[i] = a2[1];
+  }
   return 0;
 }
 // tier: -1 = the scene's own tier, 0 = flat (must be legal), 1 = generic; analysis: faithful traversal + counters
