@@ -14,8 +14,32 @@
 //                    partition leaves: `nearest` prefers the later item on ties, so the order is part of the result)
 // All arithmetic that decides something is fp64 with explicit round-to-nearest multiplies and adds (no contraction), in
 // the host builder's operation order.  Max / min of split planes go through atomics on order-preserving integer keys;
-// the compare-select folds of the host builder give the same value except for the sign of a zero, which nothing
-// downstream can see (the planes are stored with +-delta added, and boxes only feed midpoints and areas).
+// the compare-select folds of the host builder give the same value except for the sign of a zero.  A plane that is a
+// zero of either sign gives the same stored split (+-delta is added), the same midpoints' comparisons and the same areas'
+// comparisons, and the loop rule below compares numerically, so the sign reaches neither the tree nor the status
+// (tests/tree_build_cases.py holds boxes with +0.0 and -0.0 corners on the split axis to that).
+//
+// Termination.  A chosen partition with an empty side whose other child keeps the node's box is a fixed point: build_rec
+// never returns from it (a box of zero or underflowing area; Graph::BihBuild::rec refuses it with kBihLoopMessage).
+// k_bb_decide makes the same test and reports kErrLoop through the error word; the build ends with the host's status
+// and message.  The Mesh's children take the true union of their triangles' boxes, which carry the +-delta pad: a
+// partition that separates nothing costs 1.1 x a positive lcost there and is never chosen below the root -- unless a
+// vertex is infinite and lcost with it: then every cost is infinite, big / small is taken and sends everything right.
+// Graph::MeshBuild::rec and k_mb_decide refuse that fixed point the same way (kMeshLoopMessage).  (Values that are NaN
+// order differently in the host's folds and the key atomics; no equality is claimed for them, only a status.)
+//
+// Pools.  With fixed points refused, a chosen partition that separates nothing ("a step") moves one of the six faces
+// of the box to the fold of the same objects' bounds; a second step on that face over the same objects would move it
+// to the same value and is refused.  So at most six steps lie between two partitions that separate.  Contract the
+// steps: the tree that remains has at most n leaves (they hold disjoint, non-empty sets) and so at most n - 1 branches;
+// only its nodes of more than three objects (c of them, c <= n - 1) can stand below steps, and a step adds two nodes
+// (itself and its empty leaf).  Nodes <= 2n - 1 + 12c <= 14n - 13, hence kNodeCap(n) = 14n + 16.  On one level the
+// non-empty nodes hold disjoint sets (<= n), and an empty node is the sibling of one with at least three objects
+// (<= n / 3): kAccCap(n) = n + n / 3 + 2.  tests/tree_build_model.py counts both on every case of its table.  (A node
+// is 120 bytes: 1.8 GB of device address space for a million objects, written only as far as the tree grows.)
+//
+// Depth.  A level is six launches and a synchronisation, so a tree deeper than kMaxLevels levels is refused
+// (GLOME_E_LIMIT, nothing added); include/glome_hip.h states the value beside both builders.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -37,6 +61,12 @@ struct DevNode {
 };
 struct Acc { unsigned int cnt[4]; unsigned long long lmax[4], rmin[4]; };
 
+constexpr int kMaxLevels = 2048;                                           // see "Depth" above
+constexpr long long kNodeCap(long long n) { return 14 * n + 16; }          // see "Pools" above
+constexpr long long kAccCap(long long n) { return n + n / 3 + 2; }
+enum : int { kErrNone = 0, kErrPool = 1, kErrLoop = 2 };                   // the error word of k_*_decide (the largest code wins)
+enum : int { kBuilt = 0, kRefusedLimit = 1, kRefusedLoop = 2, kFailed = 3 };  // what levels() returns
+
 __device__ __forceinline__ unsigned long long dkey(double x) {  // order-preserving: a < b <=> dkey(a) < dkey(b)
   unsigned long long b = (unsigned long long)__double_as_longlong(x);
   return (b >> 63) ? ~b : (b | 0x8000000000000000ull);
@@ -50,6 +80,8 @@ __device__ __forceinline__ double d_area(const double* lo, const double* hi) {  
   double v = __dmul_rn(2.0, __dadd_rn(__dadd_rn(__dmul_rn(dx, dy), __dmul_rn(dx, dz)), __dmul_rn(dy, dz)));
   return (0 <= v) ? v : 0;
 }
+
+__device__ __forceinline__ bool d_same(double a, double b) { return a == b || (a != a && b != b); }  // Graph::same_bound
 
 struct Objs { const double* lo[3]; const double* hi[3]; const double* mid[3]; const double* area; };
 
@@ -143,8 +175,10 @@ __global__ void k_bb_decide(DevNode* nodes, const Acc* acc, int lvl_begin, int l
   else if (cost[1] < cost[3]) k = 2;  // as written in the reference (`costy < costb`, Bih.hs:283)
   else k = 3;
   const int ax = k == 3 ? 0 : k;
+  // build_rec's fixed point (see "Termination" above), with Graph::BihBuild::rec's own test
+  if ((A.cnt[k] == 0 && d_same(rmin[k], N.lo[ax])) || (A.cnt[k] == (unsigned int)N.count && d_same(lmax[k], N.hi[ax]))) { atomicMax(error, (int)kErrLoop); return; }
   const int l = atomicAdd(n_nodes, 2);
-  if (l + 2 > node_cap) { atomicExch(error, 1); return; }
+  if (l + 2 > node_cap) { atomicMax(error, (int)kErrPool); return; }
   N.leaf = 0; N.axis = ax; N.left = l; N.right = l + 1; N.ksel = k; N.nleft = (int)A.cnt[k];
   N.lsplit = __dadd_rn(lmax[k], kDelta); N.rsplit = __dsub_rn(rmin[k], kDelta);
   DevNode& L = nodes[l];
@@ -235,8 +269,14 @@ __global__ void k_mb_decide(DevNode* nodes, const AccM* acc, int lvl_begin, int 
   else if (cost[1] < cost[2] && cost[1] < cost[3]) k = 1;
   else if (cost[2] < cost[3]) k = 2;
   else k = 3;
+  if (A.cnt[k] == 0 || A.cnt[k] == (unsigned int)N.count) {  // build_tree's fixed point, with Graph::MeshBuild::rec's own test
+    const int s2 = A.cnt[k] == 0 ? 1 : 0;
+    bool same = true;
+    for (int a = 0; a < 3; a++) same = same && d_same(b[k][s2][0][a], N.lo[a]) && d_same(b[k][s2][1][a], N.hi[a]);
+    if (same) { atomicMax(error, (int)kErrLoop); return; }
+  }
   const int l = atomicAdd(n_nodes, 2);
-  if (l + 2 > node_cap) { atomicExch(error, 1); return; }
+  if (l + 2 > node_cap) { atomicMax(error, (int)kErrPool); return; }
   N.leaf = 0; N.axis = 0; N.left = l; N.right = l + 1; N.ksel = k; N.nleft = (int)A.cnt[k];
   DevNode& L = nodes[l];
   DevNode& R = nodes[l + 1];
@@ -309,15 +349,16 @@ __global__ void k_bb_scatter(int n, Objs O, const int* idx, const int* nodeof, c
   nodeof2[pos] = left ? N.left : N.right;
 }
 
-#define BB_HIP(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { err = std::string(#call) + ": " + hipGetErrorString(e_); goto done; } } while (0)
+#define BB_HIP(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { err = std::string(#call) + ": " + hipGetErrorString(e_); status = kFailed; goto done; } } while (0)
 
 // The level loop.  boxes: the objects' bounds in input order; bb: the root's box.  Leaves nodes (breadth-first device
-// numbering) and the final object order.
+// numbering) and the final object order.  Returns kBuilt, or a refusal / failure with `err` set and nothing left behind.
 template <bool MESH>
-inline bool levels(const std::vector<Box3>& boxes, const Box3& bb, hipStream_t st, std::string& err, float* gpu_ms, std::vector<DevNode>& nodes, std::vector<int>& order) {
+inline int levels(const std::vector<Box3>& boxes, const Box3& bb, hipStream_t st, std::string& err, float* gpu_ms, std::vector<DevNode>& nodes, std::vector<int>& order) {
   using AccT = typename std::conditional<MESH, AccM, Acc>::type;
   const int n = (int)boxes.size();
-  const int node_cap = 4 * n + 16, max_levels = 512, acc_cap = n + 2;
+  if (kNodeCap(n) > 0x7fffffffll) { err = "device tree build: more objects than the node pool can number"; return kRefusedLimit; }
+  const int node_cap = (int)kNodeCap(n), acc_cap = (int)kAccCap(n);
   std::vector<double> h((size_t)6 * n);
   for (int i = 0; i < n; i++) {
     const Box3& b = boxes[(size_t)i];
@@ -330,7 +371,7 @@ inline bool levels(const std::vector<Box3>& boxes, const Box3& bb, hipStream_t s
   DevNode* d_nodes = nullptr; AccT* d_acc = nullptr;
   hipEvent_t e0 = nullptr, e1 = nullptr;
   const int nblk = (n + 255) / 256, nscan = (n + kScanBlock - 1) / kScanBlock;
-  bool ok = false;
+  int status = kBuilt;
   int lvl_begin = 0, lvl_end = 1, cur = 0, nlev = 0;
   int hcnt[2] = {1, 0};
   DevNode root{};
@@ -351,9 +392,9 @@ inline bool levels(const std::vector<Box3>& boxes, const Box3& bb, hipStream_t s
   BB_HIP(hipEventRecord(e0, st));
   hipLaunchKernelGGL(k_bb_prepare, dim3(nblk), dim3(256), 0, st, n, O.lo[0], O.lo[1], O.lo[2], O.hi[0], O.hi[1], O.hi[2], d_mid, d_mid + n, d_mid + 2 * (size_t)n, d_area, d_idx[0], d_nodeof[0]);
   while (lvl_begin < lvl_end) {
-    if (++nlev > max_levels) { err = "device tree build: deeper than 512 levels"; goto done; }
+    if (++nlev > kMaxLevels) { err = "device tree build: the tree is deeper than the level limit of " + std::to_string(kMaxLevels) + " (glome_hip.h)"; status = kRefusedLimit; goto done; }
     const int ln = lvl_end - lvl_begin;
-    if (ln > acc_cap) { err = "device tree build: level wider than the accumulator pool"; goto done; }
+    if (ln > acc_cap) { err = "device tree build: level wider than the accumulator pool"; status = kFailed; goto done; }
     if constexpr (MESH) {
       hipLaunchKernelGGL(k_mb_clear, dim3((ln + 255) / 256), dim3(256), 0, st, d_acc, ln);
       hipLaunchKernelGGL(k_mb_accumulate, dim3(nblk), dim3(256), 0, st, n, O, d_idx[cur], d_nodeof[cur], d_nodes, d_acc, lvl_begin);
@@ -368,7 +409,8 @@ inline bool levels(const std::vector<Box3>& boxes, const Box3& bb, hipStream_t s
     hipLaunchKernelGGL(k_bb_scatter, dim3(nblk), dim3(256), 0, st, n, O, d_idx[cur], d_nodeof[cur], d_nodes, d_pre, d_bsum, d_idx[cur ^ 1], d_nodeof[cur ^ 1]);
     BB_HIP(hipMemcpyAsync(hcnt, d_cnt, sizeof(hcnt), hipMemcpyDeviceToHost, st));
     BB_HIP(hipStreamSynchronize(st));
-    if (hcnt[1]) { err = "device tree build: node pool exhausted"; goto done; }
+    if (hcnt[1] == kErrLoop) { err = MESH ? Graph::kMeshLoopMessage : Graph::kBihLoopMessage; status = kRefusedLoop; goto done; }
+    if (hcnt[1]) { err = "device tree build: node pool exhausted"; status = kFailed; goto done; }
     cur ^= 1;
     lvl_begin = lvl_end; lvl_end = hcnt[0];
   }
@@ -378,14 +420,13 @@ inline bool levels(const std::vector<Box3>& boxes, const Box3& bb, hipStream_t s
   BB_HIP(hipMemcpyAsync(order.data(), d_idx[cur], sizeof(int) * n, hipMemcpyDeviceToHost, st));
   BB_HIP(hipStreamSynchronize(st));
   if (gpu_ms) BB_HIP(hipEventElapsedTime(gpu_ms, e0, e1));
-  ok = true;
 done:
   (void)hipFree(d_box); (void)hipFree(d_mid); (void)hipFree(d_area);
   for (int q = 0; q < 2; q++) { (void)hipFree(d_idx[q]); (void)hipFree(d_nodeof[q]); }
   (void)hipFree(d_pre); (void)hipFree(d_bsum); (void)hipFree(d_cnt); (void)hipFree(d_nodes); (void)hipFree(d_acc);
   if (e0) (void)hipEventDestroy(e0);
   if (e1) (void)hipEventDestroy(e1);
-  return ok;
+  return status;
 }
 
 // breadth-first device numbering -> the preorder trees of the host builders (explicit stack: deep trees)
@@ -412,10 +453,10 @@ inline void to_preorder(const std::vector<DevNode>& nodes, TREE& T, LEAF&& leaf,
 }
 
 // `bih` (Bih.hs:309-324): fills T like Graph::BihBuild, `ids` = the leaf items
-inline bool build(const std::vector<Box3>& boxes, const std::vector<int>& ids, const Box3& bb, BihTree& T, hipStream_t st, std::string& err, float* gpu_ms) {
+inline int build(const std::vector<Box3>& boxes, const std::vector<int>& ids, const Box3& bb, BihTree& T, hipStream_t st, std::string& err, float* gpu_ms) {
   std::vector<DevNode> nodes;
   std::vector<int> order;
-  if (!levels<false>(boxes, bb, st, err, gpu_ms, nodes, order)) return false;
+  if (const int rc = levels<false>(boxes, bb, st, err, gpu_ms, nodes, order)) return rc;
   T.bb = bb;
   to_preorder(nodes, T,
     [&](BihTree::Node& tn, const DevNode& d) {
@@ -423,13 +464,13 @@ inline bool build(const std::vector<Box3>& boxes, const std::vector<int>& ids, c
       for (int k = 0; k < d.count; k++) tn.items.push_back(ids[(size_t)order[(size_t)(d.start + k)]]);
     },
     [&](BihTree::Node& tn, const DevNode& d) { tn.leaf = false; tn.lsplit = d.lsplit; tn.rsplit = d.rsplit; tn.axis = d.axis; tn.left = tn.right = -1; });
-  return true;
+  return kBuilt;
 }
 // the Mesh's BVH (build_tree, Mesh.hs:69-113): fills M.nodes like Graph::MeshBuild; tbb = the triangles' boxes
-inline bool build_mesh(const std::vector<Box3>& tbb, MeshData& M, hipStream_t st, std::string& err, float* gpu_ms) {
+inline int build_mesh(const std::vector<Box3>& tbb, MeshData& M, hipStream_t st, std::string& err, float* gpu_ms) {
   std::vector<DevNode> nodes;
   std::vector<int> order;
-  if (!levels<true>(tbb, M.bb, st, err, gpu_ms, nodes, order)) return false;
+  if (const int rc = levels<true>(tbb, M.bb, st, err, gpu_ms, nodes, order)) return rc;
   auto box_of = [](const DevNode& d) { return Box3{{d.lo[0], d.lo[1], d.lo[2]}, {d.hi[0], d.hi[1], d.hi[2]}}; };
   to_preorder(nodes, M,
     [&](MeshData::Node& tn, const DevNode& d) {
@@ -437,7 +478,7 @@ inline bool build_mesh(const std::vector<Box3>& tbb, MeshData& M, hipStream_t st
       for (int k = 0; k < d.count; k++) tn.tris.push_back(order[(size_t)(d.start + k)]);
     },
     [&](MeshData::Node& tn, const DevNode& d) { tn.leaf = false; tn.lbb = box_of(nodes[(size_t)d.left]); tn.rbb = box_of(nodes[(size_t)d.right]); tn.left = tn.right = -1; });
-  return true;
+  return kBuilt;
 }
 #undef BB_HIP
 

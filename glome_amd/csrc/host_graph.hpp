@@ -426,6 +426,19 @@ struct Graph {
   }
 
   // ---------------- BIH builder, Bih.hs:211-285 (Q11) ----------------
+  // what glome_sb_bih and glome_sb_bih_dev say of an input on which the reference's build_rec does not terminate (BihBuild::rec)
+  static constexpr const char* kBihLoopMessage =
+      "bih: a node of more than three items chooses a partition that separates nothing and leaves its box unchanged (a box of zero or "
+      "underflowing surface area, e.g. four points): build_rec (Bih.hs:211-285) does not terminate on this input";
+  static constexpr const char* kMeshLoopMessage =
+      "mesh: a node chooses a partition that separates nothing and leaves its box unchanged (a vertex that is not finite): build_tree "
+      "(Mesh.hs:69-113) does not terminate on this input";
+  // equal as the next call would see them: numerically (a zero of either sign decides alike), or both NaN
+  static bool same_bound(double a, double b) { return a == b || (a != a && b != b); }
+  static bool same_box(const Box3& a, const Box3& b) {
+    return same_bound(a.lo.x, b.lo.x) && same_bound(a.lo.y, b.lo.y) && same_bound(a.lo.z, b.lo.z) && same_bound(a.hi.x, b.hi.x) && same_bound(a.hi.y, b.hi.y) &&
+           same_bound(a.hi.z, b.hi.z);
+  }
   struct BihBuild {
     const std::vector<Box3>& boxes;  // per input object
     const std::vector<int>& ids;     // node ids of the objects
@@ -470,6 +483,10 @@ struct Graph {
       else if (cost[1] < cost[2] && cost[1] < cost[3]) k = 1;
       else if (cost[1] < cost[3]) k = 2;  // as written in the reference (`costy < costb`, Bih.hs:283)
       else k = 3;
+      // A chosen partition with an empty side whose other child keeps the node's box hands the same objects down in the same box:
+      // the child decides as this node did, and build_rec (like this recursion) never returns.  It takes a box of zero or
+      // underflowing area (a separating-nothing candidate otherwise costs 1.1 or 1.2 x costorig and loses), e.g. four points.
+      if ((L[k].empty() && same_bound(rmin[k], comp(bb.lo, AX[k]))) || (R[k].empty() && same_bound(lmax[k], comp(bb.hi, AX[k])))) throw scene_error(kBihLoopMessage);
       int l = rec(L[k], lbb[k], box_mid(lbb[k]), depth + 1);
       int r = rec(R[k], rbb[k], box_mid(rbb[k]), depth + 1);
       BihTree::Node& n = T.nodes[me];
@@ -660,6 +677,9 @@ struct Graph {
       else if (cost[1] < cost[2] && cost[1] < cost[3]) k = 1;
       else if (cost[2] < cost[3]) k = 2;
       else k = 3;
+      // build_tree's fixed point, as BihBuild::rec's: the same triangles in the same box decide the same again.  A triangle's box is padded,
+      // so a partition that separates nothing costs 1.1 x a positive lcost and loses -- unless lcost is not finite (a vertex at infinity)
+      if ((L[k].empty() && same_box(rbb[k], box)) || (R[k].empty() && same_box(lbb[k], box))) throw scene_error(kMeshLoopMessage);
       int l = rec(L[k], lbb[k], depth + 1);
       int r = rec(R[k], rbb[k], depth + 1);
       MeshData::Node& n = M.nodes[me];

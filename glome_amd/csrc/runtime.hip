@@ -500,6 +500,9 @@ int glome_ctx_device_info(glome_ctx* c, char* name, int cap, int* cu_count, int*
 }
 
 // ---- bih, built on the device (bih_build_device.hpp) ----
+static int32_t bihdev_status(int rc) {  // a refusal of the level loop as a status of the C ABI
+  return rc == bihdev::kRefusedLimit ? GLOME_E_LIMIT : rc == bihdev::kRefusedLoop ? GLOME_E_SCENE : GLOME_E_HIP;
+}
 int32_t glome_sb_bih_dev(glome_ctx* ctx, glome_sb* sb, const int32_t* ids, int32_t n, float* gpu_ms) {
   if (!ctx || !sb) { g_global_error = "null ctx or builder"; return GLOME_E_INVALID; }
   if (gpu_ms) *gpu_ms = 0;
@@ -517,7 +520,7 @@ int32_t glome_sb_bih_dev(glome_ctx* ctx, glome_sb* sb, const int32_t* ids, int32
     HIPCHK(ctx, hipSetDevice(ctx->device));
     auto T = std::make_shared<BihTree>();
     std::string err;
-    if (!bihdev::build(boxes, v, bb, *T, ctx->stream, err, gpu_ms)) { ctx->err = sb->err = err; return GLOME_E_LIMIT; }
+    if (const int rc = bihdev::build(boxes, v, bb, *T, ctx->stream, err, gpu_ms)) { ctx->err = sb->err = err; return bihdev_status(rc); }
     T->order = v;
     Node nd; nd.kind = K_BIH; nd.bih = T;
     return G.add(nd);
@@ -543,7 +546,7 @@ int32_t glome_sb_mesh_dev(glome_ctx* ctx, glome_sb* sb, const double* verts, int
     auto D = G.mesh_data(std::move(V), std::move(N), std::move(T), std::move(M), tbb);
     HIPCHK(ctx, hipSetDevice(ctx->device));
     std::string err;
-    if (!bihdev::build_mesh(tbb, *D, ctx->stream, err, gpu_ms)) { ctx->err = sb->err = err; return GLOME_E_LIMIT; }
+    if (const int rc = bihdev::build_mesh(tbb, *D, ctx->stream, err, gpu_ms)) { ctx->err = sb->err = err; return bihdev_status(rc); }
     return G.mesh_node(D);
   } catch (const scene_error& e) { ctx->err = sb->err = e.what(); return GLOME_E_SCENE; }
   catch (const std::exception& e) { ctx->err = sb->err = e.what(); return GLOME_E_INVALID; }

@@ -124,6 +124,10 @@ int32_t glome_sb_transform(glome_sb*, int32_t id, const double* xfms /* n*24 */,
 int32_t glome_sb_difference(glome_sb*, int32_t a, int32_t b);                                    /* Csg.hs:26-27 */
 int32_t glome_sb_difference_retexture(glome_sb*, int32_t a, int32_t b);                          /* Csg.hs:29-30: `Difference a b False` -- the surface hollowed out by b keeps b's textures (Csg.hs:42-43) */
 int32_t glome_sb_intersection(glome_sb*, const int32_t* ids, int n);                             /* Csg.hs:64-65 */
+/* GLOME_E_SCENE, no node added, for an infinite box (Bih.hs:319-322) and for an input on which the reference's build_rec does not
+ * terminate: a node of more than three items whose chosen partition leaves one side empty and the other child's box unchanged (a
+ * box of zero or underflowing surface area: four points on a line).  glome_sb_mesh refuses build_tree's fixed point (a vertex at
+ * infinity) the same way; glome_sb_load_nff / glome_sb_load_show go through the same constructors. */
 int32_t glome_sb_bih(glome_sb*, const int32_t* ids, int n);                                      /* Bih.hs:309-324 */
 /* tris: 8 ints per triangle = a b c na nb nc tex tag (-1 = none), Mesh.hs:27-29; mats = the mesh's texture vector */
 int32_t glome_sb_mesh(glome_sb*, const double* verts, int nv, const double* norms, int nn,
@@ -276,11 +280,18 @@ long glome_sb_bih_dump(glome_sb*, int32_t id, long cap, double* lsplit, double* 
 /* `bih` (Bih.hs:309-324) built on the GPU of `ctx`: the same node as glome_sb_bih over the same ids -- the tree of the
  * reference's build_rec (Bih.hs:211-285), node for node and bit for bit -- made level by level by four kernels per tree
  * level instead of by recursion on the host (100k triangles: see DESIGN.md).  *gpu_ms (may be NULL) = device time of the
- * build.  Needs the HIP half of the library (a context); the host builder stays the default and the checker. */
+ * build.  Needs the HIP half of the library (a context); the host builder stays the default and the checker.
+ *   Statuses are glome_sb_bih's (GLOME_E_SCENE with its message for an infinite box and for an input on which build_rec does not
+ * terminate, GLOME_E_INVALID for a bad id) and one of its own: a level of the tree costs six launches and a synchronisation, so a
+ * tree deeper than 2048 levels is refused with GLOME_E_LIMIT and a message naming the limit (the host builder has none).  The node
+ * and accumulator pools are sized from the item count by a bound that holds for every input (bih_build_device.hpp), so nothing
+ * else is refused.  A refused call adds no node; the context and the builder work on the next call. */
 int32_t glome_sb_bih_dev(glome_ctx*, glome_sb*, const int32_t* ids, int32_t n, float* gpu_ms);
 
 /* `mesh` (Mesh.hs:50-134) with its two-box BVH (build_tree, Mesh.hs:69-113) built on the GPU of `ctx`: arguments and
- * result as glome_sb_mesh, the tree the host builder makes (boxes, leaf order). */
+ * result as glome_sb_mesh, the tree the host builder makes (boxes, leaf order).  Statuses are glome_sb_mesh's (GLOME_E_SCENE
+ * with its message for a mesh on which build_tree does not terminate: a vertex at infinity) and the same limit of 2048 levels,
+ * refused the same way (GLOME_E_LIMIT, no node added); fewer than three triangles are built on the host. */
 int32_t glome_sb_mesh_dev(glome_ctx*, glome_sb*, const double* verts, int nv, const double* norms, int nn, const int32_t* tris, int nt, const int32_t* mats, int nm,
                           float* gpu_ms);
 
