@@ -744,6 +744,43 @@ static bool launch_events(glome_ctx* ctx, hipEvent_t& e0, hipEvent_t& e1) {
   if (pooled) ctx->pool_used += 2;
   return pooled;
 }
+// A light launch between a pair of the pool while timing is on: it takes part in glome_ctx_timing_begin / _end like a render launch.  (The
+// caller returns before this for an empty launch: no pair is taken for it.)
+template <class Launch> static int timed_launch(glome_ctx* ctx, Launch launch) {
+  hipEvent_t e0, e1;
+  const bool pooled = ctx->timing && launch_events(ctx, e0, e1);
+  if (pooled) HIPCHK(ctx, hipEventRecord(e0, ctx->stream));
+  launch();
+  HIPCHK(ctx, hipGetLastError());
+  if (pooled) HIPCHK(ctx, hipEventRecord(e1, ctx->stream));
+  return 0;
+}
+// a launch nobody waits for: what it ORs into the slot's error word is reported at the next synchronize
+static void mark_launched(glome_ctx* ctx) { ctx->slot().launched = true; ctx->slot().launched_on = ctx->stream; }
+// the lights of a launch's arguments (DRenderArgs, DTraceArgs; the caller has refused nlights > kMaxLights)
+template <class Args> static void fill_lights(Args& A, const glome_light* lights, int nlights) {
+  for (int i = 0; i < nlights; i++) {
+    memcpy(A.lights[i].pos, lights[i].pos, 12); memcpy(A.lights[i].color, lights[i].color, 12);
+    A.lights[i].rad = lights[i].rad; A.lights[i].shadow = lights[i].shadow;
+  }
+  A.nlights = nlights;
+}
+// What a launch asked for statistics does once it is on the stream: the wait, the slot's counters into `stats` (n_tiles and n_pixels are
+// the caller's), the time between the launch's events if it recorded them, and the error word read and cleared with the counters.
+static int read_stats(glome_ctx* ctx, glome_stats* stats, bool timed, hipEvent_t ev_start, hipEvent_t ev_stop) {
+  HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+  DCounters c;
+  HIPCHK(ctx, hipMemcpy(&c, ctx->slot().d_counters, sizeof(c), hipMemcpyDeviceToHost));
+  stats->rays_primary = c.rays_primary; stats->rays_shadow = c.rays_shadow; stats->rays_secondary = c.rays_secondary;
+  stats->bih_nodes = c.bih_nodes; stats->mesh_nodes = c.mesh_nodes; stats->prim_tests = c.prim_tests;
+  if (timed) HIPCHK(ctx, hipEventElapsedTime(&stats->kernel_ms, ev_start, ev_stop));
+  ctx->slot().launched = false;
+  if (c.error) {
+    HIPCHK(ctx, hipMemset(&ctx->slot().d_counters->error, 0, sizeof(unsigned int)));
+    return device_error_status(ctx, c.error);
+  }
+  return 0;
+}
 // the instance instances.hpp chose (choose_render / choose_sampler), on the context's stream and slot (whose overflow workspace the caller has sized: ensure_overflow)
 static int launch_chosen(glome_scene* s, const Choice& ch, InstanceKind kind, int grid, size_t lds, const DRenderArgs& A) {
   glome_ctx* ctx = s->ctx;
@@ -786,11 +823,8 @@ static int render_impl(glome_scene* s, const glome_camera* cam, const glome_ligh
   if (nframes > 1 && (frame_stride <= 0 || frame_stride > 0xffffffffll)) { ctx->err = "frame batches: positive frame stride"; return GLOME_E_INVALID; }
   for (int f = 1; f < nframes; f++) memcpy(&A.more_cams[f - 1], cam + f, sizeof(DCamera));
   A.nframes = nframes; A.frame_stride = nframes > 1 ? (uint32_t)frame_stride : 0u;
-  for (int i = 0; i < nlights; i++) {
-    memcpy(A.lights[i].pos, lights[i].pos, 12); memcpy(A.lights[i].color, lights[i].color, 12);
-    A.lights[i].rad = lights[i].rad; A.lights[i].shadow = lights[i].shadow;
-  }
-  A.nlights = nlights; A.width = P->width; A.height = P->height; A.fog = P->fog; A.maxdepth = P->maxdepth;
+  fill_lights(A, lights, nlights);
+  A.width = P->width; A.height = P->height; A.fog = P->fog; A.maxdepth = P->maxdepth;
   memcpy(A.thresholds, P->thresholds, 16);
   A.tiles = tt->dev; A.tile_lut = tt->lut; A.items = tt->items; A.ntiles = (int)tt->host.size(); A.total_waves = tt->total_waves;
   {
@@ -878,19 +912,10 @@ static int render_impl(glome_scene* s, const glome_camera* cam, const glome_ligh
   }
   if (stats) {
     memset(stats, 0, sizeof(*stats));
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    DCounters c;
-    HIPCHK(ctx, hipMemcpy(&c, ctx->slot().d_counters, sizeof(c), hipMemcpyDeviceToHost));
-    stats->rays_primary = c.rays_primary; stats->rays_shadow = c.rays_shadow; stats->rays_secondary = c.rays_secondary;
-    stats->bih_nodes = c.bih_nodes; stats->mesh_nodes = c.mesh_nodes; stats->prim_tests = c.prim_tests;
-    if (A.ntiles > 0) HIPCHK(ctx, hipEventElapsedTime(&stats->kernel_ms, ev_start, ev_stop));
     stats->n_tiles = A.ntiles; stats->n_pixels = (int32_t)tt->pixels;
-    ctx->slot().launched = false;
-    if (c.error) {
-      HIPCHK(ctx, hipMemset(&ctx->slot().d_counters->error, 0, sizeof(unsigned int)));
-      return device_error_status(ctx, c.error);
-    }
-  } else if (A.ntiles > 0) { ctx->slot().launched = true; ctx->slot().launched_on = ctx->stream; }
+    return read_stats(ctx, stats, A.ntiles > 0, ev_start, ev_stop);
+  }
+  if (A.ntiles > 0) mark_launched(ctx);
   return 0;
 }
 
@@ -916,6 +941,52 @@ int glome_render_packed_batch_dev(glome_scene* s, const glome_camera* cams, int 
   return render_impl(s, cams, lights, nlights, P, nullptr, packed_dev, stats, 0, nframes, frame_stride_pixels);
 }
 
+// ---- host-buffer forms: the caller's arrays staged through HBM ----
+// in: a device copy of an input (h null: the allocation alone).  out: the device twin of an output, copied back by fetch(); null when h is
+// null -- an output the caller does not want.  inout: both.  An allocation or a copy in that fails clears `ok`; an output that is not
+// wanted does not.  Everything is freed on every exit.
+struct Staging {
+  struct Out { void* h; const void* d; size_t bytes; };
+  std::vector<void*> bufs;
+  std::vector<Out> outs;
+  bool ok = true;
+  Staging() = default;
+  Staging(const Staging&) = delete;
+  ~Staging() { for (void* p : bufs) (void)hipFree(p); }
+  template <class T> T* in(const T* h, size_t n) {
+    T* d = nullptr;
+    if (hipMalloc((void**)&d, std::max<size_t>(1, n) * sizeof(T)) != hipSuccess) { ok = false; return nullptr; }
+    bufs.push_back(d);
+    if (h && hipMemcpy(d, h, n * sizeof(T), hipMemcpyHostToDevice) != hipSuccess) { ok = false; return nullptr; }
+    return d;
+  }
+  template <class T> T* out(T* h, size_t n, bool copy_in = false) {
+    T* d = h ? in<T>(copy_in ? h : nullptr, n) : nullptr;
+    if (d) outs.push_back({h, d, n * sizeof(T)});
+    return d;
+  }
+  template <class T> T* inout(T* h, size_t n) { return out(h, n, true); }
+  // the streams of a ray batch, staged in this order (a braced list); tmax stays null where the call has none
+  RayStream rays(const RayStream& h, size_t n) { return {in(h.ox, n), in(h.oy, n), in(h.oz, n), in(h.dx, n), in(h.dy, n), in(h.dz, n), h.tmax ? in(h.tmax, n) : nullptr}; }
+  hipError_t fetch() const {
+    for (const Out& o : outs)
+      if (hipError_t e = hipMemcpy(o.h, o.d, o.bytes, hipMemcpyDeviceToHost)) return e;
+    return hipSuccess;
+  }
+};
+// The tail of every host form, its arguments checked and staged: the device form, the wait and the slot's error word where the device form
+// has not seen to both itself (it has when it was given `stats`), the outputs back to the caller.
+template <class Dev> static int run_staged(glome_ctx* ctx, const Staging& st, bool dev_waited, Dev dev) {
+  if (!st.ok) { ctx->err = "staging allocation failed"; return GLOME_E_HIP; }
+  if (int rc = dev()) return rc;
+  if (!dev_waited) {
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    if (int rc = check_device_error(ctx)) return rc;
+  }
+  HIPCHK(ctx, st.fetch());
+  return 0;
+}
+
 int glome_render(glome_scene* s, const glome_camera* cam, const glome_light* lights, int nlights, const glome_render_params* P, float* rgbad,
                  uint32_t* packed, glome_stats* stats) {
   if (!s) return GLOME_E_INVALID;
@@ -924,23 +995,12 @@ int glome_render(glome_scene* s, const glome_camera* cam, const glome_light* lig
   if (rc) return rc;
   if (!rgbad) { ctx->err = "null framebuffer"; return GLOME_E_INVALID; }
   HIPCHK(ctx, hipSetDevice(ctx->device));
-  size_t np = (size_t)P->width * P->height;
-  float* d5 = nullptr; uint32_t* dp = nullptr;
-  HIPCHK(ctx, hipMalloc((void**)&d5, np * 5 * sizeof(float)));
-  // tiles this call does not own keep the caller's values
-  hipError_t e = hipMemcpy(d5, rgbad, np * 5 * sizeof(float), hipMemcpyHostToDevice);
-  if (e == hipSuccess && packed) { e = hipMalloc((void**)&dp, np * 4); if (e == hipSuccess) e = hipMemcpy(dp, packed, np * 4, hipMemcpyHostToDevice); }
-  if (e != hipSuccess) { ctx->err = hipGetErrorString(e); (void)hipFree(d5); if (dp) (void)hipFree(dp); return GLOME_E_HIP; }
+  const size_t np = (size_t)P->width * P->height;
+  Staging st;
+  float* d5 = st.inout(rgbad, np * 5);  // tiles this call does not own keep the caller's values
+  uint32_t* dp = st.inout(packed, np);
   glome_stats local;
-  rc = glome_render_dev(s, cam, lights, nlights, P, d5, dp, stats ? stats : &local);
-  if (rc == 0) {
-    e = hipMemcpy(rgbad, d5, np * 5 * sizeof(float), hipMemcpyDeviceToHost);
-    if (e == hipSuccess && packed) e = hipMemcpy(packed, dp, np * 4, hipMemcpyDeviceToHost);
-    if (e != hipSuccess) { ctx->err = hipGetErrorString(e); rc = GLOME_E_HIP; }
-  }
-  (void)hipFree(d5);
-  if (dp) (void)hipFree(dp);
-  return rc;
+  return run_staged(ctx, st, true, [&] { return glome_render_dev(s, cam, lights, nlights, P, d5, dp, stats ? stats : &local); });
 }
 
 // ---- per-ray seams ----
@@ -974,7 +1034,7 @@ int glome_rayint_batch_dev(glome_scene* s, size_t n, const float* ox, const floa
     if (int rc = reset_counters(ctx)) return rc;
     launch_rayint_batch_generic(batch_grid(ctx, n, 0), ctx->stream, s->dev, n, R, H, ctx->slot().d_counters);
   }
-  ctx->slot().launched = true; ctx->slot().launched_on = ctx->stream;  // (a limit hit here is this call's to report, at the next synchronize)
+  mark_launched(ctx);  // (a limit hit here is this call's to report, at the next synchronize)
   HIPCHK(ctx, hipGetLastError());
   return 0;
 }
@@ -994,29 +1054,12 @@ int glome_shadow_batch_dev(glome_scene* s, size_t n, const float* ox, const floa
     if (int rc = reset_counters(ctx)) return rc;
     launch_shadow_batch_generic(batch_grid(ctx, n, 0), ctx->stream, s->dev, n, R, occluded, ctx->slot().d_counters);
   }
-  ctx->slot().launched = true; ctx->slot().launched_on = ctx->stream;
+  mark_launched(ctx);
   HIPCHK(ctx, hipGetLastError());
   return 0;
 }
 
-// host-buffer wrappers: stage the SoA streams through HBM
-struct Staging {
-  glome_ctx* ctx;
-  std::vector<void*> bufs;
-  ~Staging() { for (void* p : bufs) (void)hipFree(p); }
-  template <class T> T* in(const T* h, size_t n) {
-    T* d = nullptr;
-    if (hipMalloc((void**)&d, std::max<size_t>(1, n) * sizeof(T)) != hipSuccess) return nullptr;
-    bufs.push_back(d);
-    if (h && hipMemcpy(d, h, n * sizeof(T), hipMemcpyHostToDevice) != hipSuccess) return nullptr;
-    return d;
-  }
-  // the seven streams of a ray batch
-  int rays(const float* const (&h)[7], size_t n, float* (&d)[7]) {
-    for (int k = 0; k < 7; k++) if (!(d[k] = in(h[k], n))) { ctx->err = "staging allocation failed"; return GLOME_E_HIP; }
-    return 0;
-  }
-};
+// the host-buffer forms (Staging, run_staged)
 int glome_rayint_batch(glome_scene* s, size_t n, const float* ox, const float* oy, const float* oz, const float* dx, const float* dy,
                        const float* dz, const float* tmax, float* t, int32_t* prim, float* nx, float* ny, float* nz, int32_t* tex8) {
   if (!s) return GLOME_E_INVALID;
@@ -1024,26 +1067,10 @@ int glome_rayint_batch(glome_scene* s, size_t n, const float* ox, const float* o
   if (n == 0) return 0;
   if (!ox || !oy || !oz || !dx || !dy || !dz || !tmax) { ctx->err = "null ray stream"; return GLOME_E_INVALID; }
   HIPCHK(ctx, hipSetDevice(ctx->device));
-  Staging st{ctx, {}};
-  float* din[7];
-  if (int rc = st.rays({ox, oy, oz, dx, dy, dz, tmax}, n, din)) return rc;
-  float* dt = t ? st.in<float>(nullptr, n) : nullptr;
-  int32_t* dprim = prim ? st.in<int32_t>(nullptr, n) : nullptr;
-  float* dnx = nx ? st.in<float>(nullptr, n) : nullptr;
-  float* dny = ny ? st.in<float>(nullptr, n) : nullptr;
-  float* dnz = nz ? st.in<float>(nullptr, n) : nullptr;
-  int32_t* dtex = tex8 ? st.in<int32_t>(nullptr, 8 * n) : nullptr;
-  int rc = glome_rayint_batch_dev(s, n, din[0], din[1], din[2], din[3], din[4], din[5], din[6], dt, dprim, dnx, dny, dnz, dtex);
-  if (rc) return rc;
-  HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-  if ((rc = check_device_error(ctx))) return rc;
-  if (t) HIPCHK(ctx, hipMemcpy(t, dt, n * 4, hipMemcpyDeviceToHost));
-  if (prim) HIPCHK(ctx, hipMemcpy(prim, dprim, n * 4, hipMemcpyDeviceToHost));
-  if (nx) HIPCHK(ctx, hipMemcpy(nx, dnx, n * 4, hipMemcpyDeviceToHost));
-  if (ny) HIPCHK(ctx, hipMemcpy(ny, dny, n * 4, hipMemcpyDeviceToHost));
-  if (nz) HIPCHK(ctx, hipMemcpy(nz, dnz, n * 4, hipMemcpyDeviceToHost));
-  if (tex8) HIPCHK(ctx, hipMemcpy(tex8, dtex, n * 32, hipMemcpyDeviceToHost));
-  return 0;
+  Staging st;
+  const RayStream R = st.rays({ox, oy, oz, dx, dy, dz, tmax}, n);
+  const HitStream H{st.out(t, n), st.out(prim, n), st.out(nx, n), st.out(ny, n), st.out(nz, n), st.out(tex8, 8 * n)};
+  return run_staged(ctx, st, false, [&] { return glome_rayint_batch_dev(s, n, R.ox, R.oy, R.oz, R.dx, R.dy, R.dz, R.tmax, H.t, H.prim, H.nx, H.ny, H.nz, H.tex8); });
 }
 int glome_shadow_batch(glome_scene* s, size_t n, const float* ox, const float* oy, const float* oz, const float* dx, const float* dy,
                        const float* dz, const float* tmax, uint8_t* occluded) {
@@ -1052,16 +1079,10 @@ int glome_shadow_batch(glome_scene* s, size_t n, const float* ox, const float* o
   if (n == 0) return 0;
   if (!ox || !oy || !oz || !dx || !dy || !dz || !tmax || !occluded) { ctx->err = "null stream"; return GLOME_E_INVALID; }
   HIPCHK(ctx, hipSetDevice(ctx->device));
-  Staging st{ctx, {}};
-  float* din[7];
-  if (int rc = st.rays({ox, oy, oz, dx, dy, dz, tmax}, n, din)) return rc;
-  uint8_t* docc = st.in<uint8_t>(nullptr, n);
-  int rc = glome_shadow_batch_dev(s, n, din[0], din[1], din[2], din[3], din[4], din[5], din[6], docc);
-  if (rc) return rc;
-  HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-  if ((rc = check_device_error(ctx))) return rc;
-  HIPCHK(ctx, hipMemcpy(occluded, docc, n, hipMemcpyDeviceToHost));
-  return 0;
+  Staging st;
+  const RayStream R = st.rays({ox, oy, oz, dx, dy, dz, tmax}, n);
+  uint8_t* docc = st.out(occluded, n);
+  return run_staged(ctx, st, false, [&] { return glome_shadow_batch_dev(s, n, R.ox, R.oy, R.oz, R.dx, R.dy, R.dz, R.tmax, docc); });
 }
 int glome_inside_batch(glome_scene* s, size_t n, const float* px, const float* py, const float* pz, uint8_t* inside) {
   if (!s) return GLOME_E_INVALID;
@@ -1069,18 +1090,15 @@ int glome_inside_batch(glome_scene* s, size_t n, const float* px, const float* p
   if (n == 0) return 0;
   if (!px || !py || !pz || !inside) { ctx->err = "null stream"; return GLOME_E_INVALID; }
   HIPCHK(ctx, hipSetDevice(ctx->device));
-  Staging st{ctx, {}};
+  Staging st;
   float *dx = st.in(px, n), *dy = st.in(py, n), *dz = st.in(pz, n);
-  uint8_t* din = st.in<uint8_t>(nullptr, n);
-  if (!dx || !dy || !dz || !din) { ctx->err = "staging allocation failed"; return GLOME_E_HIP; }
-  if (int rcc = reset_counters(ctx)) return rcc;
-  launch_inside_batch(batch_grid(ctx, n, 0), ctx->stream, s->dev, n, dx, dy, dz, din, ctx->slot().d_counters);
-  HIPCHK(ctx, hipGetLastError());
-  HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-  int rc = check_device_error(ctx);
-  if (rc) return rc;
-  HIPCHK(ctx, hipMemcpy(inside, din, n, hipMemcpyDeviceToHost));
-  return 0;
+  uint8_t* din = st.out(inside, n);
+  return run_staged(ctx, st, false, [&]() -> int {  // (the seam has no device-pointer form: its launch stands here)
+    if (int rc = reset_counters(ctx)) return rc;
+    launch_inside_batch(batch_grid(ctx, n, 0), ctx->stream, s->dev, n, dx, dy, dz, din, ctx->slot().d_counters);
+    HIPCHK(ctx, hipGetLastError());
+    return 0;
+  });
 }
 
 // ---- updates of a committed scene: what the four updates share ----
@@ -1102,14 +1120,9 @@ template <class Dev> static int run_blocking(glome_ctx* ctx, float* gpu_ms, Dev 
   return check_device_error(ctx);
 }
 // The frame of the updates' blocking host forms.  check(): what both forms of the call refuse.  validate(): what the host form alone can
-// see, the values in the caller's arrays.  stage(in) copies the arrays to the device through `in` and returns the device form as a
+// see, the values in the caller's arrays.  stage(st) copies the arrays to the device through st.in and returns the device form as a
 // callable: the copies stay outside the timed span, the device form runs inside it.  Refusals keep this order: check, validation, device
 // work.  empty: the call names nothing to update -- once it has passed the check and the validation it is complete.
-struct StageIn {
-  Staging stg;
-  bool ok = true;
-  template <class T> T* operator()(const T* h, size_t n) { T* d = stg.in<T>(h, n); ok = ok && d; return d; }
-};
 template <class Check, class Validate, class Stage> static int blocking_update(glome_scene* s, float* gpu_ms, Check check, Validate validate, Stage stage, bool empty = false) {
   if (!s) return GLOME_E_INVALID;
   glome_ctx* ctx = s->ctx;
@@ -1119,9 +1132,9 @@ template <class Check, class Validate, class Stage> static int blocking_update(g
   if (empty) return 0;
   HIPCHK(ctx, hipSetDevice(ctx->device));
   if (int rc = quiesce(ctx)) return rc;
-  StageIn in{{ctx, {}}};
-  auto dev = stage(in);
-  if (!in.ok) { ctx->err = "staging allocation failed"; return GLOME_E_HIP; }
+  Staging st;
+  auto dev = stage(st);
+  if (!st.ok) { ctx->err = "staging allocation failed"; return GLOME_E_HIP; }
   return run_blocking(ctx, gpu_ms, dev);
 }
 // One event pair per update while timing is on; with the update's split switch (GLOME_DEBUG_MESH_UPDATE_SPLIT,
@@ -1145,7 +1158,6 @@ template <class K, class... Args> static void launch_lanes(glome_ctx* ctx, K ker
   const uint32_t max_items = (uint32_t)ctx->prop.multiProcessorCount * 32u * 4u;
   hipLaunchKernelGGL(kernel, dim3(std::min<uint32_t>((n + 63u) >> 6, max_items)), dim3(64), 0, ctx->stream, args...);
 }
-static void mark_launched(glome_ctx* ctx) { ctx->slot().launched = true; ctx->slot().launched_on = ctx->stream; }
 // an update's workspace, `words` float4, allocated at the object's first update and kept until glome_scene_release
 static int ensure_ws(glome_scene* s, float4*& d_ws, size_t words) {
   if (d_ws) return 0;
@@ -1337,9 +1349,9 @@ template <class T> static int mesh_update_host(glome_scene* s, int32_t mesh_id, 
         for (size_t k = 0; k < 3 * (size_t)nn; k++) if (!std::isfinite(norms[k])) { s->ctx->err = "mesh update: a normal coordinate is not finite"; return GLOME_E_INVALID; }
         return 0;
       },
-      [&](StageIn& in) {
-        T* dv = in(verts, 3 * (size_t)nv);
-        T* dn = nn ? in(norms, 3 * (size_t)nn) : nullptr;
+      [&](Staging& st) {
+        T* dv = st.in(verts, 3 * (size_t)nv);
+        T* dn = nn ? st.in(norms, 3 * (size_t)nn) : nullptr;
         return [=] { return mesh_update_dev<T>(s, mesh_id, dv, nv, dn, nn); };
       });
 }
@@ -1435,8 +1447,8 @@ template <class T> static int bih_update_host(glome_scene* s, int32_t bih_id, co
         for (size_t k = 0; k < 9 * (size_t)n; k++) if (!std::isfinite(pts9[k])) { s->ctx->err = "bih update: a vertex coordinate is not finite"; return GLOME_E_INVALID; }
         return 0;
       },
-      [&](StageIn& in) {
-        T* dp = in(pts9, 9 * (size_t)n);
+      [&](Staging& st) {
+        T* dp = st.in(pts9, 9 * (size_t)n);
         return [=] { return bih_update_dev<T>(s, bih_id, dp, n); };
       });
 }
@@ -1477,10 +1489,10 @@ int glome_scene_bih_update_indexed(glome_scene* s, int32_t bih_id, const void* v
         }
         return 0;
       },
-      [&](StageIn& in) {
+      [&](Staging& st) {
         const size_t vbytes = 3 * (size_t)nv * (dtype == GLOME_F32 ? sizeof(float) : sizeof(double));
-        char* dv = in((const char*)verts, vbytes);  // the caller's arrays as they are: no widened, gathered copy
-        int32_t* di = in(idx3, 3 * (size_t)n);
+        char* dv = st.in((const char*)verts, vbytes);  // the caller's arrays as they are: no widened, gathered copy
+        int32_t* di = st.in(idx3, 3 * (size_t)n);
         return [=] { return glome_scene_bih_update_indexed_dev(s, bih_id, dv, dtype, nv, di, n); };
       });
 }
@@ -1501,8 +1513,8 @@ int glome_scene_sphere_bih_update(glome_scene* s, int32_t bih_id, const double* 
         for (size_t k = 0; k < (size_t)n; k++) if (!(c3r[4 * k + 3] > 0)) { s->ctx->err = "sphere bih update: radius of item " + std::to_string(k) + " is not positive"; return GLOME_E_INVALID; }
         return 0;
       },
-      [&](StageIn& in) {
-        double* dp = in(c3r, 4 * (size_t)n);
+      [&](Staging& st) {
+        double* dp = st.in(c3r, 4 * (size_t)n);
         return [=] { return glome_scene_sphere_bih_update_dev(s, bih_id, dp, n); };
       });
 }
@@ -1527,9 +1539,9 @@ int glome_scene_sphere_bih_update_f32(glome_scene* s, int32_t bih_id, const floa
         for (size_t k = 0; k < (size_t)n; k++) if (!(radii[k] > 0)) { s->ctx->err = "sphere bih update: radius of item " + std::to_string(k) + " is not positive"; return GLOME_E_INVALID; }
         return 0;
       },
-      [&](StageIn& in) {
-        float* dc = in(centres3, 3 * (size_t)n);
-        float* dr = in(radii, (size_t)n);
+      [&](Staging& st) {
+        float* dc = st.in(centres3, 3 * (size_t)n);
+        float* dr = st.in(radii, (size_t)n);
         return [=] { return glome_scene_sphere_bih_update_f32_dev(s, bih_id, dc, dr, n); };
       });
 }
@@ -1655,8 +1667,8 @@ int glome_scene_instance_update(glome_scene* s, const int32_t* ids, const double
     for (int k = 0; k < n; k++) if (int rc = instance_matrix_check(s, ids[k], U[(size_t)k], xfms + 24 * (size_t)k)) return rc;
     return 0;
   };
-  return blocking_update(s, gpu_ms, [&] { return instance_update_check(s, ids, xfms, n, U); }, validate, [&](StageIn& in) {
-    double* dx = in(xfms, 24 * (size_t)n);
+  return blocking_update(s, gpu_ms, [&] { return instance_update_check(s, ids, xfms, n, U); }, validate, [&](Staging& st) {
+    double* dx = st.in(xfms, 24 * (size_t)n);
     return [=] { return glome_scene_instance_update_dev(s, ids, dx, n); };
   }, n == 0);
 }
@@ -1750,12 +1762,12 @@ int glome_scene_instance_update_from(glome_scene* s, const int32_t* ids, const g
     }
     return 0;
   };
-  return blocking_update(s, gpu_ms, check, validate, [&](StageIn& in) {
+  return blocking_update(s, gpu_ms, check, validate, [&](Staging& st) {
     // the caller's array as it is, in its own dtype and stride (the tail after the last item is not the call's to read)
     const size_t elems = (size_t)(n - 1) * (size_t)stride + (size_t)xfm::width_of(src->form);
     glome_xfm_source d = *src;
-    d.data = in((const char*)src->data, elems * (src->dtype == GLOME_F32 ? sizeof(float) : sizeof(double)));
-    d.base = src->base ? in(src->base, 24 * (size_t)n) : nullptr;
+    d.data = st.in((const char*)src->data, elems * (src->dtype == GLOME_F32 ? sizeof(float) : sizeof(double)));
+    d.base = src->base ? st.in(src->base, 24 * (size_t)n) : nullptr;
     d.stride = stride;
     return [=] { return glome_scene_instance_update_from_dev(s, ids, &d, n); };
   }, n == 0);
@@ -1854,6 +1866,25 @@ int glome_scene_bih_refit(glome_scene* s, int32_t bih_id, float* gpu_ms) {
 }
 
 // ---- the trace seam: Trace.trace over a caller's ray streams (trace_kernels.hpp) ----
+// the limits of a call that shades, on its lights and its depth (the trace seam, the lens frames)
+static int shading_limits(glome_ctx* ctx, int nlights, int maxdepth) {
+  if (nlights > kMaxLights) { ctx->err = "too many lights"; return GLOME_E_LIMIT; }
+  if (maxdepth < 1 || maxdepth > kMaxTraceDepth) { ctx->err = "maxdepth must be in 1.." + std::to_string(kMaxTraceDepth); return GLOME_E_LIMIT; }
+  return 0;
+}
+// Everything a trace call of n > 0 rays is refused for on its arguments, in one order for both forms: trace_launch asks it first, the host
+// forms before they stage anything.  host_form: `work` is the caller's array, nothing the device reads -- its staged twin is a device
+// allocation, aligned far beyond 16 bytes.
+static int trace_check(glome_ctx* ctx, size_t n, const RayStream& R, const glome_light* lights, int nlights, const glome_trace_params* P,
+                       const float* rgbad, bool with_work, const uint32_t* work, bool host_form) {
+  if (!R.ox || !R.oy || !R.oz || !R.dx || !R.dy || !R.dz) { ctx->err = "null ray stream"; return GLOME_E_INVALID; }
+  if ((!rgbad && !with_work) || !P || nlights < 0 || (nlights > 0 && !lights)) { ctx->err = "bad argument"; return GLOME_E_INVALID; }
+  if (with_work && !work) { ctx->err = "null work buffer"; return GLOME_E_INVALID; }
+  if (with_work && !host_form && ((uintptr_t)work & 15u)) { ctx->err = "the work buffer must be 16-byte aligned"; return GLOME_E_INVALID; }
+  if (int rc = shading_limits(ctx, nlights, P->maxdepth)) return rc;
+  if (n > ((size_t)1 << 31)) { ctx->err = "a trace launch carries at most 2^31 rays"; return GLOME_E_LIMIT; }
+  return 0;
+}
 // One launch for both forms.  with_work: glome_trace_work_batch_dev -- `work` receives a record per ray, rgbad may be null, and the launch
 // takes the counting instance whatever count_work says; else `work` is null and rgbad is required.
 static int trace_launch(glome_scene* s, size_t n, const float* ox, const float* oy, const float* oz, const float* dx, const float* dy,
@@ -1863,22 +1894,13 @@ static int trace_launch(glome_scene* s, size_t n, const float* ox, const float* 
   if (!s) return GLOME_E_INVALID;
   glome_ctx* ctx = s->ctx;
   if (n == 0) return 0;
-  if (!ox || !oy || !oz || !dx || !dy || !dz) { ctx->err = "null ray stream"; return GLOME_E_INVALID; }
-  if ((!rgbad && !with_work) || !P || nlights < 0 || (nlights > 0 && !lights)) { ctx->err = "bad argument"; return GLOME_E_INVALID; }
-  if (with_work && !work) { ctx->err = "null work buffer"; return GLOME_E_INVALID; }
-  if (with_work && ((uintptr_t)work & 15u)) { ctx->err = "the work buffer must be 16-byte aligned"; return GLOME_E_INVALID; }
-  if (nlights > kMaxLights) { ctx->err = "too many lights"; return GLOME_E_LIMIT; }
-  if (P->maxdepth < 1 || P->maxdepth > kMaxTraceDepth) { ctx->err = "maxdepth must be in 1.." + std::to_string(kMaxTraceDepth); return GLOME_E_LIMIT; }
-  if (n > ((size_t)1 << 31)) { ctx->err = "a trace launch carries at most 2^31 rays"; return GLOME_E_LIMIT; }
+  if (int rc = trace_check(ctx, n, {ox, oy, oz, dx, dy, dz, tmax}, lights, nlights, P, rgbad, with_work, work, false)) return rc;
   HIPCHK(ctx, hipSetDevice(ctx->device));
   DTraceArgs A;
   memset(&A, 0, sizeof(A));
   A.S = s->dev;
-  for (int i = 0; i < nlights; i++) {
-    memcpy(A.lights[i].pos, lights[i].pos, 12); memcpy(A.lights[i].color, lights[i].color, 12);
-    A.lights[i].rad = lights[i].rad; A.lights[i].shadow = lights[i].shadow;
-  }
-  A.nlights = nlights; A.maxdepth = P->maxdepth; A.n = (uint32_t)n;
+  fill_lights(A, lights, nlights);
+  A.maxdepth = P->maxdepth; A.n = (uint32_t)n;
   A.check_unit = P->faithful ? 0 : 1;
   A.want_counters = stats ? 1 : 0;
   A.ox = ox; A.oy = oy; A.oz = oz; A.dx = dx; A.dy = dy; A.dz = dz; A.tmax = tmax;
@@ -1904,21 +1926,10 @@ static int trace_launch(glome_scene* s, size_t n, const float* ox, const float* 
   }
   HIPCHK(ctx, hipGetLastError());
   if (timed) HIPCHK(ctx, hipEventRecord(ev_stop, ctx->stream));
-  if (!stats) { ctx->slot().launched = true; ctx->slot().launched_on = ctx->stream; return 0; }  // (a refusal or a limit is reported at the next synchronize)
+  if (!stats) { mark_launched(ctx); return 0; }  // (a refusal or a limit is reported at the next synchronize)
   memset(stats, 0, sizeof(*stats));
-  HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-  DCounters c;
-  HIPCHK(ctx, hipMemcpy(&c, ctx->slot().d_counters, sizeof(c), hipMemcpyDeviceToHost));
-  stats->rays_primary = c.rays_primary; stats->rays_shadow = c.rays_shadow; stats->rays_secondary = c.rays_secondary;
-  stats->bih_nodes = c.bih_nodes; stats->mesh_nodes = c.mesh_nodes; stats->prim_tests = c.prim_tests;
-  HIPCHK(ctx, hipEventElapsedTime(&stats->kernel_ms, ev_start, ev_stop));
   stats->n_tiles = (int32_t)items; stats->n_pixels = (int32_t)std::min<size_t>(n, 0x7fffffff);
-  ctx->slot().launched = false;
-  if (c.error) {
-    HIPCHK(ctx, hipMemset(&ctx->slot().d_counters->error, 0, sizeof(unsigned int)));
-    return device_error_status(ctx, c.error);
-  }
-  return 0;
+  return read_stats(ctx, stats, true, ev_start, ev_stop);
 }
 int glome_trace_batch_dev(glome_scene* s, size_t n, const float* ox, const float* oy, const float* oz, const float* dx, const float* dy,
                           const float* dz, const float* tmax, const glome_light* lights, int nlights, const glome_trace_params* P,
@@ -1930,35 +1941,22 @@ int glome_trace_work_batch_dev(glome_scene* s, size_t n, const float* ox, const 
                                float* rgbad, uint32_t* work, glome_stats* stats) {
   return trace_launch(s, n, ox, oy, oz, dx, dy, dz, tmax, lights, nlights, P, rgbad, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, true, work, stats);
 }
-// the rays of a host-buffer trace call, staged: din[6] stays null without tmax
-static int stage_rays(glome_ctx* ctx, Staging& st, size_t n, const float* const h[7], float* din[7]) {
-  for (int k = 0; k < (h[6] ? 7 : 6); k++) if (!(din[k] = st.in(h[k], n))) { ctx->err = "staging allocation failed"; return GLOME_E_HIP; }
-  return 0;
-}
 int glome_trace_work_batch(glome_scene* s, size_t n, const float* ox, const float* oy, const float* oz, const float* dx, const float* dy,
                            const float* dz, const float* tmax, const glome_light* lights, int nlights, const glome_trace_params* P,
                            float* rgbad, uint32_t* work, glome_stats* stats) {
   if (!s) return GLOME_E_INVALID;
   glome_ctx* ctx = s->ctx;
   if (n == 0) return 0;
-  if (!ox || !oy || !oz || !dx || !dy || !dz) { ctx->err = "null ray stream"; return GLOME_E_INVALID; }
-  if (!P) { ctx->err = "bad argument"; return GLOME_E_INVALID; }
-  if (!work) { ctx->err = "null work buffer"; return GLOME_E_INVALID; }
-  if (n > ((size_t)1 << 31)) { ctx->err = "a trace launch carries at most 2^31 rays"; return GLOME_E_LIMIT; }
+  if (int rc = trace_check(ctx, n, {ox, oy, oz, dx, dy, dz, tmax}, lights, nlights, P, rgbad, true, work, true)) return rc;
   HIPCHK(ctx, hipSetDevice(ctx->device));
-  Staging st{ctx, {}};
-  float* din[7] = {};
-  const float* const h[7] = {ox, oy, oz, dx, dy, dz, tmax};
-  if (int rcs = stage_rays(ctx, st, n, h, din)) return rcs;
-  float* d5 = rgbad ? st.in<float>(nullptr, n * 5) : nullptr;
-  uint32_t* dwork = st.in<uint32_t>(nullptr, n * kWorkWords);  // (a device allocation: aligned far beyond 16 bytes)
-  if ((rgbad && !d5) || !dwork) { ctx->err = "staging allocation failed"; return GLOME_E_HIP; }
+  Staging st;
+  const RayStream R = st.rays({ox, oy, oz, dx, dy, dz, tmax}, n);
+  float* d5 = st.out(rgbad, n * 5);
+  uint32_t* dwork = st.out(work, n * kWorkWords);
   glome_stats local;
-  int rc = glome_trace_work_batch_dev(s, n, din[0], din[1], din[2], din[3], din[4], din[5], din[6], lights, nlights, P, d5, dwork, stats ? stats : &local);
-  if (rc) return rc;
-  if (rgbad) HIPCHK(ctx, hipMemcpy(rgbad, d5, n * 20, hipMemcpyDeviceToHost));
-  HIPCHK(ctx, hipMemcpy(work, dwork, n * kWorkWords * 4, hipMemcpyDeviceToHost));
-  return 0;
+  return run_staged(ctx, st, true, [&] {
+    return glome_trace_work_batch_dev(s, n, R.ox, R.oy, R.oz, R.dx, R.dy, R.dz, R.tmax, lights, nlights, P, d5, dwork, stats ? stats : &local);
+  });
 }
 int glome_trace_batch(glome_scene* s, size_t n, const float* ox, const float* oy, const float* oz, const float* dx, const float* dy,
                       const float* dz, const float* tmax, const glome_light* lights, int nlights, const glome_trace_params* P,
@@ -1966,33 +1964,16 @@ int glome_trace_batch(glome_scene* s, size_t n, const float* ox, const float* oy
   if (!s) return GLOME_E_INVALID;
   glome_ctx* ctx = s->ctx;
   if (n == 0) return 0;
-  if (!ox || !oy || !oz || !dx || !dy || !dz) { ctx->err = "null ray stream"; return GLOME_E_INVALID; }
-  if (!rgbad || !P) { ctx->err = "bad argument"; return GLOME_E_INVALID; }
-  if (n > ((size_t)1 << 31)) { ctx->err = "a trace launch carries at most 2^31 rays"; return GLOME_E_LIMIT; }
+  if (int rc = trace_check(ctx, n, {ox, oy, oz, dx, dy, dz, tmax}, lights, nlights, P, rgbad, false, nullptr, true)) return rc;
   HIPCHK(ctx, hipSetDevice(ctx->device));
-  Staging st{ctx, {}};
-  float* din[7] = {};
-  const float* const h[7] = {ox, oy, oz, dx, dy, dz, tmax};
-  if (int rcs = stage_rays(ctx, st, n, h, din)) return rcs;
-  float* d5 = st.in<float>(nullptr, n * 5);
-  float* dt = t ? st.in<float>(nullptr, n) : nullptr;
-  int32_t* dprim = prim ? st.in<int32_t>(nullptr, n) : nullptr;
-  float* dnx = nx ? st.in<float>(nullptr, n) : nullptr;
-  float* dny = ny ? st.in<float>(nullptr, n) : nullptr;
-  float* dnz = nz ? st.in<float>(nullptr, n) : nullptr;
-  int32_t* dtex = tex8 ? st.in<int32_t>(nullptr, 8 * n) : nullptr;
-  if (!d5 || (t && !dt) || (prim && !dprim) || (nx && !dnx) || (ny && !dny) || (nz && !dnz) || (tex8 && !dtex)) { ctx->err = "staging allocation failed"; return GLOME_E_HIP; }
+  Staging st;
+  const RayStream R = st.rays({ox, oy, oz, dx, dy, dz, tmax}, n);
+  float* d5 = st.out(rgbad, n * 5);
+  const HitStream H{st.out(t, n), st.out(prim, n), st.out(nx, n), st.out(ny, n), st.out(nz, n), st.out(tex8, 8 * n)};
   glome_stats local;
-  int rc = glome_trace_batch_dev(s, n, din[0], din[1], din[2], din[3], din[4], din[5], din[6], lights, nlights, P, d5, dt, dprim, dnx, dny, dnz, dtex, stats ? stats : &local);
-  if (rc) return rc;
-  HIPCHK(ctx, hipMemcpy(rgbad, d5, n * 20, hipMemcpyDeviceToHost));
-  if (t) HIPCHK(ctx, hipMemcpy(t, dt, n * 4, hipMemcpyDeviceToHost));
-  if (prim) HIPCHK(ctx, hipMemcpy(prim, dprim, n * 4, hipMemcpyDeviceToHost));
-  if (nx) HIPCHK(ctx, hipMemcpy(nx, dnx, n * 4, hipMemcpyDeviceToHost));
-  if (ny) HIPCHK(ctx, hipMemcpy(ny, dny, n * 4, hipMemcpyDeviceToHost));
-  if (nz) HIPCHK(ctx, hipMemcpy(nz, dnz, n * 4, hipMemcpyDeviceToHost));
-  if (tex8) HIPCHK(ctx, hipMemcpy(tex8, dtex, n * 32, hipMemcpyDeviceToHost));
-  return 0;
+  return run_staged(ctx, st, true, [&] {
+    return glome_trace_batch_dev(s, n, R.ox, R.oy, R.oz, R.dx, R.dy, R.dz, R.tmax, lights, nlights, P, d5, H.t, H.prim, H.nx, H.ny, H.nz, H.tex8, stats ? stats : &local);
+  });
 }
 
 // ---- frames through the trace seam: raygen and resolve (lens_kernels.hpp), and the pass loop that chains them around a trace launch ----
@@ -2029,17 +2010,12 @@ static int resolve_check(glome_ctx* ctx, int32_t width, int32_t height, int32_t 
   if (first_pixel < 0 || n_pixels < 0 || first_pixel > total || n_pixels > total - first_pixel) { ctx->err = "pixel range outside the frame"; return GLOME_E_INVALID; }
   return 0;
 }
-// the two launches (arguments checked; both take part in glome_ctx_timing_begin / _end like a render launch)
+// the blocks of a raygen launch of n rays: a wave per 64, at most CUs * 128 -- the kernels stride
+static int lens_grid(glome_ctx* ctx, uint32_t n) { return (int)std::min<uint32_t>((n + 63u) >> 6, (uint32_t)ctx->prop.multiProcessorCount * 32u * 4u); }
+// the two launches (arguments checked; timed_launch: both take part in glome_ctx_timing_begin / _end like a render launch)
 static int lens_launch_rays(glome_ctx* ctx, const DLensArgs& A) {
   if (A.n == 0) return 0;
-  hipEvent_t e0, e1;
-  const bool pooled = ctx->timing && launch_events(ctx, e0, e1);
-  if (pooled) HIPCHK(ctx, hipEventRecord(e0, ctx->stream));
-  const uint32_t items = (A.n + 63u) >> 6;
-  launch_camera_rays((int)std::min<uint32_t>(items, (uint32_t)ctx->prop.multiProcessorCount * 32u * 4u), ctx->stream, A);
-  HIPCHK(ctx, hipGetLastError());
-  if (pooled) HIPCHK(ctx, hipEventRecord(e1, ctx->stream));
-  return 0;
+  return timed_launch(ctx, [&] { launch_camera_rays(lens_grid(ctx, A.n), ctx->stream, A); });
 }
 static int lens_launch_resolve(glome_ctx* ctx, int32_t samples, int64_t first_pixel, int64_t n_pixels, const float* in, float* rgbad, uint32_t* packed) {
   if (n_pixels == 0) return 0;
@@ -2047,13 +2023,7 @@ static int lens_launch_resolve(glome_ctx* ctx, int32_t samples, int64_t first_pi
   A.samples_in = in; A.rgbad = rgbad; A.packed = packed;
   A.first_pixel = (uint32_t)first_pixel; A.n_pixels = (uint32_t)n_pixels; A.samples = samples;
   A.vec = ((uintptr_t)in & 15u) == 0 ? 1 : 0;
-  hipEvent_t e0, e1;
-  const bool pooled = ctx->timing && launch_events(ctx, e0, e1);
-  if (pooled) HIPCHK(ctx, hipEventRecord(e0, ctx->stream));
-  launch_resolve((int)((n_pixels + 63) / 64), ctx->stream, A);  // (a wave per 64 pixels: at most 2^24 blocks)
-  HIPCHK(ctx, hipGetLastError());
-  if (pooled) HIPCHK(ctx, hipEventRecord(e1, ctx->stream));
-  return 0;
+  return timed_launch(ctx, [&] { launch_resolve((int)((n_pixels + 63) / 64), ctx->stream, A); });  // (a wave per 64 pixels: at most 2^24 blocks)
 }
 int glome_camera_rays_dev(glome_ctx* ctx, const glome_camera* cam, const glome_raygen_params* P, int64_t first_ray, int64_t n_rays,
                           float* ox, float* oy, float* oz, float* dx, float* dy, float* dz) {
@@ -2073,15 +2043,14 @@ int glome_camera_rays(glome_ctx* ctx, const glome_camera* cam, const glome_rayge
   if (!ox || !oy || !oz || !dx || !dy || !dz) { ctx->err = "null ray stream"; return GLOME_E_INVALID; }
   if (n_rays == 0) return 0;
   HIPCHK(ctx, hipSetDevice(ctx->device));
-  Staging st{ctx, {}};
-  float* h[6] = {ox, oy, oz, dx, dy, dz};
-  float* d[6];
-  for (int k = 0; k < 6; k++) if (!(d[k] = st.in<float>(nullptr, (size_t)n_rays))) { ctx->err = "staging allocation failed"; return GLOME_E_HIP; }
-  A.ox = d[0]; A.oy = d[1]; A.oz = d[2]; A.dx = d[3]; A.dy = d[4]; A.dz = d[5];
-  if (int rc = lens_launch_rays(ctx, A)) return rc;
-  HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-  for (int k = 0; k < 6; k++) HIPCHK(ctx, hipMemcpy(h[k], d[k], (size_t)n_rays * sizeof(float), hipMemcpyDeviceToHost));
-  return 0;
+  Staging st;
+  const size_t n = (size_t)n_rays;
+  A.ox = st.out(ox, n); A.oy = st.out(oy, n); A.oz = st.out(oz, n); A.dx = st.out(dx, n); A.dy = st.out(dy, n); A.dz = st.out(dz, n);
+  return run_staged(ctx, st, true, [&]() -> int {  // (raygen raises nothing in the slot's error word: the wait is all there is to see to)
+    if (int rc = lens_launch_rays(ctx, A)) return rc;
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    return 0;
+  });
 }
 int glome_resolve_dev(glome_ctx* ctx, int32_t width, int32_t height, int32_t samples, int64_t first_pixel, int64_t n_pixels,
                       const float* rgbad_samples, float* rgbad, uint32_t* packed) {
@@ -2112,8 +2081,49 @@ static int render_lens_check(glome_ctx* ctx, const glome_camera* cam, const glom
   if (!rgbad && !packed) { ctx->err = "a frame needs somewhere to go: rgbad, packed or both"; return GLOME_E_INVALID; }
   if (!TP || nlights < 0 || (nlights > 0 && !lights) || rays_per_pass < 0) { ctx->err = "bad argument"; return GLOME_E_INVALID; }
   if ((int64_t)RP->width * RP->height * RP->samples > (1ll << 31)) { ctx->err = "glome_render_lens renders at most 2^31 rays per frame"; return GLOME_E_INVALID; }
-  if (nlights > kMaxLights) { ctx->err = "too many lights"; return GLOME_E_LIMIT; }
-  if (TP->maxdepth < 1 || TP->maxdepth > kMaxTraceDepth) { ctx->err = "maxdepth must be in 1.." + std::to_string(kMaxTraceDepth); return GLOME_E_LIMIT; }
+  return shading_limits(ctx, nlights, TP->maxdepth);
+}
+// The workspace of a pass of `rays` rays, carved: the six streams into A, then the results.
+static int lens_workspace(glome_ctx* ctx, size_t rays, DLensArgs& A, float** results) {
+  if (int rc = ensure_lens(ctx, rays)) return rc;
+  const size_t sf = lens_stream_floats(rays);
+  float* w = ctx->slot().d_lens;
+  A.ox = w; A.oy = w + sf; A.oz = w + 2 * sf; A.dx = w + 3 * sf; A.dy = w + 4 * sf; A.dz = w + 5 * sf;
+  *results = w + 6 * sf;
+  return 0;
+}
+// a stage's statistics added to its frame's: the trace launch's own, and the times of the launches before and after it
+static void add_stats(glome_stats* sum, const glome_stats& ps, float ms_before, float ms_after) {
+  sum->rays_primary += ps.rays_primary; sum->rays_shadow += ps.rays_shadow; sum->rays_secondary += ps.rays_secondary;
+  sum->bih_nodes += ps.bih_nodes; sum->mesh_nodes += ps.mesh_nodes; sum->prim_tests += ps.prim_tests;
+  sum->kernel_ms += ms_before + ps.kernel_ms + ms_after;
+  sum->n_tiles += ps.n_tiles;
+}
+// One traced stage of a lens frame: produce() launches what puts n rays into the workspace's streams (A), the trace seam turns them into n
+// results, consume() launches what takes the results.  With `stats` the two launches are timed between ev2 and ev3 (the trace launch in
+// between records ev0 / ev1), the call waits for the stage and adds it to the frame's statistics; without, it waits for nothing.
+template <class Produce, class Consume>
+static int traced_stage(glome_scene* s, const DLensArgs& A, float* results, size_t n, const glome_light* lights, int nlights, const glome_trace_params* TP,
+                        glome_stats* stats, Produce produce, Consume consume) {
+  glome_ctx* ctx = s->ctx;
+  float ms_produce = 0, ms_consume = 0;
+  glome_stats ps;
+  if (stats) HIPCHK(ctx, hipEventRecord(ctx->ev2, ctx->stream));
+  if (int rc = produce()) return rc;
+  if (stats) HIPCHK(ctx, hipEventRecord(ctx->ev3, ctx->stream));
+  if (int rc = glome_trace_batch_dev(s, n, A.ox, A.oy, A.oz, A.dx, A.dy, A.dz, nullptr, lights, nlights, TP, results, nullptr, nullptr, nullptr, nullptr, nullptr,
+                                     nullptr, stats ? &ps : nullptr)) return rc;
+  if (stats) {  // (the trace launch has synchronised the stream: the producer's pair is complete)
+    HIPCHK(ctx, hipEventElapsedTime(&ms_produce, ctx->ev2, ctx->ev3));
+    HIPCHK(ctx, hipEventRecord(ctx->ev2, ctx->stream));
+  }
+  if (int rc = consume()) return rc;
+  if (stats) {
+    HIPCHK(ctx, hipEventRecord(ctx->ev3, ctx->stream));
+    HIPCHK(ctx, hipEventSynchronize(ctx->ev3));
+    HIPCHK(ctx, hipEventElapsedTime(&ms_consume, ctx->ev2, ctx->ev3));
+    add_stats(stats, ps, ms_produce, ms_consume);
+  }
   return 0;
 }
 int glome_render_lens_dev(glome_scene* s, const glome_camera* cam, const glome_raygen_params* RP, const glome_light* lights, int nlights,
@@ -2125,36 +2135,14 @@ int glome_render_lens_dev(glome_scene* s, const glome_camera* cam, const glome_r
   const int64_t pixels = (int64_t)RP->width * RP->height, samples = RP->samples;
   HIPCHK(ctx, hipSetDevice(ctx->device));
   const int64_t per_pass = std::min<int64_t>(pixels, std::max<int64_t>(1, (rays_per_pass ? rays_per_pass : kLensRaysPerPass) / samples));  // pixels
-  if (int rc = ensure_lens(ctx, (size_t)(per_pass * samples))) return rc;
-  const size_t sf = lens_stream_floats((size_t)(per_pass * samples));
-  float* w = ctx->slot().d_lens;
-  A.ox = w; A.oy = w + sf; A.oz = w + 2 * sf; A.dx = w + 3 * sf; A.dy = w + 4 * sf; A.dz = w + 5 * sf;
-  float* results = w + 6 * sf;
+  float* results;
+  if (int rc = lens_workspace(ctx, (size_t)(per_pass * samples), A, &results)) return rc;
   if (stats) memset(stats, 0, sizeof(*stats));
   for (int64_t p0 = 0; p0 < pixels; p0 += per_pass) {
     const int64_t np = std::min(per_pass, pixels - p0), n = np * samples;
     A.first_pixel = (uint32_t)p0; A.first_s = 0; A.n = (uint32_t)n;
-    float ms_rays = 0, ms_resolve = 0;
-    glome_stats ps;
-    if (stats) HIPCHK(ctx, hipEventRecord(ctx->ev2, ctx->stream));
-    if (int rc = lens_launch_rays(ctx, A)) return rc;
-    if (stats) HIPCHK(ctx, hipEventRecord(ctx->ev3, ctx->stream));
-    if (int rc = glome_trace_batch_dev(s, (size_t)n, A.ox, A.oy, A.oz, A.dx, A.dy, A.dz, nullptr, lights, nlights, TP, results, nullptr, nullptr, nullptr, nullptr,
-                                       nullptr, nullptr, stats ? &ps : nullptr)) return rc;
-    if (stats) {  // (the trace launch has synchronised the stream: the raygen pair is complete)
-      HIPCHK(ctx, hipEventElapsedTime(&ms_rays, ctx->ev2, ctx->ev3));
-      HIPCHK(ctx, hipEventRecord(ctx->ev2, ctx->stream));
-    }
-    if (int rc = lens_launch_resolve(ctx, (int32_t)samples, p0, np, results, rgbad_dev, packed_dev)) return rc;
-    if (stats) {
-      HIPCHK(ctx, hipEventRecord(ctx->ev3, ctx->stream));
-      HIPCHK(ctx, hipEventSynchronize(ctx->ev3));
-      HIPCHK(ctx, hipEventElapsedTime(&ms_resolve, ctx->ev2, ctx->ev3));
-      stats->rays_primary += ps.rays_primary; stats->rays_shadow += ps.rays_shadow; stats->rays_secondary += ps.rays_secondary;
-      stats->bih_nodes += ps.bih_nodes; stats->mesh_nodes += ps.mesh_nodes; stats->prim_tests += ps.prim_tests;
-      stats->kernel_ms += ms_rays + ps.kernel_ms + ms_resolve;
-      stats->n_tiles += ps.n_tiles;
-    }
+    if (int rc = traced_stage(s, A, results, (size_t)n, lights, nlights, TP, stats, [&] { return lens_launch_rays(ctx, A); },
+                              [&] { return lens_launch_resolve(ctx, (int32_t)samples, p0, np, results, rgbad_dev, packed_dev); })) return rc;
   }
   if (stats) stats->n_pixels = (int32_t)pixels;
   return 0;
@@ -2167,15 +2155,11 @@ int glome_render_lens(glome_scene* s, const glome_camera* cam, const glome_rayge
   if (int rc = render_lens_check(ctx, cam, RP, lights, nlights, TP, rays_per_pass, rgbad, packed, A)) return rc;
   HIPCHK(ctx, hipSetDevice(ctx->device));
   const size_t np = (size_t)RP->width * RP->height;
-  Staging st{ctx, {}};
-  float* d5 = rgbad ? st.in<float>(nullptr, np * 5) : nullptr;
-  uint32_t* dp = packed ? st.in<uint32_t>(nullptr, np) : nullptr;
-  if ((rgbad && !d5) || (packed && !dp)) { ctx->err = "staging allocation failed"; return GLOME_E_HIP; }
+  Staging st;
+  float* d5 = st.out(rgbad, np * 5);
+  uint32_t* dp = st.out(packed, np);
   glome_stats local;
-  if (int rc = glome_render_lens_dev(s, cam, RP, lights, nlights, TP, rays_per_pass, d5, dp, stats ? stats : &local)) return rc;
-  if (rgbad) HIPCHK(ctx, hipMemcpy(rgbad, d5, np * 5 * sizeof(float), hipMemcpyDeviceToHost));
-  if (packed) HIPCHK(ctx, hipMemcpy(packed, dp, np * sizeof(uint32_t), hipMemcpyDeviceToHost));
-  return 0;
+  return run_staged(ctx, st, true, [&] { return glome_render_lens_dev(s, cam, RP, lights, nlights, TP, rays_per_pass, d5, dp, stats ? stats : &local); });
 }
 
 // ---- adaptive lens frames: a pass in rounds, one per level of the rule (adaptive_rule.hpp, lens_adaptive_kernels.hpp) ----
@@ -2201,28 +2185,6 @@ static int render_lens_adaptive_check(glome_ctx* ctx, const glome_camera* cam, c
   if (const char* why = adaptive_rule_error(AP->base_samples, RP->samples, AP->threshold)) { ctx->err = why; return GLOME_E_INVALID; }
   return 0;
 }
-// the two launches of a round that are this path's own (timed like lens_launch_rays / _resolve)
-static int adapt_launch_rays(glome_ctx* ctx, const DLensListArgs& A) {
-  if (A.L.n == 0) return 0;
-  hipEvent_t e0, e1;
-  const bool pooled = ctx->timing && launch_events(ctx, e0, e1);
-  if (pooled) HIPCHK(ctx, hipEventRecord(e0, ctx->stream));
-  const uint32_t items = (A.L.n + 63u) >> 6;
-  launch_camera_rays_list((int)std::min<uint32_t>(items, (uint32_t)ctx->prop.multiProcessorCount * 32u * 4u), ctx->stream, A);
-  HIPCHK(ctx, hipGetLastError());
-  if (pooled) HIPCHK(ctx, hipEventRecord(e1, ctx->stream));
-  return 0;
-}
-static int adapt_launch_fold(glome_ctx* ctx, bool first, const DAdaptFoldArgs& A) {
-  if (A.n == 0) return 0;
-  hipEvent_t e0, e1;
-  const bool pooled = ctx->timing && launch_events(ctx, e0, e1);
-  if (pooled) HIPCHK(ctx, hipEventRecord(e0, ctx->stream));
-  launch_adaptive_fold((int)((A.n + 63u) / 64u), ctx->stream, first, A);  // (a wave per 64 entries: at most 2^24 blocks)
-  HIPCHK(ctx, hipGetLastError());
-  if (pooled) HIPCHK(ctx, hipEventRecord(e1, ctx->stream));
-  return 0;
-}
 int glome_render_lens_adaptive_dev(glome_scene* s, const glome_camera* cam, const glome_raygen_params* RP, const glome_light* lights, int nlights,
                                    const glome_trace_params* TP, const glome_adaptive_params* AP, int64_t rays_per_pass, float* rgbad_dev,
                                    uint32_t* packed_dev, uint8_t* counts_dev, glome_stats* stats) {
@@ -2234,12 +2196,9 @@ int glome_render_lens_adaptive_dev(glome_scene* s, const glome_camera* cam, cons
   HIPCHK(ctx, hipSetDevice(ctx->device));
   const int64_t per_pass = std::min<int64_t>(pixels, std::max<int64_t>(1, (rays_per_pass ? rays_per_pass : kLensRaysPerPass) / max));  // pixels
   const size_t round_rays = (size_t)(per_pass * std::max(base, max / 2));  // the most a round holds: round 0's, or the last round's with every pixel listed
-  if (int rc = ensure_lens(ctx, round_rays)) return rc;
+  float* results;
+  if (int rc = lens_workspace(ctx, round_rays, A, &results)) return rc;
   if (int rc = ensure_adapt(ctx, (size_t)per_pass)) return rc;
-  const size_t sf = lens_stream_floats(round_rays);
-  float* w = ctx->slot().d_lens;
-  A.ox = w; A.oy = w + sf; A.oz = w + 2 * sf; A.dx = w + 3 * sf; A.dy = w + 4 * sf; A.dz = w + 5 * sf;
-  float* results = w + 6 * sf;
   uint32_t* counters = ctx->slot().d_adapt;
   float* state = reinterpret_cast<float*>(counters + kAdaptCounterWords);
   uint32_t* lists[2] = {counters + kAdaptCounterWords + 5 * per_pass, counters + kAdaptCounterWords + 6 * per_pass};
@@ -2252,40 +2211,27 @@ int glome_render_lens_adaptive_dev(glome_scene* s, const glome_camera* cam, cons
     for (int64_t level = base;; level *= 2, round++) {
       const int64_t h = level / 2, n = round == 0 ? np * base : (int64_t)len * h;
       const bool last = level == max;
-      float ms_rays = 0, ms_fold = 0;
-      glome_stats ps;
-      if (stats) HIPCHK(ctx, hipEventRecord(ctx->ev2, ctx->stream));
-      if (round == 0) {  // samples [0, base) of every pixel of the pass: k_camera_rays's own frame order at samples = base
-        A.samples = (int32_t)base; A.first_pixel = (uint32_t)p0; A.first_s = 0; A.n = (uint32_t)n;
-        if (int rc = lens_launch_rays(ctx, A)) return rc;
-      } else {
+      auto rays = [&]() -> int {
+        if (round == 0) {  // samples [0, base) of every pixel of the pass: k_camera_rays's own frame order at samples = base
+          A.samples = (int32_t)base; A.first_pixel = (uint32_t)p0; A.first_s = 0; A.n = (uint32_t)n;
+          return lens_launch_rays(ctx, A);
+        }
         DLensListArgs LA;
         LA.L = A; LA.L.first_pixel = (uint32_t)p0; LA.L.n = (uint32_t)n;
         LA.list = lists[(round - 1) & 1]; LA.pass_pixels = (uint32_t)np; LA.h = (uint32_t)h;
-        if (int rc = adapt_launch_rays(ctx, LA)) return rc;
-      }
-      if (stats) HIPCHK(ctx, hipEventRecord(ctx->ev3, ctx->stream));
-      if (int rc = glome_trace_batch_dev(s, (size_t)n, A.ox, A.oy, A.oz, A.dx, A.dy, A.dz, nullptr, lights, nlights, TP, results, nullptr, nullptr, nullptr, nullptr,
-                                         nullptr, nullptr, stats ? &ps : nullptr)) return rc;
-      if (stats) {  // (the trace launch has synchronised the stream: the raygen pair is complete)
-        HIPCHK(ctx, hipEventElapsedTime(&ms_rays, ctx->ev2, ctx->ev3));
-        HIPCHK(ctx, hipEventRecord(ctx->ev2, ctx->stream));
-      }
-      DAdaptFoldArgs F;
-      F.samples_in = results; F.rgbad = rgbad_dev; F.packed = packed_dev; F.counts = counts_dev;
-      F.state = state; F.list_in = lists[(round - 1) & 1]; F.list_out = lists[round & 1]; F.counter = counters + round;
-      F.first_pixel = (uint32_t)p0; F.pass_pixels = (uint32_t)np; F.n = len;
-      F.level = (int32_t)level; F.last = last ? 1 : 0; F.threshold = AP->threshold;
-      if (int rc = adapt_launch_fold(ctx, round == 0, F)) return rc;
-      if (stats) {
-        HIPCHK(ctx, hipEventRecord(ctx->ev3, ctx->stream));
-        HIPCHK(ctx, hipEventSynchronize(ctx->ev3));
-        HIPCHK(ctx, hipEventElapsedTime(&ms_fold, ctx->ev2, ctx->ev3));
-        stats->rays_primary += ps.rays_primary; stats->rays_shadow += ps.rays_shadow; stats->rays_secondary += ps.rays_secondary;
-        stats->bih_nodes += ps.bih_nodes; stats->mesh_nodes += ps.mesh_nodes; stats->prim_tests += ps.prim_tests;
-        stats->kernel_ms += ms_rays + ps.kernel_ms + ms_fold;
-        stats->n_tiles += ps.n_tiles;
-      }
+        if (LA.L.n == 0) return 0;
+        return timed_launch(ctx, [&] { launch_camera_rays_list(lens_grid(ctx, LA.L.n), ctx->stream, LA); });
+      };
+      auto fold = [&]() -> int {
+        DAdaptFoldArgs F;
+        F.samples_in = results; F.rgbad = rgbad_dev; F.packed = packed_dev; F.counts = counts_dev;
+        F.state = state; F.list_in = lists[(round - 1) & 1]; F.list_out = lists[round & 1]; F.counter = counters + round;
+        F.first_pixel = (uint32_t)p0; F.pass_pixels = (uint32_t)np; F.n = len;
+        F.level = (int32_t)level; F.last = last ? 1 : 0; F.threshold = AP->threshold;
+        if (F.n == 0) return 0;
+        return timed_launch(ctx, [&] { launch_adaptive_fold((int)((F.n + 63u) / 64u), ctx->stream, round == 0, F); });  // (a wave per 64 entries: at most 2^24 blocks)
+      };
+      if (int rc = traced_stage(s, A, results, (size_t)n, lights, nlights, TP, stats, rays, fold)) return rc;
       if (last) break;
       // the next round's size: 4 bytes and one wait for the stream
       HIPCHK(ctx, hipMemcpyAsync(&len, counters + round, sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
@@ -2306,17 +2252,12 @@ int glome_render_lens_adaptive(glome_scene* s, const glome_camera* cam, const gl
   if (int rc = render_lens_adaptive_check(ctx, cam, RP, lights, nlights, TP, AP, rays_per_pass, rgbad, packed, A)) return rc;
   HIPCHK(ctx, hipSetDevice(ctx->device));
   const size_t np = (size_t)RP->width * RP->height;
-  Staging st{ctx, {}};
-  float* d5 = rgbad ? st.in<float>(nullptr, np * 5) : nullptr;
-  uint32_t* dp = packed ? st.in<uint32_t>(nullptr, np) : nullptr;
-  uint8_t* dc = counts ? st.in<uint8_t>(nullptr, np) : nullptr;
-  if ((rgbad && !d5) || (packed && !dp) || (counts && !dc)) { ctx->err = "staging allocation failed"; return GLOME_E_HIP; }
+  Staging st;
+  float* d5 = st.out(rgbad, np * 5);
+  uint32_t* dp = st.out(packed, np);
+  uint8_t* dc = st.out(counts, np);
   glome_stats local;
-  if (int rc = glome_render_lens_adaptive_dev(s, cam, RP, lights, nlights, TP, AP, rays_per_pass, d5, dp, dc, stats ? stats : &local)) return rc;
-  if (rgbad) HIPCHK(ctx, hipMemcpy(rgbad, d5, np * 5 * sizeof(float), hipMemcpyDeviceToHost));
-  if (packed) HIPCHK(ctx, hipMemcpy(packed, dp, np * sizeof(uint32_t), hipMemcpyDeviceToHost));
-  if (counts) HIPCHK(ctx, hipMemcpy(counts, dc, np * sizeof(uint8_t), hipMemcpyDeviceToHost));
-  return 0;
+  return run_staged(ctx, st, true, [&] { return glome_render_lens_adaptive_dev(s, cam, RP, lights, nlights, TP, AP, rays_per_pass, d5, dp, dc, stats ? stats : &local); });
 }
 
 // ---- tile payload transport ----
