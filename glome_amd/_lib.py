@@ -127,6 +127,8 @@ SYMBOLS = [
     ("glome_sb_instance_transform", C.c_int, [vp, C.c_int32, c_dp]),
     ("glome_sb_bih_items", C.c_int32, [vp, C.c_int32, c_ip, C.c_int32]),
     ("glome_sb_bih_refit", C.c_int, [vp, C.c_int32]),
+    ("glome_sb_bih_resplit", C.c_int, [vp, C.c_int32]),
+    ("glome_sb_bih_layout", C.c_int, [vp, C.c_int32, C.POINTER(C.c_int64)]),
     ("glome_sb_bihs_above", C.c_int32, [vp, C.c_int32, C.c_int32, c_ip, C.c_int32]),
     ("glome_sb_mesh_set_vertices", C.c_int, [vp, C.c_int32, c_dp, C.c_int, c_dp, C.c_int]),
     ("glome_sb_tex", C.c_int32, [vp, C.c_int32, C.c_int32]),
@@ -176,6 +178,14 @@ SYMBOLS = [
     ("glome_xfm_source_size", C.c_size_t, []),
     ("glome_scene_instance_update_from", C.c_int, [vp, c_ip, C.POINTER(XfmSource), C.c_int, C.POINTER(C.c_float)]),
     ("glome_scene_instance_update_from_dev", C.c_int, [vp, c_ip, C.POINTER(XfmSource), C.c_int]),
+    ("glome_scene_bih_rebuild", C.c_int, [vp, C.c_int32, c_dp, C.c_int, C.POINTER(C.c_float)]),
+    ("glome_scene_bih_rebuild_dev", C.c_int, [vp, C.c_int32, vp, C.c_int, C.POINTER(C.c_float)]),
+    ("glome_scene_bih_rebuild_indexed", C.c_int, [vp, C.c_int32, vp, C.c_int32, C.c_int, c_ip, C.c_int, C.POINTER(C.c_float)]),
+    ("glome_scene_bih_rebuild_indexed_dev", C.c_int, [vp, C.c_int32, vp, C.c_int32, C.c_int, vp, C.c_int, C.POINTER(C.c_float)]),
+    ("glome_scene_sphere_bih_rebuild", C.c_int, [vp, C.c_int32, c_dp, C.c_int, C.POINTER(C.c_float)]),
+    ("glome_scene_sphere_bih_rebuild_dev", C.c_int, [vp, C.c_int32, vp, C.c_int, C.POINTER(C.c_float)]),
+    ("glome_scene_bih_layout", C.c_int, [vp, C.c_int32, C.POINTER(C.c_int64)]),
+    ("glome_scene_bih_rebuild_stages", C.c_int, [vp, c_dp]),
     ("glome_scene_nested_updates", C.c_int, [vp, C.c_int]),
     ("glome_scene_bih_refit", C.c_int, [vp, C.c_int32, C.POINTER(C.c_float)]),
     ("glome_scene_bih_refit_dev", C.c_int, [vp, C.c_int32]),

@@ -385,6 +385,19 @@ class Builder:
         bih_set_triangles / instance_set_transforms of something below, call it for every bih above, inner trees first (bihs_above)."""
         self._chk(self.lib.glome_sb_bih_refit(self.h, int(node)), "glome_sb_bih_refit")
 
+    def bih_resplit(self, node):
+        """The tree built again in place from its items' bounds as they stand (glome_sb_bih_resplit): the tree `bih` makes over
+        bih_items(node) in that order, under the old id; the update order stays.  After bih_set_triangles / bih_set_spheres of a pose
+        that has degraded the tree; then bih_refit of the bihs above, inner trees first."""
+        self._chk(self.lib.glome_sb_bih_resplit(self.h, int(node)), "glome_sb_bih_resplit")
+
+    def bih_layout(self, node):
+        """What a commit lays out for a bih of plain triangles or plain spheres (glome_sb_bih_layout): a dict of `slots` (node slots,
+        treelet padding included), `pairs` (pair records), `records` and `depth`."""
+        out = (C.c_int64 * 4)()
+        self._chk(self.lib.glome_sb_bih_layout(self.h, int(node), out), "glome_sb_bih_layout")
+        return dict(zip(("slots", "pairs", "records", "depth"), (int(x) for x in out)))
+
     def bihs_above(self, root, node):
         """the bihs above `node` in the scene under `root`, in an order in which they can be refitted (glome_sb_bihs_above); raises with
         the reason when an update of `node` would be refused even with nested updates on"""
@@ -672,6 +685,54 @@ class Scene:
         dtype = 1 if np.asarray(verts).dtype == np.float32 else 0
         return self._host_update(self.lib.glome_scene_bih_update_indexed, bih_id, [(verts, np.float32 if dtype else np.float64, 3), (idx, np.int32, 3)],
                                  lambda p, n: (p[0], dtype, n[0], p[1], n[1]), ptr={np.float32: C.c_void_p, np.float64: C.c_void_p, np.int32: L.c_ip})
+
+    def _rebuild(self, call, host, dev, bih_id, values, what, per_row):
+        """the rebuilds that take one float64 array: NumPy takes the host form, a CUDA torch.float64 tensor the device form; both block and
+        return the device milliseconds"""
+        if hasattr(values, "data_ptr"):
+            p, n = self._dev_arg(values, call, what, ("torch.float64",), per_row)
+            ms = C.c_float(0)
+            self._chk(dev(self.h, int(bih_id), p, n, C.byref(ms)), dev.__name__)
+            return ms.value
+        return self._host_update(host, bih_id, [(values, np.float64, per_row)], lambda p, n: (p[0], n[0]))
+
+    def bih_rebuild(self, bih_id, pts9):
+        """A committed triangle bih re-split in place from new triangles (glome_scene_bih_rebuild): the scene a commit after
+        Builder.bih_set_triangles and Builder.bih_resplit would have made.  Arguments as bih_update; NOT asynchronous in either form: returns
+        the device milliseconds when the scene is complete."""
+        return self._rebuild("bih_rebuild", self.lib.glome_scene_bih_rebuild, self.lib.glome_scene_bih_rebuild_dev, bih_id, pts9, "pts9", 9)
+
+    def sphere_bih_rebuild(self, bih_id, c3r):
+        """A committed sphere bih re-split in place from new centres and radii (glome_scene_sphere_bih_rebuild); arguments as
+        sphere_bih_update, blocking like bih_rebuild."""
+        return self._rebuild("sphere_bih_rebuild", self.lib.glome_scene_sphere_bih_rebuild, self.lib.glome_scene_sphere_bih_rebuild_dev, bih_id, c3r, "c3r", 4)
+
+    def bih_rebuild_indexed(self, bih_id, verts, idx):
+        """bih_rebuild from a vertex array [nv, 3], float32 or float64, and an int32 table [n, 3] (glome_scene_bih_rebuild_indexed);
+        arguments as bih_update_indexed, blocking like bih_rebuild."""
+        if hasattr(verts, "data_ptr") or hasattr(idx, "data_ptr"):
+            pv, nv = self._dev_arg(verts, "bih_rebuild_indexed", "verts", ("torch.float32", "torch.float64"), 3)
+            pi, n = self._dev_arg(idx, "bih_rebuild_indexed", "idx", ("torch.int32",), 3)
+            dtype = 1 if str(verts.dtype) == "torch.float32" else 0  # GLOME_F32 / GLOME_F64
+            ms = C.c_float(0)
+            self._chk(self.lib.glome_scene_bih_rebuild_indexed_dev(self.h, int(bih_id), pv, dtype, nv, pi, n, C.byref(ms)), "glome_scene_bih_rebuild_indexed_dev")
+            return ms.value
+        dtype = 1 if np.asarray(verts).dtype == np.float32 else 0
+        return self._host_update(self.lib.glome_scene_bih_rebuild_indexed, bih_id, [(verts, np.float32 if dtype else np.float64, 3), (idx, np.int32, 3)],
+                                 lambda p, n: (p[0], dtype, n[0], p[1], n[1]), ptr={np.float32: C.c_void_p, np.float64: C.c_void_p, np.int32: L.c_ip})
+
+    def bih_layout(self, bih_id):
+        """A committed triangle or sphere bih as it stands (glome_scene_bih_layout): a dict of `slots`, `pairs`, `records`, `depth`, and the
+        capacities `slot_cap` and `pair_cap` of its node and pair segments."""
+        out = (C.c_int64 * 6)()
+        self._chk(self.lib.glome_scene_bih_layout(self.h, int(bih_id), out), "glome_scene_bih_layout")
+        return dict(zip(("slots", "pairs", "records", "depth", "slot_cap", "pair_cap"), (int(x) for x in out)))
+
+    def bih_rebuild_stages(self):
+        """the last rebuild's host wall-clock milliseconds by stage (glome_scene_bih_rebuild_stages): boxes, levels, tables, upload, values"""
+        out = np.zeros(5)
+        self._chk(self.lib.glome_scene_bih_rebuild_stages(self.h, out.ctypes.data_as(L.c_dp)), "glome_scene_bih_rebuild_stages")
+        return dict(zip(("boxes", "levels", "tables", "upload", "values"), out.tolist()))
 
     def bih_update_f32(self, bih_id, pts9):
         """bih_update from float32 (glome_scene_bih_update_f32): nine values per item; the scene bih_update gives for the widened array, bit

@@ -351,21 +351,27 @@ __global__ void k_bb_scatter(int n, Objs O, const int* idx, const int* nodeof, c
 
 #define BB_HIP(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { err = std::string(#call) + ": " + hipGetErrorString(e_); status = kFailed; goto done; } } while (0)
 
-// The level loop.  boxes: the objects' bounds in input order; bb: the root's box.  Leaves nodes (breadth-first device
-// numbering) and the final object order.  Returns kBuilt, or a refusal / failure with `err` set and nothing left behind.
+// A built node as the host needs it to lay a tree out: the topology and the node's segment of the object array, 24 bytes of DevNode's
+// 120 (a caller that makes the planes again itself -- the rebuild of a committed tree, runtime.hip -- reads these back instead)
+struct PackedNode { int start, count, left, right, axis, leaf; };
+__global__ void k_bb_pack(const DevNode* nodes, int n, PackedNode* out) {
+  int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const DevNode& N = nodes[i];
+  out[i] = PackedNode{N.start, N.count, N.left, N.right, N.axis, N.leaf};
+}
+
+// The level loop.  d_box: the n objects' bounds in input order on the device, SoA (lo.x[n] lo.y[n] lo.z[n] hi.x[n] hi.y[n] hi.z[n]);
+// bb: the root's box.  Leaves the nodes (breadth-first device numbering) -- whole in `nodes`, or, when `packed` is given, their
+// topology alone in *packed -- and the final object order.  Returns kBuilt, or a refusal / failure with `err` set and nothing left behind.
 template <bool MESH>
-inline int levels(const std::vector<Box3>& boxes, const Box3& bb, hipStream_t st, std::string& err, float* gpu_ms, std::vector<DevNode>& nodes, std::vector<int>& order) {
+inline int levels_dev(const double* d_box, int n, const Box3& bb, hipStream_t st, std::string& err, float* gpu_ms, std::vector<DevNode>& nodes, std::vector<int>& order,
+                      std::vector<PackedNode>* packed = nullptr) {
   using AccT = typename std::conditional<MESH, AccM, Acc>::type;
-  const int n = (int)boxes.size();
   if (kNodeCap(n) > 0x7fffffffll) { err = "device tree build: more objects than the node pool can number"; return kRefusedLimit; }
   const int node_cap = (int)kNodeCap(n), acc_cap = (int)kAccCap(n);
-  std::vector<double> h((size_t)6 * n);
-  for (int i = 0; i < n; i++) {
-    const Box3& b = boxes[(size_t)i];
-    const double v[6] = {b.lo.x, b.lo.y, b.lo.z, b.hi.x, b.hi.y, b.hi.z};
-    for (int a = 0; a < 6; a++) h[(size_t)a * n + i] = v[a];
-  }
-  double* d_box = nullptr; double* d_mid = nullptr; double* d_area = nullptr;
+  double* d_mid = nullptr; double* d_area = nullptr;
+  PackedNode* d_packed = nullptr;
   int* d_idx[2] = {nullptr, nullptr}; int* d_nodeof[2] = {nullptr, nullptr};
   int* d_pre = nullptr; int* d_bsum = nullptr; int* d_cnt = nullptr;
   DevNode* d_nodes = nullptr; AccT* d_acc = nullptr;
@@ -376,12 +382,11 @@ inline int levels(const std::vector<Box3>& boxes, const Box3& bb, hipStream_t st
   int hcnt[2] = {1, 0};
   DevNode root{};
   Objs O{};
-  BB_HIP(hipMalloc((void**)&d_box, sizeof(double) * 6 * n)); BB_HIP(hipMalloc((void**)&d_mid, sizeof(double) * 3 * n)); BB_HIP(hipMalloc((void**)&d_area, sizeof(double) * n));
+  BB_HIP(hipMalloc((void**)&d_mid, sizeof(double) * 3 * n)); BB_HIP(hipMalloc((void**)&d_area, sizeof(double) * n));
   for (int q = 0; q < 2; q++) { BB_HIP(hipMalloc((void**)&d_idx[q], sizeof(int) * n)); BB_HIP(hipMalloc((void**)&d_nodeof[q], sizeof(int) * n)); }
   BB_HIP(hipMalloc((void**)&d_pre, sizeof(int) * n)); BB_HIP(hipMalloc((void**)&d_bsum, sizeof(int) * (nscan + 1))); BB_HIP(hipMalloc((void**)&d_cnt, sizeof(int) * 2));
   BB_HIP(hipMalloc((void**)&d_nodes, sizeof(DevNode) * (size_t)node_cap)); BB_HIP(hipMalloc((void**)&d_acc, sizeof(AccT) * (size_t)acc_cap));
   BB_HIP(hipEventCreate(&e0)); BB_HIP(hipEventCreate(&e1));
-  BB_HIP(hipMemcpyAsync(d_box, h.data(), sizeof(double) * 6 * n, hipMemcpyHostToDevice, st));
   root.start = 0; root.count = n;
   root.lo[0] = bb.lo.x; root.lo[1] = bb.lo.y; root.lo[2] = bb.lo.z; root.hi[0] = bb.hi.x; root.hi[1] = bb.hi.y; root.hi[2] = bb.hi.z;
   { D3 m = box_mid(bb); root.mid[0] = m.x; root.mid[1] = m.y; root.mid[2] = m.z; }
@@ -415,13 +420,21 @@ inline int levels(const std::vector<Box3>& boxes, const Box3& bb, hipStream_t st
     lvl_begin = lvl_end; lvl_end = hcnt[0];
   }
   BB_HIP(hipEventRecord(e1, st));
-  nodes.resize((size_t)lvl_end); order.resize((size_t)n);
-  BB_HIP(hipMemcpyAsync(nodes.data(), d_nodes, sizeof(DevNode) * nodes.size(), hipMemcpyDeviceToHost, st));
+  order.resize((size_t)n);
+  if (packed) {
+    packed->resize((size_t)lvl_end);
+    BB_HIP(hipMalloc((void**)&d_packed, sizeof(PackedNode) * packed->size()));
+    hipLaunchKernelGGL(k_bb_pack, dim3((lvl_end + 255) / 256), dim3(256), 0, st, (const DevNode*)d_nodes, lvl_end, d_packed);
+    BB_HIP(hipMemcpyAsync(packed->data(), d_packed, sizeof(PackedNode) * packed->size(), hipMemcpyDeviceToHost, st));
+  } else {
+    nodes.resize((size_t)lvl_end);
+    BB_HIP(hipMemcpyAsync(nodes.data(), d_nodes, sizeof(DevNode) * nodes.size(), hipMemcpyDeviceToHost, st));
+  }
   BB_HIP(hipMemcpyAsync(order.data(), d_idx[cur], sizeof(int) * n, hipMemcpyDeviceToHost, st));
   BB_HIP(hipStreamSynchronize(st));
   if (gpu_ms) BB_HIP(hipEventElapsedTime(gpu_ms, e0, e1));
 done:
-  (void)hipFree(d_box); (void)hipFree(d_mid); (void)hipFree(d_area);
+  (void)hipFree(d_mid); (void)hipFree(d_area); (void)hipFree(d_packed);
   for (int q = 0; q < 2; q++) { (void)hipFree(d_idx[q]); (void)hipFree(d_nodeof[q]); }
   (void)hipFree(d_pre); (void)hipFree(d_bsum); (void)hipFree(d_cnt); (void)hipFree(d_nodes); (void)hipFree(d_acc);
   if (e0) (void)hipEventDestroy(e0);
@@ -429,16 +442,36 @@ done:
   return status;
 }
 
+// The same from the objects' bounds on the host: uploads them, then levels_dev
+template <bool MESH>
+inline int levels(const std::vector<Box3>& boxes, const Box3& bb, hipStream_t st, std::string& err, float* gpu_ms, std::vector<DevNode>& nodes, std::vector<int>& order) {
+  const int n = (int)boxes.size();
+  std::vector<double> h((size_t)6 * n);
+  for (int i = 0; i < n; i++) {
+    const Box3& b = boxes[(size_t)i];
+    const double v[6] = {b.lo.x, b.lo.y, b.lo.z, b.hi.x, b.hi.y, b.hi.z};
+    for (int a = 0; a < 6; a++) h[(size_t)a * n + i] = v[a];
+  }
+  double* d_box = nullptr;
+  hipError_t e = hipMalloc((void**)&d_box, sizeof(double) * 6 * n);
+  if (e == hipSuccess) e = hipMemcpyAsync(d_box, h.data(), sizeof(double) * 6 * n, hipMemcpyHostToDevice, st);
+  if (e != hipSuccess) { err = std::string("device tree build: the objects' boxes: ") + hipGetErrorString(e); (void)hipFree(d_box); return kFailed; }
+  const int rc = levels_dev<MESH>(d_box, n, bb, st, err, gpu_ms, nodes, order);  // (it ends with a synchronisation: h has been read)
+  if (rc != kBuilt) (void)hipStreamSynchronize(st);
+  (void)hipFree(d_box);
+  return rc;
+}
+
 // breadth-first device numbering -> the preorder trees of the host builders (explicit stack: deep trees)
-template <class TREE, class LEAF, class BRANCH>
-inline void to_preorder(const std::vector<DevNode>& nodes, TREE& T, LEAF&& leaf, BRANCH&& branch) {
+template <class DN, class TREE, class LEAF, class BRANCH>
+inline void to_preorder(const std::vector<DN>& nodes, TREE& T, LEAF&& leaf, BRANCH&& branch) {
   T.nodes.clear(); T.depth = 0;
   struct Item { int dev, parent, depth; bool right; };
   std::vector<Item> stack{{0, -1, 0, false}};
   while (!stack.empty()) {
     Item it = stack.back();
     stack.pop_back();
-    const DevNode& d = nodes[(size_t)it.dev];
+    const DN& d = nodes[(size_t)it.dev];
     const int me = (int)T.nodes.size();
     T.nodes.push_back({});
     T.depth = std::max(T.depth, it.depth + 1);

@@ -255,6 +255,28 @@ int glome_sb_bih_refit(glome_sb* sb, int32_t bih_id) {
     return 0;
   });
 }
+int glome_sb_bih_resplit(glome_sb* sb, int32_t bih_id) {
+  return guard(sb, [&] {
+    sb->graph.bih_resplit(bih_id);
+    return 0;
+  });
+}
+int glome_sb_bih_layout(glome_sb* sb, int32_t bih_id, int64_t out4[4]) {
+  return guard(sb, [&] {
+    if (!out4) throw std::invalid_argument("bih_layout: null output");
+    const Graph& G = sb_graph(sb);
+    if (G.at(bih_id).kind != K_BIH) throw std::invalid_argument(std::string("bih_layout: node ") + std::to_string(bih_id) + " is a " + kind_name(G.at(bih_id).kind) + ", not a Bih");
+    FlatScene F;  // the commit's own layout, of a scene that is only this tree
+    Flattener fl(G, F);
+    fl.run(bih_id);
+    for (const LeafBihUpdateInfo& U : F.leaf_bih_updates) {
+      if (U.node != bih_id) continue;
+      out4[0] = U.n_slots; out4[1] = U.n_pair_recs; out4[2] = U.n_recs; out4[3] = U.depth;
+      return 0;
+    }
+    throw std::invalid_argument("bih_layout: bih " + std::to_string(bih_id) + " is not a leaf bih: its items are not all plain triangles or all plain spheres");
+  });
+}
 int32_t glome_sb_bihs_above(glome_sb* sb, int32_t root, int32_t node_id, int32_t* out, int32_t cap) {
   return guard(sb, [&] {
     FlatScene F;

@@ -60,6 +60,9 @@ struct LeafBihUpdateInfo {
   uint32_t hdr = 0;               // bihhdr index
   uint32_t first_slot = 0, n_slots = 0;  // its node slots (bihnodes index, count; unused slots included)
   uint32_t first_prim = 0, first_rec = 0, n_recs = 0;
+  uint32_t n_pair_recs = 0;       // its pair records in `tripairs` (LeafBihLayout::n_pair_recs) ...
+  uint64_t first_pair_word = 0;   // ... from this float index on
+  int depth = 0;                  // BihTree::depth
   uint32_t row_words = 2;         // 2 for triangles, 1 for spheres
   bool pk = false;                // the tree has the packet form: pknodes and tripairs follow (never a sphere tree)
   std::vector<uint32_t> rows;
@@ -147,6 +150,153 @@ GLOME_HD float round_down(double d) { float f = (float)d; return ((double)f > d)
 
 constexpr uint32_t BREF_LEAF_BIT = 1u << 29, BREF_FIRST_LIMIT = 1u << 26;  // child references, see rt_device.hpp
 
+// Node slots of a committed bih: only branches (and leaves of 7+ items, whose extent lives in a slot) get one.  Branches are laid out
+// in small treelets -- a node, then its branch children, then a grandchild, four 16-byte nodes to a 64-byte cache
+// line -- and the treelets depth first, so the step after a fetch usually finds its node in the line just fetched
+// and a subtree is contiguous.  References are explicit, so the traversal does not care about the order.
+// slot[k]: node k's slot from the tree's (line-aligned) base, 0xffffffff for none; returns the slots used, skipped ones included.
+inline uint32_t bih_slots(const BihTree& T, std::vector<uint32_t>& slot) {
+  slot.assign(T.nodes.size(), 0xffffffffu);
+  uint32_t nslots = 0;
+  std::vector<int> roots;  // treelet roots still to place (a stack: depth first)
+  if (!T.nodes.empty() && !T.nodes[0].leaf) roots.push_back(0);
+  while (!roots.empty()) {
+    int x = roots.back(); roots.pop_back();
+    int group[4]; int ng = 0;
+    group[ng++] = x;
+    for (int q = 0; q < ng && ng < 4; q++) {  // breadth first inside the treelet
+      const BihTree::Node& b = T.nodes[group[q]];
+      if (!T.nodes[b.left].leaf && ng < 4) group[ng++] = b.left;
+      if (!T.nodes[b.right].leaf && ng < 4) group[ng++] = b.right;
+    }
+    // a treelet never straddles a cache line: one that would is started on the next line (the skipped slots stay unused)
+    if ((nslots & 3u) + (uint32_t)ng > 4u) nslots = (nslots + 3u) & ~3u;
+    for (int q = 0; q < ng; q++) slot[group[q]] = nslots++;
+    // branch children of the group's members that did not fit start treelets of their own; right pushed first so the
+    // left subtree is laid out next
+    for (int q = ng - 1; q >= 0; q--) {
+      const BihTree::Node& b = T.nodes[group[q]];
+      if (!T.nodes[b.right].leaf && slot[b.right] == 0xffffffffu) roots.push_back(b.right);
+      if (!T.nodes[b.left].leaf && slot[b.left] == 0xffffffffu) roots.push_back(b.left);
+    }
+  }
+  for (size_t k = 0; k < T.nodes.size(); k++) if (T.nodes[k].leaf && T.nodes[k].items.size() > 6) slot[k] = nslots++;
+  return nslots;
+}
+
+// A tree's branch nodes by tree level, deepest first (a level's children were refitted by the launch before it): what the Mesh's update
+// launches k_mesh_refit_level over, and the triangle bih's update and an item bih's refit k_bih_level.  `nodes`: a BihTree's or a
+// MeshData's, each with leaf / left / right; stored(k): where node k lies in its pool.  Nothing for a tree whose root is a leaf.
+template <class Nodes, class Stored>
+inline void tree_levels(const Nodes& nodes, Stored stored, std::vector<uint32_t>& level_nodes, std::vector<uint32_t>& level_off) {
+  if (nodes.empty() || nodes[0].leaf) return;
+  std::vector<int> depth(nodes.size(), 0), order{0};  // (a parent before its children, whatever the numbering)
+  for (size_t q = 0; q < order.size(); q++) {
+    const auto& bn = nodes[(size_t)order[q]];
+    if (bn.leaf) continue;
+    for (int c : {bn.left, bn.right}) { depth[(size_t)c] = depth[(size_t)order[q]] + 1; order.push_back(c); }
+  }
+  int deepest = 0;
+  for (int k : order) if (!nodes[(size_t)k].leaf) deepest = std::max(deepest, depth[(size_t)k]);
+  std::vector<uint32_t> per_level((size_t)deepest + 2, 0);
+  for (int k : order) if (!nodes[(size_t)k].leaf) per_level[(size_t)(deepest - depth[(size_t)k]) + 1]++;
+  for (size_t l = 1; l < per_level.size(); l++) per_level[l] += per_level[l - 1];
+  level_off = per_level;
+  level_nodes.resize(per_level.back());
+  std::vector<uint32_t> fill(per_level.begin(), per_level.end() - 1);
+  for (int k : order) if (!nodes[(size_t)k].leaf) level_nodes[fill[(size_t)(deepest - depth[(size_t)k])]++] = stored((size_t)k);
+}
+
+// The topology half of a committed triangle or sphere bih (class BC_TRI / BC_SPHERE): everything Flattener::emit_bih lays out for the
+// tree that depends on its shape and on where its segments start, and on no coordinate -- so that a commit and a rebuild of the tree in a
+// committed scene (glome_sb_bih_layout reports its sizes) lay the same tree out alike.  The tree's leaves are emitted in preorder with
+// nothing in between: record j of the tree is recs[first_rec + j] and tris / spheres[first_prim + j], and a triangle tree's pair records
+// follow one another from float index first_pair_word of `tripairs`.  item_of[i]: the index of leaf item i in the update order.
+struct LeafBihLayout {
+  uint32_t base = 0, n_slots = 0;     // the node slots: bihnodes / pknodes [base, base + max(n_slots, 1))
+  uint32_t first_rec = 0, first_prim = 0, n_recs = 0;
+  uint64_t first_pair_word = 0;
+  uint32_t n_pair_recs = 0;           // pair records laid out (a tree that gives the packet form up part way keeps the ones before)
+  bool pk = false;                    // the tree has the packet form
+  int depth = 0;
+  std::vector<uint32_t> slot;         // per tree node (bih_slots)
+  std::vector<uint32_t> ref;          // per tree node: the reference a parent (ref[0]: the header) holds (rt_device.hpp BREF_*)
+  std::vector<uint32_t> pkleaf;       // per tree node, a leaf as the packet walk refers to it: byte offset of its first pair record | 3
+  std::vector<uint32_t> leaf_first;   // per tree node, a leaf's first record as an offset from first_rec
+  std::vector<uint8_t> paired;        // per tree node: the leaf has pair records
+  std::vector<uint32_t> pair_words;   // per pair record: the count word and the record-index word (emit_pairs)
+  std::vector<uint32_t> node_zw;      // per slot: words .z .w of the bihnodes entry (a branch's child references; a slot leaf's count and first record)
+  std::vector<uint32_t> pk_zw;        // per slot: words .z .w of the pknodes entry (branches of a tree that has the packet form)
+  std::vector<uint32_t> rows;         // LeafBihUpdateInfo::rows
+  std::vector<uint32_t> level_nodes, level_off;  // LeafBihUpdateInfo's
+  uint32_t hdr2[4] = {0, 0, 0, 0};    // bihhdr[3 h + 2]: records-to-pool delta, packet root, packet flag, depth
+};
+inline LeafBihLayout leaf_bih_layout(const BihTree& T, uint32_t cls, const std::vector<uint32_t>& item_of, uint32_t base, uint32_t first_rec, uint32_t first_prim,
+                                     uint64_t first_pair_word) {
+  constexpr uint32_t kPairHalfB = 1u << 29, kPairBoth = 1u << 30, kNoPair = 0xffffffffu;  // (LeafBihUpdateInfo's)
+  LeafBihLayout L;
+  L.base = base; L.first_rec = first_rec; L.first_prim = first_prim; L.first_pair_word = first_pair_word; L.depth = T.depth;
+  L.n_slots = bih_slots(T, L.slot);
+  if (base + L.n_slots >= BREF_FIRST_LIMIT) throw limit_error("too many BIH nodes");
+  bool pk = cls == BC_TRI && base + L.n_slots < (1u << 27);  // (a node's byte offset is a reference: 31 bits)
+  const size_t nn = T.nodes.size();
+  L.ref.assign(nn, 0); L.pkleaf.assign(nn, 3u); L.leaf_first.assign(nn, 0); L.paired.assign(nn, 0);
+  L.node_zw.assign(2 * (size_t)std::max<uint32_t>(L.n_slots, 1u), 0); L.pk_zw = L.node_zw;
+  uint64_t pair_at = first_pair_word;  // (a float index)
+  for (size_t k = 0; k < nn; k++) {
+    const BihTree::Node& bn = T.nodes[k];
+    if (!bn.leaf) { L.ref[k] = base + L.slot[k]; continue; }
+    const uint32_t count = (uint32_t)bn.items.size(), leaf_rec = first_rec + L.n_recs;
+    L.leaf_first[k] = L.n_recs;
+    if ((uint64_t)leaf_rec + count >= BREF_FIRST_LIMIT) throw limit_error("too many records for the BIH leaf references");
+    bool paired = false;
+    if (cls == BC_TRI && count && pk) {
+      if ((pair_at + (uint64_t)count * kPairWords) * 4 >= (1ull << 31)) pk = false;  // (a pair record's byte offset is a reference)
+      else {
+        L.pkleaf[k] = (uint32_t)(pair_at * 4u) | 3u; paired = true;
+        for (uint32_t j = 0; j < count; j += 2) { L.pair_words.push_back(count - j); L.pair_words.push_back(leaf_rec + j); }
+        pair_at += (uint64_t)((count + 1u) / 2u) * kPairWords;
+      }
+    }
+    L.paired[k] = paired;
+    for (uint32_t q = 0; q < count; q++) {
+      L.rows.push_back(item_of[(size_t)bn.items[q]]);
+      if (cls != BC_TRI) continue;
+      const uint32_t pair = (L.pkleaf[k] & ~3u) / 4u + (q / 2u) * kPairWords;  // (a float index: below 2^29)
+      L.rows.push_back(!paired ? kNoPair : (pair | (q & 1u ? kPairHalfB : 0u) | (q + 1 == count && !(q & 1u) ? kPairBoth : 0u)));
+    }
+    if (count == 0) L.ref[k] = BREF_LEAF_BIT;
+    else if (count <= 6) L.ref[k] = BREF_LEAF_BIT | (count << 26) | leaf_rec;
+    else {
+      L.node_zw[2 * (size_t)L.slot[k]] = count; L.node_zw[2 * (size_t)L.slot[k] + 1] = leaf_rec;
+      L.ref[k] = BREF_LEAF_BIT | (7u << 26) | (base + L.slot[k]);
+    }
+    L.n_recs += count;
+  }
+  L.pk = pk;
+  L.n_pair_recs = (uint32_t)(L.pair_words.size() / 2);
+  for (size_t k = 0; k < nn; k++) {
+    const BihTree::Node& bn = T.nodes[k];
+    if (bn.leaf) continue;
+    L.node_zw[2 * (size_t)L.slot[k]] = (uint32_t)bn.axis | (L.ref[bn.left] << 2); L.node_zw[2 * (size_t)L.slot[k] + 1] = L.ref[bn.right];
+    // The hand-written packet walk (bih_packet_asm.hpp) reads its own copy: a branch child is referred to by its BYTE OFFSET
+    // in this pool with the child's axis in the two low bits (scalar loads ignore them), a leaf child by the byte offset of
+    // its first pair record (tripairs) with both low bits set -- the step's code is picked, the near child's node asked for
+    // and a leaf's triangles fetched without a shift, a mask or a multiplication.  (An empty leaf is 3: never entered.)
+    if (pk) {
+      auto pkref = [&](int c) { return T.nodes[c].leaf ? L.pkleaf[c] : (((base + L.slot[c]) << 4) | (uint32_t)T.nodes[c].axis); };
+      L.pk_zw[2 * (size_t)L.slot[k]] = pkref(bn.left); L.pk_zw[2 * (size_t)L.slot[k] + 1] = pkref(bn.right);
+    }
+  }
+  if (cls == BC_TRI && !pk) for (size_t j = 0; j < L.n_recs; j++) L.rows[2 * j + 1] = kNoPair;  // (the packet form was given up part way)
+  tree_levels(T.nodes, [&](size_t k) { return base + L.slot[k]; }, L.level_nodes, L.level_off);
+  // (y: the root in the packet walk's form, z: 1 when this tree has that form -- triangle leaves, byte offsets that fit a reference;
+  // w: the tree's depth -- a leaf class never has kBihItemsInPlace, its trees have packet walks of their own)
+  const uint32_t pkroot = (pk && !T.nodes.empty() && !T.nodes[0].leaf) ? (((base + L.slot[0]) << 4) | (uint32_t)T.nodes[0].axis) : 0u;
+  L.hdr2[0] = L.n_recs ? first_prim - first_rec : 0u; L.hdr2[1] = pkroot; L.hdr2[2] = pk ? 1u : 0u; L.hdr2[3] = (uint32_t)T.depth;
+  return L;
+}
+
 class Flattener {
  public:
   Flattener(const Graph& g, FlatScene& out) : G(g), F(out) {}
@@ -194,7 +344,7 @@ class Flattener {
   // kPairWords words: every component of p1, e1, e2 of triangles 2j and 2j + 1 as an (A, B) pair -- p1x p1y p1z e1x e1y e1z e2x
   // e2y e2z, 18 floats -- then the number of the leaf's triangles from 2j on (what the walk's loop counts down) and the record
   // index of triangle 2j (what a hit reports).  An odd last triangle is paired with itself; the walk ignores that half.
-  uint32_t emit_pairs(uint32_t first_prim, uint32_t count, uint32_t first_rec) {
+  uint32_t emit_pairs(uint32_t first_prim, uint32_t count, const uint32_t* words) {  // words: the layout's two per record (LeafBihLayout::pair_words)
     const uint32_t at = (uint32_t)F.tripairs.size();
     for (uint32_t j = 0; j < count; j += 2) {
       const size_t a = first_prim + j, b = j + 1 < count ? a + 1 : a;
@@ -203,8 +353,8 @@ class Flattener {
         const F4 &A = F.tris[3 * a + w], &B = F.tris[3 * b + w];
         r[6 * w + 0] = A.x; r[6 * w + 1] = B.x; r[6 * w + 2] = A.y; r[6 * w + 3] = B.y; r[6 * w + 4] = A.z; r[6 * w + 5] = B.z;
       }
-      r[18] = as_float_bits(count - j);
-      r[19] = as_float_bits(first_rec + j);
+      r[18] = as_float_bits(words[j]);  // (two words per record, a record per two triangles: record j / 2's are words[j], words[j + 1])
+      r[19] = as_float_bits(words[j + 1]);
       F.tripairs.insert(F.tripairs.end(), r, r + kPairWords);
     }
     return at * 4u;  // byte offset of the leaf's first record
@@ -784,27 +934,73 @@ class Flattener {
     return (k >= R_SPHERE && k <= R_CONE) || (k == R_LIST && (c.x & RF_PRIMLIST) != 0);
   }
 
-  // A tree's branch nodes by tree level, deepest first (a level's children were refitted by the launch before it): what the Mesh's update
-  // launches k_mesh_refit_level over, and the triangle bih's update and an item bih's refit k_bih_level.  `nodes`: a BihTree's or a
-  // MeshData's, each with leaf / left / right; stored(k): where node k lies in its pool.  Nothing for a tree whose root is a leaf.
-  template <class Nodes, class Stored>
-  static void tree_levels(const Nodes& nodes, Stored stored, std::vector<uint32_t>& level_nodes, std::vector<uint32_t>& level_off) {
-    if (nodes.empty() || nodes[0].leaf) return;
-    std::vector<int> depth(nodes.size(), 0), order{0};  // (a parent before its children, whatever the numbering)
-    for (size_t q = 0; q < order.size(); q++) {
-      const auto& bn = nodes[(size_t)order[q]];
-      if (bn.leaf) continue;
-      for (int c : {bn.left, bn.right}) { depth[(size_t)c] = depth[(size_t)order[q]] + 1; order.push_back(c); }
+  // A branch's two planes as the device holds them.  A child that is an empty leaf (a quarter of the leaves the reference builder makes)
+  // gets a plane at -inf / +inf: the interval tests of the traversal (`near < t1`, `t2 < far`) then fail for it whatever the ray, so
+  // the device never enters it and needs no test for it.  The other child's interval does not depend on this plane.
+  static void branch_planes(const BihTree::Node& bn, const std::vector<uint32_t>& ref, float& ls, float& rs) {
+    const float inf = std::numeric_limits<float>::infinity();
+    ls = ref[(size_t)bn.left] == BREF_LEAF_BIT ? -inf : round_up(bn.lsplit);
+    rs = ref[(size_t)bn.right] == BREF_LEAF_BIT ? inf : round_down(bn.rsplit);
+  }
+
+  // A triangle or sphere bih (emit_bih, which has reserved the header and the node slots): where everything goes is leaf_bih_layout's,
+  // which reads no coordinate; the values -- records, pool entries, pair values, planes, the box -- are filled in here.
+  U4 emit_leaf_bih(const Node& n, int id, uint32_t cls, uint32_t hdr, uint32_t base) {
+    const BihTree& T = *n.bih;
+    LeafBihUpdateInfo U;  // its update tables
+    U.node = id; U.cls = cls; U.row_words = cls == BC_TRI ? 2u : 1u; U.hdr = hdr; U.first_slot = base;
+    const std::vector<int> order = T.update_order();
+    U.n_items = (int)order.size();
+    std::vector<uint32_t> item_of(G.nodes.size(), 0xffffffffu);  // item node id -> its index in the update order (whichever way the tree was made)
+    std::vector<char> prim_seen(G.nodes.size(), 0);  // an item, or a primitive under two items, that the tree holds twice has two records: one row cannot name both
+    for (size_t k = 0; k < order.size(); k++) {
+      const int t = G.peel_wrappers(order[k]);
+      if ((item_of[(size_t)order[k]] != 0xffffffffu || prim_seen[(size_t)t]) && U.plain.ok) {
+        U.plain.ok = false;
+        U.plain.why_not = "bih " + std::to_string(id) + " holds " + U.item_word() + " " + std::to_string(t) + " more than once";
+      }
+      item_of[(size_t)order[k]] = (uint32_t)k; prim_seen[(size_t)t] = 1;
     }
-    int deepest = 0;
-    for (int k : order) if (!nodes[(size_t)k].leaf) deepest = std::max(deepest, depth[(size_t)k]);
-    std::vector<uint32_t> per_level((size_t)deepest + 2, 0);
-    for (int k : order) if (!nodes[(size_t)k].leaf) per_level[(size_t)(deepest - depth[(size_t)k]) + 1]++;
-    for (size_t l = 1; l < per_level.size(); l++) per_level[l] += per_level[l - 1];
-    level_off = per_level;
-    level_nodes.resize(per_level.back());
-    std::vector<uint32_t> fill(per_level.begin(), per_level.end() - 1);
-    for (int k : order) if (!nodes[(size_t)k].leaf) level_nodes[fill[(size_t)(deepest - depth[(size_t)k])]++] = stored((size_t)k);
+    const uint32_t first_rec = (uint32_t)F.recs.size(), first_prim = (uint32_t)(cls == BC_TRI ? F.tris.size() / 3 : F.spheres.size());
+    LeafBihLayout L = leaf_bih_layout(T, cls, item_of, base, first_rec, first_prim, (uint64_t)F.tripairs.size());
+    size_t pair_rec = 0;
+    for (size_t k = 0; k < T.nodes.size(); k++) {
+      const BihTree::Node& bn = T.nodes[k];
+      if (!bn.leaf) continue;
+      const uint32_t count = (uint32_t)bn.items.size(), at = L.leaf_first[k];
+      for (uint32_t q = 0; q < count; q++) {
+        Peeled p = peel(bn.items[q]);
+        U4 rec = emit_prim(G.at(p.id));
+        rec.x |= p.flags; rec.z = p.own;
+        if (rec.y != first_prim + at + q) throw scene_error("internal: BIH leaf pools are not contiguous");  // (both are emitted in leaf order)
+        F.recs.push_back(rec);
+      }
+      if (!L.paired[k]) continue;
+      if ((emit_pairs(first_prim + at, count, &L.pair_words[2 * pair_rec]) | 3u) != L.pkleaf[k]) throw scene_error("internal: BIH pair records are not contiguous");
+      pair_rec += (count + 1u) / 2u;
+    }
+    for (uint32_t s = 0; s < std::max<uint32_t>(L.n_slots, 1u); s++) F.bihnodes[base + s] = F4{0.0f, 0.0f, as_float_bits(L.node_zw[2 * (size_t)s]), as_float_bits(L.node_zw[2 * (size_t)s + 1])};
+    for (size_t k = 0; k < T.nodes.size(); k++) {
+      const BihTree::Node& bn = T.nodes[k];
+      if (bn.leaf) continue;
+      const size_t s = L.slot[k];
+      float ls, rs;
+      branch_planes(bn, L.ref, ls, rs);
+      F.bihnodes[base + s].x = ls; F.bihnodes[base + s].y = rs;
+      if (L.pk) F.pknodes[base + s] = F4{ls, rs, as_float_bits(L.pk_zw[2 * s]), as_float_bits(L.pk_zw[2 * s + 1])};
+    }
+    F.bihhdr[3 * hdr] = mk4u(round_down(T.bb.lo.x), round_down(T.bb.lo.y), round_down(T.bb.lo.z), L.ref[0]);
+    F.bihhdr[3 * hdr + 1] = mk4u(round_up(T.bb.hi.x), round_up(T.bb.hi.y), round_up(T.bb.hi.z), cls);
+    F.bihhdr[3 * hdr + 2] = F4{as_float_bits(L.hdr2[0]), as_float_bits(L.hdr2[1]), as_float_bits(L.hdr2[2]), as_float_bits(L.hdr2[3])};
+    if (cls == BC_TRI) F.pk_all = F.pk_all && L.pk;
+    F.max_sphere_bih_depth = std::max(F.max_sphere_bih_depth, T.depth);
+    U.n_slots = L.n_slots; U.n_recs = L.n_recs; U.pk = L.pk; U.n_pair_recs = L.n_pair_recs; U.first_pair_word = L.first_pair_word; U.depth = T.depth;
+    if (L.n_recs) { U.first_prim = first_prim; U.first_rec = first_rec; }
+    U.rows = std::move(L.rows); U.level_nodes = std::move(L.level_nodes); U.level_off = std::move(L.level_off);
+    box6(T.bb, U.bound6);
+    F.leaf_bih_updates.push_back(std::move(U));
+    movable_bihs.insert(id);
+    return U4{R_BIH, hdr, 0, (uint32_t)n.uid};
   }
 
   // BIH: nodes in preorder; leaf items become consecutive records, and (for homogeneous leaves) consecutive pool
@@ -826,78 +1022,32 @@ class Flattener {
     uint32_t cls = all_tri ? BC_TRI : (all_sph ? BC_SPHERE : (all_simple ? BC_SIMPLE : (all_csg ? BC_CSG : BC_GENERIC)));
     uint32_t hdr = (uint32_t)(F.bihhdr.size() / 3);
     F.bihhdr.resize(F.bihhdr.size() + 3);  // reserved now: items of a generic BIH may emit nested BIHs before we fill it
-    // Node slots: only branches (and leaves of 7+ items, whose extent lives in a slot) get one.  Branches are laid out
-    // in small treelets -- a node, then its branch children, then a grandchild, four 16-byte nodes to a 64-byte cache
-    // line -- and the treelets depth first, so the step after a fetch usually finds its node in the line just fetched
-    // and a subtree is contiguous.  References are explicit, so the traversal does not care about the order.
-    std::vector<uint32_t> slot(T.nodes.size(), 0xffffffffu);
+    // Node slots (bih_slots): treelets of branches, then the leaves of 7+ items
+    std::vector<uint32_t> slot;
     uint32_t base = (uint32_t)F.bihnodes.size();
     base = (base + 3u) & ~3u;  // line-align this tree's first treelet
-    uint32_t nslots = 0;
-    {
-      std::vector<int> roots;  // treelet roots still to place (a stack: depth first)
-      if (!T.nodes.empty() && !T.nodes[0].leaf) roots.push_back(0);
-      while (!roots.empty()) {
-        int x = roots.back(); roots.pop_back();
-        int group[4]; int ng = 0;
-        group[ng++] = x;
-        for (int q = 0; q < ng && ng < 4; q++) {  // breadth first inside the treelet
-          const BihTree::Node& b = T.nodes[group[q]];
-          if (!T.nodes[b.left].leaf && ng < 4) group[ng++] = b.left;
-          if (!T.nodes[b.right].leaf && ng < 4) group[ng++] = b.right;
-        }
-        // a treelet never straddles a cache line: one that would is started on the next line (the skipped slots stay unused)
-        if ((nslots & 3u) + (uint32_t)ng > 4u) nslots = (nslots + 3u) & ~3u;
-        for (int q = 0; q < ng; q++) slot[group[q]] = nslots++;
-        // branch children of the group's members that did not fit start treelets of their own; right pushed first so the
-        // left subtree is laid out next
-        for (int q = ng - 1; q >= 0; q--) {
-          const BihTree::Node& b = T.nodes[group[q]];
-          if (!T.nodes[b.right].leaf && slot[b.right] == 0xffffffffu) roots.push_back(b.right);
-          if (!T.nodes[b.left].leaf && slot[b.left] == 0xffffffffu) roots.push_back(b.left);
-        }
-      }
-      for (size_t k = 0; k < T.nodes.size(); k++) if (T.nodes[k].leaf && T.nodes[k].items.size() > 6) slot[k] = nslots++;
-    }
+    const uint32_t nslots = bih_slots(T, slot);
     F.bihnodes.resize(base + std::max<uint32_t>(nslots, 1u));
     if (base + nslots >= BREF_FIRST_LIMIT) throw limit_error("too many BIH nodes");
-    bool pk = cls == BC_TRI && base + nslots < (1u << 27);  // (a node's byte offset is a reference: 31 bits)
+    // The primitive classes (BC_TRI, BC_SPHERE, BC_SIMPLE) emit their items fresh, without the memo, so their pool entries are consecutive
+    // and leaf follows leaf; the items of BC_CSG / BC_GENERIC go through the memoising emit(): a node shared with another parent keeps one
+    // record value (an Instance: one xfm slot), and an item's own records lie between the leaves
+    if (cls == BC_TRI || cls == BC_SPHERE) {
+      F.pknodes.resize(F.bihnodes.size(), F4{0, 0, 0, 0});
+      return emit_leaf_bih(n, id, cls, hdr, base);
+    }
     F.pknodes.resize(F.bihnodes.size(), F4{0, 0, 0, 0});
     // pass 1: leaves -- a leaf's item records are consecutive, and so the child reference that describes each leaf is built here
-    // (rt_device.hpp: BREF_*).  The primitive classes (BC_TRI, BC_SPHERE, BC_SIMPLE) emit their items fresh, without the memo, so their
-    // pool entries are consecutive too and leaf follows leaf; the items of BC_CSG / BC_GENERIC go through the memoising emit(): a node
-    // shared with another parent keeps one record value (an Instance: one xfm slot), and an item's own records lie between the leaves
+    // (rt_device.hpp: BREF_*)
     std::vector<uint32_t> ref(T.nodes.size(), 0);
-    std::vector<uint32_t> pkleaf(T.nodes.size(), 3u);  // a leaf as the packet walk refers to it: byte offset of its first pair record | 3
-    uint32_t delta = 0;
-    bool have_delta = false;
-    bool in_place = cls != BC_TRI && cls != BC_SPHERE;  // (those two have their own packet walk)
-    LeafBihUpdateInfo U;            // a triangle or sphere bih: its update tables
+    bool in_place = true;
     std::vector<int> item_ids;        // a bih of class BC_CSG / BC_GENERIC: its items in emission order, and their records
     std::vector<uint32_t> item_recs;
     bool has_inst = false;            // ... one of them is an Instance (under wrappers): the tree gets an InstBihInfo
-    std::vector<uint32_t> item_of;  // a triangle bih: item node id -> its index in the update order (BihTree::update_order, whichever way the tree was made)
-    const bool leaf_bih = cls == BC_TRI || cls == BC_SPHERE;
-    if (leaf_bih) {
-      U.node = id; U.cls = cls; U.row_words = cls == BC_TRI ? 2u : 1u; U.hdr = hdr; U.first_slot = base; U.n_slots = nslots;
-      const std::vector<int> order = T.update_order();
-      U.n_items = (int)order.size();
-      item_of.assign(G.nodes.size(), 0xffffffffu);
-      std::vector<char> prim_seen(G.nodes.size(), 0);  // an item, or a primitive under two items, that the tree holds twice has two records: one row cannot name both
-      for (size_t k = 0; k < order.size(); k++) {
-        const int t = G.peel_wrappers(order[k]);
-        if ((item_of[(size_t)order[k]] != 0xffffffffu || prim_seen[(size_t)t]) && U.plain.ok) {
-          U.plain.ok = false;
-          U.plain.why_not = "bih " + std::to_string(id) + " holds " + U.item_word() + " " + std::to_string(t) + " more than once";
-        }
-        item_of[(size_t)order[k]] = (uint32_t)k; prim_seen[(size_t)t] = 1;
-      }
-    }
     for (size_t k = 0; k < T.nodes.size(); k++) {
       const BihTree::Node& bn = T.nodes[k];
       if (!bn.leaf) { ref[k] = base + slot[k]; continue; }
       std::vector<U4> items;
-      uint32_t first_prim = 0;
       for (size_t q = 0; q < bn.items.size(); q++) {
         int it = bn.items[q];
         U4 rec;
@@ -907,7 +1057,6 @@ class Flattener {
           rec = emit_prim(G.at(p.id));
           rec.x |= p.flags; rec.z = p.own;
         }
-        if (q == 0) first_prim = rec.y;
         in_place = in_place && item_in_place(rec);
         items.push_back(rec);
       }
@@ -920,25 +1069,6 @@ class Flattener {
       }
       if (first_rec + items.size() >= BREF_FIRST_LIMIT) throw limit_error("too many records for the BIH leaf references");
       uint32_t count = (uint32_t)items.size();
-      if (count && leaf_bih) {
-        uint32_t dl = first_prim - first_rec;  // both are emitted in leaf order, so this is one constant per BIH
-        if (have_delta && dl != delta) throw scene_error("internal: BIH leaf pools are not contiguous");
-        delta = dl; have_delta = true;
-      }
-      bool paired = false;
-      if (cls == BC_TRI && count && pk) {
-        if (((uint64_t)F.tripairs.size() + (uint64_t)count * kPairWords) * 4 >= (1ull << 31)) pk = false;  // (a pair record's byte offset is a reference)
-        else { pkleaf[k] = emit_pairs(first_prim, count, first_rec) | 3u; paired = true; }
-      }
-      if (leaf_bih && count) {
-        if (U.rows.empty()) { U.first_prim = first_prim; U.first_rec = first_rec; }
-        for (uint32_t q = 0; q < count; q++) {
-          U.rows.push_back(item_of[(size_t)bn.items[q]]);
-          if (cls != BC_TRI) continue;
-          const uint32_t pair = (pkleaf[k] & ~3u) / 4u + (q / 2u) * kPairWords;  // (a float index: below 2^29)
-          U.rows.push_back(!paired ? U.kNoPair : (pair | (q & 1u ? U.kPairHalfB : 0u) | (q + 1 == count && !(q & 1u) ? U.kPairBoth : 0u)));
-        }
-      }
       if (count == 0) ref[k] = BREF_LEAF_BIT;
       else if (count <= 6) ref[k] = BREF_LEAF_BIT | (count << 26) | first_rec;
       else {
@@ -949,39 +1079,18 @@ class Flattener {
     for (size_t k = 0; k < T.nodes.size(); k++) {
       const BihTree::Node& bn = T.nodes[k];
       if (bn.leaf) continue;
-      // A child that is an empty leaf (a quarter of the leaves the reference builder makes) gets a plane at -inf / +inf:
-      // the interval tests of the traversal (`near < t1`, `t2 < far`) then fail for it whatever the ray, so the device
-      // never enters it and needs no test for it.  The other child's interval does not depend on this plane.
-      const float inf = std::numeric_limits<float>::infinity();
-      float ls = ref[bn.left] == BREF_LEAF_BIT ? -inf : round_up(bn.lsplit), rs = ref[bn.right] == BREF_LEAF_BIT ? inf : round_down(bn.rsplit);
+      float ls, rs;
+      branch_planes(bn, ref, ls, rs);
       F.bihnodes[base + slot[k]] = F4{ls, rs, as_float_bits((uint32_t)bn.axis | (ref[bn.left] << 2)), as_float_bits(ref[bn.right])};
-      // The hand-written packet walk (bih_packet_asm.hpp) reads its own copy: a branch child is referred to by its BYTE OFFSET
-      // in this pool with the child's axis in the two low bits (scalar loads ignore them), a leaf child by the byte offset of
-      // its first pair record (tripairs) with both low bits set -- the step's code is picked, the near child's node asked for
-      // and a leaf's triangles fetched without a shift, a mask or a multiplication.  (An empty leaf is 3: never entered.)
-      if (pk) {
-        auto pkref = [&](int c) { return T.nodes[c].leaf ? pkleaf[c] : (((base + slot[c]) << 4) | (uint32_t)T.nodes[c].axis); };
-        F.pknodes[base + slot[k]] = F4{ls, rs, as_float_bits(pkref(bn.left)), as_float_bits(pkref(bn.right))};
-      }
     }
     F.bihhdr[3 * hdr] = mk4u(round_down(T.bb.lo.x), round_down(T.bb.lo.y), round_down(T.bb.lo.z), ref[0]);
     F.bihhdr[3 * hdr + 1] = mk4u(round_up(T.bb.hi.x), round_up(T.bb.hi.y), round_up(T.bb.hi.z), cls);
-    if (cls == BC_TRI) F.pk_all = F.pk_all && pk;
-    // (y: the root in the packet walk's form, z: 1 when this tree has that form -- triangle leaves, byte offsets that fit a reference)
-    const uint32_t pkroot = (pk && !T.nodes.empty() && !T.nodes[0].leaf) ? (((base + slot[0]) << 4) | (uint32_t)T.nodes[0].axis) : 0u;
-    // (w: the tree's depth -- the generic tier walks a tree as a packet when its per-wave stack holds it -- and, in bit 31, whether
+    // (x: the records-to-pool delta of a triangle or sphere tree, y / z: the packet walk's root and flag, a triangle tree's -- emit_leaf_bih;
+    // w: the tree's depth -- the generic tier walks a tree as a packet when its per-wave stack holds it -- and, in bit 31, whether
     // every item is answered in place: kBihItemsInPlace)
     in_place = in_place && !T.nodes.empty() && !T.nodes[0].leaf;
-    F.bihhdr[3 * hdr + 2] = F4{as_float_bits(delta), as_float_bits(pkroot), as_float_bits(pk ? 1u : 0u), as_float_bits((uint32_t)T.depth | (in_place ? kBihItemsInPlace : 0u))};
-    if (cls == BC_SPHERE || cls == BC_TRI || in_place) F.max_sphere_bih_depth = std::max(F.max_sphere_bih_depth, T.depth);
-    if (leaf_bih) {
-      U.n_recs = (uint32_t)(U.rows.size() / U.row_words); U.pk = pk;
-      box6(T.bb, U.bound6);
-      if (cls == BC_TRI && !pk) for (size_t j = 0; j < U.n_recs; j++) U.rows[2 * j + 1] = U.kNoPair;  // (the packet form was given up part way)
-      tree_levels(T.nodes, [&](size_t k) { return base + slot[k]; }, U.level_nodes, U.level_off);
-      F.leaf_bih_updates.push_back(std::move(U));
-      movable_bihs.insert(id);
-    }
+    F.bihhdr[3 * hdr + 2] = F4{as_float_bits(0u), as_float_bits(0u), as_float_bits(0u), as_float_bits((uint32_t)T.depth | (in_place ? kBihItemsInPlace : 0u))};
+    if (in_place) F.max_sphere_bih_depth = std::max(F.max_sphere_bih_depth, T.depth);
     if (has_inst) {
       movable_bihs.insert(id);
       InstBihInfo B;

@@ -494,8 +494,8 @@ struct Graph {
       return me;
     }
   };
-  int bih(const std::vector<int>& ids) {  // Bih.hs:309-324
-    if (ids.empty()) { Node n; n.kind = K_VOID; return add(n); }
+  // the tree `bih` makes over a non-empty id list: what the constructor and bih_resplit share
+  std::shared_ptr<BihTree> bih_tree(const std::vector<int>& ids) const {
     std::vector<Box3> boxes;
     Box3 bb = box_empty();
     for (int i : ids) boxes.push_back(bound(i));
@@ -509,8 +509,24 @@ struct Graph {
     for (size_t k = 0; k < all.size(); k++) all[k] = (int)k;
     BihBuild B{boxes, ids, *T};
     B.rec(all, bb, box_mid(bb), 0);
-    Node n; n.kind = K_BIH; n.bih = T;
+    return T;
+  }
+  int bih(const std::vector<int>& ids) {  // Bih.hs:309-324
+    if (ids.empty()) { Node n; n.kind = K_VOID; return add(n); }
+    Node n; n.kind = K_BIH; n.bih = bih_tree(ids);
     return add(n);
+  }
+  // The tree built again in place (glome_sb_bih_resplit): the tree `bih` builds over the node's items in update order, from their bounds as
+  // they stand -- node for node and bit for bit, same box -- where bih_set_triangles / bih_set_spheres / bih_refit keep what the builder
+  // decided.  The update order stays: a tree read from a `show` text, whose `order` is empty, records its preorder item list first, so item
+  // k means the same item before and after.  Refused as the constructor refuses (an infinite box, kBihLoopMessage), and then the node is
+  // untouched: the new tree is complete before the old one goes.  The reference has no such call; the result is what `bih` gives.
+  void bih_resplit(int id) {
+    if (at(id).kind != K_BIH) throw std::invalid_argument(std::string("bih_resplit: node ") + std::to_string(id) + " is a " + kind_name(at(id).kind) + ", not a Bih");
+    const std::vector<int> order = nodes[(size_t)id].bih->update_order();
+    if (order.empty()) return;  // (a `show` text's tree of no items: `bih` of nothing is Void, and there is nothing to split)
+    std::shared_ptr<BihTree> T = bih_tree(order);
+    *nodes[(size_t)id].bih = std::move(*T);  // in place: every copy of the node shares the tree
   }
 
   // Same tree, new triangles (glome_sb_bih_set_triangles): item k of the tree (BihTree::update_order), a Triangle under any number of

@@ -8,6 +8,7 @@
 // update_common.hpp.
 #include <hip/hip_runtime.h>
 
+#include <chrono>
 #include <cmath>
 #include <cstdio>
 #include <cstring>
@@ -31,6 +32,7 @@
 #include "bih_update_kernels.hpp"
 #include "item_bih_update_kernels.hpp"
 #include "sphere_bih_update_kernels.hpp"
+#include "bih_rebuild_kernels.hpp"
 
 using namespace glome;
 
@@ -174,8 +176,22 @@ struct glome_scene {
     const uint32_t* d_levels = nullptr;
     const uint32_t* d_level_off = nullptr;
     float4* d_ws = nullptr;            // two words per record, two per node slot, then the bound's partial boxes: allocated at the first update
+    // what a rebuild (glome_scene_bih_rebuild) needs beyond an update's tables: per item, in update order, its record as commit emitted it
+    // (flags and kind, -, own-texture word, builder id: .y is made again with the leaf order); what the tree's node segment and pair segment
+    // hold (slots; pair records), initially their committed size; and what the device tables above and the workspace hold
+    std::vector<U4> item_recs;
+    uint32_t slot_cap = 0, pair_cap = 0;
+    size_t levels_cap = 0, level_off_cap = 0, ws_words = 0;
   };
   std::map<int, LeafBihUpd> leaf_bihs;
+  // what commit derived from every bih's depth, kept so that a rebuild can derive it again: per bih header its tree's depth and whether it
+  // counts towards max_sphere_bih_depth (flatten.hpp emit_bih); the Meshes' deepest tree; and the pools a rebuild may extend -- entries in
+  // use and entries allocated of bihnodes / pknodes, float words of tripairs
+  std::vector<int> hdr_depth;
+  std::vector<uint8_t> hdr_packet_service;
+  int max_mesh_depth = 0;
+  size_t bihnodes_used = 0, bihnodes_cap = 0, tripairs_used = 0, tripairs_cap = 0;
+  double rebuild_stage_ms[5] = {0, 0, 0, 0, 0};  // the last rebuild's wall-clock by stage (glome_scene_bih_rebuild_stages)
   // and for glome_scene_instance_update: every Instance of the scene by its builder id, and every bih that holds one as an item
   // (flatten.hpp InstanceUpdateInfo, InstBihInfo)
   std::map<int, InstanceUpdateInfo> insts;
@@ -596,9 +612,21 @@ glome_scene* glome_scene_commit(glome_ctx* ctx, glome_sb* sb, int32_t root) {
   for (LeafBihUpdateInfo& U : F.leaf_bih_updates) {
     glome_scene::LeafBihUpd& m = s->leaf_bihs[U.node];
     if ((!U.rows.empty() && upload(s, U.rows, &m.d_rows)) || (!U.level_nodes.empty() && (upload(s, U.level_nodes, &m.d_levels) || upload(s, U.level_off, &m.d_level_off)))) { glome_scene_release(s); return nullptr; }
+    m.item_recs.assign((size_t)U.n_items, U4{0, 0, 0, 0});
+    for (uint32_t j = 0; j < U.n_recs; j++) m.item_recs[U.rows[(size_t)j * U.row_words]] = F.recs[(size_t)U.first_rec + j];
+    m.slot_cap = std::max<uint32_t>(U.n_slots, 1u); m.pair_cap = U.n_pair_recs;
+    m.levels_cap = U.level_nodes.size(); m.level_off_cap = U.level_nodes.empty() ? 0 : U.level_off.size();
     U.rows = {}; U.level_nodes = {};
     m.info = std::move(U);
   }
+  for (size_t h = 0; 3 * h + 2 < F.bihhdr.size(); h++) {
+    uint32_t w; memcpy(&w, &F.bihhdr[3 * h + 2].w, 4);
+    uint32_t cl; memcpy(&cl, &F.bihhdr[3 * h + 1].w, 4);
+    s->hdr_depth.push_back((int)(w & ~kBihItemsInPlace));
+    s->hdr_packet_service.push_back(cl == BC_SPHERE || cl == BC_TRI || (w & kBihItemsInPlace) != 0);
+  }
+  s->max_mesh_depth = F.max_mesh_depth;
+  s->bihnodes_used = s->bihnodes_cap = F.bihnodes.size(); s->tripairs_used = s->tripairs_cap = F.tripairs.size();
   for (InstBihInfo& B : F.inst_bihs) {
     glome_scene::InstBih& m = s->ibihs[B.node];
     if ((!B.level_nodes.empty() && upload(s, B.level_nodes, &m.d_levels)) || upload(s, B.rec_off, &m.d_rec_off) || upload(s, B.child_bound, &m.d_bounds)) { glome_scene_release(s); return nullptr; }
@@ -1396,7 +1424,9 @@ template <class Src> static int leaf_bih_update_launch(glome_scene* s, int32_t b
   const LeafBihUpdateInfo& U = m->info;
   const uint32_t n_src = kSphereSrc<Src> ? (uint32_t)n : 3u * (uint32_t)n;  // what the bounds fold: spheres, or vertices
   // a box per record and per node slot, and the bound's partial boxes
-  if (int rc = ensure_ws(s, m->d_ws, 2 * ((size_t)U.n_recs + U.n_slots + upd::kBoundMaxBlocks))) return rc;
+  const size_t ws_words = 2 * ((size_t)U.n_recs + U.n_slots + upd::kBoundMaxBlocks);
+  if (int rc = ensure_ws(s, m->d_ws, ws_words)) return rc;
+  if (!m->ws_words) m->ws_words = ws_words;  // (what it was allocated with: a rebuild may ask for more)
   // The levels run a launch each: the merged launch of the narrow levels (k_bih_levels_merged) stays behind GLOME_DEBUG_BIH_UPDATE_MERGED
   // until tools/probe/bih_update_rate.py has shown on the hardware that it wins beyond the run-to-run spread
   const bool merged = getenv("GLOME_DEBUG_BIH_UPDATE_MERGED") != nullptr;
@@ -1544,6 +1574,303 @@ int glome_scene_sphere_bih_update_f32(glome_scene* s, int32_t bih_id, const floa
         float* dr = st.in(radii, (size_t)n);
         return [=] { return glome_scene_sphere_bih_update_f32_dev(s, bih_id, dc, dr, n); };
       });
+}
+
+// ---- a committed leaf bih re-split: the tree built again in place from new items (bih_rebuild_kernels.hpp, bih_build_device.hpp) ----
+// glome_sb_bih_set_triangles / _set_spheres, glome_sb_bih_resplit and a commit, without the commit: (a) the items' fp64 boxes from the
+// update's source, (b) the device builder's level loop over them, (c) the tree's topology and the final object order back, (d) the layout
+// function of the commit (flatten.hpp leaf_bih_layout) against the tree's own segments and the tables it gives uploaded, (e) the update's
+// launches for the values.  (a) to (c) write scratch alone, and every refusal is found there or before: a refused call leaves the scene as it was.
+// Not asynchronous in either form: a level costs a synchronisation, (c) and (d) wait.
+static void drop_alloc(glome_scene* s, const void* p) {
+  if (!p) return;
+  auto it = std::find(s->allocs.begin(), s->allocs.end(), (void*)p);
+  if (it != s->allocs.end()) s->allocs.erase(it);
+  (void)hipFree((void*)p);
+}
+// a device table of the scene's with room for `need` elements: kept when it has, else a new one of that size (the old one is freed: the caller has quiesced)
+template <class T> static int table_room(glome_scene* s, const T*& d, size_t& cap, size_t need) {
+  if (need <= cap && d) return 0;
+  void* nd = nullptr;
+  HIPCHK(s->ctx, hipMalloc(&nd, std::max<size_t>(1, need) * sizeof(T)));
+  drop_alloc(s, d);
+  s->allocs.push_back(nd);
+  d = (const T*)nd; cap = need;
+  return 0;
+}
+// a pool of the scene's grown to hold `cap` elements of T, its first `used` copied (the caller has quiesced: no launch reads the old one)
+template <class T> static int pool_grow(glome_scene* s, const T*& d, size_t used, size_t cap) {
+  void* nd = nullptr;
+  HIPCHK(s->ctx, hipMalloc(&nd, cap * sizeof(T)));
+  if (hipMemset(nd, 0, cap * sizeof(T)) != hipSuccess || hipMemcpy(nd, d, used * sizeof(T), hipMemcpyDeviceToDevice) != hipSuccess) {
+    (void)hipFree(nd);
+    s->ctx->err = "rebuild: copying a pool failed";
+    return GLOME_E_HIP;
+  }
+  drop_alloc(s, d);
+  s->allocs.push_back(nd);
+  d = (const T*)nd;
+  return 0;
+}
+// What commit derives from the trees' depths (Flattener::run, scene_caps), derived again from the depths as they now stand
+struct DepthRules { int max_bih_depth = 0, max_sphere_bih_depth = 0; SceneCaps caps; };
+static DepthRules depth_rules(const glome_scene* s, uint32_t hdr, int depth) {
+  DepthRules R;
+  for (size_t h = 0; h < s->hdr_depth.size(); h++) {
+    const int d = h == hdr ? depth : s->hdr_depth[h];
+    R.max_bih_depth = std::max(R.max_bih_depth, d);
+    if (s->hdr_packet_service[h]) R.max_sphere_bih_depth = std::max(R.max_sphere_bih_depth, d);
+  }
+  struct View { uint32_t tier; int max_sphere_bih_depth, max_bih_depth, max_mesh_depth; std::vector<U4> entries, recs; std::vector<F4> bihhdr; } V;
+  V.tier = s->dev.tier; V.max_sphere_bih_depth = R.max_sphere_bih_depth; V.max_bih_depth = R.max_bih_depth; V.max_mesh_depth = s->max_mesh_depth;
+  R.caps = scene_caps(V);  // (no entries: the class mask, which no depth changes, stays the commit's)
+  return R;
+}
+static unsigned long long host_dkey(double x) {  // bihdev::dkey
+  unsigned long long b; memcpy(&b, &x, 8);
+  return (b >> 63) ? ~b : (b | 0x8000000000000000ull);
+}
+template <class Src> static int leaf_bih_rebuild(glome_scene* s, int32_t bih_id, glome_scene::LeafBihUpd* m, Src src, int n, const char* what, float* gpu_ms) {
+  glome_ctx* ctx = s->ctx;
+  constexpr bool SPH = kSphereSrc<Src>;
+  if (gpu_ms) *gpu_ms = 0;
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  if (int rc = quiesce(ctx)) return rc;
+  if (n == 0) return 0;
+  LeafBihUpdateInfo& U = m->info;
+  auto refuse = [&](int rc, const std::string& why) { ctx->err = std::string(what) + ": " + why; return rc; };
+  if (U.cls == BC_TRI && !U.pk) return refuse(GLOME_E_LIMIT, "bih " + std::to_string(bih_id) + " was committed without the packet walk's node form and cannot be rebuilt");
+  const auto t_begin = std::chrono::steady_clock::now();
+  // (a) the items' boxes, their join and the validation flag: scratch
+  struct Scratch { double* box = nullptr; unsigned long long* root = nullptr; ~Scratch() { (void)hipFree(box); (void)hipFree(root); } } sc;
+  struct RootWords { unsigned long long key[6]; double bound[6]; unsigned int flag, pad; } rw;
+  HIPCHK(ctx, hipMalloc((void**)&sc.box, sizeof(double) * 6 * (size_t)n));
+  HIPCHK(ctx, hipMalloc((void**)&sc.root, sizeof(RootWords)));
+  for (int a = 0; a < 3; a++) { rw.key[a] = host_dkey(kInfinity); rw.key[3 + a] = host_dkey(-kInfinity); rw.bound[a] = rw.bound[3 + a] = 0; }
+  rw.flag = rw.pad = 0;
+  HIPCHK(ctx, hipMemcpyAsync(sc.root, &rw, sizeof(rw), hipMemcpyHostToDevice, ctx->stream));
+  if (gpu_ms) HIPCHK(ctx, hipEventRecord(ctx->ev0, ctx->stream));
+  {
+    RootWords* d = (RootWords*)sc.root;
+    hipLaunchKernelGGL((bihrebuild::k_item_boxes<Src, SPH>), dim3(((uint32_t)n + 255u) / 256u), dim3(256), 0, ctx->stream, src, (uint32_t)n, sc.box, d->key, &d->flag);
+    hipLaunchKernelGGL(bihrebuild::k_root_box, dim3(1), dim3(64), 0, ctx->stream, (const unsigned long long*)d->key, d->bound);
+  }
+  HIPCHK(ctx, hipGetLastError());
+  HIPCHK(ctx, hipMemcpyAsync(&rw, sc.root, sizeof(rw), hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+  const auto t_boxes = std::chrono::steady_clock::now();
+  if (rw.flag & bihrebuild::kBadIndex) return refuse(GLOME_E_INVALID, "an item has a vertex index outside the vertex array");
+  if (rw.flag) return refuse(GLOME_E_INVALID, SPH ? "a value is not finite or a radius is not positive" : "a vertex coordinate is not finite");
+  const Box3 bb{{rw.bound[0], rw.bound[1], rw.bound[2]}, {rw.bound[3], rw.bound[4], rw.bound[5]}};
+  if (bb.lo.x == -kInfinity || bb.lo.y == -kInfinity || bb.lo.z == -kInfinity || bb.hi.x == kInfinity || bb.hi.y == kInfinity || bb.hi.z == kInfinity) {
+    ctx->err = "bih: infinite bounding box";  // (the constructor's message)
+    return GLOME_E_SCENE;
+  }
+  // (b), (c) the level loop; the topology and the object order back
+  BihTree T;
+  {
+    std::vector<bihdev::DevNode> none;
+    std::vector<bihdev::PackedNode> packed;
+    std::vector<int> order;
+    std::string err;
+    if (const int rc = bihdev::levels_dev<false>(sc.box, n, bb, ctx->stream, err, nullptr, none, order, &packed)) { ctx->err = err; return bihdev_status(rc); }
+    T.bb = bb;
+    bihdev::to_preorder(packed, T,
+      [&](BihTree::Node& tn, const bihdev::PackedNode& d) {
+        tn.leaf = true; tn.lsplit = tn.rsplit = 0; tn.axis = -1; tn.left = tn.right = -1;
+        for (int k = 0; k < d.count; k++) tn.items.push_back(order[(size_t)(d.start + k)]);  // (items by their index in the update order)
+      },
+      [&](BihTree::Node& tn, const bihdev::PackedNode& d) { tn.leaf = false; tn.lsplit = tn.rsplit = 0; tn.axis = d.axis; tn.left = tn.right = -1; });
+  }
+  const auto t_levels = std::chrono::steady_clock::now();
+  // (d) the commit's layout against the tree's segments -- or, for a tree that has outgrown one, against a new segment at the pool's end
+  std::vector<uint32_t> ident((size_t)n);
+  for (int k = 0; k < n; k++) ident[(size_t)k] = (uint32_t)k;
+  uint32_t base = U.first_slot;
+  uint64_t pair_word = U.first_pair_word;
+  size_t nodes_used = s->bihnodes_used, pairs_used = s->tripairs_used;
+  {
+    std::vector<uint32_t> slot;
+    const uint32_t need = std::max<uint32_t>(bih_slots(T, slot), 1u);
+    uint64_t pairs = 0;
+    if (U.cls == BC_TRI) for (const BihTree::Node& bn : T.nodes) pairs += (bn.items.size() + 1) / 2;
+    if (need > m->slot_cap) { base = (uint32_t)((s->bihnodes_used + 3u) & ~(size_t)3u); nodes_used = (size_t)base + need; }
+    if (pairs > m->pair_cap) { pair_word = (s->tripairs_used + 15u) & ~(uint64_t)15u; pairs_used = (size_t)(pair_word + pairs * kPairWords); }
+    if (nodes_used >= (1ull << 27) || (uint64_t)pairs_used * 4 >= (1ull << 31))
+      return refuse(GLOME_E_LIMIT, "the rebuilt tree's segments would lie beyond what a reference of the packet walk can address");
+  }
+  LeafBihLayout L;
+  try { L = leaf_bih_layout(T, U.cls, ident, base, U.first_rec, U.first_prim, pair_word); }
+  catch (const limit_error& e) { return refuse(GLOME_E_LIMIT, e.what()); }
+  if (U.pk && !L.pk) return refuse(GLOME_E_LIMIT, "the rebuilt tree would lose the packet walk's node form");
+  if (L.n_recs != U.n_recs) return refuse(GLOME_E_HIP, "internal: the rebuilt tree holds another number of records");
+  const DepthRules R = depth_rules(s, U.hdr, T.depth);
+  if (s->dev.tier == 0 && R.max_bih_depth > kFlatStack)
+    return refuse(GLOME_E_LIMIT, "the rebuilt tree is " + std::to_string(T.depth) + " levels deep, deeper than the flat tier's stack (" + std::to_string(kFlatStack) + "): a commit would take the generic tier");
+  const auto t_tables = std::chrono::steady_clock::now();
+  // nothing is refused from here on: the pools first
+  DScene& D = s->dev;
+  if (nodes_used > s->bihnodes_cap) {
+    const size_t cap = nodes_used + nodes_used / 4;
+    if (int rc = pool_grow(s, D.bihnodes, s->bihnodes_used, cap)) return rc;
+    if (int rc = pool_grow(s, D.pknodes, s->bihnodes_used, cap)) return rc;
+    s->bihnodes_cap = cap; D.pknodes_bytes = (uint32_t)(cap * sizeof(F4));
+  }
+  if (pairs_used > s->tripairs_cap) {
+    const size_t cap = pairs_used + pairs_used / 4;
+    if (int rc = pool_grow(s, D.tripairs, s->tripairs_used, cap)) return rc;
+    s->tripairs_cap = cap;
+  }
+  const uint32_t n_slots = std::max<uint32_t>(L.n_slots, 1u);
+  if (base != U.first_slot) m->slot_cap = n_slots;           // (the old segment is abandoned)
+  if (pair_word != U.first_pair_word) m->pair_cap = L.n_pair_recs;
+  s->bihnodes_used = nodes_used; s->tripairs_used = pairs_used;
+  // the node words in both pools (planes zero: (e) makes them), the records in the new leaf order, the pair records' count and index words
+  {
+    std::vector<F4> nodes(n_slots), pk(n_slots, F4{0, 0, 0, 0});
+    for (uint32_t q = 0; q < n_slots; q++) {
+      nodes[q] = F4{0.0f, 0.0f, as_float_bits(L.node_zw[2 * (size_t)q]), as_float_bits(L.node_zw[2 * (size_t)q + 1])};
+      if (L.pk) pk[q] = F4{0.0f, 0.0f, as_float_bits(L.pk_zw[2 * (size_t)q]), as_float_bits(L.pk_zw[2 * (size_t)q + 1])};
+    }
+    HIPCHK(ctx, hipMemcpy((F4*)D.bihnodes + base, nodes.data(), nodes.size() * sizeof(F4), hipMemcpyHostToDevice));
+    HIPCHK(ctx, hipMemcpy((F4*)D.pknodes + base, pk.data(), pk.size() * sizeof(F4), hipMemcpyHostToDevice));
+    std::vector<U4> recs(L.n_recs);
+    for (uint32_t j = 0; j < L.n_recs; j++) { recs[j] = m->item_recs[L.rows[(size_t)j * U.row_words]]; recs[j].y = U.first_prim + j; }
+    if (!recs.empty()) HIPCHK(ctx, hipMemcpy((U4*)D.recs + U.first_rec, recs.data(), recs.size() * sizeof(U4), hipMemcpyHostToDevice));
+    if (L.n_pair_recs) {
+      std::vector<float> pairs((size_t)L.n_pair_recs * kPairWords, 0.0f);
+      for (uint32_t q = 0; q < L.n_pair_recs; q++) { pairs[(size_t)q * kPairWords + 18] = as_float_bits(L.pair_words[2 * (size_t)q]); pairs[(size_t)q * kPairWords + 19] = as_float_bits(L.pair_words[2 * (size_t)q + 1]); }
+      HIPCHK(ctx, hipMemcpy((float*)D.tripairs + pair_word, pairs.data(), pairs.size() * sizeof(float), hipMemcpyHostToDevice));
+    }
+  }
+  // the update's tables, and the header's words 2 and 3 and ref[0]
+  {
+    size_t rows_cap = (size_t)U.n_recs * U.row_words;
+    if (int rc = table_room(s, m->d_rows, rows_cap, L.rows.size())) return rc;
+    if (!L.rows.empty()) HIPCHK(ctx, hipMemcpy((void*)m->d_rows, L.rows.data(), L.rows.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+    if (!L.level_nodes.empty()) {
+      if (int rc = table_room(s, m->d_levels, m->levels_cap, L.level_nodes.size())) return rc;
+      if (int rc = table_room(s, m->d_level_off, m->level_off_cap, L.level_off.size())) return rc;
+      HIPCHK(ctx, hipMemcpy((void*)m->d_levels, L.level_nodes.data(), L.level_nodes.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+      HIPCHK(ctx, hipMemcpy((void*)m->d_level_off, L.level_off.data(), L.level_off.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+    }
+    F4* hdr = (F4*)D.bihhdr + 3 * (size_t)U.hdr;
+    HIPCHK(ctx, hipMemcpy(&hdr[0].w, &L.ref[0], 4, hipMemcpyHostToDevice));
+    HIPCHK(ctx, hipMemcpy(&hdr[2], L.hdr2, 16, hipMemcpyHostToDevice));
+  }
+  U.first_slot = base; U.n_slots = L.n_slots; U.first_pair_word = pair_word; U.n_pair_recs = L.n_pair_recs; U.pk = L.pk; U.depth = T.depth;
+  U.level_off = L.level_nodes.empty() ? std::vector<uint32_t>() : L.level_off;
+  // the workspace is two words per record and per slot, then the bound's partial boxes
+  {
+    const size_t words = 2 * ((size_t)U.n_recs + U.n_slots + upd::kBoundMaxBlocks);
+    if (m->d_ws && words > m->ws_words) { drop_alloc(s, m->d_ws); m->d_ws = nullptr; m->ws_words = 0; }
+  }
+  // everything commit derives from the trees' depths and the pool's size
+  s->hdr_depth[U.hdr] = T.depth;
+  s->info.max_bih_depth = R.max_bih_depth; s->info.n_bih_nodes = (int64_t)s->bihnodes_used;
+  s->tr.stack_cap = R.caps.stack_cap; s->tr.n_bih_nodes = (int64_t)s->bihnodes_used; s->ovf_cap = R.caps.ovf_cap;
+  D.pk_generic_cap = getenv("GLOME_DEBUG_NO_GENERIC_PACKETS") ? 0 : R.caps.pk_generic_cap;
+  const auto t_upload = std::chrono::steady_clock::now();
+  // (e) the values: records, pair values, planes, the box, the nested bound -- the update itself, on the same source
+  if (int rc = leaf_bih_update_launch(s, bih_id, m, src, n)) return rc;
+  if (gpu_ms) HIPCHK(ctx, hipEventRecord(ctx->ev1, ctx->stream));
+  HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+  if (gpu_ms) HIPCHK(ctx, hipEventElapsedTime(gpu_ms, ctx->ev0, ctx->ev1));
+  {
+    const auto t_end = std::chrono::steady_clock::now();
+    auto ms = [](std::chrono::steady_clock::time_point a, std::chrono::steady_clock::time_point b) { return std::chrono::duration<double, std::milli>(b - a).count(); };
+    const double v[5] = {ms(t_begin, t_boxes), ms(t_boxes, t_levels), ms(t_levels, t_tables), ms(t_tables, t_upload), ms(t_upload, t_end)};
+    std::copy(v, v + 5, s->rebuild_stage_ms);
+  }
+  return check_device_error(ctx);
+}
+int glome_scene_bih_rebuild_stages(const glome_scene* s, double out5[5]) {
+  if (!s || !out5) return GLOME_E_INVALID;
+  std::copy(s->rebuild_stage_ms, s->rebuild_stage_ms + 5, out5);
+  return 0;
+}
+// the device forms: the update's own checks, then the rebuild on the caller's device arrays
+int glome_scene_bih_rebuild_dev(glome_scene* s, int32_t bih_id, const double* pts9_dev, int n, float* gpu_ms) {
+  if (!s) return GLOME_E_INVALID;
+  glome_scene::LeafBihUpd* m = nullptr;
+  if (int rc = leaf_bih_update_check(s, BC_TRI, "bih rebuild", bih_id, pts9_dev, n, &m)) return rc;
+  return leaf_bih_rebuild(s, bih_id, m, upd::DensePts<double>{pts9_dev}, n, "bih rebuild", gpu_ms);
+}
+static int bih_rebuild_indexed_check(glome_scene* s, int32_t bih_id, const void* verts, int32_t dtype, int nv, const int32_t* idx3, int n, glome_scene::LeafBihUpd** out) {
+  glome_ctx* ctx = s->ctx;
+  if (int rc = leaf_bih_update_check(s, BC_TRI, "bih rebuild", bih_id, idx3, n, out)) return rc;
+  if (dtype != GLOME_F64 && dtype != GLOME_F32) { ctx->err = "bih rebuild: dtype " + std::to_string(dtype) + " is neither GLOME_F64 nor GLOME_F32"; return GLOME_E_INVALID; }
+  if (nv < 0 || (nv && !verts)) { ctx->err = "bih rebuild: null vertex array"; return GLOME_E_INVALID; }
+  if (n > 0 && nv == 0) { ctx->err = "bih rebuild: " + std::to_string(n) + " items index an array of no vertices"; return GLOME_E_INVALID; }
+  return 0;
+}
+int glome_scene_bih_rebuild_indexed_dev(glome_scene* s, int32_t bih_id, const void* verts_dev, int32_t dtype, int nv, const int32_t* idx3_dev, int n, float* gpu_ms) {
+  if (!s) return GLOME_E_INVALID;
+  glome_scene::LeafBihUpd* m = nullptr;
+  if (int rc = bih_rebuild_indexed_check(s, bih_id, verts_dev, dtype, nv, idx3_dev, n, &m)) return rc;
+  if (dtype == GLOME_F32) return leaf_bih_rebuild(s, bih_id, m, indexed_pts<float>(s->ctx, verts_dev, nv, idx3_dev), n, "bih rebuild", gpu_ms);
+  return leaf_bih_rebuild(s, bih_id, m, indexed_pts<double>(s->ctx, verts_dev, nv, idx3_dev), n, "bih rebuild", gpu_ms);
+}
+int glome_scene_sphere_bih_rebuild_dev(glome_scene* s, int32_t bih_id, const double* c3r_dev, int n, float* gpu_ms) {
+  if (!s) return GLOME_E_INVALID;
+  glome_scene::LeafBihUpd* m = nullptr;
+  if (int rc = leaf_bih_update_check(s, BC_SPHERE, "sphere bih rebuild", bih_id, c3r_dev, n, &m)) return rc;
+  return leaf_bih_rebuild(s, bih_id, m, sphupd::SphPacked64{c3r_dev}, n, "sphere bih rebuild", gpu_ms);
+}
+// the host forms: the checks, the values in the caller's arrays, then the arrays staged as they are and the device form
+int glome_scene_bih_rebuild(glome_scene* s, int32_t bih_id, const double* pts9, int n, float* gpu_ms) {
+  if (!s) return GLOME_E_INVALID;
+  if (gpu_ms) *gpu_ms = 0;
+  glome_scene::LeafBihUpd* m = nullptr;
+  if (int rc = leaf_bih_update_check(s, BC_TRI, "bih rebuild", bih_id, pts9, n, &m)) return rc;
+  for (size_t k = 0; k < 9 * (size_t)n; k++) if (!std::isfinite(pts9[k])) { s->ctx->err = "bih rebuild: a vertex coordinate is not finite"; return GLOME_E_INVALID; }
+  HIPCHK(s->ctx, hipSetDevice(s->ctx->device));
+  Staging st;
+  double* dp = st.in(pts9, 9 * (size_t)n);
+  if (!st.ok) { s->ctx->err = "staging allocation failed"; return GLOME_E_HIP; }
+  return glome_scene_bih_rebuild_dev(s, bih_id, dp, n, gpu_ms);
+}
+int glome_scene_bih_rebuild_indexed(glome_scene* s, int32_t bih_id, const void* verts, int32_t dtype, int nv, const int32_t* idx3, int n, float* gpu_ms) {
+  if (!s) return GLOME_E_INVALID;
+  if (gpu_ms) *gpu_ms = 0;
+  glome_ctx* ctx = s->ctx;
+  glome_scene::LeafBihUpd* m = nullptr;
+  if (int rc = bih_rebuild_indexed_check(s, bih_id, verts, dtype, nv, idx3, n, &m)) return rc;
+  for (size_t k = 0; k < 3 * (size_t)n; k++) {  // only referenced vertices count: an unreferenced one may be anything
+    const int32_t i = idx3[k];
+    if (i < 0 || i >= nv) { ctx->err = "bih rebuild: item " + std::to_string(k / 3) + " has vertex index " + std::to_string(i) + ", outside [0, " + std::to_string(nv) + ")"; return GLOME_E_INVALID; }
+    bool finite = true;
+    for (int a = 0; a < 3; a++) finite = finite && (dtype == GLOME_F32 ? std::isfinite(((const float*)verts)[3 * (size_t)i + a]) : std::isfinite(((const double*)verts)[3 * (size_t)i + a]));
+    if (!finite) { ctx->err = "bih rebuild: a vertex coordinate is not finite (vertex " + std::to_string(i) + ", of item " + std::to_string(k / 3) + ")"; return GLOME_E_INVALID; }
+  }
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  Staging st;
+  char* dv = st.in((const char*)verts, 3 * (size_t)nv * (dtype == GLOME_F32 ? sizeof(float) : sizeof(double)));
+  int32_t* di = st.in(idx3, 3 * (size_t)n);
+  if (!st.ok) { ctx->err = "staging allocation failed"; return GLOME_E_HIP; }
+  return glome_scene_bih_rebuild_indexed_dev(s, bih_id, dv, dtype, nv, di, n, gpu_ms);
+}
+int glome_scene_sphere_bih_rebuild(glome_scene* s, int32_t bih_id, const double* c3r, int n, float* gpu_ms) {
+  if (!s) return GLOME_E_INVALID;
+  if (gpu_ms) *gpu_ms = 0;
+  glome_scene::LeafBihUpd* m = nullptr;
+  if (int rc = leaf_bih_update_check(s, BC_SPHERE, "sphere bih rebuild", bih_id, c3r, n, &m)) return rc;
+  for (size_t k = 0; k < 4 * (size_t)n; k++) if (!std::isfinite(c3r[k])) { s->ctx->err = "sphere bih rebuild: a value is not finite"; return GLOME_E_INVALID; }
+  for (size_t k = 0; k < (size_t)n; k++) if (!(c3r[4 * k + 3] > 0)) { s->ctx->err = "sphere bih rebuild: radius of item " + std::to_string(k) + " is not positive"; return GLOME_E_INVALID; }
+  HIPCHK(s->ctx, hipSetDevice(s->ctx->device));
+  Staging st;
+  double* dp = st.in(c3r, 4 * (size_t)n);
+  if (!st.ok) { s->ctx->err = "staging allocation failed"; return GLOME_E_HIP; }
+  return glome_scene_sphere_bih_rebuild_dev(s, bih_id, dp, n, gpu_ms);
+}
+// slots, pair records, records, depth of the tree as it stands, then what its node segment and its pair segment hold
+int glome_scene_bih_layout(const glome_scene* s, int32_t bih_id, int64_t out6[6]) {
+  if (!s || !out6) return GLOME_E_INVALID;
+  auto it = s->leaf_bihs.find(bih_id);
+  if (it == s->leaf_bihs.end()) { s->ctx->err = "bih layout: node " + std::to_string(bih_id) + " is not a bih of plain triangles or plain spheres of this scene"; return GLOME_E_INVALID; }
+  const LeafBihUpdateInfo& U = it->second.info;
+  out6[0] = U.n_slots; out6[1] = U.n_pair_recs; out6[2] = U.n_recs; out6[3] = U.depth; out6[4] = it->second.slot_cap; out6[5] = it->second.pair_cap;
+  return 0;
 }
 
 // ---- new matrices for committed Instances (item_bih_update_kernels.hpp) ----

@@ -19,7 +19,9 @@
  *   - `_dev` variants take DEVICE pointers and run asynchronously on the context's HIP stream.
  *   - A glome_ctx owns one device + one stream and is single-threaded; distinct contexts may be
  *     driven from distinct threads.  A glome_scene is immutable after commit, but for the vertices of its
- *     meshes (glome_scene_mesh_update) and the triangles of its triangle bihs (glome_scene_bih_update).
+ *     meshes (glome_scene_mesh_update), the items of its triangle and sphere bihs (glome_scene_bih_update,
+ *     glome_scene_sphere_bih_update) and those trees' own topology (glome_scene_bih_rebuild), the matrices of its
+ *     Instances (glome_scene_instance_update) and the planes of the bihs above them (glome_scene_bih_refit).
  *   - There is NO CPU fallback: every compute entry point fails with GLOME_E_NO_DEVICE when no
  *     gfx950 device is usable.  Builder and flatten-inspection calls are host-only.
  */
@@ -204,6 +206,24 @@ int glome_sb_instance_transform(glome_sb*, int32_t id, double out[24]);
  * order).  That sequence is the specification of glome_scene_bih_refit.  GLOME_E_INVALID for an id that is not a Bih; GLOME_E_SCENE with
  * the constructor's "bih: infinite bounding box" when the joined box reaches +-1e6, and nothing is touched then.  Host only. */
 int glome_sb_bih_refit(glome_sb*, int32_t bih_id);
+/* The tree built again in place, from its items' bounds as they stand: where glome_sb_bih_set_triangles, _set_spheres and _bih_refit keep
+ * what the builder decided, this call decides again.  bih_id names a Bih node, whoever made it, of any items (not only triangles or
+ * spheres).  The node becomes the tree glome_sb_bih builds over glome_sb_bih_items(bih_id), in that order: node for node and bit for bit,
+ * same box (glome_sb_bih_dump and glome_sb_show tell), as if the caller had handed the same ids to the constructor -- but under the old
+ * id, so whatever holds the bih (a group, an Instance, a bih above: which keeps the planes it was built with, glome_sb_bih_refit) holds
+ * the new tree.  The update order does not change: a tree read by glome_sb_load_show, whose order is its preorder item list, records
+ * that list first, so item k of a later _set_triangles names the same item before and after.  Statuses are glome_sb_bih's: GLOME_E_SCENE
+ * with the constructor's messages for an infinite box and for an input on which build_rec does not terminate; GLOME_E_INVALID for an id
+ * that is not a Bih.  All or nothing: a refused call leaves the node untouched.  The reference has no such call (`bih` is a pure
+ * constructor).  Host only.  glome_sb_bih_set_triangles / _set_triangles_indexed / _set_spheres, then this call, then glome_sb_bih_refit
+ * of the bihs above, inner trees first, is the sequence a re-split of a deformed tree is specified by. */
+int glome_sb_bih_resplit(glome_sb*, int32_t bih_id);
+/* What a commit lays out for a bih of plain triangles or of plain spheres (the trees glome_scene_bih_update / _sphere_bih_update serve):
+ * out4 = node slots (branches in treelets of four with their padding, and leaves of 7 or more items), pair records of the packet walk
+ * (one per two triangles of a leaf; 0 for spheres), records (one per leaf item), and the tree's depth -- of a scene that is only this
+ * tree; in a larger scene the counts are the same and only the segments' bases differ.  Runs the flattener, no GPU.  With it a caller
+ * sees what a re-split costs in device memory before asking for it.  GLOME_E_INVALID for a node that is not such a bih. */
+int glome_sb_bih_layout(glome_sb*, int32_t bih_id, int64_t out4[4]);
 /* The bihs above node_id -- a Mesh, a bih of plain triangles or of plain spheres, an Instance, or a bih that holds a Mesh, a Bih or an Instance as an item --
  * in the scene under `root`: every Bih on any path from root (or from a Warp material's frame / scene) down to the node, in an order in
  * which they can be refitted, a tree after every tree below it.  Returns their number (0: none) and fills out[0 .. min(number, cap)).
@@ -557,6 +577,53 @@ int glome_scene_bih_refit(glome_scene*, int32_t bih_id, float* gpu_ms);
 int glome_scene_bih_refit_dev(glome_scene*, int32_t bih_id);       /* asynchronous on the current stream / slot */
 int32_t glome_scene_bihs_above(const glome_scene*, int32_t node_id, int32_t* out, int32_t cap);
 int32_t glome_scene_stale_bihs(const glome_scene*, int32_t* out, int32_t cap);
+
+/* ---- a committed triangle or sphere bih re-split in place ----
+ * Where the updates above keep what the builder decided, a rebuild decides again: the committed tree is built again on the GPU from the
+ * new items, in place, and everything else of the scene stays.  The arguments are the matching update's -- glome_scene_bih_update,
+ * _bih_update_indexed, _sphere_bih_update: the same items in the same update order, the same checks of count and pointers up front, the
+ * same rule for a tree under other trees (refused, or, with glome_scene_nested_updates on, accepted: the object's fp64 bound is left in
+ * the bounds table and the bihs above are marked stale, glome_scene_bih_refit of them follows), every refusal of the update in the
+ * update's words ("bih rebuild: ...").
+ *   Contract.  After the call the scene answers every render, sampler, trace and per-ray seam call, bit for bit, work counters bih_nodes
+ * and prim_tests included, as a glome_scene_commit of the same builder after glome_sb_bih_set_triangles (_indexed, _set_spheres) with the
+ * same array, glome_sb_bih_resplit, and glome_sb_bih_refit of the bihs above, inner trees first.  The tree's own segments of the pools --
+ * node slots in both node forms, pair records, triangles or spheres, records -- hold the words that commit uploads, child references
+ * shifted by the segment's base.  The updates' fp32 subnormal-as-zero deviation holds.
+ *   Sequence, on the current stream and slot: a kernel makes the items' fp64 boxes straight from the caller's arrays (min(p) - delta /
+ * max(p) + delta, c - r / c + r: glome_sb_bound's own operations) and validates them; the device builder's level loop (glome_sb_bih_dev)
+ * runs over those boxes; the built topology and the object order come back; the host lays the tree out with the commit's own layout
+ * function and uploads node words, records in the new leaf order, the pair records' count and index words, the update's tables and the
+ * header's words; the update's kernels fill in every value.  NOT asynchronous, in either form: a level costs a synchronisation.  The
+ * call waits for every launch of the context (all slots) first and returns when the scene is complete; *gpu_ms (may be NULL) is the
+ * HIP-event time from the first kernel to the last.  The _dev forms take DEVICE arrays and differ in nothing else.
+ *   All or nothing.  Everything up to the readback writes scratch alone, and every refusal is found by then: GLOME_E_INVALID for a value
+ * that is not finite, a radius that is not positive, a vertex index outside [0, nv) (the host forms look before anything is launched and
+ * name the item; the _dev forms find it in the box kernel, through a flag of the call's own -- not the context's sticky error word --
+ * and report it at once; a bad index is clamped before the load); GLOME_E_SCENE with the constructor's messages for an infinite box and
+ * for an input on which build_rec does not terminate; GLOME_E_LIMIT for a tree deeper than the device builder's 2,048 levels.  The scene
+ * is then as it was.
+ *   Capacity.  A tree's node segment and its pair segment hold what commit gave them (glome_scene_bih_layout: out6 = node slots, pair
+ * records, records, depth of the tree as it stands, then the capacities of the two segments).  A rebuilt tree that fits is laid out from
+ * the segment's unchanged base; one that does not gets new segments at the line-aligned end of the pools, which are reallocated with a
+ * quarter of headroom when they are full; the old segment is abandoned (not reclaimed).  GLOME_E_LIMIT, scene untouched, when the new
+ * segments would pass what a child reference or the packet walk's byte offsets can address, when a tree would lose the packet walk's
+ * node form (or never had it), and -- in a scene of the flat tier -- when the tree would be deeper than the flat tier's stack (32), where
+ * a commit would have taken the generic tier.
+ *   Everything commit derives from the trees' depths is derived again: the header's depth word, glome_scene_info's max_bih_depth and
+ * n_bih_nodes, the stack entries per lane in LDS and beyond, the generic tier's packet stack, the update's workspace.  A rebuilt tree may
+ * be deeper than anything the commit saw.  The walk-entry table and the cull pass name a tree by its header, which does not move. */
+int glome_scene_bih_rebuild(glome_scene*, int32_t bih_id, const double* pts9, int n, float* gpu_ms);
+int glome_scene_bih_rebuild_dev(glome_scene*, int32_t bih_id, const double* pts9_dev, int n, float* gpu_ms);
+int glome_scene_bih_rebuild_indexed(glome_scene*, int32_t bih_id, const void* verts, int32_t dtype, int nv, const int32_t* idx3, int n, float* gpu_ms);
+int glome_scene_bih_rebuild_indexed_dev(glome_scene*, int32_t bih_id, const void* verts_dev, int32_t dtype, int nv, const int32_t* idx3_dev, int n, float* gpu_ms);
+int glome_scene_sphere_bih_rebuild(glome_scene*, int32_t bih_id, const double* c3r, int n, float* gpu_ms);
+int glome_scene_sphere_bih_rebuild_dev(glome_scene*, int32_t bih_id, const double* c3r_dev, int n, float* gpu_ms);
+int glome_scene_bih_layout(const glome_scene*, int32_t bih_id, int64_t out6[6]);
+/* The last rebuild of the scene by stage, host wall-clock milliseconds: the boxes (kernel, and the wait for the flag and the root's box),
+ * the level loop with the readback, the tables on the host, their upload, the update's kernels with the final wait.  Zeros before the
+ * first rebuild.  For measurement (tools/probe/bih_rebuild_rate.py). */
+int glome_scene_bih_rebuild_stages(const glome_scene*, double out5[5]);
 
 /* ---- per-ray seams (Solid.hs:146-166), host buffers ---- */
 /* closest hit: t < 0 marks a miss (RayMiss), and then prim is -1, tex8 all -1 and the normal UNSPECIFIED (whatever the traversal
