@@ -655,13 +655,30 @@ class Scene:
         (returns None; the tensor must stay alive until it has run)."""
         return self._one_array_update("bih_update", self.lib.glome_scene_bih_update, self.lib.glome_scene_bih_update_dev, np.float64, bih_id, pts9, "pts9", 9)
 
-    def _one_array_update(self, call, host, dev, dtype, bih_id, values, what, per_row):
-        """the leaf bih updates that take one array of per_row values per item: the library's host and device form"""
+    def _dev_call(self, dev, bih_id, args, blocking):
+        """the device form `dev` of a leaf bih call: an update's is asynchronous and returns None; a rebuild's (blocking) takes the
+        milliseconds' address last and returns them"""
+        ms = C.c_float(0)
+        self._chk(dev(self.h, int(bih_id), *args, *([C.byref(ms)] if blocking else [])), dev.__name__)
+        return ms.value if blocking else None
+
+    def _one_array_update(self, call, host, dev, dtype, bih_id, values, what, per_row, blocking=False):
+        """the leaf bih updates and rebuilds that take one array of per_row values per item: the library's host and device form.
+        blocking: the device form, too, returns the device milliseconds (a rebuild's)"""
         if hasattr(values, "data_ptr"):  # a torch tensor: the device form
-            p, n = self._dev_arg(values, call, what, _TORCH_NAME[dtype], per_row)
-            self._chk(dev(self.h, int(bih_id), p, n), dev.__name__)
-            return None
+            return self._dev_call(dev, bih_id, self._dev_arg(values, call, what, _TORCH_NAME[dtype], per_row), blocking)
         return self._host_update(host, bih_id, [(values, dtype, per_row)], lambda p, n: (p[0], n[0]))
+
+    def _indexed(self, call, host, dev, bih_id, verts, idx, blocking=False):
+        """bih_update_indexed / bih_rebuild_indexed: the library's host and device form"""
+        if hasattr(verts, "data_ptr") or hasattr(idx, "data_ptr"):  # torch tensors: the device form
+            pv, nv = self._dev_arg(verts, call, "verts", ("torch.float32", "torch.float64"), 3)
+            pi, n = self._dev_arg(idx, call, "idx", ("torch.int32",), 3)
+            dtype = 1 if str(verts.dtype) == "torch.float32" else 0  # GLOME_F32 / GLOME_F64
+            return self._dev_call(dev, bih_id, (pv, dtype, nv, pi, n), blocking)
+        dtype = 1 if np.asarray(verts).dtype == np.float32 else 0
+        return self._host_update(host, bih_id, [(verts, np.float32 if dtype else np.float64, 3), (idx, np.int32, 3)],
+                                 lambda p, n: (p[0], dtype, n[0], p[1], n[1]), ptr={np.float32: C.c_void_p, np.float64: C.c_void_p, np.int32: L.c_ip})
 
     def sphere_bih_update(self, bih_id, c3r):
         """New centres and radii for a committed sphere bih, its planes refitted on the GPU (glome_scene_sphere_bih_update): the scene a
@@ -676,50 +693,23 @@ class Scene:
         bit; only referenced vertices count.  NumPy arrays take the host form (a float32 array is staged as float32, anything else as
         float64) and return the device milliseconds; CUDA torch tensors -- float32 or float64 vertices, int32 indices -- take the device
         form, asynchronous on the context's stream (returns None; the tensors must stay alive until it has run)."""
-        if hasattr(verts, "data_ptr") or hasattr(idx, "data_ptr"):  # torch tensors: the device form
-            pv, nv = self._dev_arg(verts, "bih_update_indexed", "verts", ("torch.float32", "torch.float64"), 3)
-            pi, n = self._dev_arg(idx, "bih_update_indexed", "idx", ("torch.int32",), 3)
-            dtype = 1 if str(verts.dtype) == "torch.float32" else 0  # GLOME_F32 / GLOME_F64
-            self._chk(self.lib.glome_scene_bih_update_indexed_dev(self.h, int(bih_id), pv, dtype, nv, pi, n), "glome_scene_bih_update_indexed_dev")
-            return None
-        dtype = 1 if np.asarray(verts).dtype == np.float32 else 0
-        return self._host_update(self.lib.glome_scene_bih_update_indexed, bih_id, [(verts, np.float32 if dtype else np.float64, 3), (idx, np.int32, 3)],
-                                 lambda p, n: (p[0], dtype, n[0], p[1], n[1]), ptr={np.float32: C.c_void_p, np.float64: C.c_void_p, np.int32: L.c_ip})
-
-    def _rebuild(self, call, host, dev, bih_id, values, what, per_row):
-        """the rebuilds that take one float64 array: NumPy takes the host form, a CUDA torch.float64 tensor the device form; both block and
-        return the device milliseconds"""
-        if hasattr(values, "data_ptr"):
-            p, n = self._dev_arg(values, call, what, ("torch.float64",), per_row)
-            ms = C.c_float(0)
-            self._chk(dev(self.h, int(bih_id), p, n, C.byref(ms)), dev.__name__)
-            return ms.value
-        return self._host_update(host, bih_id, [(values, np.float64, per_row)], lambda p, n: (p[0], n[0]))
+        return self._indexed("bih_update_indexed", self.lib.glome_scene_bih_update_indexed, self.lib.glome_scene_bih_update_indexed_dev, bih_id, verts, idx)
 
     def bih_rebuild(self, bih_id, pts9):
         """A committed triangle bih re-split in place from new triangles (glome_scene_bih_rebuild): the scene a commit after
         Builder.bih_set_triangles and Builder.bih_resplit would have made.  Arguments as bih_update; NOT asynchronous in either form: returns
         the device milliseconds when the scene is complete."""
-        return self._rebuild("bih_rebuild", self.lib.glome_scene_bih_rebuild, self.lib.glome_scene_bih_rebuild_dev, bih_id, pts9, "pts9", 9)
+        return self._one_array_update("bih_rebuild", self.lib.glome_scene_bih_rebuild, self.lib.glome_scene_bih_rebuild_dev, np.float64, bih_id, pts9, "pts9", 9, blocking=True)
 
     def sphere_bih_rebuild(self, bih_id, c3r):
         """A committed sphere bih re-split in place from new centres and radii (glome_scene_sphere_bih_rebuild); arguments as
         sphere_bih_update, blocking like bih_rebuild."""
-        return self._rebuild("sphere_bih_rebuild", self.lib.glome_scene_sphere_bih_rebuild, self.lib.glome_scene_sphere_bih_rebuild_dev, bih_id, c3r, "c3r", 4)
+        return self._one_array_update("sphere_bih_rebuild", self.lib.glome_scene_sphere_bih_rebuild, self.lib.glome_scene_sphere_bih_rebuild_dev, np.float64, bih_id, c3r, "c3r", 4, blocking=True)
 
     def bih_rebuild_indexed(self, bih_id, verts, idx):
         """bih_rebuild from a vertex array [nv, 3], float32 or float64, and an int32 table [n, 3] (glome_scene_bih_rebuild_indexed);
         arguments as bih_update_indexed, blocking like bih_rebuild."""
-        if hasattr(verts, "data_ptr") or hasattr(idx, "data_ptr"):
-            pv, nv = self._dev_arg(verts, "bih_rebuild_indexed", "verts", ("torch.float32", "torch.float64"), 3)
-            pi, n = self._dev_arg(idx, "bih_rebuild_indexed", "idx", ("torch.int32",), 3)
-            dtype = 1 if str(verts.dtype) == "torch.float32" else 0  # GLOME_F32 / GLOME_F64
-            ms = C.c_float(0)
-            self._chk(self.lib.glome_scene_bih_rebuild_indexed_dev(self.h, int(bih_id), pv, dtype, nv, pi, n, C.byref(ms)), "glome_scene_bih_rebuild_indexed_dev")
-            return ms.value
-        dtype = 1 if np.asarray(verts).dtype == np.float32 else 0
-        return self._host_update(self.lib.glome_scene_bih_rebuild_indexed, bih_id, [(verts, np.float32 if dtype else np.float64, 3), (idx, np.int32, 3)],
-                                 lambda p, n: (p[0], dtype, n[0], p[1], n[1]), ptr={np.float32: C.c_void_p, np.float64: C.c_void_p, np.int32: L.c_ip})
+        return self._indexed("bih_rebuild_indexed", self.lib.glome_scene_bih_rebuild_indexed, self.lib.glome_scene_bih_rebuild_indexed_dev, bih_id, verts, idx, blocking=True)
 
     def bih_layout(self, bih_id):
         """A committed triangle or sphere bih as it stands (glome_scene_bih_layout): a dict of `slots`, `pairs`, `records`, `depth`, and the

@@ -181,7 +181,7 @@ struct glome_scene {
     // hold (slots; pair records), initially their committed size; and what the device tables above and the workspace hold
     std::vector<U4> item_recs;
     uint32_t slot_cap = 0, pair_cap = 0;
-    size_t levels_cap = 0, level_off_cap = 0, ws_words = 0;
+    size_t rows_cap = 0, levels_cap = 0, level_off_cap = 0, ws_words = 0;
   };
   std::map<int, LeafBihUpd> leaf_bihs;
   // what commit derived from every bih's depth, kept so that a rebuild can derive it again: per bih header its tree's depth and whether it
@@ -325,6 +325,42 @@ template <class T> static int upload(glome_scene* s, const std::vector<T>& v, co
   *out = (const T*)d;
   return 0;
 }
+static void drop_alloc(glome_scene* s, const void* p) {
+  if (!p) return;
+  auto it = std::find(s->allocs.begin(), s->allocs.end(), (void*)p);
+  if (it != s->allocs.end()) s->allocs.erase(it);
+  (void)hipFree((void*)p);
+}
+// a fresh allocation becomes the scene's in place of what `slot` held, which is freed (no launch reads it: the caller has quiesced)
+template <class T> static void adopt(glome_scene* s, const T*& slot, T*& fresh) {
+  if (!fresh) return;
+  drop_alloc(s, slot);
+  s->allocs.push_back(fresh);
+  slot = fresh; fresh = nullptr;
+}
+// The device tables of a leaf bih's update -- rows, level_nodes, level_off (flatten.hpp LeafBihLayout; a tree whose root is a leaf has no
+// levels) -- filled from a layout: by commit for the first time, by a rebuild again.  room(): a fresh allocation for every table that
+// lacks the room, all of them before anything is copied; fill(): the copies; take(): the fresh ones become the scene's and the
+// capacities follow.  Until take() the scene is as it was, and what room() allocated goes with this.
+struct LeafTables {
+  struct One { const uint32_t*& d; size_t& cap; const std::vector<uint32_t>& v; uint32_t* fresh; };
+  One t[3];
+  LeafTables(glome_scene::LeafBihUpd& m, const std::vector<uint32_t>& rows, const std::vector<uint32_t>& level_nodes, const std::vector<uint32_t>& level_off)
+      : t{{m.d_rows, m.rows_cap, rows, nullptr}, {m.d_levels, m.levels_cap, level_nodes, nullptr}, {m.d_level_off, m.level_off_cap, level_off, nullptr}} {}
+  LeafTables(const LeafTables&) = delete;
+  ~LeafTables() { for (One& o : t) (void)hipFree(o.fresh); }
+  int room(glome_ctx* ctx) {
+    for (One& o : t) if (!o.v.empty() && (o.v.size() > o.cap || !o.d)) HIPCHK(ctx, hipMalloc((void**)&o.fresh, o.v.size() * sizeof(uint32_t)));
+    return 0;
+  }
+  int fill(glome_ctx* ctx) {
+    for (One& o : t) if (!o.v.empty()) HIPCHK(ctx, hipMemcpy(o.fresh ? o.fresh : (uint32_t*)o.d, o.v.data(), o.v.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+    return 0;
+  }
+  void take(glome_scene* s) {
+    for (One& o : t) if (o.fresh) { o.cap = o.v.size(); adopt(s, o.d, o.fresh); }
+  }
+};
 
 const char* glome_global_error(void) { return g_global_error.c_str(); }
 
@@ -611,11 +647,13 @@ glome_scene* glome_scene_commit(glome_ctx* ctx, glome_sb* sb, int32_t root) {
   }
   for (LeafBihUpdateInfo& U : F.leaf_bih_updates) {
     glome_scene::LeafBihUpd& m = s->leaf_bihs[U.node];
-    if ((!U.rows.empty() && upload(s, U.rows, &m.d_rows)) || (!U.level_nodes.empty() && (upload(s, U.level_nodes, &m.d_levels) || upload(s, U.level_off, &m.d_level_off)))) { glome_scene_release(s); return nullptr; }
+    LeafTables tables(m, U.rows, U.level_nodes, U.level_off);
+    if (tables.room(ctx) || tables.fill(ctx)) { glome_scene_release(s); return nullptr; }
+    tables.take(s);
+    s->info.device_bytes += (int64_t)((U.rows.size() + U.level_nodes.size() + U.level_off.size()) * sizeof(uint32_t));
     m.item_recs.assign((size_t)U.n_items, U4{0, 0, 0, 0});
     for (uint32_t j = 0; j < U.n_recs; j++) m.item_recs[U.rows[(size_t)j * U.row_words]] = F.recs[(size_t)U.first_rec + j];
     m.slot_cap = std::max<uint32_t>(U.n_slots, 1u); m.pair_cap = U.n_pair_recs;
-    m.levels_cap = U.level_nodes.size(); m.level_off_cap = U.level_nodes.empty() ? 0 : U.level_off.size();
     U.rows = {}; U.level_nodes = {};
     m.info = std::move(U);
   }
@@ -1147,11 +1185,11 @@ template <class Dev> static int run_blocking(glome_ctx* ctx, float* gpu_ms, Dev 
   if (gpu_ms) HIPCHK(ctx, hipEventElapsedTime(gpu_ms, ctx->ev0, ctx->ev1));
   return check_device_error(ctx);
 }
-// The frame of the updates' blocking host forms.  check(): what both forms of the call refuse.  validate(): what the host form alone can
-// see, the values in the caller's arrays.  stage(st) copies the arrays to the device through st.in and returns the device form as a
-// callable: the copies stay outside the timed span, the device form runs inside it.  Refusals keep this order: check, validation, device
-// work.  empty: the call names nothing to update -- once it has passed the check and the validation it is complete.
-template <class Check, class Validate, class Stage> static int blocking_update(glome_scene* s, float* gpu_ms, Check check, Validate validate, Stage stage, bool empty = false) {
+// The front half of a blocking host form that changes a committed scene.  check(): what both forms of the call refuse.  validate(): what
+// the host form alone can see, the values in the caller's arrays.  stage(st) copies the arrays to the device through st.in and returns
+// the device form as a callable, which run(dev) is given while the copies live.  Refusals keep this order: check, validation, device
+// work.  empty: the call names nothing to change -- once it has passed the check and the validation it is complete.
+template <class Check, class Validate, class Stage, class Run> static int staged_front(glome_scene* s, float* gpu_ms, Check check, Validate validate, Stage stage, Run run, bool empty = false) {
   if (!s) return GLOME_E_INVALID;
   glome_ctx* ctx = s->ctx;
   if (gpu_ms) *gpu_ms = 0;
@@ -1163,7 +1201,12 @@ template <class Check, class Validate, class Stage> static int blocking_update(g
   Staging st;
   auto dev = stage(st);
   if (!st.ok) { ctx->err = "staging allocation failed"; return GLOME_E_HIP; }
-  return run_blocking(ctx, gpu_ms, dev);
+  return run(dev);
+}
+// The frame of the updates' blocking host forms: the front half, then the device form timed and waited for -- the copies stay outside the
+// timed span, the device form runs inside it.
+template <class Check, class Validate, class Stage> static int blocking_update(glome_scene* s, float* gpu_ms, Check check, Validate validate, Stage stage, bool empty = false) {
+  return staged_front(s, gpu_ms, check, validate, stage, [&](auto dev) { return run_blocking(s->ctx, gpu_ms, dev); }, empty);
 }
 // One event pair per update while timing is on; with the update's split switch (GLOME_DEBUG_MESH_UPDATE_SPLIT,
 // GLOME_DEBUG_BIH_UPDATE_SPLIT: tools/probe/*_update_rate.py) one per stage -- records, levels, bound.
@@ -1398,11 +1441,16 @@ int glome_scene_mesh_update_f32(glome_scene* s, int32_t mesh_id, const float* ve
 
 // ---- new items for a committed leaf bih: triangles (bih_update_kernels.hpp) or spheres (sphere_bih_update_kernels.hpp) ----
 // One path serves both classes: the record (LeafBihUpdateInfo) says what differs in the tables, the source type what differs in the kernels.
-// What both forms refuse before anything is launched; *out = the bih's tables.  cls: the class the call is for; what: the call's name in
-// its texts ("bih update", "sphere bih update"); `items`: the array there is one entry per item of.
+// The source forms, the two actions on them and the entry points follow the rebuild, below.
+// A refusal of one of these calls: the call's name, then why (texts are made by a refusal alone)
+static int refuse(glome_ctx* ctx, const char* what, const std::string& why, int rc = GLOME_E_INVALID) {
+  ctx->err = std::string(what) + ": " + why;
+  return rc;
+}
+// What both forms of every call refuse before anything is launched; *out = the bih's tables.  cls: the class the call is for; what: the
+// call's name in its texts ("bih update", "sphere bih rebuild"); `items`: the array there is one entry per item of.
 static int leaf_bih_update_check(glome_scene* s, uint32_t cls, const char* what, int32_t bih_id, const void* items, int n, glome_scene::LeafBihUpd** out) {
-  glome_ctx* ctx = s->ctx;
-  auto refuse = [&](const std::string& why) { ctx->err = std::string(what) + ": " + why; return GLOME_E_INVALID; };  // (texts are made by a refusal alone)
+  auto refuse = [&](const std::string& why) { return ::refuse(s->ctx, what, why); };
   const char* word = cls == BC_SPHERE ? "sphere" : "triangle";
   auto it = s->leaf_bihs.find(bih_id);
   if (it == s->leaf_bihs.end() || it->second.info.cls != cls) return refuse("node " + std::to_string(bih_id) + " is not a bih of plain " + word + "s of this scene");
@@ -1413,8 +1461,8 @@ static int leaf_bih_update_check(glome_scene* s, uint32_t cls, const char* what,
   *out = &it->second;
   return 0;
 }
-static int bih_update_check(glome_scene* s, int32_t bih_id, const void* pts9, int n, glome_scene::LeafBihUpd** out) { return leaf_bih_update_check(s, BC_TRI, "bih update", bih_id, pts9, n, out); }
-static int sphere_bih_update_check(glome_scene* s, int32_t bih_id, const void* c3r, int n, glome_scene::LeafBihUpd** out) { return leaf_bih_update_check(s, BC_SPHERE, "sphere bih update", bih_id, c3r, n, out); }
+// an update's workspace, in words of one float4: a box, two words, per record and per node slot, and the bound's partial boxes
+static size_t leaf_ws_words(uint32_t n_recs, uint32_t n_slots) { return 2 * ((size_t)n_recs + n_slots + upd::kBoundMaxBlocks); }
 // The launches of an update the checks have accepted, on the current stream.  `src` yields the n items: a point source their 3 n vertices
 // (update_common.hpp), a sphere source their spheres (sphere_bih_update_kernels.hpp); every kernel that reads them is its instance for
 // that source.  The source's kind picks the records kernel and the two partial-box kernels; all else is one sequence.
@@ -1423,8 +1471,7 @@ template <class Src> static int leaf_bih_update_launch(glome_scene* s, int32_t b
   HIPCHK(ctx, hipSetDevice(ctx->device));
   const LeafBihUpdateInfo& U = m->info;
   const uint32_t n_src = kSphereSrc<Src> ? (uint32_t)n : 3u * (uint32_t)n;  // what the bounds fold: spheres, or vertices
-  // a box per record and per node slot, and the bound's partial boxes
-  const size_t ws_words = 2 * ((size_t)U.n_recs + U.n_slots + upd::kBoundMaxBlocks);
+  const size_t ws_words = leaf_ws_words(U.n_recs, U.n_slots);
   if (int rc = ensure_ws(s, m->d_ws, ws_words)) return rc;
   if (!m->ws_words) m->ws_words = ws_words;  // (what it was allocated with: a rebuild may ask for more)
   // The levels run a launch each: the merged launch of the narrow levels (k_bih_levels_merged) stays behind GLOME_DEBUG_BIH_UPDATE_MERGED
@@ -1462,154 +1509,25 @@ template <class Src> static int leaf_bih_update_launch(glome_scene* s, int32_t b
   mark_launched(ctx);  // (a value that is not finite, a radius that is not positive or an index outside the vertex array is reported at the next synchronize)
   return 0;
 }
-template <class T> static int bih_update_dev(glome_scene* s, int32_t bih_id, const T* pts9_dev, int n) {
-  if (!s) return GLOME_E_INVALID;
-  glome_scene::LeafBihUpd* m = nullptr;
-  if (int rc = bih_update_check(s, bih_id, pts9_dev, n, &m)) return rc;
-  return leaf_bih_update_launch(s, bih_id, m, upd::DensePts<T>{pts9_dev}, n);
-}
-// the host form, for an array of T: staged as it is
-template <class T> static int bih_update_host(glome_scene* s, int32_t bih_id, const T* pts9, int n, float* gpu_ms) {
-  glome_scene::LeafBihUpd* m = nullptr;
-  return blocking_update(
-      s, gpu_ms, [&] { return bih_update_check(s, bih_id, pts9, n, &m); },
-      [&]() -> int {
-        for (size_t k = 0; k < 9 * (size_t)n; k++) if (!std::isfinite(pts9[k])) { s->ctx->err = "bih update: a vertex coordinate is not finite"; return GLOME_E_INVALID; }
-        return 0;
-      },
-      [&](Staging& st) {
-        T* dp = st.in(pts9, 9 * (size_t)n);
-        return [=] { return bih_update_dev<T>(s, bih_id, dp, n); };
-      });
-}
-int glome_scene_bih_update_dev(glome_scene* s, int32_t bih_id, const double* pts9_dev, int n) { return bih_update_dev<double>(s, bih_id, pts9_dev, n); }
-int glome_scene_bih_update(glome_scene* s, int32_t bih_id, const double* pts9, int n, float* gpu_ms) { return bih_update_host<double>(s, bih_id, pts9, n, gpu_ms); }
-int glome_scene_bih_update_f32_dev(glome_scene* s, int32_t bih_id, const float* pts9_dev, int n) { return bih_update_dev<float>(s, bih_id, pts9_dev, n); }
-int glome_scene_bih_update_f32(glome_scene* s, int32_t bih_id, const float* pts9, int n, float* gpu_ms) { return bih_update_host<float>(s, bih_id, pts9, n, gpu_ms); }
-
-// The indexed forms: the items' vertices are verts[3 * idx3[3 k + c] ..], a vertex array of `dtype` and an index table.  What both forms
-// refuse beyond bih_update_check, before anything is launched.
-static int bih_update_indexed_check(glome_scene* s, int32_t bih_id, const void* verts, int32_t dtype, int nv, const int32_t* idx3, int n, glome_scene::LeafBihUpd** out) {
-  glome_ctx* ctx = s->ctx;
-  if (int rc = bih_update_check(s, bih_id, idx3, n, out)) return rc;  // (the array it asks for is the one there is one entry per item of)
-  if (dtype != GLOME_F64 && dtype != GLOME_F32) { ctx->err = "bih update: dtype " + std::to_string(dtype) + " is neither GLOME_F64 nor GLOME_F32"; return GLOME_E_INVALID; }
-  if (nv < 0 || (nv && !verts)) { ctx->err = "bih update: null vertex array"; return GLOME_E_INVALID; }
-  if (n > 0 && nv == 0) { ctx->err = "bih update: " + std::to_string(n) + " items index an array of no vertices"; return GLOME_E_INVALID; }
-  return 0;
-}
-int glome_scene_bih_update_indexed_dev(glome_scene* s, int32_t bih_id, const void* verts_dev, int32_t dtype, int nv, const int32_t* idx3_dev, int n) {
-  if (!s) return GLOME_E_INVALID;
-  glome_scene::LeafBihUpd* m = nullptr;
-  if (int rc = bih_update_indexed_check(s, bih_id, verts_dev, dtype, nv, idx3_dev, n, &m)) return rc;
-  if (dtype == GLOME_F32) return leaf_bih_update_launch(s, bih_id, m, indexed_pts<float>(s->ctx, verts_dev, nv, idx3_dev), n);
-  return leaf_bih_update_launch(s, bih_id, m, indexed_pts<double>(s->ctx, verts_dev, nv, idx3_dev), n);
-}
-int glome_scene_bih_update_indexed(glome_scene* s, int32_t bih_id, const void* verts, int32_t dtype, int nv, const int32_t* idx3, int n, float* gpu_ms) {
-  glome_scene::LeafBihUpd* m = nullptr;
-  return blocking_update(
-      s, gpu_ms, [&] { return bih_update_indexed_check(s, bih_id, verts, dtype, nv, idx3, n, &m); },
-      [&]() -> int {
-        glome_ctx* ctx = s->ctx;
-        for (size_t k = 0; k < 3 * (size_t)n; k++) {  // only referenced vertices count: an unreferenced one may be anything
-          const int32_t i = idx3[k];
-          if (i < 0 || i >= nv) { ctx->err = "bih update: item " + std::to_string(k / 3) + " has vertex index " + std::to_string(i) + ", outside [0, " + std::to_string(nv) + ")"; return GLOME_E_INVALID; }
-          bool finite = true;
-          for (int a = 0; a < 3; a++) finite = finite && (dtype == GLOME_F32 ? std::isfinite(((const float*)verts)[3 * (size_t)i + a]) : std::isfinite(((const double*)verts)[3 * (size_t)i + a]));
-          if (!finite) { ctx->err = "bih update: a vertex coordinate is not finite (vertex " + std::to_string(i) + ", of item " + std::to_string(k / 3) + ")"; return GLOME_E_INVALID; }
-        }
-        return 0;
-      },
-      [&](Staging& st) {
-        const size_t vbytes = 3 * (size_t)nv * (dtype == GLOME_F32 ? sizeof(float) : sizeof(double));
-        char* dv = st.in((const char*)verts, vbytes);  // the caller's arrays as they are: no widened, gathered copy
-        int32_t* di = st.in(idx3, 3 * (size_t)n);
-        return [=] { return glome_scene_bih_update_indexed_dev(s, bih_id, dv, dtype, nv, di, n); };
-      });
-}
-
-// The sphere bih's forms: fp64 cx cy cz r interleaved; and fp32 in two streams, centres [n, 3] and radii [n].
-int glome_scene_sphere_bih_update_dev(glome_scene* s, int32_t bih_id, const double* c3r_dev, int n) {
-  if (!s) return GLOME_E_INVALID;
-  glome_scene::LeafBihUpd* m = nullptr;
-  if (int rc = sphere_bih_update_check(s, bih_id, c3r_dev, n, &m)) return rc;
-  return leaf_bih_update_launch(s, bih_id, m, sphupd::SphPacked64{c3r_dev}, n);
-}
-int glome_scene_sphere_bih_update(glome_scene* s, int32_t bih_id, const double* c3r, int n, float* gpu_ms) {
-  glome_scene::LeafBihUpd* m = nullptr;
-  return blocking_update(
-      s, gpu_ms, [&] { return sphere_bih_update_check(s, bih_id, c3r, n, &m); },
-      [&]() -> int {
-        for (size_t k = 0; k < 4 * (size_t)n; k++) if (!std::isfinite(c3r[k])) { s->ctx->err = "sphere bih update: a value is not finite"; return GLOME_E_INVALID; }
-        for (size_t k = 0; k < (size_t)n; k++) if (!(c3r[4 * k + 3] > 0)) { s->ctx->err = "sphere bih update: radius of item " + std::to_string(k) + " is not positive"; return GLOME_E_INVALID; }
-        return 0;
-      },
-      [&](Staging& st) {
-        double* dp = st.in(c3r, 4 * (size_t)n);
-        return [=] { return glome_scene_sphere_bih_update_dev(s, bih_id, dp, n); };
-      });
-}
-static int sphere_bih_update_f32_check(glome_scene* s, int32_t bih_id, const float* centres3, const float* radii, int n, glome_scene::LeafBihUpd** out) {
-  if (int rc = sphere_bih_update_check(s, bih_id, centres3, n, out)) return rc;
-  if (n && !radii) { s->ctx->err = "sphere bih update: null radius array"; return GLOME_E_INVALID; }
-  return 0;
-}
-int glome_scene_sphere_bih_update_f32_dev(glome_scene* s, int32_t bih_id, const float* centres3_dev, const float* radii_dev, int n) {
-  if (!s) return GLOME_E_INVALID;
-  glome_scene::LeafBihUpd* m = nullptr;
-  if (int rc = sphere_bih_update_f32_check(s, bih_id, centres3_dev, radii_dev, n, &m)) return rc;
-  return leaf_bih_update_launch(s, bih_id, m, sphupd::SphSplit32{centres3_dev, radii_dev}, n);
-}
-int glome_scene_sphere_bih_update_f32(glome_scene* s, int32_t bih_id, const float* centres3, const float* radii, int n, float* gpu_ms) {
-  glome_scene::LeafBihUpd* m = nullptr;
-  return blocking_update(
-      s, gpu_ms, [&] { return sphere_bih_update_f32_check(s, bih_id, centres3, radii, n, &m); },
-      [&]() -> int {
-        for (size_t k = 0; k < 3 * (size_t)n; k++) if (!std::isfinite(centres3[k])) { s->ctx->err = "sphere bih update: a value is not finite"; return GLOME_E_INVALID; }
-        for (size_t k = 0; k < (size_t)n; k++) if (!std::isfinite(radii[k])) { s->ctx->err = "sphere bih update: a value is not finite"; return GLOME_E_INVALID; }
-        for (size_t k = 0; k < (size_t)n; k++) if (!(radii[k] > 0)) { s->ctx->err = "sphere bih update: radius of item " + std::to_string(k) + " is not positive"; return GLOME_E_INVALID; }
-        return 0;
-      },
-      [&](Staging& st) {
-        float* dc = st.in(centres3, 3 * (size_t)n);
-        float* dr = st.in(radii, (size_t)n);
-        return [=] { return glome_scene_sphere_bih_update_f32_dev(s, bih_id, dc, dr, n); };
-      });
-}
 
 // ---- a committed leaf bih re-split: the tree built again in place from new items (bih_rebuild_kernels.hpp, bih_build_device.hpp) ----
-// glome_sb_bih_set_triangles / _set_spheres, glome_sb_bih_resplit and a commit, without the commit: (a) the items' fp64 boxes from the
-// update's source, (b) the device builder's level loop over them, (c) the tree's topology and the final object order back, (d) the layout
-// function of the commit (flatten.hpp leaf_bih_layout) against the tree's own segments and the tables it gives uploaded, (e) the update's
-// launches for the values.  (a) to (c) write scratch alone, and every refusal is found there or before: a refused call leaves the scene as it was.
-// Not asynchronous in either form: a level costs a synchronisation, (c) and (d) wait.
-static void drop_alloc(glome_scene* s, const void* p) {
-  if (!p) return;
-  auto it = std::find(s->allocs.begin(), s->allocs.end(), (void*)p);
-  if (it != s->allocs.end()) s->allocs.erase(it);
-  (void)hipFree((void*)p);
-}
-// a device table of the scene's with room for `need` elements: kept when it has, else a new one of that size (the old one is freed: the caller has quiesced)
-template <class T> static int table_room(glome_scene* s, const T*& d, size_t& cap, size_t need) {
-  if (need <= cap && d) return 0;
-  void* nd = nullptr;
-  HIPCHK(s->ctx, hipMalloc(&nd, std::max<size_t>(1, need) * sizeof(T)));
-  drop_alloc(s, d);
-  s->allocs.push_back(nd);
-  d = (const T*)nd; cap = need;
-  return 0;
-}
-// a pool of the scene's grown to hold `cap` elements of T, its first `used` copied (the caller has quiesced: no launch reads the old one)
+// glome_sb_bih_set_triangles / _set_spheres, glome_sb_bih_resplit and a commit, without the commit.  boxes and tree write scratch alone;
+// plan, the layout function of the commit (flatten.hpp leaf_bih_layout) against the tree's own segments, reads the scene and writes
+// nothing; every refusal is found in those three, so a refused call leaves the scene as it was.  apply cannot refuse, and a HIP call
+// of its that fails leaves the scene's record with the old tree.  Not asynchronous in either form: a level costs a synchronisation,
+// tree and apply wait.
+// a pool of the scene's moved to an allocation with room for `cap` elements of T, its first `used` copied (the caller has quiesced: no
+// launch reads the old one, which is freed at once, so two copies of one pool are alive at a time).  The pool holds what it held: the
+// scene's record, which does not know the new room yet, still describes it.
 template <class T> static int pool_grow(glome_scene* s, const T*& d, size_t used, size_t cap) {
-  void* nd = nullptr;
-  HIPCHK(s->ctx, hipMalloc(&nd, cap * sizeof(T)));
+  T* nd = nullptr;
+  HIPCHK(s->ctx, hipMalloc((void**)&nd, cap * sizeof(T)));
   if (hipMemset(nd, 0, cap * sizeof(T)) != hipSuccess || hipMemcpy(nd, d, used * sizeof(T), hipMemcpyDeviceToDevice) != hipSuccess) {
     (void)hipFree(nd);
     s->ctx->err = "rebuild: copying a pool failed";
     return GLOME_E_HIP;
   }
-  drop_alloc(s, d);
-  s->allocs.push_back(nd);
-  d = (const T*)nd;
+  adopt(s, d, nd);
   return 0;
 }
 // What commit derives from the trees' depths (Flattener::run, scene_caps), derived again from the depths as they now stand
@@ -1630,158 +1548,185 @@ static unsigned long long host_dkey(double x) {  // bihdev::dkey
   unsigned long long b; memcpy(&b, &x, 8);
   return (b >> 63) ? ~b : (b | 0x8000000000000000ull);
 }
-template <class Src> static int leaf_bih_rebuild(glome_scene* s, int32_t bih_id, glome_scene::LeafBihUpd* m, Src src, int n, const char* what, float* gpu_ms) {
-  glome_ctx* ctx = s->ctx;
-  constexpr bool SPH = kSphereSrc<Src>;
-  if (gpu_ms) *gpu_ms = 0;
-  HIPCHK(ctx, hipSetDevice(ctx->device));
-  if (int rc = quiesce(ctx)) return rc;
-  if (n == 0) return 0;
-  LeafBihUpdateInfo& U = m->info;
-  auto refuse = [&](int rc, const std::string& why) { ctx->err = std::string(what) + ": " + why; return rc; };
-  if (U.cls == BC_TRI && !U.pk) return refuse(GLOME_E_LIMIT, "bih " + std::to_string(bih_id) + " was committed without the packet walk's node form and cannot be rebuilt");
-  const auto t_begin = std::chrono::steady_clock::now();
-  // (a) the items' boxes, their join and the validation flag: scratch
-  struct Scratch { double* box = nullptr; unsigned long long* root = nullptr; ~Scratch() { (void)hipFree(box); (void)hipFree(root); } } sc;
-  struct RootWords { unsigned long long key[6]; double bound[6]; unsigned int flag, pad; } rw;
-  HIPCHK(ctx, hipMalloc((void**)&sc.box, sizeof(double) * 6 * (size_t)n));
-  HIPCHK(ctx, hipMalloc((void**)&sc.root, sizeof(RootWords)));
-  for (int a = 0; a < 3; a++) { rw.key[a] = host_dkey(kInfinity); rw.key[3 + a] = host_dkey(-kInfinity); rw.bound[a] = rw.bound[3 + a] = 0; }
-  rw.flag = rw.pad = 0;
-  HIPCHK(ctx, hipMemcpyAsync(sc.root, &rw, sizeof(rw), hipMemcpyHostToDevice, ctx->stream));
-  if (gpu_ms) HIPCHK(ctx, hipEventRecord(ctx->ev0, ctx->stream));
-  {
-    RootWords* d = (RootWords*)sc.root;
-    hipLaunchKernelGGL((bihrebuild::k_item_boxes<Src, SPH>), dim3(((uint32_t)n + 255u) / 256u), dim3(256), 0, ctx->stream, src, (uint32_t)n, sc.box, d->key, &d->flag);
-    hipLaunchKernelGGL(bihrebuild::k_root_box, dim3(1), dim3(64), 0, ctx->stream, (const unsigned long long*)d->key, d->bound);
+// boxes: the items' fp64 boxes from the update's source, their join and the validation flag, in scratch
+struct RebuildScratch {
+  struct RootWords { unsigned long long key[6]; double bound[6]; unsigned int flag, pad; };
+  double* box = nullptr;
+  RootWords* root = nullptr;
+  RootWords rw;  // the host's copy: what goes up, then what comes back
+  ~RebuildScratch() { (void)hipFree(box); (void)hipFree(root); }
+  // room for n boxes; the root words at the empty box, no flag
+  int init(glome_ctx* ctx, int n) {
+    HIPCHK(ctx, hipMalloc((void**)&box, sizeof(double) * 6 * (size_t)n));
+    HIPCHK(ctx, hipMalloc((void**)&root, sizeof(RootWords)));
+    for (int a = 0; a < 3; a++) { rw.key[a] = host_dkey(kInfinity); rw.key[3 + a] = host_dkey(-kInfinity); rw.bound[a] = rw.bound[3 + a] = 0; }
+    rw.flag = rw.pad = 0;
+    HIPCHK(ctx, hipMemcpyAsync(root, &rw, sizeof(rw), hipMemcpyHostToDevice, ctx->stream));
+    return 0;
   }
+};
+template <class Src> static int rebuild_boxes(glome_ctx* ctx, Src src, int n, const char* what, RebuildScratch& sc, Box3& bb) {
+  constexpr bool SPH = kSphereSrc<Src>;
+  RebuildScratch::RootWords& rw = sc.rw;
+  hipLaunchKernelGGL((bihrebuild::k_item_boxes<Src, SPH>), dim3(((uint32_t)n + 255u) / 256u), dim3(256), 0, ctx->stream, src, (uint32_t)n, sc.box, sc.root->key, &sc.root->flag);
+  hipLaunchKernelGGL(bihrebuild::k_root_box, dim3(1), dim3(64), 0, ctx->stream, (const unsigned long long*)sc.root->key, sc.root->bound);
   HIPCHK(ctx, hipGetLastError());
   HIPCHK(ctx, hipMemcpyAsync(&rw, sc.root, sizeof(rw), hipMemcpyDeviceToHost, ctx->stream));
   HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-  const auto t_boxes = std::chrono::steady_clock::now();
-  if (rw.flag & bihrebuild::kBadIndex) return refuse(GLOME_E_INVALID, "an item has a vertex index outside the vertex array");
-  if (rw.flag) return refuse(GLOME_E_INVALID, SPH ? "a value is not finite or a radius is not positive" : "a vertex coordinate is not finite");
-  const Box3 bb{{rw.bound[0], rw.bound[1], rw.bound[2]}, {rw.bound[3], rw.bound[4], rw.bound[5]}};
+  if (rw.flag & bihrebuild::kBadIndex) return refuse(ctx, what, "an item has a vertex index outside the vertex array");
+  if (rw.flag) return refuse(ctx, what, SPH ? "a value is not finite or a radius is not positive" : "a vertex coordinate is not finite");
+  bb = Box3{{rw.bound[0], rw.bound[1], rw.bound[2]}, {rw.bound[3], rw.bound[4], rw.bound[5]}};
   if (bb.lo.x == -kInfinity || bb.lo.y == -kInfinity || bb.lo.z == -kInfinity || bb.hi.x == kInfinity || bb.hi.y == kInfinity || bb.hi.z == kInfinity) {
     ctx->err = "bih: infinite bounding box";  // (the constructor's message)
     return GLOME_E_SCENE;
   }
-  // (b), (c) the level loop; the topology and the object order back
-  BihTree T;
-  {
-    std::vector<bihdev::DevNode> none;
-    std::vector<bihdev::PackedNode> packed;
-    std::vector<int> order;
-    std::string err;
-    if (const int rc = bihdev::levels_dev<false>(sc.box, n, bb, ctx->stream, err, nullptr, none, order, &packed)) { ctx->err = err; return bihdev_status(rc); }
-    T.bb = bb;
-    bihdev::to_preorder(packed, T,
-      [&](BihTree::Node& tn, const bihdev::PackedNode& d) {
-        tn.leaf = true; tn.lsplit = tn.rsplit = 0; tn.axis = -1; tn.left = tn.right = -1;
-        for (int k = 0; k < d.count; k++) tn.items.push_back(order[(size_t)(d.start + k)]);  // (items by their index in the update order)
-      },
-      [&](BihTree::Node& tn, const bihdev::PackedNode& d) { tn.leaf = false; tn.lsplit = tn.rsplit = 0; tn.axis = d.axis; tn.left = tn.right = -1; });
-  }
-  const auto t_levels = std::chrono::steady_clock::now();
-  // (d) the commit's layout against the tree's segments -- or, for a tree that has outgrown one, against a new segment at the pool's end
-  std::vector<uint32_t> ident((size_t)n);
-  for (int k = 0; k < n; k++) ident[(size_t)k] = (uint32_t)k;
-  uint32_t base = U.first_slot;
-  uint64_t pair_word = U.first_pair_word;
-  size_t nodes_used = s->bihnodes_used, pairs_used = s->tripairs_used;
+  return 0;
+}
+// tree: the device builder's level loop over the boxes; the topology and the final object order back.  Items by their index in the update order.
+static int rebuild_tree(glome_ctx* ctx, double* box, int n, const Box3& bb, BihTree& T) {
+  std::vector<bihdev::DevNode> none;
+  std::vector<bihdev::PackedNode> packed;
+  std::vector<int> order;
+  std::string err;
+  if (const int rc = bihdev::levels_dev<false>(box, n, bb, ctx->stream, err, nullptr, none, order, &packed)) { ctx->err = err; return bihdev_status(rc); }
+  T.bb = bb;
+  bihdev::to_preorder(packed, T,
+    [&](BihTree::Node& tn, const bihdev::PackedNode& d) {
+      tn.leaf = true; tn.lsplit = tn.rsplit = 0; tn.axis = -1; tn.left = tn.right = -1;
+      for (int k = 0; k < d.count; k++) tn.items.push_back(order[(size_t)(d.start + k)]);
+    },
+    [&](BihTree::Node& tn, const bihdev::PackedNode& d) { tn.leaf = false; tn.lsplit = tn.rsplit = 0; tn.axis = d.axis; tn.left = tn.right = -1; });
+  return 0;
+}
+// plan: what the scene will hold once the tree stands in it.  Where its node segment and its pair segment start -- the tree's own, or,
+// for a tree that has outgrown one, a new one at the pool's end --, the pools' entries in use and allocated after that (allocated: the
+// scene's own figure while the pool has the room), what the tree's segments hold, the commit's layout against them, and what commit
+// derives from the depths.  Every refusal that is not the boxes' or the builder's is made here, of a scene that is not written to; no
+// device call.
+struct RebuildPlan {
+  uint32_t base = 0, slot_cap = 0, pair_cap = 0;
+  uint64_t pair_word = 0;
+  size_t nodes_used = 0, nodes_cap = 0, pairs_used = 0, pairs_cap = 0;
+  LeafBihLayout L;
+  DepthRules R;
+};
+static int rebuild_plan(const glome_scene* s, int32_t bih_id, const glome_scene::LeafBihUpd& m, const BihTree& T, const char* what, RebuildPlan& P) {
+  glome_ctx* ctx = s->ctx;
+  const LeafBihUpdateInfo& U = m.info;
+  if (U.cls == BC_TRI && !U.pk) return refuse(ctx, what, "bih " + std::to_string(bih_id) + " was committed without the packet walk's node form and cannot be rebuilt", GLOME_E_LIMIT);
+  std::vector<uint32_t> ident((size_t)U.n_items);
+  for (size_t k = 0; k < ident.size(); k++) ident[k] = (uint32_t)k;
+  P.base = U.first_slot; P.pair_word = U.first_pair_word; P.nodes_used = s->bihnodes_used; P.pairs_used = s->tripairs_used;
   {
     std::vector<uint32_t> slot;
     const uint32_t need = std::max<uint32_t>(bih_slots(T, slot), 1u);
     uint64_t pairs = 0;
     if (U.cls == BC_TRI) for (const BihTree::Node& bn : T.nodes) pairs += (bn.items.size() + 1) / 2;
-    if (need > m->slot_cap) { base = (uint32_t)((s->bihnodes_used + 3u) & ~(size_t)3u); nodes_used = (size_t)base + need; }
-    if (pairs > m->pair_cap) { pair_word = (s->tripairs_used + 15u) & ~(uint64_t)15u; pairs_used = (size_t)(pair_word + pairs * kPairWords); }
-    if (nodes_used >= (1ull << 27) || (uint64_t)pairs_used * 4 >= (1ull << 31))
-      return refuse(GLOME_E_LIMIT, "the rebuilt tree's segments would lie beyond what a reference of the packet walk can address");
+    if (need > m.slot_cap) { P.base = (uint32_t)((s->bihnodes_used + 3u) & ~(size_t)3u); P.nodes_used = (size_t)P.base + need; }
+    if (pairs > m.pair_cap) { P.pair_word = (s->tripairs_used + 15u) & ~(uint64_t)15u; P.pairs_used = (size_t)(P.pair_word + pairs * kPairWords); }
+    if (P.nodes_used >= (1ull << 27) || (uint64_t)P.pairs_used * 4 >= (1ull << 31))
+      return refuse(ctx, what, "the rebuilt tree's segments would lie beyond what a reference of the packet walk can address", GLOME_E_LIMIT);
   }
-  LeafBihLayout L;
-  try { L = leaf_bih_layout(T, U.cls, ident, base, U.first_rec, U.first_prim, pair_word); }
-  catch (const limit_error& e) { return refuse(GLOME_E_LIMIT, e.what()); }
-  if (U.pk && !L.pk) return refuse(GLOME_E_LIMIT, "the rebuilt tree would lose the packet walk's node form");
-  if (L.n_recs != U.n_recs) return refuse(GLOME_E_HIP, "internal: the rebuilt tree holds another number of records");
-  const DepthRules R = depth_rules(s, U.hdr, T.depth);
-  if (s->dev.tier == 0 && R.max_bih_depth > kFlatStack)
-    return refuse(GLOME_E_LIMIT, "the rebuilt tree is " + std::to_string(T.depth) + " levels deep, deeper than the flat tier's stack (" + std::to_string(kFlatStack) + "): a commit would take the generic tier");
-  const auto t_tables = std::chrono::steady_clock::now();
-  // nothing is refused from here on: the pools first
+  P.nodes_cap = P.nodes_used > s->bihnodes_cap ? P.nodes_used + P.nodes_used / 4 : s->bihnodes_cap;
+  P.pairs_cap = P.pairs_used > s->tripairs_cap ? P.pairs_used + P.pairs_used / 4 : s->tripairs_cap;
+  LeafBihLayout& L = P.L;
+  try { L = leaf_bih_layout(T, U.cls, ident, P.base, U.first_rec, U.first_prim, P.pair_word); }
+  catch (const limit_error& e) { return refuse(ctx, what, e.what(), GLOME_E_LIMIT); }
+  if (U.pk && !L.pk) return refuse(ctx, what, "the rebuilt tree would lose the packet walk's node form", GLOME_E_LIMIT);
+  if (L.n_recs != U.n_recs) return refuse(ctx, what, "internal: the rebuilt tree holds another number of records", GLOME_E_HIP);
+  P.slot_cap = P.base != U.first_slot ? std::max<uint32_t>(L.n_slots, 1u) : m.slot_cap;  // (an outgrown segment is abandoned)
+  P.pair_cap = P.pair_word != U.first_pair_word ? L.n_pair_recs : m.pair_cap;
+  P.R = depth_rules(s, U.hdr, T.depth);
+  if (s->dev.tier == 0 && P.R.max_bih_depth > kFlatStack)
+    return refuse(ctx, what, "the rebuilt tree is " + std::to_string(T.depth) + " levels deep, deeper than the flat tier's stack (" + std::to_string(kFlatStack) + "): a commit would take the generic tier", GLOME_E_LIMIT);
+  return 0;
+}
+// apply: the plan carried out.  Every allocation first -- each pool a segment has outgrown moved to a larger one (pool_grow: it holds
+// what it held), a fresh table for each that lacks the room --, then the uploads, then the scene's record and what commit derives from
+// the depths and the pools' sizes, in one block that no call that can fail interrupts: a failure before it returns with the record, and
+// the tables it points to, still the old tree's.
+static int rebuild_apply(glome_scene* s, glome_scene::LeafBihUpd* m, const RebuildPlan& P) {
+  glome_ctx* ctx = s->ctx;
   DScene& D = s->dev;
-  if (nodes_used > s->bihnodes_cap) {
-    const size_t cap = nodes_used + nodes_used / 4;
-    if (int rc = pool_grow(s, D.bihnodes, s->bihnodes_used, cap)) return rc;
-    if (int rc = pool_grow(s, D.pknodes, s->bihnodes_used, cap)) return rc;
-    s->bihnodes_cap = cap; D.pknodes_bytes = (uint32_t)(cap * sizeof(F4));
+  LeafBihUpdateInfo& U = m->info;
+  const LeafBihLayout& L = P.L;
+  if (P.nodes_cap > s->bihnodes_cap) {
+    if (int rc = pool_grow(s, D.bihnodes, s->bihnodes_used, P.nodes_cap)) return rc;
+    if (int rc = pool_grow(s, D.pknodes, s->bihnodes_used, P.nodes_cap)) return rc;
   }
-  if (pairs_used > s->tripairs_cap) {
-    const size_t cap = pairs_used + pairs_used / 4;
-    if (int rc = pool_grow(s, D.tripairs, s->tripairs_used, cap)) return rc;
-    s->tripairs_cap = cap;
-  }
-  const uint32_t n_slots = std::max<uint32_t>(L.n_slots, 1u);
-  if (base != U.first_slot) m->slot_cap = n_slots;           // (the old segment is abandoned)
-  if (pair_word != U.first_pair_word) m->pair_cap = L.n_pair_recs;
-  s->bihnodes_used = nodes_used; s->tripairs_used = pairs_used;
-  // the node words in both pools (planes zero: (e) makes them), the records in the new leaf order, the pair records' count and index words
+  if (P.pairs_cap > s->tripairs_cap)
+    if (int rc = pool_grow(s, D.tripairs, s->tripairs_used, P.pairs_cap)) return rc;
+  LeafTables tables(*m, L.rows, L.level_nodes, L.level_off);
+  if (int rc = tables.room(ctx)) return rc;
+  // the node words in both pools (planes zero: the values stage makes them), the records in the new leaf order, the pair records' count
+  // and index words; the update's tables; the header's ref[0] and words 2 and 3
   {
+    const uint32_t n_slots = std::max<uint32_t>(L.n_slots, 1u);
     std::vector<F4> nodes(n_slots), pk(n_slots, F4{0, 0, 0, 0});
     for (uint32_t q = 0; q < n_slots; q++) {
       nodes[q] = F4{0.0f, 0.0f, as_float_bits(L.node_zw[2 * (size_t)q]), as_float_bits(L.node_zw[2 * (size_t)q + 1])};
       if (L.pk) pk[q] = F4{0.0f, 0.0f, as_float_bits(L.pk_zw[2 * (size_t)q]), as_float_bits(L.pk_zw[2 * (size_t)q + 1])};
     }
-    HIPCHK(ctx, hipMemcpy((F4*)D.bihnodes + base, nodes.data(), nodes.size() * sizeof(F4), hipMemcpyHostToDevice));
-    HIPCHK(ctx, hipMemcpy((F4*)D.pknodes + base, pk.data(), pk.size() * sizeof(F4), hipMemcpyHostToDevice));
+    HIPCHK(ctx, hipMemcpy((F4*)D.bihnodes + P.base, nodes.data(), nodes.size() * sizeof(F4), hipMemcpyHostToDevice));
+    HIPCHK(ctx, hipMemcpy((F4*)D.pknodes + P.base, pk.data(), pk.size() * sizeof(F4), hipMemcpyHostToDevice));
     std::vector<U4> recs(L.n_recs);
     for (uint32_t j = 0; j < L.n_recs; j++) { recs[j] = m->item_recs[L.rows[(size_t)j * U.row_words]]; recs[j].y = U.first_prim + j; }
     if (!recs.empty()) HIPCHK(ctx, hipMemcpy((U4*)D.recs + U.first_rec, recs.data(), recs.size() * sizeof(U4), hipMemcpyHostToDevice));
     if (L.n_pair_recs) {
       std::vector<float> pairs((size_t)L.n_pair_recs * kPairWords, 0.0f);
       for (uint32_t q = 0; q < L.n_pair_recs; q++) { pairs[(size_t)q * kPairWords + 18] = as_float_bits(L.pair_words[2 * (size_t)q]); pairs[(size_t)q * kPairWords + 19] = as_float_bits(L.pair_words[2 * (size_t)q + 1]); }
-      HIPCHK(ctx, hipMemcpy((float*)D.tripairs + pair_word, pairs.data(), pairs.size() * sizeof(float), hipMemcpyHostToDevice));
+      HIPCHK(ctx, hipMemcpy((float*)D.tripairs + P.pair_word, pairs.data(), pairs.size() * sizeof(float), hipMemcpyHostToDevice));
     }
-  }
-  // the update's tables, and the header's words 2 and 3 and ref[0]
-  {
-    size_t rows_cap = (size_t)U.n_recs * U.row_words;
-    if (int rc = table_room(s, m->d_rows, rows_cap, L.rows.size())) return rc;
-    if (!L.rows.empty()) HIPCHK(ctx, hipMemcpy((void*)m->d_rows, L.rows.data(), L.rows.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-    if (!L.level_nodes.empty()) {
-      if (int rc = table_room(s, m->d_levels, m->levels_cap, L.level_nodes.size())) return rc;
-      if (int rc = table_room(s, m->d_level_off, m->level_off_cap, L.level_off.size())) return rc;
-      HIPCHK(ctx, hipMemcpy((void*)m->d_levels, L.level_nodes.data(), L.level_nodes.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-      HIPCHK(ctx, hipMemcpy((void*)m->d_level_off, L.level_off.data(), L.level_off.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-    }
+    if (int rc = tables.fill(ctx)) return rc;
     F4* hdr = (F4*)D.bihhdr + 3 * (size_t)U.hdr;
     HIPCHK(ctx, hipMemcpy(&hdr[0].w, &L.ref[0], 4, hipMemcpyHostToDevice));
     HIPCHK(ctx, hipMemcpy(&hdr[2], L.hdr2, 16, hipMemcpyHostToDevice));
   }
-  U.first_slot = base; U.n_slots = L.n_slots; U.first_pair_word = pair_word; U.n_pair_recs = L.n_pair_recs; U.pk = L.pk; U.depth = T.depth;
-  U.level_off = L.level_nodes.empty() ? std::vector<uint32_t>() : L.level_off;
-  // the workspace is two words per record and per slot, then the bound's partial boxes
-  {
-    const size_t words = 2 * ((size_t)U.n_recs + U.n_slots + upd::kBoundMaxBlocks);
-    if (m->d_ws && words > m->ws_words) { drop_alloc(s, m->d_ws); m->d_ws = nullptr; m->ws_words = 0; }
-  }
-  // everything commit derives from the trees' depths and the pool's size
-  s->hdr_depth[U.hdr] = T.depth;
-  s->info.max_bih_depth = R.max_bih_depth; s->info.n_bih_nodes = (int64_t)s->bihnodes_used;
-  s->tr.stack_cap = R.caps.stack_cap; s->tr.n_bih_nodes = (int64_t)s->bihnodes_used; s->ovf_cap = R.caps.ovf_cap;
-  D.pk_generic_cap = getenv("GLOME_DEBUG_NO_GENERIC_PACKETS") ? 0 : R.caps.pk_generic_cap;
-  const auto t_upload = std::chrono::steady_clock::now();
-  // (e) the values: records, pair values, planes, the box, the nested bound -- the update itself, on the same source
-  if (int rc = leaf_bih_update_launch(s, bih_id, m, src, n)) return rc;
+  // the record: the pools and tables, the tree's segments, the update's figures, the workspace when the tree has outgrown it (two words
+  // per record and per slot: the next update makes a larger one), and everything commit derives from the trees' depths and the pool's size
+  if (P.nodes_cap > s->bihnodes_cap) D.pknodes_bytes = (uint32_t)(P.nodes_cap * sizeof(F4));
+  tables.take(s);
+  s->bihnodes_used = P.nodes_used; s->bihnodes_cap = P.nodes_cap; s->tripairs_used = P.pairs_used; s->tripairs_cap = P.pairs_cap;
+  m->slot_cap = P.slot_cap; m->pair_cap = P.pair_cap;
+  U.first_slot = P.base; U.n_slots = L.n_slots; U.first_pair_word = P.pair_word; U.n_pair_recs = L.n_pair_recs; U.pk = L.pk; U.depth = L.depth;
+  U.level_off = L.level_off;
+  if (m->d_ws && leaf_ws_words(U.n_recs, U.n_slots) > m->ws_words) { drop_alloc(s, m->d_ws); m->d_ws = nullptr; m->ws_words = 0; }
+  s->hdr_depth[U.hdr] = L.depth;
+  s->info.max_bih_depth = P.R.max_bih_depth; s->info.n_bih_nodes = (int64_t)s->bihnodes_used;
+  s->tr.stack_cap = P.R.caps.stack_cap; s->tr.n_bih_nodes = (int64_t)s->bihnodes_used; s->ovf_cap = P.R.caps.ovf_cap;
+  D.pk_generic_cap = getenv("GLOME_DEBUG_NO_GENERIC_PACKETS") ? 0 : P.R.caps.pk_generic_cap;
+  return 0;
+}
+// The driver: the five stages, the wall clock between them (glome_scene_bih_rebuild_stages), the context's event pair around the device work
+template <class Src> static int leaf_bih_rebuild(glome_scene* s, int32_t bih_id, glome_scene::LeafBihUpd* m, Src src, int n, const char* what, float* gpu_ms) {
+  glome_ctx* ctx = s->ctx;
+  using clock = std::chrono::steady_clock;
+  if (gpu_ms) *gpu_ms = 0;
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  if (int rc = quiesce(ctx)) return rc;
+  if (n == 0) return 0;
+  clock::time_point t[6];
+  RebuildScratch sc;
+  Box3 bb;
+  BihTree T;
+  RebuildPlan P;
+  t[0] = clock::now();
+  if (int rc = sc.init(ctx, n)) return rc;
+  if (gpu_ms) HIPCHK(ctx, hipEventRecord(ctx->ev0, ctx->stream));
+  if (int rc = rebuild_boxes(ctx, src, n, what, sc, bb)) return rc;
+  t[1] = clock::now();
+  if (int rc = rebuild_tree(ctx, sc.box, n, bb, T)) return rc;
+  t[2] = clock::now();
+  if (int rc = rebuild_plan(s, bih_id, *m, T, what, P)) return rc;
+  t[3] = clock::now();
+  if (int rc = rebuild_apply(s, m, P)) return rc;
+  t[4] = clock::now();
+  if (int rc = leaf_bih_update_launch(s, bih_id, m, src, n)) return rc;  // values: records, pair values, planes, the box, the nested bound -- the update itself, on the same source
   if (gpu_ms) HIPCHK(ctx, hipEventRecord(ctx->ev1, ctx->stream));
   HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
   if (gpu_ms) HIPCHK(ctx, hipEventElapsedTime(gpu_ms, ctx->ev0, ctx->ev1));
-  {
-    const auto t_end = std::chrono::steady_clock::now();
-    auto ms = [](std::chrono::steady_clock::time_point a, std::chrono::steady_clock::time_point b) { return std::chrono::duration<double, std::milli>(b - a).count(); };
-    const double v[5] = {ms(t_begin, t_boxes), ms(t_boxes, t_levels), ms(t_levels, t_tables), ms(t_tables, t_upload), ms(t_upload, t_end)};
-    std::copy(v, v + 5, s->rebuild_stage_ms);
-  }
+  t[5] = clock::now();
+  for (int k = 0; k < 5; k++) s->rebuild_stage_ms[k] = std::chrono::duration<double, std::milli>(t[k + 1] - t[k]).count();
   return check_device_error(ctx);
 }
 int glome_scene_bih_rebuild_stages(const glome_scene* s, double out5[5]) {
@@ -1789,80 +1734,148 @@ int glome_scene_bih_rebuild_stages(const glome_scene* s, double out5[5]) {
   std::copy(s->rebuild_stage_ms, s->rebuild_stage_ms + 5, out5);
   return 0;
 }
-// the device forms: the update's own checks, then the rebuild on the caller's device arrays
-int glome_scene_bih_rebuild_dev(glome_scene* s, int32_t bih_id, const double* pts9_dev, int n, float* gpu_ms) {
-  if (!s) return GLOME_E_INVALID;
-  glome_scene::LeafBihUpd* m = nullptr;
-  if (int rc = leaf_bih_update_check(s, BC_TRI, "bih rebuild", bih_id, pts9_dev, n, &m)) return rc;
-  return leaf_bih_rebuild(s, bih_id, m, upd::DensePts<double>{pts9_dev}, n, "bih rebuild", gpu_ms);
+
+// ---- the leaf bih calls: four source forms, two actions ----
+// A form says in what arrays a call is given its n items: its class; items(), the array there is one entry per item of; check(), what
+// both forms of a call refuse beyond leaf_bih_update_check; validate(), what the host form alone can see, the values in the caller's
+// arrays; stage(), the form over device copies of the arrays; visit(), the source its kernels read (update_common.hpp,
+// sphere_bih_update_kernels.hpp).  Every text takes the call's name.
+template <class T> static bool all_finite(const T* v, size_t n) {
+  for (size_t k = 0; k < n; k++) if (!std::isfinite(v[k])) return false;
+  return true;
 }
-static int bih_rebuild_indexed_check(glome_scene* s, int32_t bih_id, const void* verts, int32_t dtype, int nv, const int32_t* idx3, int n, glome_scene::LeafBihUpd** out) {
-  glome_ctx* ctx = s->ctx;
-  if (int rc = leaf_bih_update_check(s, BC_TRI, "bih rebuild", bih_id, idx3, n, out)) return rc;
-  if (dtype != GLOME_F64 && dtype != GLOME_F32) { ctx->err = "bih rebuild: dtype " + std::to_string(dtype) + " is neither GLOME_F64 nor GLOME_F32"; return GLOME_E_INVALID; }
-  if (nv < 0 || (nv && !verts)) { ctx->err = "bih rebuild: null vertex array"; return GLOME_E_INVALID; }
-  if (n > 0 && nv == 0) { ctx->err = "bih rebuild: " + std::to_string(n) + " items index an array of no vertices"; return GLOME_E_INVALID; }
+// triangles, nine values of T each
+template <class T> struct DenseTris {
+  static constexpr uint32_t cls = BC_TRI;
+  const T* pts9; int n;
+  const void* items() const { return pts9; }
+  int check(glome_ctx*, const char*) const { return 0; }
+  int validate(glome_ctx* ctx, const char* what) const { return all_finite(pts9, 9 * (size_t)n) ? 0 : refuse(ctx, what, "a vertex coordinate is not finite"); }
+  DenseTris stage(Staging& st) const { return {st.in(pts9, 9 * (size_t)n), n}; }  // (staged as it is)
+  template <class F> int visit(glome_ctx*, F f) const { return f(upd::DensePts<T>{pts9}); }
+};
+// triangles whose vertices are verts[3 * idx3[3 k + c] ..]: a vertex array of `dtype` and an index table, as a simulation holds a mesh
+struct IndexedTris {
+  static constexpr uint32_t cls = BC_TRI;
+  const void* verts; int32_t dtype; int nv; const int32_t* idx3; int n;
+  const void* items() const { return idx3; }
+  int check(glome_ctx* ctx, const char* what) const {
+    if (dtype != GLOME_F64 && dtype != GLOME_F32) return refuse(ctx, what, "dtype " + std::to_string(dtype) + " is neither GLOME_F64 nor GLOME_F32");
+    if (nv < 0 || (nv && !verts)) return refuse(ctx, what, "null vertex array");
+    if (n > 0 && nv == 0) return refuse(ctx, what, std::to_string(n) + " items index an array of no vertices");
+    return 0;
+  }
+  int validate(glome_ctx* ctx, const char* what) const {
+    for (size_t k = 0; k < 3 * (size_t)n; k++) {  // only referenced vertices count: an unreferenced one may be anything
+      const int32_t i = idx3[k];
+      if (i < 0 || i >= nv) return refuse(ctx, what, "item " + std::to_string(k / 3) + " has vertex index " + std::to_string(i) + ", outside [0, " + std::to_string(nv) + ")");
+      if (!(dtype == GLOME_F32 ? all_finite((const float*)verts + 3 * (size_t)i, 3) : all_finite((const double*)verts + 3 * (size_t)i, 3)))
+        return refuse(ctx, what, "a vertex coordinate is not finite (vertex " + std::to_string(i) + ", of item " + std::to_string(k / 3) + ")");
+    }
+    return 0;
+  }
+  IndexedTris stage(Staging& st) const {  // the caller's arrays as they are: no widened, gathered copy
+    const size_t vbytes = 3 * (size_t)nv * (dtype == GLOME_F32 ? sizeof(float) : sizeof(double));
+    const char* dv = st.in((const char*)verts, vbytes);
+    return {dv, dtype, nv, st.in(idx3, 3 * (size_t)n), n};
+  }
+  template <class F> int visit(glome_ctx* ctx, F f) const {
+    if (dtype == GLOME_F32) return f(indexed_pts<float>(ctx, verts, nv, idx3));
+    return f(indexed_pts<double>(ctx, verts, nv, idx3));
+  }
+};
+// what a host form refuses of n spheres' radii, every value having been found finite: the first that is not positive.  radius(k): item k's
+template <class Radius> static int positive_radii(glome_ctx* ctx, const char* what, int n, Radius radius) {
+  for (size_t k = 0; k < (size_t)n; k++) if (!(radius(k) > 0)) return refuse(ctx, what, "radius of item " + std::to_string(k) + " is not positive");
   return 0;
 }
+// spheres, fp64 cx cy cz r interleaved
+struct PackedSpheres {
+  static constexpr uint32_t cls = BC_SPHERE;
+  const double* c3r; int n;
+  const void* items() const { return c3r; }
+  int check(glome_ctx*, const char*) const { return 0; }
+  int validate(glome_ctx* ctx, const char* what) const {
+    if (!all_finite(c3r, 4 * (size_t)n)) return refuse(ctx, what, "a value is not finite");
+    return positive_radii(ctx, what, n, [&](size_t k) { return c3r[4 * k + 3]; });
+  }
+  PackedSpheres stage(Staging& st) const { return {st.in(c3r, 4 * (size_t)n), n}; }
+  template <class F> int visit(glome_ctx*, F f) const { return f(sphupd::SphPacked64{c3r}); }
+};
+// spheres, fp32 in two streams: centres [n, 3] and radii [n]
+struct SplitSpheres {
+  static constexpr uint32_t cls = BC_SPHERE;
+  const float* centres3; const float* radii; int n;
+  const void* items() const { return centres3; }
+  int check(glome_ctx* ctx, const char* what) const { return n && !radii ? refuse(ctx, what, "null radius array") : 0; }
+  int validate(glome_ctx* ctx, const char* what) const {
+    if (!all_finite(centres3, 3 * (size_t)n) || !all_finite(radii, (size_t)n)) return refuse(ctx, what, "a value is not finite");
+    return positive_radii(ctx, what, n, [&](size_t k) { return radii[k]; });
+  }
+  SplitSpheres stage(Staging& st) const { return {st.in(centres3, 3 * (size_t)n), st.in(radii, (size_t)n), n}; }
+  template <class F> int visit(glome_ctx*, F f) const { return f(sphupd::SphSplit32{centres3, radii}); }
+};
+// The actions.  refit: the values made again on the tree as it stands (leaf_bih_update_launch), asynchronous in the device form, timed by
+// the event pair and waited for in the host form.  rebuild: the tree first (leaf_bih_rebuild), which times and waits itself in both forms.
+enum LeafAct { kRefit, kRebuild };
+static const char* leaf_what(uint32_t cls, LeafAct act) {
+  return cls == BC_SPHERE ? (act == kRebuild ? "sphere bih rebuild" : "sphere bih update") : (act == kRebuild ? "bih rebuild" : "bih update");
+}
+template <class Form> static int leaf_form_check(glome_scene* s, const char* what, int32_t bih_id, const Form& f, glome_scene::LeafBihUpd** out) {
+  if (int rc = leaf_bih_update_check(s, Form::cls, what, bih_id, f.items(), f.n, out)) return rc;
+  return f.check(s->ctx, what);
+}
+// the device form: the checks, then the action on the caller's device arrays
+template <LeafAct A, class Form> static int leaf_bih_dev(glome_scene* s, int32_t bih_id, const Form& f, float* gpu_ms = nullptr) {
+  if (!s) return GLOME_E_INVALID;
+  const char* what = leaf_what(Form::cls, A);
+  glome_scene::LeafBihUpd* m = nullptr;
+  if (int rc = leaf_form_check(s, what, bih_id, f, &m)) return rc;
+  return f.visit(s->ctx, [&](auto src) {
+    if constexpr (A == kRebuild) return leaf_bih_rebuild(s, bih_id, m, src, f.n, what, gpu_ms);
+    else return leaf_bih_update_launch(s, bih_id, m, src, f.n);
+  });
+}
+// the host form: the checks, the values in the caller's arrays, then the arrays staged as they are and the device form
+template <LeafAct A, class Form> static int leaf_bih_host(glome_scene* s, int32_t bih_id, const Form& f, float* gpu_ms) {
+  const char* what = leaf_what(Form::cls, A);
+  glome_scene::LeafBihUpd* m = nullptr;
+  return staged_front(
+      s, gpu_ms, [&] { return leaf_form_check(s, what, bih_id, f, &m); }, [&] { return f.validate(s->ctx, what); },
+      [&](Staging& st) {
+        const Form d = f.stage(st);
+        return [=] { return leaf_bih_dev<A>(s, bih_id, d, gpu_ms); };
+      },
+      [&](auto dev) { return A == kRebuild ? dev() : run_blocking(s->ctx, gpu_ms, dev); });
+}
+int glome_scene_bih_update_dev(glome_scene* s, int32_t bih_id, const double* pts9_dev, int n) { return leaf_bih_dev<kRefit>(s, bih_id, DenseTris<double>{pts9_dev, n}); }
+int glome_scene_bih_update(glome_scene* s, int32_t bih_id, const double* pts9, int n, float* gpu_ms) { return leaf_bih_host<kRefit>(s, bih_id, DenseTris<double>{pts9, n}, gpu_ms); }
+int glome_scene_bih_update_f32_dev(glome_scene* s, int32_t bih_id, const float* pts9_dev, int n) { return leaf_bih_dev<kRefit>(s, bih_id, DenseTris<float>{pts9_dev, n}); }
+int glome_scene_bih_update_f32(glome_scene* s, int32_t bih_id, const float* pts9, int n, float* gpu_ms) { return leaf_bih_host<kRefit>(s, bih_id, DenseTris<float>{pts9, n}, gpu_ms); }
+int glome_scene_bih_update_indexed_dev(glome_scene* s, int32_t bih_id, const void* verts_dev, int32_t dtype, int nv, const int32_t* idx3_dev, int n) {
+  return leaf_bih_dev<kRefit>(s, bih_id, IndexedTris{verts_dev, dtype, nv, idx3_dev, n});
+}
+int glome_scene_bih_update_indexed(glome_scene* s, int32_t bih_id, const void* verts, int32_t dtype, int nv, const int32_t* idx3, int n, float* gpu_ms) {
+  return leaf_bih_host<kRefit>(s, bih_id, IndexedTris{verts, dtype, nv, idx3, n}, gpu_ms);
+}
+int glome_scene_sphere_bih_update_dev(glome_scene* s, int32_t bih_id, const double* c3r_dev, int n) { return leaf_bih_dev<kRefit>(s, bih_id, PackedSpheres{c3r_dev, n}); }
+int glome_scene_sphere_bih_update(glome_scene* s, int32_t bih_id, const double* c3r, int n, float* gpu_ms) { return leaf_bih_host<kRefit>(s, bih_id, PackedSpheres{c3r, n}, gpu_ms); }
+int glome_scene_sphere_bih_update_f32_dev(glome_scene* s, int32_t bih_id, const float* centres3_dev, const float* radii_dev, int n) {
+  return leaf_bih_dev<kRefit>(s, bih_id, SplitSpheres{centres3_dev, radii_dev, n});
+}
+int glome_scene_sphere_bih_update_f32(glome_scene* s, int32_t bih_id, const float* centres3, const float* radii, int n, float* gpu_ms) {
+  return leaf_bih_host<kRefit>(s, bih_id, SplitSpheres{centres3, radii, n}, gpu_ms);
+}
+int glome_scene_bih_rebuild_dev(glome_scene* s, int32_t bih_id, const double* pts9_dev, int n, float* gpu_ms) { return leaf_bih_dev<kRebuild>(s, bih_id, DenseTris<double>{pts9_dev, n}, gpu_ms); }
+int glome_scene_bih_rebuild(glome_scene* s, int32_t bih_id, const double* pts9, int n, float* gpu_ms) { return leaf_bih_host<kRebuild>(s, bih_id, DenseTris<double>{pts9, n}, gpu_ms); }
 int glome_scene_bih_rebuild_indexed_dev(glome_scene* s, int32_t bih_id, const void* verts_dev, int32_t dtype, int nv, const int32_t* idx3_dev, int n, float* gpu_ms) {
-  if (!s) return GLOME_E_INVALID;
-  glome_scene::LeafBihUpd* m = nullptr;
-  if (int rc = bih_rebuild_indexed_check(s, bih_id, verts_dev, dtype, nv, idx3_dev, n, &m)) return rc;
-  if (dtype == GLOME_F32) return leaf_bih_rebuild(s, bih_id, m, indexed_pts<float>(s->ctx, verts_dev, nv, idx3_dev), n, "bih rebuild", gpu_ms);
-  return leaf_bih_rebuild(s, bih_id, m, indexed_pts<double>(s->ctx, verts_dev, nv, idx3_dev), n, "bih rebuild", gpu_ms);
-}
-int glome_scene_sphere_bih_rebuild_dev(glome_scene* s, int32_t bih_id, const double* c3r_dev, int n, float* gpu_ms) {
-  if (!s) return GLOME_E_INVALID;
-  glome_scene::LeafBihUpd* m = nullptr;
-  if (int rc = leaf_bih_update_check(s, BC_SPHERE, "sphere bih rebuild", bih_id, c3r_dev, n, &m)) return rc;
-  return leaf_bih_rebuild(s, bih_id, m, sphupd::SphPacked64{c3r_dev}, n, "sphere bih rebuild", gpu_ms);
-}
-// the host forms: the checks, the values in the caller's arrays, then the arrays staged as they are and the device form
-int glome_scene_bih_rebuild(glome_scene* s, int32_t bih_id, const double* pts9, int n, float* gpu_ms) {
-  if (!s) return GLOME_E_INVALID;
-  if (gpu_ms) *gpu_ms = 0;
-  glome_scene::LeafBihUpd* m = nullptr;
-  if (int rc = leaf_bih_update_check(s, BC_TRI, "bih rebuild", bih_id, pts9, n, &m)) return rc;
-  for (size_t k = 0; k < 9 * (size_t)n; k++) if (!std::isfinite(pts9[k])) { s->ctx->err = "bih rebuild: a vertex coordinate is not finite"; return GLOME_E_INVALID; }
-  HIPCHK(s->ctx, hipSetDevice(s->ctx->device));
-  Staging st;
-  double* dp = st.in(pts9, 9 * (size_t)n);
-  if (!st.ok) { s->ctx->err = "staging allocation failed"; return GLOME_E_HIP; }
-  return glome_scene_bih_rebuild_dev(s, bih_id, dp, n, gpu_ms);
+  return leaf_bih_dev<kRebuild>(s, bih_id, IndexedTris{verts_dev, dtype, nv, idx3_dev, n}, gpu_ms);
 }
 int glome_scene_bih_rebuild_indexed(glome_scene* s, int32_t bih_id, const void* verts, int32_t dtype, int nv, const int32_t* idx3, int n, float* gpu_ms) {
-  if (!s) return GLOME_E_INVALID;
-  if (gpu_ms) *gpu_ms = 0;
-  glome_ctx* ctx = s->ctx;
-  glome_scene::LeafBihUpd* m = nullptr;
-  if (int rc = bih_rebuild_indexed_check(s, bih_id, verts, dtype, nv, idx3, n, &m)) return rc;
-  for (size_t k = 0; k < 3 * (size_t)n; k++) {  // only referenced vertices count: an unreferenced one may be anything
-    const int32_t i = idx3[k];
-    if (i < 0 || i >= nv) { ctx->err = "bih rebuild: item " + std::to_string(k / 3) + " has vertex index " + std::to_string(i) + ", outside [0, " + std::to_string(nv) + ")"; return GLOME_E_INVALID; }
-    bool finite = true;
-    for (int a = 0; a < 3; a++) finite = finite && (dtype == GLOME_F32 ? std::isfinite(((const float*)verts)[3 * (size_t)i + a]) : std::isfinite(((const double*)verts)[3 * (size_t)i + a]));
-    if (!finite) { ctx->err = "bih rebuild: a vertex coordinate is not finite (vertex " + std::to_string(i) + ", of item " + std::to_string(k / 3) + ")"; return GLOME_E_INVALID; }
-  }
-  HIPCHK(ctx, hipSetDevice(ctx->device));
-  Staging st;
-  char* dv = st.in((const char*)verts, 3 * (size_t)nv * (dtype == GLOME_F32 ? sizeof(float) : sizeof(double)));
-  int32_t* di = st.in(idx3, 3 * (size_t)n);
-  if (!st.ok) { ctx->err = "staging allocation failed"; return GLOME_E_HIP; }
-  return glome_scene_bih_rebuild_indexed_dev(s, bih_id, dv, dtype, nv, di, n, gpu_ms);
+  return leaf_bih_host<kRebuild>(s, bih_id, IndexedTris{verts, dtype, nv, idx3, n}, gpu_ms);
 }
-int glome_scene_sphere_bih_rebuild(glome_scene* s, int32_t bih_id, const double* c3r, int n, float* gpu_ms) {
-  if (!s) return GLOME_E_INVALID;
-  if (gpu_ms) *gpu_ms = 0;
-  glome_scene::LeafBihUpd* m = nullptr;
-  if (int rc = leaf_bih_update_check(s, BC_SPHERE, "sphere bih rebuild", bih_id, c3r, n, &m)) return rc;
-  for (size_t k = 0; k < 4 * (size_t)n; k++) if (!std::isfinite(c3r[k])) { s->ctx->err = "sphere bih rebuild: a value is not finite"; return GLOME_E_INVALID; }
-  for (size_t k = 0; k < (size_t)n; k++) if (!(c3r[4 * k + 3] > 0)) { s->ctx->err = "sphere bih rebuild: radius of item " + std::to_string(k) + " is not positive"; return GLOME_E_INVALID; }
-  HIPCHK(s->ctx, hipSetDevice(s->ctx->device));
-  Staging st;
-  double* dp = st.in(c3r, 4 * (size_t)n);
-  if (!st.ok) { s->ctx->err = "staging allocation failed"; return GLOME_E_HIP; }
-  return glome_scene_sphere_bih_rebuild_dev(s, bih_id, dp, n, gpu_ms);
-}
+int glome_scene_sphere_bih_rebuild_dev(glome_scene* s, int32_t bih_id, const double* c3r_dev, int n, float* gpu_ms) { return leaf_bih_dev<kRebuild>(s, bih_id, PackedSpheres{c3r_dev, n}, gpu_ms); }
+int glome_scene_sphere_bih_rebuild(glome_scene* s, int32_t bih_id, const double* c3r, int n, float* gpu_ms) { return leaf_bih_host<kRebuild>(s, bih_id, PackedSpheres{c3r, n}, gpu_ms); }
 // slots, pair records, records, depth of the tree as it stands, then what its node segment and its pair segment hold
 int glome_scene_bih_layout(const glome_scene* s, int32_t bih_id, int64_t out6[6]) {
   if (!s || !out6) return GLOME_E_INVALID;
