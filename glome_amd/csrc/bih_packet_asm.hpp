@@ -68,6 +68,19 @@
 //                ties -> later item); a leaf's odd last triangle is a pair whose B half is computed and ignored.  A hit
 //                records the triangle's record index: the pair record carries A's, B's is the next (one v_add_u32 on the lanes
 //                that hit; until round 12 an s_add_u32 per pair test and a v_mov).
+//   early leave  (round 13) a lane hits only with 0 <= b1 <= 1, and of the flagship frame's 17.3 pair tests per live item 5.2 have no
+//                such lane for A or for B (tools/probe/bih_cull_study.cpp's PAIRS line).  The test is therefore cut in two
+//                (GLOME_PKW_PAIR_B1 / _REST below): first D, s1, the divisor, D . s1, the two reciprocals and b1 = (D . s1) * inv, then
+//                a vote over the leaf's lanes (GLOME_PKW_PAIR_VOTE: why it never drops a lane the chain accepts is written there),
+//                and with nobody left the walk goes on to what follows the pair (L_out: the leaf's next record, or the pops) --
+//                the decision the count word takes after the chains.  Every value is the parent's bit for bit: only independent
+//                instructions changed places.  No register more: the reciprocal takes s1.x's pair and s2.x the divisor's, whose
+//                `!= 0` votes leave for VCC and s[K28:K29] first and open the two chains as a scalar move.  Instructions per path,
+//                the record's loads and their wait included (MODE 1 | MODE 2; vector ones in brackets: 16 + 1 packed and 4 plain up to
+//                the vote): left after b1 26 [21] and 2 (the leaf's last pair) or 4 at L_out; run through 64 [48] + 3 [3] per
+//                triangle hit | 68 [48]; until round 12 every test was 62 [51 | 45].
+//   update       (round 13, MODE 1) the three moves of a hit run under an EXEC that is empty for two triangles in three: an
+//                s_cbranch_execz over them, to where the count is tested as the fall-through does.  MODE 2's update is scalar.
 //   pop          6 scalar-type and the dispatch.  ONE test of the stack pointer: m0 - 1 is >= CAP, unsigned, for an entry beyond
 //                the LDS part and for the empty stack alike (0xffffffff); L_popslow tells them apart, two instructions on the one
 //                pop that ends a walk instead of one on every pop.  Entered with phase != 0 and sp = 0 the block so leaves through
@@ -99,7 +112,7 @@ namespace glome {
 // destinations), K0 .. K39 below.
 //   K0..K3 node set A, K4..K7 node set B (lsplit, rsplit, left, right) | K8..K25 a pair record (p1x p1y p1z e1x e1y e1z e2x e2y
 //   e2z, each as (A, B)), K26 the triangles left in its leaf, K27 the first one's record index | K28 K29 a popped entry's mask, v_cmpx's other
-//   destination | K30 K31 EXEC at entry | K32 the caller's m0 | K33 the destination of a dispatch's s_and (nothing reads it) | K34 K35 a leaf's lanes |
+//   destination | K30 K31 EXEC at entry | K32 the caller's m0 | K33 the destination of a dispatch's s_and (nothing reads it), inside a leaf 0.5 for the pair test's vote | K34 K35 a leaf's lanes |
 //   K36..K39 buffer descriptor over the node pool
 #ifndef GLOME_PKW_BASE
 #define GLOME_PKW_BASE 36
@@ -315,8 +328,9 @@ namespace glome {
 
 // The block's scratch vector registers: 16 consecutive ones from GLOME_PKW_VBASE (even: they are used as aligned pairs),
 // T0 .. T15.  Named, not allocated by the compiler, because the packed arithmetic needs both the pair and its halves.
-//   branch step: (T0, T1) the two plane distances | leaf: (T0 T1) (T2 T3) (T4 T5) D = o - p1, then b2, t, 1 / divisor;
-//   (T6 T7) (T8 T9) (T10 T11) s1 = dir x e2, then s2 = D x e1, then min / max of the barycentrics; (T12 T13) divisor; (T14 T15) b1
+//   branch step: (T0, T1) the two plane distances | leaf: (T0 T1) (T2 T3) (T4 T5) D = o - p1, then (T0 T1) b2, (T2 T3) t;
+//   (T6 T7) (T8 T9) (T10 T11) s1 = dir x e2, then (T6 T7) 1 / divisor, (T8 T9) the vote's h, s2.y, max of the barycentrics, (T10 T11) s2.z;
+//   (T12 T13) divisor, then s2.x, then min of the barycentrics; (T14 T15) D . s1, then b1
 #ifndef GLOME_PKW_VBASE
 #define GLOME_PKW_VBASE 64
 #endif
@@ -407,7 +421,7 @@ constexpr uint32_t PKREF_LEAF = 3u;  // low bits of a reference in the walk's ow
 //   after a Z step    X 2, Y 4, leaf 6, Z 7
 //   after a pop       X 4, Y 4, Z 4, leaf 5     (always into set A)
 //   at the root       X 4, Y 4, Z 4, leaf 4     (L_node / L_node2: a fresh walk, and a re-entry after a C++ step)
-// s[K33] is the s_and's destination, nothing reads it.
+// s[K33] is the s_and's destination, nothing reads it (a leaf sets it to 0.5 for its votes and has no dispatch).
 #define GLOME_PKW_AFTER_X(S)                                                                            \
   "  s_bitcmp1_b32 %[ref], 1\n"                                                                         \
   "  s_cbranch_scc1 L_zl" S "_%=\n"                                                                     \
@@ -558,7 +572,6 @@ constexpr uint32_t PKREF_LEAF = 3u;  // low bits of a reference in the walk's ow
 #define PKW_B1 "v[" T14 ":" T15 "]"
 #define PKW_B2 PKW_DX
 #define PKW_TT PKW_DY
-#define PKW_INV PKW_DZ
 #define PKW_P1X "s[" K8 ":" K9 "]"
 #define PKW_P1Y "s[" K10 ":" K11 "]"
 #define PKW_P1Z "s[" K12 ":" K13 "]"
@@ -568,7 +581,14 @@ constexpr uint32_t PKREF_LEAF = 3u;  // low bits of a reference in the walk's ow
 #define PKW_E2X "s[" K20 ":" K21 "]"
 #define PKW_E2Y "s[" K22 ":" K23 "]"
 #define PKW_E2Z "s[" K24 ":" K25 "]"
-#define GLOME_PKW_PAIR_ARITH                                                                                          \
+// Round 13: the test in two parts with a vote between them.  Part one is D, s1, the divisor, D . s1, the two reciprocals and
+// b1 = (D . s1) * inv -- 16 packed and 2 plain; the reciprocals stand before D . s1's last fma (gfx950 wants one instruction
+// between a transcendental and a plain VALU reader of its result) and go where s1.x was, dead by then.  Part two is the parent's
+// rest; s2.x goes where the divisor was, so the reciprocal lives to the last multiplies in sixteen temporaries.  Only independent
+// instructions changed places and registers their names: every operation has the parent's operands, every value its bits.
+#define PKW_S2X PKW_DIV
+#define PKW_INV PKW_AX
+#define GLOME_PKW_PAIR_B1                                                                                             \
   "  v_pk_add_f32 " PKW_DX ", %[P0], " PKW_P1X PKW_BL2 PKW_NEG1 "\n"   /* D = o - p1 */                                \
   "  v_pk_add_f32 " PKW_DY ", %[P0], " PKW_P1Y PKW_BH2 PKW_NEG1 "\n"                                                   \
   "  v_pk_add_f32 " PKW_DZ ", %[P1], " PKW_P1Z PKW_BL2 PKW_NEG1 "\n"                                                   \
@@ -583,38 +603,59 @@ constexpr uint32_t PKREF_LEAF = 3u;  // low bits of a reference in the walk's ow
   "  v_pk_fma_f32 " PKW_DIV ", " PKW_AZ ", " PKW_E1Z ", " PKW_DIV "\n"                                                 \
   "  v_pk_mul_f32 " PKW_B1 ", " PKW_DY ", " PKW_AY "\n"                /* D . s1 */                                     \
   "  v_pk_fma_f32 " PKW_B1 ", " PKW_DX ", " PKW_AX ", " PKW_B1 "\n"                                                    \
+  "  v_rcp_f32 v" T6 ", v" T12 "\n"                                    /* 1 / divisor (over s1.x, dead now) */          \
+  "  v_rcp_f32 v" T7 ", v" T13 "\n"                                                                                    \
   "  v_pk_fma_f32 " PKW_B1 ", " PKW_DZ ", " PKW_AZ ", " PKW_B1 "\n"                                                    \
-  "  v_pk_mul_f32 " PKW_AY ", " PKW_DX ", " PKW_E1Z PKW_NEG0 "\n"      /* s2 = D x e1 (over s1) */                      \
-  "  v_pk_mul_f32 " PKW_AX ", " PKW_DZ ", " PKW_E1Y PKW_NEG0 "\n"                                                      \
+  "  v_pk_mul_f32 " PKW_B1 ", " PKW_B1 ", " PKW_INV "\n"
+// The vote: may any lane of the leaf still hit A or B?  A lane hits only with 0 <= b1 <= 1.  h = b1 - 0.5 (0.5 is the high half
+// of s[K32:K33], set at L_leaf), and a lane stays unless |h| > 0.5 holds as an ordered comparison.  It never drops a lane with
+// 0 <= b1 <= 1: for 0.25 <= b1 <= 1 the subtraction is exact (Sterbenz: 0.5 / 2 <= b1 <= 2 * 0.5), h in [-0.25, 0.5]; for
+// 0 <= b1 < 0.25 the exact difference lies in [-0.5, -0.25), both ends are fp32 numbers and rounding is monotonic, so h lies in
+// [-0.5, -0.25]; a subnormal b1 is flushed to a zero of either sign (0 - 0.5 = -0.5), and -0 counts as 0 here and in the chain.
+// A NaN b1 (0 / 0: zero divisor and numerator) gives a NaN h, `|h| > 0.5` is false, the lane stays -- v_min3 drops the NaN
+// in the chain and such a lane can go on to hit.  An infinite b1 leaves; so does 1 + ulp (h = 0.5 + 2^-23, exact).  What it keeps
+// beyond the chain's own test: b1 in [-2^-25, 0), where h rounds to -0.5; the chain rejects those.  The divisor test is not part of
+// the vote.  A leaf's odd last triangle stands in both halves (flatten.hpp emit_pairs), so B votes as A does.  EXEC = the leaf's
+// lanes and is not touched: a v_cmp gives 0 for the others.  Nobody left: SCC = 0.
+#define GLOME_PKW_PAIR_VOTE                                                                                           \
+  "  v_pk_add_f32 " PKW_AY ", " PKW_B1 ", s[" K32 ":" K33 "] op_sel:[0,1] op_sel_hi:[1,1]" PKW_NEG1 "\n"  /* h (over s1.y, dead now) */ \
+  "  v_cmp_ngt_f32_e64 vcc, |v" T8 "|, 0.5\n"                                                                          \
+  "  v_cmp_ngt_f32_e64 s[" K28 ":" K29 "], |v" T9 "|, 0.5\n"                                                           \
+  "  s_or_b64 vcc, vcc, s[" K28 ":" K29 "]\n"
+// Part two.  The `divisor != 0` votes leave the vector registers first (A's into VCC, B's into s[K28:K29]: under EXEC = the leaf's
+// lanes the bits a v_cmpx would give), then s2.x takes the divisor's place.
+// Leaves (A, B) of: min(b1, b2, t) T12 T13, max(b1, b1 + b2) T8 T9, t T2 T3.
+#define GLOME_PKW_PAIR_REST                                                                                           \
+  "  v_cmp_neq_f32 vcc, 0, v" T12 "\n"                                                                                 \
+  "  v_cmp_neq_f32_e64 s[" K28 ":" K29 "], 0, v" T13 "\n"                                                              \
+  "  v_pk_mul_f32 " PKW_AY ", " PKW_DX ", " PKW_E1Z PKW_NEG0 "\n"      /* s2 = D x e1 (over s1 and the divisor) */      \
+  "  v_pk_mul_f32 " PKW_S2X ", " PKW_DZ ", " PKW_E1Y PKW_NEG0 "\n"                                                     \
   "  v_pk_mul_f32 " PKW_AZ ", " PKW_DY ", " PKW_E1X PKW_NEG0 "\n"                                                      \
   "  v_pk_fma_f32 " PKW_AY ", " PKW_DZ ", " PKW_E1X ", " PKW_AY "\n"                                                   \
-  "  v_pk_fma_f32 " PKW_AX ", " PKW_DY ", " PKW_E1Z ", " PKW_AX "\n"                                                   \
+  "  v_pk_fma_f32 " PKW_S2X ", " PKW_DY ", " PKW_E1Z ", " PKW_S2X "\n"                                                 \
   "  v_pk_fma_f32 " PKW_AZ ", " PKW_DX ", " PKW_E1Y ", " PKW_AZ "\n"                                                   \
-  "  v_rcp_f32 v" T4 ", v" T12 "\n"                                    /* 1 / divisor (over D.z, dead now) */           \
-  "  v_rcp_f32 v" T5 ", v" T13 "\n"                                                                                    \
   "  v_pk_mul_f32 " PKW_B2 ", %[P2], " PKW_AY PKW_BL2 "\n"             /* dir . s2 (over D.x) */                        \
   "  v_pk_mul_f32 " PKW_TT ", " PKW_AY ", " PKW_E2Y "\n"               /* e2 . s2 (over D.y) */                         \
-  "  v_pk_fma_f32 " PKW_B2 ", %[P1], " PKW_AX ", " PKW_B2 PKW_BH3 "\n"                                                 \
-  "  v_pk_fma_f32 " PKW_TT ", " PKW_AX ", " PKW_E2X ", " PKW_TT "\n"                                                   \
+  "  v_pk_fma_f32 " PKW_B2 ", %[P1], " PKW_S2X ", " PKW_B2 PKW_BH3 "\n"                                                \
+  "  v_pk_fma_f32 " PKW_TT ", " PKW_S2X ", " PKW_E2X ", " PKW_TT "\n"                                                  \
   "  v_pk_fma_f32 " PKW_B2 ", %[P2], " PKW_AZ ", " PKW_B2 PKW_BH3 "\n"                                                 \
   "  v_pk_fma_f32 " PKW_TT ", " PKW_AZ ", " PKW_E2Z ", " PKW_TT "\n"                                                   \
   "  v_pk_mul_f32 " PKW_B2 ", " PKW_B2 ", " PKW_INV "\n"                                                               \
-  "  v_pk_mul_f32 " PKW_B1 ", " PKW_B1 ", " PKW_INV "\n"                                                               \
   "  v_pk_mul_f32 " PKW_TT ", " PKW_TT ", " PKW_INV "\n"                                                               \
-  "  v_min3_f32 v" T6 ", v" T14 ", v" T0 ", v" T2 "\n"                 /* lo = min(b1, b2, t) */                        \
-  "  v_min3_f32 v" T7 ", v" T15 ", v" T1 ", v" T3 "\n"                                                                 \
+  "  v_min3_f32 v" T12 ", v" T14 ", v" T0 ", v" T2 "\n"                /* lo = min(b1, b2, t) (over s2.x) */            \
+  "  v_min3_f32 v" T13 ", v" T15 ", v" T1 ", v" T3 "\n"                                                                \
   "  v_pk_add_f32 " PKW_AY ", " PKW_B1 ", " PKW_B2 "\n"                                                                \
   "  v_max_f32 v" T8 ", v" T14 ", v" T8 "\n"                           /* hi = max(b1, b1 + b2) */                      \
   "  v_max_f32 v" T9 ", v" T15 ", v" T9 "\n"
-// divisor == 0 || b1 < 0 || b2 < 0 || t < 0 || b1 > 1 || b1 + b2 > 1 || t > far  ->  miss.  Entered with EXEC = the lanes whose
-// interval reaches the leaf; leaves EXEC = the lanes that hit.
-#define GLOME_PKW_CHAIN(DIV, LO, HI, TT)                                                              \
-  "  v_cmpx_neq_f32 vcc, 0, v" DIV "\n"                                                               \
+// divisor == 0 || b1 < 0 || b2 < 0 || t < 0 || b1 > 1 || b1 + b2 > 1 || t > far  ->  miss.  NZ: how EXEC becomes the leaf's lanes
+// whose divisor is not zero (the vote taken in part two); leaves EXEC = the lanes that hit.
+#define GLOME_PKW_CHAIN(NZ, LO, HI, TT)                                                               \
+  NZ                                                                                                  \
   "  v_cmpx_ngt_f32 vcc, 0, v" LO "\n"                                                                \
   "  v_cmpx_nlt_f32 vcc, 1.0, v" HI "\n"                                                              \
   "  v_cmpx_ngt_f32 vcc, v" TT ", %[far]\n"
-#define GLOME_PKW_CHAIN_A GLOME_PKW_CHAIN(T12, T6, T8, T2)
-#define GLOME_PKW_CHAIN_B GLOME_PKW_CHAIN(T13, T7, T9, T3)
+#define GLOME_PKW_CHAIN_A GLOME_PKW_CHAIN("  s_mov_b64 exec, vcc\n", T12, T8, T2)  /* (EXEC was the leaf's lanes: VCC is a subset) */
+#define GLOME_PKW_CHAIN_B GLOME_PKW_CHAIN("  s_and_b64 exec, s[" K34 ":" K35 "], s[" K28 ":" K29 "]\n", T13, T9, T3)  /* (MODE 2: the leaf's lanes may have shrunk since the vote) */
 
 // what the lanes that hit do (EXEC = those lanes; TT = the half that holds their t, REC = the instruction that names the triangle:
 // the pair record carries A's record index, B's is the next).  MODE 2 goes on to the pops when no lane of the leaf is left.
@@ -624,6 +665,9 @@ constexpr uint32_t PKREF_LEAF = 3u;  // low bits of a reference in the walk's ow
   "  v_mov_b32 %[best_t], v" TT "\n"                                                                  \
   "  v_mov_b32 %[far], v" TT "\n"           /* far = min(far, t) = t: the test just passed t <= far */ \
   REC
+// MODE 1: nobody hit (EXEC empty) in most tests -- over the update to where the count is tested, as the fall-through does.
+#define GLOME_PKW_SKIP_1(L) "  s_cbranch_execz " L "\n"
+#define GLOME_PKW_SKIP_2(L) ""
 #define GLOME_PKW_UPDATE_2(TT, REC)                                                                   \
   "  s_or_b64 %[occ], %[occ], exec\n"                                                                 \
   "  s_andn2_b64 s[" K34 ":" K35 "], s[" K34 ":" K35 "], exec\n"   /* an occluded ray is finished; SCC = rays left in this leaf */ \
@@ -675,22 +719,34 @@ constexpr uint32_t PKREF_LEAF = 3u;  // low bits of a reference in the walk's ow
       /* ------------------------------------------------------------ a leaf: two triangles per test */                        \
       "L_leaf_%=:\n"                        /* %[ref] = byte offset of the first pair record | 3 */                             \
       "  s_mov_b64 s[" K34 ":" K35 "], exec\n"   /* the leaf's lanes */                                                         \
+      "  s_mov_b32 s" K33 ", 0.5\n"         /* the vote's constant, read as the high half of s[K32:K33]; the dispatches write s[K33], the leaf has none */ \
       "L_tri_%=:\n"                                                                                                             \
       "  s_load_dwordx16 s[" K8 ":" K23 "], %[pairs], %[ref]\n"                                                                 \
       "  s_load_dwordx4 s[" K24 ":" K27 "], %[pairs], %[ref] offset:0x40\n"                                                     \
       "  s_waitcnt lgkmcnt(0)\n"                                                                                                \
-      GLOME_PKW_PAIR_ARITH                                                                                                      \
+      GLOME_PKW_PAIR_B1                                                                                                         \
+      GLOME_PKW_PAIR_VOTE                                                                                                       \
+      "  s_cbranch_scc0 L_out_%=\n"         /* no ray of the leaf has b1 in [0, 1] for A or for B */                            \
+      GLOME_PKW_PAIR_REST                                                                                                       \
       GLOME_PKW_CHAIN_A                                                                                                         \
+      GLOME_PKW_SKIP_##M("L_noA_%=")                                                                                            \
       GLOME_PKW_UPDATE_##M(T2, PKW_REC_A)                                                                                   \
+      "L_noA_%=:\n"                                                                                                             \
       "  s_cmp_eq_u32 s" K26 ", 1\n"                                                                                            \
       "  s_cbranch_scc1 L_pop_%=\n"         /* that was the leaf's last */                                                      \
-      "  s_mov_b64 exec, s[" K34 ":" K35 "]\n"                                                                                  \
       GLOME_PKW_CHAIN_B                                                                                                         \
+      GLOME_PKW_SKIP_##M("L_noB_%=")                                                                                            \
       GLOME_PKW_UPDATE_##M(T3, PKW_REC_B)                                                                                        \
+      "L_noB_%=:\n"                                                                                                             \
       "  s_cmp_eq_u32 s" K26 ", 2\n"                                                                                            \
       "  s_cbranch_scc1 L_pop_%=\n"                                                                                             \
       "  s_add_u32 %[ref], %[ref], 80\n"                                                                                        \
       "  s_mov_b64 exec, s[" K34 ":" K35 "]\n"                                                                                  \
+      "  s_branch L_tri_%=\n"                                                                                                   \
+      "L_out_%=:\n"                         /* what follows the pair, decided as above (the count is never 0); EXEC is still the leaf's lanes */ \
+      "  s_cmp_le_u32 s" K26 ", 2\n"                                                                                            \
+      "  s_cbranch_scc1 L_pop_%=\n"                                                                                             \
+      "  s_add_u32 %[ref], %[ref], 80\n"                                                                                        \
       "  s_branch L_tri_%=\n"                                                                                                   \
       /* ------------------------------------------------------------ pop until an entry some lane still wants */              \
       "L_pop_%=:\n"                                                                                                             \

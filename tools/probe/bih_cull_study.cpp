@@ -11,7 +11,8 @@
 //            rt_device.hpp) -- in the closest-hit walk and in the any-hit walk.  Every shadow result is compared with the unclipped walk's.
 // A cull only ever drops nodes in which nothing can be hit: results are unchanged (checked: same hits).
 // Per 8 x 8 packet of the `origin` walk it also prints, per live item, the events of the wave-wide walks (EVENTS) and where the dispatches
-// of the hand-written walk go, by the site they leave from (TRANS): what tools/probe/item_breakdown.py prices.
+// of the hand-written walk go, by the site they leave from (TRANS), and how many pair tests no ray can pass after b1 (PAIRS): what
+// tools/probe/item_breakdown.py prices.
 //
 //   g++ -O2 -std=c++17 -I glome_amd/csrc -I include tools/probe/bih_cull_study.cpp -o /tmp/bih_cull_study && /tmp/bih_cull_study 224 8 3
 //   (S5: 708 8 3 -- N > 300 selects the 3840 x 2160 frame)
@@ -45,6 +46,21 @@ struct Study {
   std::vector<int>* leaves = nullptr;
   std::vector<std::pair<int, int>>* went = nullptr;
   bool entered = false;
+  // per pair test a ray takes part in (leaf, pair of the leaf, flags): 1 = b1 in [0, 1] (divisor not zero) for A or B, 2 = the same with
+  // b2 >= 0 and b1 + b2 <= 1, 4 / 8 = the ray hits A / B within its `far` -- what the leaf test of bih_packet_asm.hpp can leave out (round 13)
+  struct PairRec { int leaf, pair, flags; };
+  std::vector<PairRec>* pairs = nullptr;
+  int b_flags(const Tri& t, D3 o, D3 d) const {
+    D3 s1 = cross(d, t.e2);
+    double div = dot(s1, t.e1);
+    if (div == 0) return 0;
+    double inv = 1.0 / div;
+    D3 dd = o - t.p;
+    double b1 = dot(dd, s1) * inv;
+    if (!(b1 >= 0 && b1 <= 1)) return 0;
+    double b2 = dot(d, cross(dd, t.e1)) * inv;
+    return (b2 >= 0 && b1 + b2 <= 1) ? 3 : 1;
+  }
   bool tri_hit(const Tri& t, D3 o, D3 d, double tmax, double& tt) const {
     D3 s1 = cross(d, t.e2);
     double div = dot(s1, t.e1);
@@ -100,10 +116,13 @@ struct Study {
         const BihTree::Node& n = T->nodes[k];
         if (n.leaf) {
           if (leaves && !n.items.empty()) leaves->push_back(k);
-          for (int it : n.items) {
+          for (size_t q = 0; q < n.items.size(); q++) {
+            const int it = n.items[q];
+            if (pairs && q % 2 == 0) pairs->push_back({k, (int)(q / 2), b_flags(tris[it], o, d) | (q + 1 < n.items.size() ? b_flags(tris[n.items[q + 1]], o, d) : 0)});
             tests++;
             double tt;
             if (tri_hit(tris[it], o, d, farv, tt)) {
+              if (pairs) pairs->back().flags |= q % 2 ? 8 : 4;
               if (mode == 2) return tt;
               if (best < 0 || !(best < tt)) { best = tt; farv = std::min(farv, tt); }
             }
@@ -226,10 +245,20 @@ int main(int argc, char** argv) {
     // and the kind of node they go to: 0 / 1 / 2 a branch along x / y / z, 3 a leaf.  A step dispatches to the child the packet goes on
     // with: the near one when any ray enters it, else the far one; the far child of a both-step is reached by the pop of its entry, when a
     // ray still enters it then (a ray that has found a nearer hit, or an occluder, does not); a step that enters neither child dispatches nothing.
-    struct Ev { double items = 0, live = 0, walks = 0, steps = 0, pushes = 0, leaf_visits = 0, pair_tests = 0, kind[4] = {0, 0, 0, 0}, trans[5][4] = {}; } ev[2];  // [0] primary, [1] shadow
+    struct Ev { double items = 0, live = 0, walks = 0, steps = 0, pushes = 0, leaf_visits = 0, pair_tests = 0, pair_b1 = 0, pair_b1b2 = 0, tris = 0, tris_hit = 0, kind[4] = {0, 0, 0, 0}, trans[5][4] = {}; } ev[2];  // [0] primary, [1] shadow
     std::vector<int> lv;
     std::vector<std::pair<int, int>> wv;
+    std::vector<Study::PairRec> pv;
     auto tally = [&](Ev& e) {
+      // the pair tests of the packet: per (leaf, pair) the flags of every ray that enters the leaf, or-ed
+      std::sort(pv.begin(), pv.end(), [](const Study::PairRec& a, const Study::PairRec& b) { return a.leaf != b.leaf ? a.leaf < b.leaf : a.pair < b.pair; });
+      for (size_t a = 0; a < pv.size();) {
+        size_t b = a; int m = 0;
+        for (; b < pv.size() && pv[b].leaf == pv[a].leaf && pv[b].pair == pv[a].pair; b++) m |= pv[b].flags;
+        e.pair_b1 += (m & 1) != 0; e.pair_b1b2 += (m & 2) != 0; e.tris_hit += ((m & 4) != 0) + ((m & 8) != 0);
+        e.tris += std::min<double>(2.0, (double)S.T->nodes[pv[a].leaf].items.size() - 2.0 * pv[a].pair);
+        a = b;
+      }
       std::sort(lv.begin(), lv.end()); lv.erase(std::unique(lv.begin(), lv.end()), lv.end());
       std::sort(wv.begin(), wv.end());
       long steps = 0, pushes = 0;
@@ -260,7 +289,7 @@ int main(int argc, char** argv) {
       all.clear();
       long own_max = 0;
       bool live = false;
-      lv.clear(); wv.clear(); S.leaves = &lv; S.went = &wv;
+      lv.clear(); wv.clear(); pv.clear(); S.leaves = &lv; S.went = &wv; S.pairs = &pv;
       for (int j = 0; j < 64; j++) {
         int px = bx + j % 8, py = by + j / 8;
         double xc = ((double(px) / W) * 2 - 1) * (double(W) / H), yc = -((double(py) / H) * 2 - 1);
@@ -276,7 +305,7 @@ int main(int argc, char** argv) {
       all.clear();
       ev[0].items += 1; ev[0].live += live;
       if (live) tally(ev[0]);
-      lv.clear(); wv.clear();
+      lv.clear(); wv.clear(); pv.clear();
       for (size_t j = 0; j < so.size(); j++) {
         vis.clear(); S.visited = &vis;
         S.walk(so[j], sdv[j], sl[j], 2);
@@ -288,7 +317,7 @@ int main(int argc, char** argv) {
       (void)own_max;
       if (live) tally(ev[1]);
     }
-    S.visited = nullptr; S.leaves = nullptr; S.went = nullptr;
+    S.visited = nullptr; S.leaves = nullptr; S.went = nullptr; S.pairs = nullptr;
     if (clipped) {  // one JSON line: means per live item
       const double n = std::max(1.0, ev[0].live);
       printf("EVENTS {\"walk\": \"origin\", \"items_sampled\": %.0f, \"live_items\": %.0f", ev[0].items, ev[0].live);
@@ -297,6 +326,13 @@ int main(int argc, char** argv) {
         printf(", \"%s\": {\"walks\": %.4f, \"branch_steps\": %.3f, \"pushes\": %.3f, \"leaf_visits\": %.3f, \"pair_tests\": %.3f, \"near_only\": %.3f, \"far_only\": %.3f, \"both\": %.3f, "
                "\"neither\": %.3f}", nm[w], ev[w].walks / n, ev[w].steps / n, ev[w].pushes / n, ev[w].leaf_visits / n, ev[w].pair_tests / n, ev[w].kind[1] / n, ev[w].kind[2] / n, ev[w].kind[3] / n,
                ev[w].kind[0] / n);
+      printf("}\n");
+      // what the pair tests could leave out, per live item: tests where some entering ray has b1 in range for A or B (the others can stop
+      // after b1), the same with b2 added, and -- what prices the skipped update -- the triangles tested and those some ray hits within far
+      printf("PAIRS {\"walk\": \"origin\", \"live_items\": %.0f", ev[0].live);
+      for (int w = 0; w < 2; w++)
+        printf(", \"%s\": {\"pair_tests\": %.3f, \"some_ray_b1\": %.3f, \"some_ray_b1_b2\": %.3f, \"triangles\": %.3f, \"triangles_hit\": %.3f}", nm[w], ev[w].pair_tests / n, ev[w].pair_b1 / n,
+               ev[w].pair_b1b2 / n, ev[w].tris / n, ev[w].tris_hit / n);
       printf("}\n");
       printf("TRANS {\"walk\": \"origin\", \"live_items\": %.0f, \"targets\": [\"x\", \"y\", \"z\", \"leaf\"]", ev[0].live);
       const char* site[5] = {"after_x", "after_y", "after_z", "after_pop", "at_root"};

@@ -22,13 +22,21 @@ priced WITHOUT their dispatch.  Without --trans a dispatch is counted at its ful
 without the four kinds (older than round 11) is priced as before: one figure per step, the push where both children are entered -- which
 charged the parent's far-only steps 15 instructions too few each and put them into "outside the walks".
 
+A pair test is priced by its PATH when the study's PAIRS line is given (--pairs FILE: per walk the pair tests, those where some entering
+ray has b1 in [0, 1] for A or B, the triangles tested and those some ray hits): since round 13 a test no ray can pass leaves after b1
+(L_tri up to the vote's branch, then L_out: 2 instructions when the pair was the leaf's last -- leaf visits / pair tests of them --, else 4),
+the others run through (L_tri, L_noA, L_noB), and the closest-hit walk's update (3 vector instructions) is charged per triangle HIT.  The primary
+walk is priced from the closest-hit blocks (those with an s_cbranch_execz over the update), the shadow walk from the any-hit blocks; a
+listing without L_out (the parent's) is priced whole for every test.  The line "pair tests by kind" splits the sum into vector instructions
+and the rest: the fall of the first is what SQ_INSTS_VALU should show.
+
 Pops are charged per push (pops = pushes): every entry pushed is popped once.  The pop that finds the stack empty and ends a walk -- one
 per walk that left its root branch -- is charged nowhere, so the model's walks are short by up to one pop (20 instructions) per walk,
 about 40 per live item, which the "outside" figure holds instead.
 
   g++ -O2 -std=c++17 -I glome_amd/csrc -I include tools/probe/bih_cull_study.cpp -o BUILD/bih_cull_study && BUILD/bih_cull_study 224 8 3 | grep EVENTS > BUILD/events.txt
   python tools/kernel_mix.py 1 > /dev/null
-  python tools/probe/item_breakdown.py BUILD/events.txt [--trans BUILD/trans.txt] [--listing FILE.s] [--kernel MANGLED] [--counted 4636.2]
+  python tools/probe/item_breakdown.py BUILD/events.txt [--trans BUILD/trans.txt] [--pairs BUILD/pairs.txt] [--listing FILE.s] [--kernel MANGLED] [--counted 4636.2]
 (BUILD: any directory outside the tree's tracked files)
 """
 import json
@@ -72,6 +80,8 @@ def is_label(s):
 
 def main():
     ev = json.loads(open(sys.argv[1]).read().split("EVENTS", 1)[1].splitlines()[0])
+    pairs = json.loads(open(arg("--pairs", "")).read().split("PAIRS", 1)[1].splitlines()[0]) if "--pairs" in sys.argv else None
+    pair_paths = {1: [], 2: []}  # per mode: (early, full without updates, update) as (all, vector) instruction counts per block
     trans = json.loads(open(arg("--trans", "")).read().split("TRANS", 1)[1].splitlines()[0]) if "--trans" in sys.argv else None
     lines = kernel_lines(arg("--listing", LISTING), arg("--kernel", KERNEL))
     total = sum(1 for s in lines if not is_label(s))
@@ -122,11 +132,23 @@ def main():
                 cost["both"].append(len(body) + len(nf))
                 cost["far_only"].append(len(body) + vote + len(seg["L_n1" + tag]) + len(seg[f"L_node_{n}"]) + len(seg[f"L_node2_{n}"]))
                 cost["neither"].append(cut + vote + 1)
-        cost["pair"].append(len(seg[f"L_tri_{n}"]))
+        tri = seg[f"L_tri_{n}"]
+        nv = lambda ls: sum(1 for x in ls if x.startswith("v_"))
+        if f"L_out_{n}" in seg:  # round 13: the test in two parts
+            full = tri + seg[f"L_noA_{n}"] + seg[f"L_noB_{n}"]
+            mode = 1 if any(x.startswith("s_cbranch_execz L_noA") for x in tri) else 2
+            vote = next(i for i, x in enumerate(tri) if x.startswith("s_cbranch_scc0 L_out")) + 1
+            upd = [x for x in full if x.startswith(("v_mov_b32", "v_add_u32"))] if mode == 1 else []
+            pair_paths[mode].append(((vote, nv(tri[:vote])), (len(full) - len(upd), nv(full) - len(upd)), (len(upd) / 2.0, len(upd) / 2.0)))
+            cost["pair"].append(len(full))
+        else:
+            mode = 1 if sum(1 for x in tri if x.startswith("v_mov_b32")) >= 4 else 2
+            pair_paths[mode].append(((0, 0), (len(tri), nv(tri)), (0, 0)))
+            cost["pair"].append(len(tri))
         cost["pop"].append(len(seg[f"L_pop_{n}"]) - (DISPATCH_LEN[form]["pop"] if trans else 0))
         cost["leaf_entry"].append(len(seg[f"L_leaf_{n}"]) + (0 if trans else len(seg.get(f"L_zlA_{n}", []))))
     c = {k: sum(v) / len(v) for k, v in cost.items()}
-    rows, walks = [], 0.0
+    rows, walks, pair_kinds, valu_pairs = [], 0.0, [], [0.0, 0.0]
     for w in ("primary", "shadow"):
         e = ev[w]
         if "far_only" in e:
@@ -134,6 +156,21 @@ def main():
         else:
             parts = {"branch steps": e["branch_steps"] * c["step"], "pushes": e["pushes"] * c["push"]}
         parts.update({"pops": e["pushes"] * c["pop"], "pair tests": e["pair_tests"] * c["pair"], "leaf entries": e["leaf_visits"] * c["leaf_entry"]})
+        if pairs:
+            pw, mode = pairs[w], 1 if w == "primary" else 2
+            pp = [[sum(b[i][j] for b in pair_paths[mode]) / len(pair_paths[mode]) for j in (0, 1)] for i in (0, 1, 2)]
+            if pp[0][0]:
+                last = min(1.0, e["leaf_visits"] / e["pair_tests"])
+                n_early, n_full = pw["pair_tests"] - pw["some_ray_b1"], pw["some_ray_b1"]
+                tot = [n_early * pp[0][j] + n_full * pp[1][j] + pw["triangles_hit"] * pp[2][j] for j in (0, 1)]
+                tot[0] += n_early * (2 * last + 4 * (1 - last))
+            else:
+                n_early, n_full = 0.0, pw["pair_tests"]
+                tot = [n_full * pp[1][j] for j in (0, 1)]
+            parts["pair tests"] = tot[0]
+            pair_kinds.append(f"  {w:8s} pair tests by path: {n_early:.2f} leave after b1 at {pp[0][0]:.0f} ({pp[0][1]:.0f} vector) + L_out, {n_full:.2f} run through at {pp[1][0]:.0f} ({pp[1][1]:.0f} vector)"
+                              f" + {pp[2][0]:.0f} per triangle hit ({pw['triangles_hit']:.2f} of {pw['triangles']:.2f})  -> pair tests by kind: vector {tot[1]:.1f}, the rest {tot[0] - tot[1]:.1f}")
+            valu_pairs[0] += tot[1]; valu_pairs[1] += tot[0] - tot[1]
         if trans:
             parts["dispatches"] = sum(n_ * p_ for site, paths in DISPATCH_PATHS[form].items() for n_, p_ in zip(trans[w][site], paths))
         rows.append((w, e, parts))
@@ -149,6 +186,10 @@ def main():
         for site, paths in DISPATCH_PATHS[form].items():
             counts = [trans["primary"][site][t] + trans["shadow"][site][t] for t in range(4)]
             print(f"  dispatches {site:9s} -> x {counts[0]:.2f} y {counts[1]:.2f} z {counts[2]:.2f} leaf {counts[3]:.2f}  at {paths}: {sum(a * b for a, b in zip(counts, paths)):.1f}")
+    for line in pair_kinds:
+        print(line)
+    if pair_kinds:
+        print(f"pair tests of both walks (model): vector {valu_pairs[0]:.1f}, the rest {valu_pairs[1]:.1f} per live item")
     print(f"in the walks (model): {walks:.0f} per live item")
     if "--counted" in sys.argv:
         counted = float(arg("--counted", "0"))
